@@ -8,12 +8,18 @@ configs[1] — 2 antennas, num_samp = 262144, ntaps = 4, nchan = 4096, 10 000 fr
 scaling).  ``value`` = samples per antenna stream processed by all ranks / wall time (one sample = one
 complex time sample per antenna stream, so a chunk pair counts 262144 samples — SURVEY.md §8d).
 
-After the timed region (untimed) the run checks what it timed: the integration against the float64 mean of
-the per-frame rows over the same frames, and sampled frames against oracle rows computed in the
-``cpu_baseline`` leg (1e-5 of max|vis|); it fails otherwise.  ``other_configs`` carries
-short runs of BASELINE configs[2] (nchan = 1, num_samp = 2^20) and configs[4] (8 antennas, nchan 4096).
+A plain run sets up, warms up, times K steps and prints the line (``ms_per_step`` = wall milliseconds of one
+timed step).  ``--dump-outputs DIR`` also writes what the last timed step returned (DIR/visibilities.npy:
+float64 [n_baselines, nchan, 2], real and imaginary parts); the inputs are the same from run to run.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--no-cpu-baseline]
+Everything else is behind ``--full``: the ``cpu_baseline`` leg, and after the timed region (untimed) the check
+of what was timed -- the integration against the float64 mean of the per-frame rows over the same frames, and
+sampled frames against oracle rows computed in the ``cpu_baseline`` leg (1e-5 of max|vis|); it
+fails otherwise -- ``other_configs`` (short runs of BASELINE configs[2] (nchan = 1, num_samp = 2^20), configs[4]
+(8 antennas, nchan 4096) and other shapes), the power sample and, for N > 1, the latency of the reduce alone.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--dump-outputs DIR]
+    python bench.py --full [--no-cpu-baseline] [--no-verify] [--no-other-configs] [--no-power]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python -m torch.distributed.run --nproc-per-node 2 ... bench.py --gpus 2 --dry-run-dist   # control flow on gloo/CPU
@@ -285,6 +291,15 @@ def max_over_ranks(seconds, world, device):
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     return float(t.item())
+
+
+def dump_outputs(dirname, out):
+    """--dump-outputs: the integration the last timed step returned, complex128 [n_baselines, nchan], as float64
+    [n_baselines, nchan, 2] (real, imaginary) in DIR/visibilities.npy."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    vis = np.ascontiguousarray(out, dtype=np.complex128)
+    np.save(os.path.join(dirname, "visibilities.npy"), vis.view(np.float64).reshape(vis.shape + (2,)))
 
 
 # ----------------------------------------------------------------------------------------------
@@ -794,26 +809,30 @@ def rows_mode(args, plan, x, dev, rank, world, first_frame, frames, total_frames
                                "ms_per_step_this_rank": round(elapsed_rank / max(args.steps, 1) * 1e3, 4),
                                "rows_per_s_this_rank": round(frames * args.steps / elapsed_rank, 1)}, world)
     if rank == 0:
-        direct = plan.fx_rows(x[probe], "SPECTRUM")[:, 0].cpu().numpy() if probe else None
-        if to_file:
-            back = rowsink.RowFile(path)
-            assert back.rows.shape == (total_frames, NCHAN) and back.header == header, (back.rows.shape, back.header)
-            got = {f: np.asarray(back.rows[first_frame + f]) for f in probe}
-            for f in check_rows:
-                if f < frames:
-                    got[f] = np.asarray(back.rows[f])
-            assert np.abs(np.asarray(back.rows[-1])).max() > 0          # the last rank's last row arrived
-            rows_in_file = int(back.rows.shape[0])
-            del back
-        else:
-            got, rows_in_file = dict(kept), None
-            assert sorted(got) == probe, (sorted(got), probe)
         assert sum(r["frames"] for r in ranks) == total_frames
-        # sampled rows against a direct call on the same frames, and rank 0's against the oracle (N = 1)
-        err_direct = max([float(np.abs(got[f] - direct[i]).max() / np.abs(direct[i]).max()) for i, f in enumerate(probe)] or [0.0])
-        err_oracle = {str(f): float(np.abs(got[f] - ref).max() / np.abs(ref).max())
-                      for f, ref in sorted(check_rows.items()) if f in got}
-        assert err_direct < TOL_VIS and all(e < TOL_VIS for e in err_oracle.values()), (err_direct, err_oracle)
+        verify = None
+        if args.full:         # (untimed) the rows that arrived, checked
+            direct = plan.fx_rows(x[probe], "SPECTRUM")[:, 0].cpu().numpy() if probe else None
+            if to_file:
+                back = rowsink.RowFile(path)
+                assert back.rows.shape == (total_frames, NCHAN) and back.header == header, (back.rows.shape, back.header)
+                got = {f: np.asarray(back.rows[first_frame + f]) for f in probe}
+                for f in check_rows:
+                    if f < frames:
+                        got[f] = np.asarray(back.rows[f])
+                assert np.abs(np.asarray(back.rows[-1])).max() > 0          # the last rank's last row arrived
+                rows_in_file = int(back.rows.shape[0])
+                del back
+            else:
+                got, rows_in_file = dict(kept), None
+                assert sorted(got) == probe, (sorted(got), probe)
+            # sampled rows against a direct call on the same frames, and rank 0's against the oracle (N = 1)
+            err_direct = max([float(np.abs(got[f] - direct[i]).max() / np.abs(direct[i]).max()) for i, f in enumerate(probe)] or [0.0])
+            err_oracle = {str(f): float(np.abs(got[f] - ref).max() / np.abs(ref).max())
+                          for f, ref in sorted(check_rows.items()) if f in got}
+            assert err_direct < TOL_VIS and all(e < TOL_VIS for e in err_oracle.values()), (err_direct, err_oracle)
+            verify = {"rows_in_file": rows_in_file, "file_vs_direct_call": err_direct, "rows_vs_oracle": err_oracle,
+                      "tolerance": TOL_VIS, "checked_after_timed_region": True}
         rows_s = total_frames * args.steps / elapsed
         print(json.dumps({
             "metric": "2-ant FX correlator time series (PFB+FFT+X, one visibility row per frame into %s)"
@@ -828,8 +847,7 @@ def rows_mode(args, plan, x, dev, rank, world, first_frame, frames, total_frames
                                    "batch k + 1 queued before batch k is collected" + ("; four threads pwrite a finished slot into the file" if to_file else ""),
                        "parallelism": "frames sharded over %d GPU(s) in whole batches, disjoint windows of one row file, no collective" % world,
                        "dist_backend": args.dist_backend if world > 1 else None, "path": plan.path},
-            "verify": {"rows_in_file": rows_in_file, "file_vs_direct_call": err_direct, "rows_vs_oracle": err_oracle,
-                       "tolerance": TOL_VIS, "checked_after_timed_region": True},
+            "verify": verify,
             "ranks": {"per_rank": ranks, "rows_per_s_this_rank": spread(ranks, "rows_per_s_this_rank"),
                       "ms_per_step_this_rank": spread(ranks, "ms_per_step_this_rank")}}))
         if to_file and not args.rows_file:
@@ -853,12 +871,19 @@ def main():
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak: --frames per GPU (SURVEY.md 8d config 4, the default the driver runs); strong: --frames in "
                          "all, rank r integrates the contiguous range sharding.chunk_range(r, N, frames)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline, the check of what was timed, other_configs, the power sample and (N > 1) the "
+                         "reduce latency; a plain run only sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result of the last timed step to DIR/visibilities.npy (float64 [n_baselines, nchan, 2]: "
+                         "real, imaginary)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline (and the oracle rows it makes)")
     ap.add_argument("--cpu-seconds", type=float, default=8.0)
-    ap.add_argument("--no-power", action="store_true", help="skip the rocm-smi power sample after the timed region")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the short runs of configs[2], configs[4] and the two three-pass shapes")
+    ap.add_argument("--no-power", action="store_true", help="--full: skip the rocm-smi power sample after the timed region")
+    ap.add_argument("--no-other-configs", action="store_true",
+                    help="--full: skip the short runs of configs[2], configs[4] and the two three-pass shapes")
     ap.add_argument("--no-verify", action="store_true",
-                    help="skip the check after the timed region (profiling runs: its fx_rows launches would mix into "
+                    help="--full: skip the check after the timed region (profiling runs: its fx_rows launches would mix into "
                          "the per-kernel statistics)")
     ap.add_argument("--reduce", choices=("auto", "rccl", "torch"), default="auto",
                     help="N > 1: the cross-rank reduce.  rccl: fxc_reduce (libfxcorr calls RCCL on the plan's stream); torch: "
@@ -889,6 +914,10 @@ def main():
     ap.add_argument("--dry-run-dist", action="store_true",
                     help="run the multi-rank control flow on gloo / CPU tensors with a stand-in plan (no GPU)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.rows or args.dry_run_dist):
+        ap.error("--dump-outputs writes the integration of the headline workload (not --rows or --dry-run-dist)")
 
     if args.dry_run_dist:
         if args.frames == FRAMES:
@@ -905,7 +934,7 @@ def main():
         raise SystemExit("bench.py measures the in-tree library only (FXCORR_LIB points at %s)" % _lib.LIB_PATH)
 
     cpu, check_rows = None, {}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu, check_rows = cpu_baseline(args.cpu_seconds, args.frames)   # before any HIP initialisation in this process
 
     import numpy as np
@@ -1022,10 +1051,12 @@ def main():
     kernel_ms, launches = plan.kernel_time(reset=True)
     plan.kernel_profiling(False)
     elapsed = max_over_ranks(elapsed_rank, world, dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
 
-    # --- untimed: latency of the reduce alone (export + collective, HIP events on the plan's stream) -----
+    # --- untimed (--full): latency of the reduce alone (export + collective, HIP events on the plan's stream) -----
     reduce_us = None
-    if world > 1:
+    if world > 1 and args.full:
         plan.fx_accumulate(x[:min(pool_frames, 64)])
         lat = []
         for _ in range(12):
@@ -1037,21 +1068,23 @@ def main():
         lat.sort()
         reduce_us = round(lat[len(lat) // 2], 1)
 
-    # --- untimed: check what was timed -----------------------------------------------------------------
+    # --- untimed (--full): check what was timed -----------------------------------------------------------------
     # (i) the integration against the float64 mean of the per-frame rows over the same frames, summed over ranks;
     # (ii) rank 0's sampled frames against the oracle rows of the cpu_baseline leg (N = 1)
-    rows_sum = torch.zeros(NCHAN, dtype=torch.complex128, device=dev)
-    done = frames if args.no_verify else 0
-    while done < frames:                          # the same launches' frames as step(), 2048 rows at a time
-        n = min(pool_frames, frames - done)
-        for lo in range(0, n, 2048):
-            hi = min(n, lo + 2048)
-            rows_sum += plan.fx_rows(x[lo:hi], "SPECTRUM")[:, 0].to(torch.complex128).sum(dim=0)
-        done += n
-    if world > 1:
-        sharding.reduce_sums(rows_sum, to_all=True)
+    check = args.full and not args.no_verify
+    if check:
+        rows_sum = torch.zeros(NCHAN, dtype=torch.complex128, device=dev)
+        done = 0
+        while done < frames:                          # the same launches' frames as step(), 2048 rows at a time
+            n = min(pool_frames, frames - done)
+            for lo in range(0, n, 2048):
+                hi = min(n, lo + 2048)
+                rows_sum += plan.fx_rows(x[lo:hi], "SPECTRUM")[:, 0].to(torch.complex128).sum(dim=0)
+            done += n
+        if world > 1:
+            sharding.reduce_sums(rows_sum, to_all=True)
     verify = None
-    if rank == 0 and not args.no_verify:
+    if rank == 0 and check:
         rows_mean = (rows_sum / total_frames).cpu().numpy()
         err_rows = float(np.abs(out[0] - rows_mean).max() / np.abs(rows_mean).max())
         err_oracle = {}
@@ -1065,7 +1098,7 @@ def main():
         assert all(e < TOL_VIS for e in err_oracle.values()), verify
 
     others = None
-    if world == 1 and not args.no_other_configs:
+    if args.full and world == 1 and not args.no_other_configs:
         others = other_configs(x, dev)
 
     def busy():                                    # keeps this rank's GPU on the F+X kernel, no collective
@@ -1073,7 +1106,7 @@ def main():
         plan.acc_reset()
         plan.sync()
 
-    power = power_sample(busy, gpu_index=gpu) if not args.no_power else None
+    power = power_sample(busy, gpu_index=gpu) if args.full and not args.no_power else None
 
     # --- every rank's own numbers, for the reader of an efficiency < 1 ------------------------------------
     my = {"rank": rank, "gpu": gpu, "frames": frames, "first_frame": first_frame,
@@ -1109,6 +1142,7 @@ def main():
             "vs_baseline": None,
             "dtype": "f32",
             "data": "synthetic",
+            "full": bool(args.full),
             "config": {"workload": "configs[1]: 2-antenna FX, num_samp=262144, ntaps=4, nchan=4096, "
                                    "%d integration frames %s per step" % (args.frames, "per GPU" if args.scaling == "weak" else "in all"),
                        "frames_per_gpu": frames, "frames_total": total_frames, "resident_frames": pool_frames,

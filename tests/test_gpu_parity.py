@@ -1965,7 +1965,7 @@ def test_bench_two_ranks_share_one_gpu():
     sock.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--steps", "2",
-           "--warmup", "1", "--frames", "600"]
+           "--warmup", "1", "--frames", "600", "--full"]
     proc = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
     assert proc.returncode == 0, proc.stderr[-3000:]
     lines = [ln for ln in proc.stdout.splitlines() if ln.startswith("{")]
@@ -2012,7 +2012,7 @@ def test_bench_eight_ranks_share_one_gpu(scaling, frames):
     """The launch the driver makes for the scaling curve -- torch.distributed.run with 8 ranks -- rehearsed on this one GPU
     over gloo (ranks share the GPU, so RCCL is out and the run takes the torch.distributed transport): the per-rank table,
     the frame bookkeeping, the all-reduced check after the timed region and a clean exit of all eight children."""
-    line = _launch_bench(8, "--steps", "2", "--warmup", "1", "--frames", str(frames), "--scaling", scaling, "--no-power")
+    line = _launch_bench(8, "--full", "--steps", "2", "--warmup", "1", "--frames", str(frames), "--scaling", scaling, "--no-power")
     total = frames * 8 if scaling == "weak" else frames
     assert line["n_gpus"] == 8 and line["scaling"] == scaling and line["config"]["frames_total"] == total
     assert line["verify"]["frames"] == total and line["verify"]["integration_vs_float64_mean_of_rows"] < 1e-6
@@ -2040,13 +2040,13 @@ def test_bench_rows_mode_two_ranks_write_the_single_rank_file(tmp_path):
     import os
     from effex_amd import rowsink
     two, one = str(tmp_path / "two.fxb"), str(tmp_path / "one.fxb")
-    line = _launch_bench(2, "--rows", "--rows-batch", "16", "--rows-file", two, "--steps", "1", "--warmup", "0", "--frames", "72",
+    line = _launch_bench(2, "--full", "--rows", "--rows-batch", "16", "--rows-file", two, "--steps", "1", "--warmup", "0", "--frames", "72",
                          "--scaling", "strong")
     assert line["unit"] == "rows/s" and line["n_gpus"] == 2 and line["verify"]["rows_in_file"] == 72
     assert [r["frames"] for r in line["ranks"]["per_rank"]] == [32, 40]          # whole batches of 16: 2 + 3 (the last one short)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     proc = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--rows", "--rows-batch", "16", "--rows-file", one,
-                           "--steps", "1", "--warmup", "0", "--frames", "72", "--no-cpu-baseline"], cwd=root,
+                           "--steps", "1", "--warmup", "0", "--frames", "72", "--full", "--no-cpu-baseline"], cwd=root,
                           capture_output=True, text=True, timeout=600)
     assert proc.returncode == 0, proc.stderr[-3000:]
     assert open(two, "rb").read() == open(one, "rb").read()
@@ -2062,6 +2062,41 @@ def test_bench_rows_mode_two_ranks_write_the_single_rank_file(tmp_path):
         x = synth.synth_iq(1234, 1, 2, 262144, first_chunk=f)[0]
         ref = fx_oracle.pfb_xcorr(x[0], x[1], 4, 4096, window, 2.4e6, 1.4204e9, 0.0, "SPECTRUM")
         assert rel_err(np.asarray(back.rows[f]), ref) < TOL_VIS
+
+
+def test_bench_plain_run_dumps_the_last_steps_integration(tmp_path, plan_mod, torch):
+    """A plain bench.py run (no --full) times exactly --steps steps, reports ms_per_step, runs none of the --full extras, and
+    --dump-outputs writes the integration of its last timed step: the same, bit for bit, in a second run with the same
+    arguments, and the integration of the same frames through a plan of this process."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    frames, steps = 64, 3
+    dumped = []
+    for run in range(2):
+        out_dir = tmp_path / ("run%d" % run)
+        proc = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                               "--frames", str(frames), "--dump-outputs", str(out_dir)], cwd=root, capture_output=True, text=True,
+                              timeout=600)
+        assert proc.returncode == 0, proc.stderr[-3000:]
+        lines = [ln for ln in proc.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert line["steps"] == steps and line["warmup"] == 1 and line["roofline"]["launches"] == steps and line["full"] is False
+        assert line["ms_per_step"] > 0 and abs(frames * 262144 / (line["ms_per_step"] * 1e3) / line["value"] - 1) < 1e-2
+        assert line["cpu_baseline"] is None and line["verify"] is None and line["other_configs"] is None and line["power"] is None
+        vis = np.load(str(out_dir / "visibilities.npy"))
+        assert vis.dtype == np.float64 and vis.shape == (1, 4096, 2)
+        dumped.append(vis[..., 0] + 1j * vis[..., 1])
+    assert np.array_equal(dumped[0], dumped[1])
+    x = torch.empty((frames, 2, 262144), dtype=torch.complex64, device="cuda")
+    plan_mod.synth_fill(x, 1234, first_chunk=0)
+    with plan_mod.FxPlan(2, 4096, 4, 262144) as plan:
+        plan.set_delay(2.4e6, 1.4204e9, 0.0)
+        plan.fx_accumulate(x)
+        want = plan.finalize("SPECTRUM", 2.4e6)
+    assert np.abs(want).max() > 0 and rel_err(dumped[0], want) < TOL_VIS
 
 
 @pytest.mark.gpu

@@ -2,7 +2,7 @@
 """Developer aid: receiver bytes with DC removal on the plans that convert first (3+ antennas, more than four taps, 8192 channels,
 more than 4096 channels off the powers of two): F + X from bytes, and the conversion pass alone; 4.3 GB-equivalent of samples."""
 import sys, os, json
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from effex_amd.plan import FxPlan
 num_samp = 2 ** 18

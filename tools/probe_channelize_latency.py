@@ -5,7 +5,7 @@
     python tools/probe_channelize_latency.py
 """
 import sys, os, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from effex_amd import synth
 from effex_amd.plan import FxPlan

@@ -5,7 +5,7 @@ samples at several `--resolution` values, powers of two and not.
     [PROBE_MODE=CONTINUUM] python tools/probe_resolution_latency.py [4096,8192,...]
 """
 import sys, os, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from effex_amd import synth
 from effex_amd.correlator import Correlator, SyntheticSource

@@ -7,7 +7,7 @@ cd $root
 FXC_TOL_MEASURE=1 timeout 2400 python3 -m pytest tests -q -m gpu -x > $out/suite_measure.log 2>&1; echo "suite rc=$?" >> $out/suite_measure.log
 cp gpurun_out/observed_errors.json $out/observed_errors.json 2>/dev/null
 python3 -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1; echo "smoke rc=$?" >> $out/smoke.log
-timeout 900 python3 bench.py > $out/bench_a.json 2> $out/bench_a.err; echo "bench rc=$?" >> $out/bench_a.err
+timeout 900 python3 bench.py --full > $out/bench_a.json 2> $out/bench_a.err; echo "bench rc=$?" >> $out/bench_a.err
 var/copy_rate three > $out/copy_three.json 2>&1
 var/copy_rate > $out/copy_rate.log 2>&1
 bash tools/exp_8ant_cache.sh r06 128 > $out/exp_8ant_cache.log 2>&1

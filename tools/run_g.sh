@@ -8,7 +8,7 @@ cd $root
 FXC_TOL_MEASURE=1 timeout 3000 python3 -m pytest tests -q -m gpu > $out/suite_measure.log 2>&1; echo "suite rc=$?" >> $out/suite_measure.log
 cp gpurun_out/observed_errors.json $out/observed_errors.json 2>/dev/null
 python3 -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1; echo "smoke rc=$?" >> $out/smoke.log
-timeout 900 python3 bench.py > $out/bench.json 2> $out/bench.err; echo "bench rc=$?" >> $out/bench.err
+timeout 900 python3 bench.py --full > $out/bench.json 2> $out/bench.err; echo "bench rc=$?" >> $out/bench.err
 bash tools/collect_spec.sh r06g res1000 > $out/collect_res1000.log 2>&1
 bash tools/collect_spec.sh r06g res3000 > $out/collect_res3000.log 2>&1
 bash tools/collect_profiles.sh r06g "stream1" > $out/collect_profiles.log 2>&1
