@@ -39,6 +39,8 @@ FXC_MODE_CONTINUUM = 1
 FXC_IQ_C64 = 0
 FXC_IQ_U8 = 1
 FXC_IQ_C128 = 2
+FXC_PRODUCTS_CROSS = 0
+FXC_PRODUCTS_CROSS_AUTO = 1
 FXC_PATH_GENERIC = 0
 FXC_PATH_FUSED = 1
 FXC_PATH_STREAM = 2
@@ -76,6 +78,8 @@ SIGNATURES = {
     "fxc_spec_probe": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_char_p, _c.c_char_p, _c.c_int]),
     "fxc_last_error": (_c.c_char_p, [_vp]),
     "fxc_set_rot": (_c.c_int, [_vp, _vp]),
+    "fxc_set_products": (_c.c_int, [_vp, _c.c_int]),
+    "fxc_plan_products": (_c.c_int, [_vp, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
     "fxc_channelize": (_c.c_int, [_vp, _vp, _vp, _c.c_int64, _c.c_int]),
     "fxc_fx_accumulate": (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int]),
     "fxc_fx_rows": (_c.c_int, [_vp, _vp, _vp, _c.c_int64, _c.c_int, _c.c_int, _c.c_double]),

@@ -11,6 +11,7 @@ thread instead of a writer thread fed through a ``multiprocessing.Queue`` (``:13
 There is no CPU arithmetic path here: every F/X result comes from the HIP library.
 """
 import logging
+import os
 import time
 
 import numpy as np
@@ -304,7 +305,7 @@ class Correlator(object):
     def __init__(self, run_time=1, bandwidth=2.4e6, frequency=1.4204e9, num_samp=2 ** 18, nbins=2 ** 12,
                  gain=49.6, mode='SPECTRUM', loglevel='INFO',
                  source=None, device=0, max_num_samp=None, output_file=None, remove_dc=True, calibrate=True,
-                 output_format='csv', batch=1):
+                 output_format='csv', batch=1, autos=False):
         self.logger = logging.getLogger(__name__)
         self.logger.setLevel(getattr(logging, loglevel))
         self._max_num_samp = int(max_num_samp) if max_num_samp else Correlator._MAX_NUM_SAMP
@@ -317,6 +318,12 @@ class Correlator(object):
         if int(batch) < 1:
             raise ValueError("batch must be >= 1")
         self.batch = int(batch)
+        # autos=True: each antenna's autocorrelation beside the cross product -- `last_autos` after every row / integration,
+        # and in RUN one more file per antenna, <stem>_auto<a><ext>, in the output file's format.  They come from a plan of
+        # their own (fxc_set_products): the cross rows, and so the output file, stay exactly those of a run without autos.
+        self.autos = bool(autos)
+        self.last_autos = None          # (2, nbins) complex128 in SPECTRUM, (2,) in CONTINUUM / TEST
+        self._auto_fx_plan = None
         self._fx_plan = None
         self._f_plans = {}
         self._rot_key = None
@@ -428,6 +435,9 @@ class Correlator(object):
         if self._fx_plan is not None:
             self._fx_plan.close()
             self._fx_plan = None
+        if self._auto_fx_plan is not None:
+            self._auto_fx_plan.close()
+            self._auto_fx_plan = None
         for p in self._f_plans.values():
             p.close()
         self._f_plans = {}
@@ -566,10 +576,36 @@ class Correlator(object):
             self._rot_key = key
         return self._fx_plan
 
+    def _auto_plan(self):
+        """The two-antenna plan with autos (``FxPlan(autos=True)``) of the current shape; it needs no rot."""
+        n, nb = int(self.num_samp), int(self.nbins)
+        plan = self._auto_fx_plan
+        if plan is None or (plan.num_samp, plan.nchan) != (n, nb):
+            if plan is not None:
+                plan.close()
+            ntaps_w = int(len(self.window) / nb)
+            plan = self._auto_fx_plan = FxPlan(2, nb, ntaps_w, n, window=np.asarray(self.window)[:ntaps_w * nb],
+                                               device=self.device, autos=True)
+        return plan
+
+    def _autos_of(self, x, u8, remove_dc):
+        """The two antennas' autos of chunk pairs ``x`` ([k, 2, n] samples or [k, 2, n, 2] bytes, conditioned as the cross
+        rows are): [k, 2, nbins] complex128 in SPECTRUM, [k, 2] in CONTINUUM / TEST."""
+        plan = self._auto_plan()
+        if self.mode in ('CONTINUUM', 'TEST'):
+            mode = 'CONTINUUM'
+        else:
+            mode = 'SPECTRUM'
+        out = (plan.fx_rows_u8(x, mode, self.bandwidth, remove_dc=remove_dc) if u8
+               else plan.fx_rows(x, mode, self.bandwidth, remove_dc=remove_dc))
+        return np.asarray(out[:, plan.n_baselines:], dtype=np.complex128)
+
     def _pfb_xcorr(self):
         """effex.py:497-527 — one visibility from the chunk pair in ``gpu_iq_0`` / ``gpu_iq_1``."""
         plan = self._plan()
         u8 = getattr(self, "_u8_pair", None)
+        if u8 is not None and self.autos:
+            self.last_autos = self._autos_of(u8, True, self.remove_dc)[0]
         if u8 is not None:          # byte source: convert + de-mean + F+X in one device call
             if self.mode in ('CONTINUUM', 'TEST'):
                 out = self._row_buf((1, 1), np.complex128)
@@ -580,6 +616,8 @@ class Correlator(object):
         # _stage left there and nobody has looked at since is de-meaned on the device on the way (effex.py:394-395)
         dc = self._dc_pending
         pair = self._staged_pair()
+        if self.autos:
+            self.last_autos = self._autos_of(pair, False, dc)[0]
         if self.mode in ('CONTINUUM', 'TEST'):
             out = self._row_buf((1, 1), np.complex128)
             return plan.fx_rows(pair, 'CONTINUUM', self.bandwidth, remove_dc=dc, out=out)[0, 0]
@@ -618,6 +656,11 @@ class Correlator(object):
         plan.fx_accumulate(chunks)
         mode = 'CONTINUUM' if self.mode in ('CONTINUUM', 'TEST') else 'SPECTRUM'
         out = plan.finalize(mode, self.bandwidth)
+        if self.autos:
+            ap = self._auto_plan()
+            ap.acc_reset()
+            ap.fx_accumulate(chunks)
+            self.last_autos = ap.finalize(mode, self.bandwidth)[ap.n_baselines:]
         return out[0]
 
     # -- output (effex.py:667-696) ----------------------------------------------------------
@@ -636,6 +679,24 @@ class Correlator(object):
         return rowsink.BinSink(self.output_file, self._header_line(),
                                rowsink.spectrum_freqs(self.nbins, self.bandwidth, self.frequency) if spectrum else None,
                                int(self.nbins) if spectrum else 1, np.complex64 if spectrum else np.complex128)
+
+    def auto_file(self, a):
+        """Where RUN writes antenna ``a``'s autos: ``<stem>_auto<a><ext>`` beside the output file."""
+        stem, ext = os.path.splitext(self.output_file)
+        return '{}_auto{}{}'.format(stem, int(a), ext)
+
+    def _open_auto_sinks(self):
+        """One sink per antenna, of the output file's kind, with its header line and frequency row."""
+        spectrum = 'SPECTRUM' == self.mode
+        freqs = rowsink.spectrum_freqs(self.nbins, self.bandwidth, self.frequency) if spectrum else None
+        sinks = []
+        for a in range(2):
+            if 'bin' == self.output_format:
+                sinks.append(rowsink.BinSink(self.auto_file(a), self._header_line(), freqs, int(self.nbins) if spectrum else 1,
+                                             np.complex64 if spectrum else np.complex128))
+            else:
+                sinks.append(rowsink.CsvSink(self.auto_file(a), self._header_line(), freqs))
+        return sinks
 
     def _write_row(self, fh, vis):
         np.savetxt(fh, [np.asarray(vis, dtype=np.complex128)], delimiter=',')
@@ -674,7 +735,7 @@ class Correlator(object):
         self._gpu_iq = [self._pair_buf[0, 0], self._pair_buf[0, 1]]
         self._dc_pending = bool(self.remove_dc)
 
-    def _run_batched(self, first_pair, sink, fh):
+    def _run_batched(self, first_pair, sink, fh, auto_sinks=()):
         """The RUN state for ``batch`` > 1: chunk pairs go ``batch`` at a time through a three-slot ``FxPipeline`` -- the
         source fills a pinned slot in place (``IQSource.read_into``), the copy in, the F+X call and the rows' copy out of
         successive batches overlap, and with the binary sidecar the rows land in a mapped window of the file.  Same rows
@@ -690,6 +751,12 @@ class Correlator(object):
         def emit(out):          # out: [k, 1, nchan] complex64 or [k, 1] complex128
             for row in out[:, 0]:
                 self._write_row(fh, row)
+
+        def emit_autos(batch):
+            autos = self._autos_of(batch, u8, self.remove_dc)
+            self.last_autos = autos[-1]
+            for a, s in enumerate(auto_sinks):
+                s.write_rows(autos[:, a])
 
         def fill(view, pair):
             """view[0] from ``pair`` when there is one, the rest from the source; returns the chunk pairs filled."""
@@ -728,6 +795,8 @@ class Correlator(object):
                     k = job.result()
                     if k < K:
                         break
+                    if auto_sinks:
+                        emit_autos(view)
                     pipe.submit()
             except BaseException:
                 # the filler may sit in a blocking read (a socket source) that writes into a pinned slot of the pipe:
@@ -749,6 +818,8 @@ class Correlator(object):
                 rows += drain()
             if k:               # the stream ended inside a batch
                 tail = view[:k]
+                if auto_sinks:
+                    emit_autos(tail)
                 out = (plan.fx_rows_u8(tail, mode, self.bandwidth, remove_dc=self.remove_dc) if u8
                        else plan.fx_rows(tail, mode, self.bandwidth, remove_dc=self.remove_dc))
                 if sink is not None:
@@ -763,6 +834,7 @@ class Correlator(object):
         pair calibrates the delay (unless ``calibrate=False``), every further pair writes one csv row."""
         rows = 0
         fh = sink = None
+        auto_sinks = []
         try:
             while True:
                 if 'OFF' == self.state:
@@ -773,6 +845,8 @@ class Correlator(object):
                     else:
                         self._write_metadata()
                         fh = open(self.output_file, 'a')
+                    if self.autos:
+                        auto_sinks = self._open_auto_sinks()
                     self.start_time = time.time()
                     self.state = 'CALIBRATE' if self.calibrate else 'RUN'
                 elif self.state in ('CALIBRATE', 'RUN'):
@@ -781,7 +855,7 @@ class Correlator(object):
                         self.state = 'SHUTDOWN'
                         continue
                     if 'RUN' == self.state and self.batch > 1 and self.mode not in ['TEST']:
-                        rows += self._run_batched(pair, sink, fh)      # to the end of the stream
+                        rows += self._run_batched(pair, sink, fh, auto_sinks)      # to the end of the stream
                         self.state = 'SHUTDOWN'
                         continue
                     self._stage(pair)
@@ -795,6 +869,8 @@ class Correlator(object):
                         sink.write(self._run_task())
                     else:
                         self._write_row(fh, self._run_task())
+                    for a, s in enumerate(auto_sinks):
+                        s.write(self.last_autos[a])
                     rows += 1
                 elif 'SHUTDOWN' == self.state:
                     self.close()
@@ -805,4 +881,6 @@ class Correlator(object):
                 fh.close()
             if sink is not None:
                 sink.close()
+            for s in auto_sinks:
+                s.close()
         return rows

@@ -208,7 +208,8 @@ FX_HD int sample_offset(int j, int r) { return (kN - 1) - j - 256 * r; }
 
 // phase 1a for a frame in ring slot PH: 4-tap FIR (taps t = 0..3 on frames i, i-1, i-2, i-3, summed
 // in that order); result left in v[r]
-template <int PH>
+// G: branches per group (the kernel's AUTOS variant takes 2: 16 VGPRs fewer quads in flight, for its power sums)
+template <int PH, int G = kFirGroup>
 FX_HD void phase1_fir(const State& s, const f4* win, int tid, cf (&v)[16]) {
     const int j = tid & 255;
     const cf (&x0)[16] = s.h[PH];
@@ -218,7 +219,7 @@ FX_HD void phase1_fir(const State& s, const f4* win, int tid, cf (&v)[16]) {
     // software-pipelined in groups of kFirGroup branches: the window quads of group g + 1 are requested from LDS
     // before group g is computed, so only the first ds_read latency is exposed (2 * kFirGroup * 4 VGPRs of quads in
     // flight at the kernel's point of highest register pressure)
-    constexpr int G = kFirGroup, NG = 16 / G;
+    constexpr int NG = 16 / G;
     f4 w[2][G];
 #pragma unroll
     for (int q = 0; q < G; ++q) w[0][q] = win[q * 256 + j];
@@ -246,10 +247,35 @@ FX_HD void phase1_fir(const State& s, const f4* win, int tid, cf (&v)[16]) {
 // exchange 1 as soon as it exists -- the stores are bound by the LDS write path (64 KiB at ~85 B/clk per CU), and the
 // 72 + 60 vector instructions of the butterflies and twiddles run in its shadow instead of in front of barrier B0.
 // Call after dft16_a(v).
+// LEAN_TW (the kernel's AUTOS variant): of the fifteen twiddles only w4096^(j k1) for k1 = 1, 2, 4, 8 live in registers across
+// frames -- the others are their products, formed here per frame (11 complex multiplies, shared subexpressions; the powers pass
+// through an empty asm so that the products cannot be hoisted out of the frame loop, where they would take the registers back)
+// -- and the 22 VGPRs so freed hold the variant's power sums.
+FX_HD cf tw1_of(const cf (&pw2)[4], int k1) {
+    cf w = mk(1.f, 0.f);
+    bool have = false;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        if (k1 & (1 << b)) {
+            w = have ? cmul(w, pw2[b]) : pw2[b];
+            have = true;
+        }
+    }
+    return w;
+}
+
+template <bool LEAN_TW = false>
 FX_HD void phase1_finish_store(const State& s, cf (&v)[16], cf* region, int tid) {
     cf* mine = region + (tid >> 8) * kRegion + (tid & 255);
+    cf pw2[4] = {s.tw1[1], s.tw1[2], s.tw1[4], s.tw1[8]};
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (LEAN_TW) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b) asm volatile("" : "+v"(pw2[b].x), "+v"(pw2[b].y));
+    }
+#endif
     dft16_b_stream(v, [&](int k1, cf val) {
-        if (k1 > 0) val = cmul(val, s.tw1[k1]);
+        if (k1 > 0) val = cmul(val, LEAN_TW ? tw1_of(pw2, k1) : s.tw1[k1]);
         mine[k1 * kRowPitch] = val;
     });
 }

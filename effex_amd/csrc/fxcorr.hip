@@ -101,6 +101,7 @@ namespace {
 constexpr double kTwoPi = 6.283185307179586476925286766559;
 constexpr int kMaxTaps = 32;         // cusignal ships 8x8 / 16x16 / 32x32 channeliser kernels only
 constexpr int kMaxXAnt = 64;         // antennas the F-only + X-engine route takes (fxc_plan_create's own limit)
+constexpr int kMaxAutoAnt = 8;       // antennas fxc_set_products gives autos to (xengine_kernel<A, true>)
 constexpr int kMaxLdsFftN = 16384;   // 128 KiB of complex64 in LDS
 constexpr int kBluPrimePerRatio = 45;  // prime factors beyond 45 nfft / N: the chirp-z form (see pfb_fft_mixed_kernel, BLU)
 constexpr int kBluMaxNfft = 10240;    // two chirp-z rows in the 160 KiB of LDS: up to 5120 channels
@@ -447,7 +448,7 @@ static int plan_build(fxc_plan* p, const double* window, int force_path) {
     FXC_HIP(p, hipMalloc(&p->d_rot, rot.size() * sizeof(cd)));
     FXC_HIP(p, hipMemcpy(p->d_rot, rot.data(), rot.size() * sizeof(cd), hipMemcpyHostToDevice));
 
-    const size_t acc_n = (size_t)p->n_base * N;
+    const size_t acc_n = (size_t)acc_capacity(p);
     FXC_HIP(p, hipMalloc(&p->d_acc, acc_n * sizeof(cd)));
     FXC_HIP(p, hipMemset(p->d_acc, 0, acc_n * sizeof(cd)));
     FXC_HIP(p, hipMalloc(&p->d_sums, (acc_n + 1) * sizeof(cd)));
@@ -501,6 +502,8 @@ static int plan_build(fxc_plan* p, const double* window, int force_path) {
                                        hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
         FXC_HIP(p, hipFuncSetAttribute(reinterpret_cast<const void*>(&fx_fused4096_kernel<false, true, true>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes + kDckLdsBytes));
+        FXC_HIP(p, hipFuncSetAttribute(reinterpret_cast<const void*>(&fx_fused4096_kernel<false, false, false, true>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes + kAutoLdsBytes));
     }
     p->small = small_shape && p->n_ant == 2 && p->path == FXC_PATH_TILED;
     p->small_f = small_n && force_path != FXC_PATH_GENERIC;
@@ -738,6 +741,7 @@ int fxc_plan_create(fxc_plan** out, int device, int n_ant, int nchan, int ntaps,
     p->device = device;
     p->n_ant = n_ant;
     p->n_base = n_ant * (n_ant - 1) / 2;
+    p->n_prod = p->n_base;
     p->nchan = nchan;
     p->ntaps = ntaps;
     p->num_samp = num_samp;
@@ -848,6 +852,53 @@ int fxc_set_rot(fxc_plan* p, const double* rot_re_im) {
     // ordered after any queued finish kernel that still reads the old table
     FXC_HIP(p, hipStreamSynchronize(p->stream));
     FXC_HIP(p, hipMemcpy(p->d_rot, rot_re_im, (size_t)p->nchan * sizeof(cd), hipMemcpyHostToDevice));
+    return FXC_OK;
+}
+
+int fxc_set_products(fxc_plan* p, int products) {
+    if (!p) return fail(p, FXC_ERR_ARG, "NULL plan");
+    if (products != FXC_PRODUCTS_CROSS && products != FXC_PRODUCTS_CROSS_AUTO) return fail(p, FXC_ERR_ARG, "bad products %d", products);
+    const bool autos = products == FXC_PRODUCTS_CROSS_AUTO;
+    if (autos && (p->n_ant < 2 || p->n_ant > kMaxAutoAnt))
+        return fail(p, FXC_ERR_UNSUPPORTED, "autos are produced for 2 .. %d antennas, not %d", kMaxAutoAnt, p->n_ant);
+    // the accumulator, a queued result and a pipe's slots are all laid out in rows of the current products
+    if (p->live_pipes) return fail(p, FXC_ERR_STATE, "an fxc_pipe uses the plan");
+    if (p->res_head != p->res_tail) return fail(p, FXC_ERR_STATE, "finalize results outstanding");
+    if (p->spectra_count > 0.0 || p->pend.valid) return fail(p, FXC_ERR_STATE, "the accumulator is not empty");
+    if (autos == p->autos) return FXC_OK;
+    FXC_DEVICE(p, p->device);
+    if (autos && !p->x_resident_auto) {
+        // one-wave workgroups resident per CU, bounded by the register file as for the cross-only X-engines (plan_build)
+        const void* xfn = nullptr;
+        switch (p->n_ant) {
+            case 2: xfn = reinterpret_cast<const void*>(&xengine_kernel<2, true>); break;
+            case 3: xfn = reinterpret_cast<const void*>(&xengine_kernel<3, true>); break;
+            case 4: xfn = reinterpret_cast<const void*>(&xengine_kernel<4, true>); break;
+            case 5: xfn = reinterpret_cast<const void*>(&xengine_kernel<5, true>); break;
+            case 6: xfn = reinterpret_cast<const void*>(&xengine_kernel<6, true>); break;
+            case 7: xfn = reinterpret_cast<const void*>(&xengine_kernel<7, true>); break;
+            default: xfn = reinterpret_cast<const void*>(&xengine_kernel<8, true>); break;
+        }
+        int per_cu = 0;
+        FXC_HIP(p, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, xfn, kXThreads, 0));
+        hipFuncAttributes fa;
+        FXC_HIP(p, hipFuncGetAttributes(&fa, xfn));
+        const int regs = std::max(8, (fa.numRegs + 7) / 8 * 8);
+        per_cu = std::min(per_cu, 4 * std::min(8, 512 / regs));
+        p->x_resident_auto = (int64_t)std::max(per_cu, 1) * p->cu_count;
+    }
+    // the rows past the cross rows start from zero (they were never written, or an earlier autos plan cleared them)
+    FXC_HIP(p, hipMemsetAsync(p->d_acc, 0, (size_t)acc_capacity(p) * sizeof(cd), p->stream));
+    p->autos = autos;
+    p->n_prod = p->n_base + (autos ? p->n_ant : 0);
+    p->sums_valid = false;          // reduced sums of the other layout
+    return FXC_OK;
+}
+
+int fxc_plan_products(const fxc_plan* p, int* products, int* n_rows) {
+    if (!p) return fail(p, FXC_ERR_ARG, "NULL plan");
+    if (products) *products = p->autos ? FXC_PRODUCTS_CROSS_AUTO : FXC_PRODUCTS_CROSS;
+    if (n_rows) *n_rows = p->n_prod;
     return FXC_OK;
 }
 
@@ -1021,7 +1072,7 @@ int fxc_reduce(fxc_plan* p, void* rccl_comm, int root) {
     RcclApi* api = rccl_api();
     if (!api->handle) return fail(p, FXC_ERR_COMM, "%s", api->error.c_str());
     // raw float64 sums + the spectra count, in place, ordered on the plan's stream behind the export
-    const size_t count = 2 * ((size_t)p->n_base * p->nchan + 1);
+    const size_t count = 2 * ((size_t)p->n_prod * p->nchan + 1);
     const ncclResult_t r = root < 0 ? api->all_reduce(p->d_sums, p->d_sums, count, ncclFloat64, ncclSum, c->comm, p->stream)
                                     : api->reduce(p->d_sums, p->d_sums, count, ncclFloat64, ncclSum, root, c->comm, p->stream);
     if (r != ncclSuccess) return rccl_fail(p, api, root < 0 ? "ncclAllReduce" : "ncclReduce", r);
@@ -1077,7 +1128,7 @@ int pinned_rows_out(fxc_plan* p, void** out, int* mem_kind, int64_t n_chunks, in
         *mem_kind = FXC_MEM_DEVICE;         // (the entry's own argument checks answer)
         return FXC_OK;
     }
-    const size_t ob = mode == FXC_MODE_SPECTRUM ? (size_t)n_chunks * p->n_base * p->nchan * sizeof(cf) : (size_t)n_chunks * p->n_base * sizeof(cd);
+    const size_t ob = mode == FXC_MODE_SPECTRUM ? (size_t)n_chunks * p->n_prod * p->nchan * sizeof(cf) : (size_t)n_chunks * p->n_prod * sizeof(cd);
     void* d = pinned_device_ptr(*out, ob);
     if (!d) return fail(p, FXC_ERR_ARG, "`out` of FXC_MEM_DEVICE_TO_PINNED (%zu bytes) is not inside memory from fxc_host_alloc", ob);
     *out = d;
@@ -1099,8 +1150,8 @@ int fxc_fx_rows(fxc_plan* p, const void* x, void* out, int64_t n_chunks, int mem
     if (mem_kind == FXC_MEM_DEVICE) return fx_rows_dev(p, static_cast<const cf*>(x), out, n_chunks, mode, bandwidth);
     if (mem_kind != FXC_MEM_HOST) return fail(p, FXC_ERR_ARG, "bad mem_kind %d", mem_kind);
     const size_t xb = (size_t)n_chunks * p->n_ant * p->num_samp * sizeof(cf);
-    const size_t ob = mode == FXC_MODE_SPECTRUM ? (size_t)n_chunks * p->n_base * p->nchan * sizeof(cf)
-                                                : (size_t)n_chunks * p->n_base * sizeof(cd);
+    const size_t ob = mode == FXC_MODE_SPECTRUM ? (size_t)n_chunks * p->n_prod * p->nchan * sizeof(cf)
+                                                : (size_t)n_chunks * p->n_prod * sizeof(cd);
     return with_host_staging(p, x, xb, out, ob, [&](const cf* dx, void* dout) {
         return fx_rows_dev(p, dx, dout, n_chunks, mode, bandwidth);
     });
@@ -1110,7 +1161,7 @@ int fxc_acc_reset(fxc_plan* p) {
     if (!p) return fail(p, FXC_ERR_ARG, "NULL plan");
     FXC_DEVICE(p, p->device);
     p->pend.valid = false;                  // rows not folded yet are simply dropped
-    FXC_HIP(p, hipMemsetAsync(p->d_acc, 0, (size_t)p->n_base * p->nchan * sizeof(cd), p->stream));
+    FXC_HIP(p, hipMemsetAsync(p->d_acc, 0, (size_t)p->n_prod * p->nchan * sizeof(cd), p->stream));
     p->spectra_count = 0.0;
     return FXC_OK;
 }
@@ -1138,15 +1189,15 @@ int finalize_enqueue(fxc_plan* p, const cd* sums_src, int mode, double bandwidth
                     fxc_plan::kResSlots);
     if (!sums_src && !(p->spectra_count > 0.0)) return fail(p, FXC_ERR_STATE, "nothing accumulated");
     const int slot = (int)(p->res_head % fxc_plan::kResSlots);
-    const int64_t n = (int64_t)p->n_base * p->nchan;
-    const size_t bytes = mode == FXC_MODE_SPECTRUM ? (size_t)n * sizeof(cd) : (size_t)p->n_base * sizeof(cd);
+    const int64_t n = (int64_t)p->n_prod * p->nchan;
+    const size_t bytes = mode == FXC_MODE_SPECTRUM ? (size_t)n * sizeof(cd) : (size_t)p->n_prod * sizeof(cd);
     // small results are written into the pinned slot by the finishing kernel itself; large ones go through device
     // memory and a copy on a side stream, off the F+X stream's critical path
     const bool big = bytes > res_direct_bytes();
     if (big && !p->s_copy) {
         FXC_HIP(p, hipStreamCreateWithFlags(&p->s_copy, hipStreamNonBlocking));
         FXC_HIP(p, hipEventCreateWithFlags(&p->ev_fin, hipEventDisableTiming));
-        for (int k = 0; k < fxc_plan::kResSlots; ++k) FXC_HIP(p, hipMalloc(&p->d_res_big[k], (size_t)n * sizeof(cd)));
+        for (int k = 0; k < fxc_plan::kResSlots; ++k) FXC_HIP(p, hipMalloc(&p->d_res_big[k], (size_t)acc_capacity(p) * sizeof(cd)));
     }
     cd* out = big ? p->d_res_big[slot] : p->d_res[slot];
     cd* const user_mapped = (user_out && !big) ? static_cast<cd*>(pinned_device_ptr(user_out, bytes)) : nullptr;
@@ -1160,7 +1211,7 @@ int finalize_enqueue(fxc_plan* p, const cd* sums_src, int mode, double bandwidth
         if (mode == FXC_MODE_CONTINUUM) {
             // into a buffer of its own: d_sums may hold reduced sums (fxc_reduce) that fxc_finalize_sums(plan, NULL) has yet
             // to read, and only fxc_reduce makes that copy valid
-            if (!p->d_cont) FXC_HIP(p, hipMalloc(&p->d_cont, ((size_t)n + 1) * sizeof(cd)));
+            if (!p->d_cont) FXC_HIP(p, hipMalloc(&p->d_cont, ((size_t)acc_capacity(p) + 1) * sizeof(cd)));
             fin.sums = p->d_cont;
             fin.out = nullptr;
             sums_src = p->d_cont;
@@ -1174,11 +1225,12 @@ int finalize_enqueue(fxc_plan* p, const cd* sums_src, int mode, double bandwidth
         const int rc = flush_pending(p);
         if (rc) return rc;
         hipExtLaunchKernelGGL(finalize_spectrum_kernel, dim3(grid_for(n, 256, p->cu_count)), dim3(256), 0, p->stream, nullptr,
-                              big ? nullptr : p->ev_res[slot], 0, sums_src, out, p->d_rot, p->nchan, p->n_base);
+                              big ? nullptr : p->ev_res[slot], 0, sums_src, out, p->d_rot, p->nchan, p->n_prod, p->n_base);
     }
     if (mode == FXC_MODE_CONTINUUM)
-        hipExtLaunchKernelGGL(finalize_continuum_kernel, dim3(p->n_base), dim3(256), 0, p->stream, nullptr,
-                              big ? nullptr : p->ev_res[slot], 0, sums_src, out, p->d_rot, p->nchan, p->n_base, 1.0 / bandwidth);
+        hipExtLaunchKernelGGL(finalize_continuum_kernel, dim3(p->n_prod), dim3(256), 0, p->stream, nullptr,
+                              big ? nullptr : p->ev_res[slot], 0, sums_src, out, p->d_rot, p->nchan, p->n_prod, 1.0 / bandwidth,
+                              p->n_base);
     FXC_HIP(p, hipGetLastError());
     if (big) {
         FXC_HIP(p, hipEventRecord(p->ev_fin, p->stream));
@@ -1318,10 +1370,10 @@ namespace {
 int fx_u8_dev(fxc_plan* p, const unsigned char* x8, void* out, int64_t n_chunks, int mode, double bandwidth, int remove_dc,
               bool rows) {
     constexpr int kSlices = 32;
-    const size_t row_elems = mode == FXC_MODE_SPECTRUM ? (size_t)p->n_base * p->nchan * sizeof(cf) : (size_t)p->n_base * sizeof(cd);
+    const size_t row_elems = mode == FXC_MODE_SPECTRUM ? (size_t)p->n_prod * p->nchan * sizeof(cf) : (size_t)p->n_prod * sizeof(cd);
     // chunks per pass: at most 65535 streams (a grid dimension of the conditioning kernels), and plans without the
     // fused ingest convert a pass into a complex64 staging buffer that stays within the workspace target
-    const bool fused_in = p->n_ant == 2 && !p->prefilter && (p->path == FXC_PATH_FUSED || (p->path == FXC_PATH_TILED && (p->tiled_ring || p->small || p->x8192)) ||
+    const bool fused_in = p->n_ant == 2 && !p->autos && !p->prefilter && (p->path == FXC_PATH_FUSED || (p->path == FXC_PATH_TILED && (p->tiled_ring || p->small || p->x8192)) ||
                                                               (p->path == FXC_PATH_GENERIC && p->mixed_xf && FXC_DEV_ENV_INT("FXC_MIXED_U8", 1)));
     int64_t per_pass = std::min<int64_t>(16384, 65535 / p->n_ant);
     if (!fused_in) per_pass = std::min<int64_t>(per_pass, ws_target() / ((int64_t)p->n_ant * p->num_samp * (int64_t)sizeof(cf)));
@@ -1407,8 +1459,8 @@ int fx_u8_entry(fxc_plan* p, const void* iq_u8, void* out, int64_t n_chunks, int
     if (mem_kind != FXC_MEM_HOST) return fail(p, FXC_ERR_ARG, "bad mem_kind %d", mem_kind);
     const size_t xb = (size_t)n_chunks * p->n_ant * p->num_samp * 2;
     const size_t ob = !rows ? 0
-                            : (mode == FXC_MODE_SPECTRUM ? (size_t)n_chunks * p->n_base * p->nchan * sizeof(cf)
-                                                         : (size_t)n_chunks * p->n_base * sizeof(cd));
+                            : (mode == FXC_MODE_SPECTRUM ? (size_t)n_chunks * p->n_prod * p->nchan * sizeof(cf)
+                                                         : (size_t)n_chunks * p->n_prod * sizeof(cd));
     return with_host_staging(p, iq_u8, xb, out, ob, [&](const cf* dx, void* dout) {
         return fx_u8_dev(p, reinterpret_cast<const unsigned char*>(dx), dout, n_chunks, mode, bandwidth, remove_dc, rows);
     });
@@ -1424,7 +1476,7 @@ namespace {
 int fx_cond_dev(fxc_plan* p, const void* x, void* out, int64_t n_chunks, int mode, double bandwidth, int fmt, int remove_dc,
                 bool rows, bool x_is_scratch) {
     const size_t in_elem = fmt == FXC_IQ_C128 ? sizeof(cd) : sizeof(cf);
-    const size_t row_bytes = mode == FXC_MODE_SPECTRUM ? (size_t)p->n_base * p->nchan * sizeof(cf) : (size_t)p->n_base * sizeof(cd);
+    const size_t row_bytes = mode == FXC_MODE_SPECTRUM ? (size_t)p->n_prod * p->nchan * sizeof(cf) : (size_t)p->n_prod * sizeof(cd);
     const bool in_place = x_is_scratch && fmt == FXC_IQ_C64;
     // streams per pass: the stream index rides in grid.y, and the staging buffer stays within the workspace target
     int64_t per_pass = 65535 / p->n_ant;
@@ -1485,8 +1537,8 @@ int fx_iq_entry(fxc_plan* p, const void* x, void* out, int64_t n_chunks, int mem
     if (mem_kind != FXC_MEM_HOST) return fail(p, FXC_ERR_ARG, "bad mem_kind %d", mem_kind);
     const size_t xb = (size_t)n_chunks * p->n_ant * p->num_samp * (fmt == FXC_IQ_C128 ? sizeof(cd) : sizeof(cf));
     const size_t ob = !rows ? 0
-                            : (mode == FXC_MODE_SPECTRUM ? (size_t)n_chunks * p->n_base * p->nchan * sizeof(cf)
-                                                         : (size_t)n_chunks * p->n_base * sizeof(cd));
+                            : (mode == FXC_MODE_SPECTRUM ? (size_t)n_chunks * p->n_prod * p->nchan * sizeof(cf)
+                                                         : (size_t)n_chunks * p->n_prod * sizeof(cd));
     return with_host_staging(p, x, xb, out, ob, [&](const cf* dx, void* dout) {
         return fx_cond_dev(p, dx, dout, n_chunks, mode, bandwidth, fmt, remove_dc, rows, true);
     });
@@ -1675,8 +1727,8 @@ int fxc_pipe_create_iq(fxc_pipe** out, fxc_plan* p, int64_t chunks_per_batch, in
     q->fmt = fmt;
     q->remove_dc = remove_dc;
     q->in_bytes = (size_t)chunks_per_batch * p->n_ant * p->num_samp * (fmt == FXC_IQ_U8 ? 2 : (fmt == FXC_IQ_C128 ? sizeof(cd) : sizeof(cf)));
-    q->out_bytes = mode == FXC_MODE_SPECTRUM ? (size_t)chunks_per_batch * p->n_base * p->nchan * sizeof(cf)
-                                             : (size_t)chunks_per_batch * p->n_base * sizeof(cd);
+    q->out_bytes = mode == FXC_MODE_SPECTRUM ? (size_t)chunks_per_batch * p->n_prod * p->nchan * sizeof(cf)
+                                             : (size_t)chunks_per_batch * p->n_prod * sizeof(cd);
     q->slots.resize((size_t)depth);
     hipError_t e = hipStreamCreateWithFlags(&q->s_in, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&q->s_out, hipStreamNonBlocking);

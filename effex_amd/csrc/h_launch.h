@@ -329,25 +329,33 @@ int fold_max_splits(int64_t row_len) { return (int)std::max<int64_t>(1, std::min
 int fold_splits(int64_t n_rows, int64_t row_len) {
     return (int)std::max<int64_t>(1, std::min<int64_t>(fold_max_splits(row_len), n_rows / (8 * kFoldPhases)));
 }
-int64_t fold_part_bytes(const fxc_plan* p) { return (int64_t)fold_max_splits((int64_t)p->n_base * p->nchan) * p->n_base * p->nchan * (int64_t)sizeof(cd); }
+int64_t fold_part_bytes(const fxc_plan* p) { return (int64_t)fold_max_splits((int64_t)p->n_prod * p->nchan) * p->n_prod * p->nchan * (int64_t)sizeof(cd); }
 
 const FoldFinish kNoFinish = {nullptr, nullptr, nullptr, 0.0, 0};
 
-// acc[p][bin] += sum of the raw rows [n_base][nchan], and `fin` for every element: two launches, one when the rows are few
+// `fin` with the plan's auto rows marked (they follow the n_base cross rows of the accumulator)
+FoldFinish with_autos(const fxc_plan* p, const FoldFinish& fin) {
+    FoldFinish f = fin;
+    f.auto_from = p->n_prod > p->n_base ? (int64_t)p->n_base * p->nchan : 0;
+    return f;
+}
+
+// acc[p][bin] += sum of the raw rows [n_prod][nchan], and `fin` for every element: two launches, one when the rows are few
 // `done`: an event to complete with the last kernel (it rides on that dispatch: no packet of its own in the stream)
-int fold_rows(fxc_plan* p, const cf* raw, cd* part, int64_t n_rows, int layout, const FoldFinish& fin, hipEvent_t done = nullptr) {
-    const int64_t row_len = (int64_t)p->n_base * p->nchan;
+int fold_rows(fxc_plan* p, const cf* raw, cd* part, int64_t n_rows, int layout, const FoldFinish& fin_in, hipEvent_t done = nullptr) {
+    const FoldFinish fin = with_autos(p, fin_in);
+    const int64_t row_len = (int64_t)p->n_prod * p->nchan;
     const unsigned cols = (unsigned)((row_len + 255) / 256);
     const int splits = fold_splits(n_rows, row_len);
     if (splits == 1) {
         hipExtLaunchKernelGGL(fold_finish_kernel<cf>, dim3(cols), dim3(256 * kFoldPhases), 0, p->stream, nullptr, done, 0, raw,
-                              n_rows, p->d_acc, p->nchan, p->n_base, layout, fin);
+                              n_rows, p->d_acc, p->nchan, p->n_prod, layout, fin);
     } else {
         hipLaunchKernelGGL(fold_partial_kernel, dim3(cols, splits), dim3(256 * kFoldPhases), 0, p->stream, raw, part, row_len,
                            n_rows, splits);
         // the partials are in the rows' own layout
         hipExtLaunchKernelGGL(fold_finish_kernel<cd>, dim3(cols), dim3(256 * kFoldPhases), 0, p->stream, nullptr, done, 0,
-                              (const cd*)part, (int64_t)splits, p->d_acc, p->nchan, p->n_base, layout, fin);
+                              (const cd*)part, (int64_t)splits, p->d_acc, p->nchan, p->n_prod, layout, fin);
     }
     FXC_HIP(p, hipGetLastError());
     return FXC_OK;
@@ -361,9 +369,9 @@ int flush_pending(fxc_plan* p, const FoldFinish* fin, hipEvent_t done) {
         return fold_rows(p, p->pend.raw, p->pend.part, p->pend.n_rows, p->pend.layout, fin ? *fin : kNoFinish, done);
     }
     if (fin) {
-        const int64_t n = (int64_t)p->n_base * p->nchan;
+        const int64_t n = (int64_t)p->n_prod * p->nchan;
         hipExtLaunchKernelGGL(acc_finish_kernel, dim3(grid_for(n, 256, p->cu_count)), dim3(256), 0, p->stream, nullptr, done, 0,
-                              p->d_acc, p->nchan, p->n_base, *fin);
+                              p->d_acc, p->nchan, p->n_prod, with_autos(p, *fin));
         FXC_HIP(p, hipGetLastError());
     } else if (done) {
         FXC_HIP(p, hipEventRecord(done, p->stream));
@@ -405,7 +413,8 @@ LeadRows fused_lead(const fxc_plan* p, int64_t nc) {
     lr.first_chunk = sp.n_full;
     lr.n_frames = sp.n_tail * p->n_pts;
     lr.n_pts = p->n_pts;
-    lr.offset = nc * (int64_t)fxc::fused::kN;
+    lr.n_prod = p->autos && p->nchan == fxc::fused::kN ? p->n_prod : 1;    // (fused_autos: rows of [3][kN])
+    lr.offset = nc * (int64_t)fxc::fused::kN * lr.n_prod;
     lr.grid = fused_grid(p, nc);
     return lr;
 }
@@ -444,6 +453,9 @@ int launch_fused(fxc_plan* p, const cf* x, int64_t n_pairs, cf* out, bool spec_o
     else if (spec_out)      // (`unit` carries the stream pairs per chunk here)
         FXC_FUSED_LAUNCH((fx_fused4096_kernel<true, false>), kLdsBytes, x, num_samp, p->n_pts, n_pairs, p->d_win4, p->d_tw1,
                          p->d_tw2, out, stamps, (const cf*)nullptr, seg, p->n_ant / 2, 1);
+    else if (p->autos && p->nchan == kN)      // (plans with autos: rows of [3][kN], fx_fused4096_kernel AUTOS)
+        FXC_FUSED_LAUNCH((fx_fused4096_kernel<false, false, false, true>), kLdsBytes + kAutoLdsBytes, x, num_samp, p->n_pts, n_pairs, p->d_win4,
+                         p->d_tw1, p->d_tw2, out, stamps, (const cf*)nullptr, seg, (int)unit, rows_are_chunks ? 1 : 0);
     else
         FXC_FUSED_LAUNCH((fx_fused4096_kernel<false, false>), kLdsBytes, x, num_samp, p->n_pts, n_pairs, p->d_win4, p->d_tw1,
                          p->d_tw2, out, stamps, (const cf*)nullptr, seg, (int)unit, rows_are_chunks ? 1 : 0);
@@ -492,7 +504,7 @@ int fused_layout(const fxc_plan* p) { return p->n_ant == 2 ? 1 : (p->path == FXC
 int64_t fused_chunks_per_pass(const fxc_plan* p, int64_t n_chunks, int64_t* spec_bytes, int64_t* raw_bytes) {
     // (3 and more antennas: one raw row per chunk and frame range at most, x_ranges)
     const int64_t xr = x_ranges(p, 1);
-    const int64_t raw_per_chunk = (int64_t)p->n_base * p->nchan * (int64_t)sizeof(cf) * xr;
+    const int64_t raw_per_chunk = (int64_t)p->n_prod * p->nchan * (int64_t)sizeof(cf) * xr;
     const int64_t spec_per_chunk = p->n_ant == 2 ? 0 : (int64_t)p->n_ant * p->n_pts * p->nchan * (int64_t)sizeof(cf);
     int64_t cb = ws_target() / (raw_per_chunk + spec_per_chunk);
     if (cb < 1) cb = 1;

@@ -52,6 +52,10 @@ struct SpecKernel;      // h_rtc.h
 struct fxc_plan {
     int device = 0, cu_count = 0;
     int n_ant = 0, n_base = 0, nchan = 0, ntaps = 0;
+    // products (fxc_set_products): the n_base cross rows of a result, then with autos one row per antenna -- n_prod rows
+    bool autos = false;
+    int n_prod = 0;
+    int64_t x_resident_auto = 0;   // workgroups of xengine_kernel<n_ant, true> the device holds at once (set with the autos)
     int64_t num_samp = 0, n_pts = 0;
     int path = FXC_PATH_GENERIC;
     bool pow2 = false;
@@ -112,9 +116,9 @@ struct fxc_plan {
     int64_t x_resident = 0;        // workgroups of the X-engine kernel the device holds at once
     bool x_mfma = false;           // more than 8 antennas: xengine_mfma_kernel (k_xmfma.h)
     int64_t fused_seg = 1;         // chunks per round-robin segment of the fused kernel (fx_fused4096.h::RangeWalk)
-    cd* d_acc = nullptr;           // [n_base*nchan]
-    cd* d_sums = nullptr;          // [n_base*nchan + 1]
-    cd* d_cont = nullptr;          // [n_base*nchan + 1] the export a CONTINUUM finalize of the accumulator reduces (lazy)
+    cd* d_acc = nullptr;           // [n_prod*nchan] (allocated for the autos too: acc_capacity)
+    cd* d_sums = nullptr;          // [n_prod*nchan + 1]
+    cd* d_cont = nullptr;          // [n_prod*nchan + 1] the export a CONTINUUM finalize of the accumulator reduces (lazy)
     bool sums_valid = false;       // d_sums holds exported sums (fxc_reduce): fxc_finalize_sums(plan, NULL, ...) may read it
     // raw rows of the last fx_accumulate pass whose fold into the accumulator is still to be launched: it is launched
     // by whatever needs the accumulator or the workspace next (flush_pending) -- by a finalize together with the
@@ -179,6 +183,11 @@ struct fxc_pipe {
 
 namespace {
 
+// elements of the accumulator (and of every buffer sized like it): room for the autos rows of plans that may have them, so that
+// fxc_set_products allocates nothing
+int64_t acc_capacity(const fxc_plan* p) {
+    return (int64_t)(p->n_base + (p->n_ant >= 2 && p->n_ant <= 8 ? p->n_ant : 0)) * p->nchan;
+}
 
 int fail(const fxc_plan* p, int status, const char* fmt, ...) {
     char buf[512];

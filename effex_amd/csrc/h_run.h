@@ -3,11 +3,97 @@
 
 namespace {
 
+// ---- plans with autos (fxcorr.h, FXC_PRODUCTS_CROSS_AUTO) ---------------------------------------------------------------
+// Every shape takes one route: the plan's F stage alone -- run_channelize, what fxc_channelize runs (the tiled, wave-local,
+// per-channel-count, mixed-radix or generic F kernel of the shape) -- writes a pass of chunks' spectra to the workspace as
+// [chunk][antenna][frame][nchan] in natural bin order, then xengine_kernel<A, true> reads every spectrum once and writes raw rows
+// [n_prod][nchan]: the n_base cross rows, then the A auto rows.  A raw row is a float32 sum of at most kRowSpectra spectra: up
+// to `unit` chunks (integrations), or one of `xr` frame ranges of a chunk (k_finish.h::x_range) -- the multi-antenna fused route's
+// rows.  Byte input reaches it through the conversion pass (fx_u8_dev).
+struct AutoPass {
+    int64_t cb;          // chunks per pass
+    int64_t unit;        // chunks per raw row at most
+    int xr;              // frame ranges per chunk
+    int64_t spec_bytes, raw_bytes;
+};
+
+AutoPass autos_pass(const fxc_plan* p, int64_t n_chunks, bool rows) {
+    AutoPass a;
+    a.unit = rows ? 1 : fused_unit(p);
+    a.xr = a.unit > 1 ? 1 : (int)std::min<int64_t>((p->n_pts + kRowSpectra - 1) / kRowSpectra, 4096);
+    const int64_t spec_per_chunk = (int64_t)p->n_ant * p->n_pts * p->nchan * (int64_t)sizeof(cf);
+    const int64_t raw_per_chunk = (int64_t)p->n_prod * p->nchan * (int64_t)sizeof(cf) * a.xr;
+    int64_t cb = ws_target() / (spec_per_chunk + raw_per_chunk);
+    cb = std::max<int64_t>(1, std::min<int64_t>(cb, n_chunks));
+    cb = std::min<int64_t>(cb, std::max<int64_t>(1, 65535 / a.xr));     // groups x ranges ride in grid.y
+    a.cb = cb;
+    a.spec_bytes = (cb * spec_per_chunk + 255) / 256 * 256;
+    a.raw_bytes = (cb * raw_per_chunk + 255) / 256 * 256;
+    return a;
+}
+
+// chunks per raw row of an integration pass over nc chunks: as many X-engine workgroups as the device holds at once, within `unit`
+int64_t autos_group(const fxc_plan* p, int64_t nc, int64_t unit) {
+    const int64_t cols = std::max<int64_t>(1, (p->nchan + kXThreads - 1) / kXThreads);
+    const int64_t groups = std::max<int64_t>(1, p->x_resident_auto / cols);
+    return std::max<int64_t>(1, std::min<int64_t>(unit, (nc + groups - 1) / groups));
+}
+
+// raw[range][group][n_prod][nchan] for nc chunks starting at x
+int autos_raw_sums(fxc_plan* p, const cf* x, int64_t nc, cf* spec, cf* raw, int64_t cg, int xr) {
+    int rc = run_channelize(p, x, spec, nc * p->n_ant);
+    if (rc) return rc;
+    const dim3 grid((p->nchan + kXThreads - 1) / kXThreads, (unsigned)(((nc + cg - 1) / cg) * xr));
+#define FXC_XA_LAUNCH(A)                                                                                                        \
+    hipLaunchKernelGGL((xengine_kernel<A, true>), grid, dim3(kXThreads), 0, p->stream, spec, raw, p->n_pts, p->nchan, nc, (int)cg, \
+                       xr, (int64_t)1, p->n_pts)
+    switch (p->n_ant) {
+        case 2: FXC_XA_LAUNCH(2); break;
+        case 3: FXC_XA_LAUNCH(3); break;
+        case 4: FXC_XA_LAUNCH(4); break;
+        case 5: FXC_XA_LAUNCH(5); break;
+        case 6: FXC_XA_LAUNCH(6); break;
+        case 7: FXC_XA_LAUNCH(7); break;
+        case 8: FXC_XA_LAUNCH(8); break;
+        default: return fail(p, FXC_ERR_UNSUPPORTED, "autos for %d antennas", p->n_ant);
+    }
+#undef FXC_XA_LAUNCH
+    FXC_HIP(p, hipGetLastError());
+    return FXC_OK;
+}
+
+// 2 antennas at 4096 channels / 4 taps (complex64; byte input is converted first): the fused kernel's AUTOS variant, one pass
+// (k_fused4096.h) -- the route of the cross-only plan, whole chunks and frame ranges alike, with raw rows of [3][kN]
+bool fused_autos(const fxc_plan* p, int64_t n_chunks) {
+    return p->autos && p->path == FXC_PATH_FUSED && p->n_ant == 2 && !use_tiled(p, n_chunks);
+}
+
+int autos_accumulate_dev(fxc_plan* p, const cf* x, int64_t n_chunks) {
+    const AutoPass a = autos_pass(p, n_chunks, false);
+    int rc = ensure_ws(p, a.spec_bytes + a.raw_bytes + fold_part_bytes(p));
+    if (rc) return rc;
+    cf* spec = reinterpret_cast<cf*>(p->d_ws);
+    cf* raw = reinterpret_cast<cf*>(static_cast<char*>(p->d_ws) + a.spec_bytes);
+    cd* part = reinterpret_cast<cd*>(static_cast<char*>(p->d_ws) + a.spec_bytes + a.raw_bytes);
+    for (int64_t c0 = 0; c0 < n_chunks; c0 += a.cb) {
+        const int64_t nc = std::min(a.cb, n_chunks - c0);
+        const int64_t cg = autos_group(p, nc, a.unit);
+        const int xr = cg > 1 ? 1 : a.xr;
+        rc = autos_raw_sums(p, x + c0 * p->n_ant * p->num_samp, nc, spec, raw, cg, xr);
+        if (rc) return rc;
+        rc = fold_or_defer(p, raw, part, (nc + cg - 1) / cg * xr, 0, c0 + nc >= n_chunks);
+        if (rc) return rc;
+    }
+    p->spectra_count += (double)n_chunks * (double)p->n_pts;
+    return FXC_OK;
+}
+
 // device-resident implementation of fx_accumulate
 // dc_u8 != nullptr (fused 2-antenna plans only): x is the uint8 I,Q stream [n_chunks][2][num_samp][2] and dc_u8 its
 // per-stream conversion offsets
 int fx_accumulate_dev(fxc_plan* p, const cf* x, int64_t n_chunks, const cf* dc_u8 = nullptr) {
     if (n_chunks == 0) return FXC_OK;
+    if (p->autos && !fused_autos(p, n_chunks)) return autos_accumulate_dev(p, x, n_chunks);
     if (p->path == FXC_PATH_STREAM) {
         const int64_t blocks = stream_blocks(p);
         const int64_t cb = std::min<int64_t>(n_chunks, 65535);
@@ -136,30 +222,57 @@ int fx_accumulate_dev(fxc_plan* p, const cf* x, int64_t n_chunks, const cf* dc_u
 
 // CONTINUUM rows: one workgroup per row when there are rows enough to fill the chip, else bin slices + a second small kernel
 int launch_rows_continuum(fxc_plan* p, const cf* raw, cd* out, int nchan, int64_t rows, int n_splits, int64_t split_stride,
-                          double scale, int slots, LeadRows lead) {
+                          double scale, int slots, LeadRows lead, int n_prod = 1, int n_cross = 1) {
     const int slices = (int)std::min<int64_t>(32, nchan / 128);
     if (slices >= 2 && rows * 2 <= p->cu_count && rows <= 65535) {
         const int rg = grow(p, &p->d_rowpart, &p->rowpart_bytes, (size_t)rows * slices * sizeof(cd));
         if (rg) return rg;
         cd* part = static_cast<cd*>(p->d_rowpart);
         hipLaunchKernelGGL(rows_continuum_part_kernel, dim3(slices, (unsigned)rows), dim3(256), 0, p->stream, raw, part, p->d_rot, nchan,
-                           rows, n_splits, split_stride, slots, lead, slices);
+                           rows, n_splits, split_stride, slots, lead, slices, n_prod, n_cross);
         hipLaunchKernelGGL(rows_continuum_fin_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, p->stream, part, out, rows, slices,
                            scale);
     } else {
         hipLaunchKernelGGL(rows_continuum_kernel, dim3((int)std::min<int64_t>(rows, (int64_t)p->cu_count * 8)),
                            dim3(continuum_threads(nchan)), 0, p->stream, raw, out, p->d_rot, nchan, rows, n_splits, split_stride, scale,
-                           slots, lead);
+                           slots, lead, n_prod, n_cross);
     }
     return FXC_OK;
 }
 
-// device-resident implementation of fx_rows; out = cf[n_chunks][n_base][nchan] or cd[n_chunks][n_base]
+// fx_rows of a plan with autos: one raw row per chunk and frame range, the ranges as the rows kernels' splits
+int autos_rows_dev(fxc_plan* p, const cf* x, void* out, int64_t n_chunks, int mode, float inv_pts, double cscale) {
+    const AutoPass a = autos_pass(p, n_chunks, true);
+    int rc = ensure_ws(p, a.spec_bytes + a.raw_bytes);
+    if (rc) return rc;
+    cf* spec = reinterpret_cast<cf*>(p->d_ws);
+    cf* raw = reinterpret_cast<cf*>(static_cast<char*>(p->d_ws) + a.spec_bytes);
+    for (int64_t c0 = 0; c0 < n_chunks; c0 += a.cb) {
+        const int64_t nc = std::min(a.cb, n_chunks - c0);
+        rc = autos_raw_sums(p, x + c0 * p->n_ant * p->num_samp, nc, spec, raw, 1, a.xr);
+        if (rc) return rc;
+        const int64_t rows = nc * p->n_prod;
+        if (mode == FXC_MODE_SPECTRUM)
+            hipLaunchKernelGGL(rows_spectrum_kernel, dim3(grid_for(rows * p->nchan, 256, p->cu_count)), dim3(256), 0, p->stream, raw,
+                               static_cast<cf*>(out) + c0 * p->n_prod * p->nchan, p->d_rot, p->nchan, rows, a.xr, rows * p->nchan,
+                               inv_pts, 0, kNoLead, p->n_prod, p->n_base);
+        else {
+            rc = launch_rows_continuum(p, raw, static_cast<cd*>(out) + c0 * p->n_prod, p->nchan, rows, a.xr, rows * p->nchan, cscale, 0,
+                                       kNoLead, p->n_prod, p->n_base);
+            if (rc) return rc;
+        }
+        FXC_HIP(p, hipGetLastError());
+    }
+    return FXC_OK;
+}
+
+// device-resident implementation of fx_rows; out = cf[n_chunks][n_prod][nchan] or cd[n_chunks][n_prod]
 int fx_rows_dev(fxc_plan* p, const cf* x, void* out, int64_t n_chunks, int mode, double bandwidth,
                 const cf* dc_u8 = nullptr) {
     if (n_chunks == 0) return FXC_OK;
     const float inv_pts = (float)(1.0 / (double)p->n_pts);
     const double cscale = 1.0 / ((double)p->n_pts * (double)p->nchan * bandwidth);
+    if (p->autos && !fused_autos(p, n_chunks)) return autos_rows_dev(p, x, out, n_chunks, mode, inv_pts, cscale);
     if (p->path == FXC_PATH_STREAM) {
         const int nb = (int)stream_blocks(p);
         const int64_t cb = std::min<int64_t>(n_chunks, 65535);
@@ -173,7 +286,7 @@ int fx_rows_dev(fxc_plan* p, const cf* x, void* out, int64_t n_chunks, int mode,
             // raw[block][chunk]: the blocks play the role of the generic path's splits (nchan = n_base = 1)
             if (mode == FXC_MODE_SPECTRUM)
                 hipLaunchKernelGGL(rows_spectrum_kernel, dim3(grid_for(nc, 256, p->cu_count)), dim3(256), 0, p->stream, raw,
-                                   static_cast<cf*>(out) + c0, p->d_rot, 1, nc, nb, nc, inv_pts, 0, kNoLead);
+                                   static_cast<cf*>(out) + c0, p->d_rot, 1, nc, nb, nc, inv_pts, 0, kNoLead, 1, 1);
             else {
                 rc = launch_rows_continuum(p, raw, static_cast<cd*>(out) + c0, 1, nc, nb, nc, cscale, 0, kNoLead);
                 if (rc) return rc;
@@ -195,17 +308,18 @@ int fx_rows_dev(fxc_plan* p, const cf* x, void* out, int64_t n_chunks, int mode,
             rc = fused_raw_sums(p, reinterpret_cast<const cf*>(reinterpret_cast<const char*>(x) + c0 * in_bytes), nc, spec, raw,
                                 dc_u8 ? dc_u8 + c0 * 2 : nullptr, 1, true, dc_u8 && p->u8_dck);
             if (rc) return rc;
-            const int64_t rows = nc * p->n_base;
+            const int64_t rows = nc * p->n_prod;
             const LeadRows lead = p->n_ant == 2 ? fused_lead(p, nc) : kNoLead;
             // 3 and more antennas: the frame ranges of a chunk are the rows kernels' splits (range-major raw rows)
             const int xr = x_ranges(p, 1);
             const int64_t xr_stride = rows * p->nchan;
             if (mode == FXC_MODE_SPECTRUM)
                 hipLaunchKernelGGL(rows_spectrum_kernel, dim3(grid_for(rows * p->nchan, 256, p->cu_count)), dim3(256), 0,
-                                   p->stream, raw, static_cast<cf*>(out) + c0 * p->n_base * p->nchan, p->d_rot, p->nchan,
-                                   rows, xr, xr_stride, inv_pts, fused_layout(p), lead);
+                                   p->stream, raw, static_cast<cf*>(out) + c0 * p->n_prod * p->nchan, p->d_rot, p->nchan,
+                                   rows, xr, xr_stride, inv_pts, fused_layout(p), lead, p->n_prod, p->n_base);
             else {
-                rc = launch_rows_continuum(p, raw, static_cast<cd*>(out) + c0 * p->n_base, p->nchan, rows, xr, xr_stride, cscale, fused_layout(p), lead);
+                rc = launch_rows_continuum(p, raw, static_cast<cd*>(out) + c0 * p->n_prod, p->nchan, rows, xr, xr_stride, cscale, fused_layout(p), lead,
+                                           p->n_prod, p->n_base);
                 if (rc) return rc;
             }
             FXC_HIP(p, hipGetLastError());
@@ -225,7 +339,7 @@ int fx_rows_dev(fxc_plan* p, const cf* x, void* out, int64_t n_chunks, int mode,
             const LeadRows lead = fused_lead(p, 2 * nc);
             if (mode == FXC_MODE_SPECTRUM)
                 hipLaunchKernelGGL(rows_spectrum_kernel, dim3(grid_for(nc * N, 256, p->cu_count)), dim3(256), 0, p->stream,
-                                   raw, static_cast<cf*>(out) + c0 * N, p->d_rot, N, nc, 1, (int64_t)0, inv_pts, 3, lead);
+                                   raw, static_cast<cf*>(out) + c0 * N, p->d_rot, N, nc, 1, (int64_t)0, inv_pts, 3, lead, 1, 1);
             else {
                 rc = launch_rows_continuum(p, raw, static_cast<cd*>(out) + c0, N, nc, 1, (int64_t)0, cscale, 3, lead);
                 if (rc) return rc;
@@ -251,7 +365,7 @@ int fx_rows_dev(fxc_plan* p, const cf* x, void* out, int64_t n_chunks, int mode,
             if (rc) return rc;
             if (mode == FXC_MODE_SPECTRUM)
                 hipLaunchKernelGGL(rows_spectrum_kernel, dim3(grid_for(nc * N, 256, p->cu_count)), dim3(256), 0, p->stream,
-                                   raw, static_cast<cf*>(out) + c0 * N, p->d_rot, N, nc, n_splits, nc * N, inv_pts, 0, kNoLead);
+                                   raw, static_cast<cf*>(out) + c0 * N, p->d_rot, N, nc, n_splits, nc * N, inv_pts, 0, kNoLead, 1, 1);
             else {
                 rc = launch_rows_continuum(p, raw, static_cast<cd*>(out) + c0, N, nc, n_splits, nc * N, cscale, 0, kNoLead);
                 if (rc) return rc;
@@ -299,7 +413,7 @@ int fx_rows_dev(fxc_plan* p, const cf* x, void* out, int64_t n_chunks, int mode,
         if (mode == FXC_MODE_SPECTRUM)
             hipLaunchKernelGGL(rows_spectrum_kernel, dim3(grid_for(rows * p->nchan, 256, p->cu_count)), dim3(256), 0,
                                p->stream, raw, static_cast<cf*>(out) + c0 * p->n_base * p->nchan, p->d_rot, p->nchan,
-                               rows, g.n_splits, split_stride, inv_pts, 0, kNoLead);
+                               rows, g.n_splits, split_stride, inv_pts, 0, kNoLead, 1, 1);
         else {
             rc = launch_rows_continuum(p, raw, static_cast<cd*>(out) + c0 * p->n_base, p->nchan, rows, g.n_splits, split_stride, cscale, 0, kNoLead);
             if (rc) return rc;

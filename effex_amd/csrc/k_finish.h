@@ -20,39 +20,53 @@ __device__ __forceinline__ int64_t raw_index(int k, int slots) {
 struct LeadRows {
     int64_t first_chunk, n_frames, n_pts, offset;   // the tail: chunks from first_chunk on, n_frames frames in all
     int grid;
+    int n_prod = 1;     // rows per chunk (the fused kernel's AUTOS variant: 3 -- cross, auto 0, auto 1 -- in every raw row)
 };
 
 // slots == 3: row `row` of the caller is the pair of fused-kernel chunks 2 row (even bins) and 2 row + 1 (odd bins)
 __device__ __forceinline__ void add_lead_rows(const cf* __restrict__ raw, const LeadRows& lr, int64_t row, int nchan,
                                               int k, int slots, float& ar, float& ai) {
     if (lr.n_frames == 0) return;
+    int64_t prow = 0;           // the product row inside the chunk's rows
+    if (lr.n_prod > 1) {
+        prow = row % lr.n_prod;
+        row /= lr.n_prod;
+    }
     const int64_t vrow = slots == 3 ? 2 * row + (k & 1) : row;
     if (vrow < lr.first_chunk) return;
     const int row_len = slots == 3 ? fxc::fused::kN : nchan;
+    const int64_t lead_len = (int64_t)row_len * lr.n_prod;
     const int64_t ridx = slots == 3 ? fxc::fused::slot_of_bin(k >> 1) : raw_index(k, slots);
     const int64_t t = vrow - lr.first_chunk;   // chunk of the tail (fx_fused4096.h::range_walk_tail)
     const int64_t b_lo = fxc::range_owner(t * lr.n_pts, lr.n_frames, lr.grid);
     const int64_t b_hi = fxc::range_owner((t + 1) * lr.n_pts - 1, lr.n_frames, lr.grid);
     // the workgroups that start strictly inside that chunk (up to grid - 1 of them when one chunk pair is the whole call,
     // effex.py:490-494): four loads in flight, added in the order of the plain loop
-    const cf* __restrict__ src = raw + lr.offset + ridx;
+    const cf* __restrict__ src = raw + lr.offset + prow * row_len + ridx;
     int64_t b = b_lo + 1;
     for (; b + 3 <= b_hi; b += 4) {
-        const cf r0 = src[b * row_len], r1 = src[(b + 1) * row_len], r2 = src[(b + 2) * row_len], r3 = src[(b + 3) * row_len];
+        const cf r0 = src[b * lead_len], r1 = src[(b + 1) * lead_len], r2 = src[(b + 2) * lead_len], r3 = src[(b + 3) * lead_len];
         ar = ((ar + r0.x) + r1.x) + r2.x + r3.x;
         ai = ((ai + r0.y) + r1.y) + r2.y + r3.y;
     }
     for (; b <= b_hi; ++b) {
-        const cf r = src[b * row_len];
+        const cf r = src[b * lead_len];
         ar += r.x;
         ai += r.y;
     }
 }
 
+// Rows of a result: the n_cross baselines, then (plans with autos, fxcorr.h fxc_products) one row per antenna up to n_prod.
+// An auto row takes no rot (rot is a per-baseline phase) and its imaginary part is written as an exact 0.  n_cross == n_prod:
+// no autos (the modulo is not even formed).
+__device__ __forceinline__ bool auto_row(int64_t row, int n_prod, int n_cross) {
+    return n_cross < n_prod && (int)(row % n_prod) >= n_cross;
+}
+
 // SPECTRUM rows: out[c][p][(k + N/2) % N] = (sum_split raw) * conj(rot[k]) / n_pts   (effex.py:520-521)
 __global__ void rows_spectrum_kernel(const cf* __restrict__ raw, cf* __restrict__ out, const cd* __restrict__ rot,
                                      int nchan, int64_t rows, int n_splits, int64_t split_stride, float inv_pts,
-                                     int slots, LeadRows lead) {
+                                     int slots, LeadRows lead, int n_prod, int n_cross) {
     const int64_t total = rows * nchan;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += stride) {
@@ -79,12 +93,16 @@ __global__ void rows_spectrum_kernel(const cf* __restrict__ raw, cf* __restrict_
             ai += r.y;
         }
         add_lead_rows(raw, lead, row, nchan, k, slots, ar, ai);
+        int ks = k + nchan / 2;
+        if (ks >= nchan) ks -= nchan;
+        if (auto_row(row, n_prod, n_cross)) {
+            out[row * nchan + ks] = fxc::mk(ar * inv_pts, 0.f);
+            continue;
+        }
         const float cr = (float)rot[k].x, ci = (float)rot[k].y;
         // (ar + i ai) * (cr - i ci)
         const float orr = (ar * cr + ai * ci) * inv_pts;
         const float oi = (ai * cr - ar * ci) * inv_pts;
-        int ks = k + nchan / 2;
-        if (ks >= nchan) ks -= nchan;
         out[row * nchan + ks] = fxc::mk(orr, oi);
     }
 }
@@ -129,9 +147,10 @@ inline int continuum_threads(int nchan) { return nchan >= kContinuumThreads ? kC
 __global__ __launch_bounds__(kContinuumThreads) void rows_continuum_kernel(const cf* __restrict__ raw, cd* __restrict__ out,
                                                             const cd* __restrict__ rot, int nchan, int64_t rows,
                                                             int n_splits, int64_t split_stride, double scale,
-                                                            int slots, LeadRows lead) {
+                                                            int slots, LeadRows lead, int n_prod, int n_cross) {
     __shared__ double red[kContinuumThreads];
     for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
+        const bool au = auto_row(row, n_prod, n_cross);
         double ar = 0.0, ai = 0.0;
         for (int k = threadIdx.x; k < nchan; k += blockDim.x) {
             double xr = 0.0, xi = 0.0;
@@ -140,6 +159,10 @@ __global__ __launch_bounds__(kContinuumThreads) void rows_continuum_kernel(const
             add_lead_rows(raw, lead, row, nchan, k, slots, lr_re, lr_im);
             xr += lr_re;
             xi += lr_im;
+            if (au) {
+                ar += xr;
+                continue;
+            }
             const cd w = rot[k];
             ar += xr * w.x + xi * w.y;
             ai += xi * w.x - xr * w.y;
@@ -149,7 +172,7 @@ __global__ __launch_bounds__(kContinuumThreads) void rows_continuum_kernel(const
         if (threadIdx.x == 0) {
             cd o;
             o.x = ar * scale;
-            o.y = ai * scale;
+            o.y = ai * scale;          // (auto rows: ai stayed an exact 0)
             out[row] = o;
         }
     }
@@ -161,9 +184,11 @@ __global__ __launch_bounds__(kContinuumThreads) void rows_continuum_kernel(const
 // item of that call.
 __global__ __launch_bounds__(256) void rows_continuum_part_kernel(const cf* __restrict__ raw, cd* __restrict__ part,
                                                                  const cd* __restrict__ rot, int nchan, int64_t rows, int n_splits,
-                                                                 int64_t split_stride, int slots, LeadRows lead, int slices) {
+                                                                 int64_t split_stride, int slots, LeadRows lead, int slices,
+                                                                 int n_prod, int n_cross) {
     __shared__ double red[256];
     const int64_t row = blockIdx.y;
+    const bool au = auto_row(row, n_prod, n_cross);
     const int per = (nchan + slices - 1) / slices;
     const int k_lo = blockIdx.x * per, k_hi = k_lo + per < nchan ? k_lo + per : nchan;
     double ar = 0.0, ai = 0.0;
@@ -174,6 +199,10 @@ __global__ __launch_bounds__(256) void rows_continuum_part_kernel(const cf* __re
         add_lead_rows(raw, lead, row, nchan, k, slots, lr_re, lr_im);
         xr += lr_re;
         xi += lr_im;
+        if (au) {
+            ar += xr;
+            continue;
+        }
         const cd w = rot[k];
         ar += xr * w.x + xi * w.y;
         ai += xi * w.x - xr * w.y;
@@ -215,6 +244,7 @@ struct FoldFinish {
     const cd* rot;
     double count;     // spectra accumulated so far
     int reset;        // clear the accumulator afterwards
+    int64_t auto_from = 0;   // > 0: elements from this index on are auto rows (no rot, imaginary part 0 in `out`)
 };
 
 __device__ __forceinline__ void finish_element(cd a, cd* __restrict__ acc, int64_t idx, int k, int nchan, int64_t n,
@@ -230,10 +260,15 @@ __device__ __forceinline__ void finish_element(cd a, cd* __restrict__ acc, int64
     }
     if (fin.out) {
         const double inv = 1.0 / fin.count;
-        const cd w = fin.rot[k];
         cd o;
-        o.x = (a.x * w.x + a.y * w.y) * inv;
-        o.y = (a.y * w.x - a.x * w.y) * inv;
+        if (fin.auto_from > 0 && idx >= fin.auto_from) {
+            o.x = a.x * inv;
+            o.y = 0.0;
+        } else {
+            const cd w = fin.rot[k];
+            o.x = (a.x * w.x + a.y * w.y) * inv;
+            o.y = (a.y * w.x - a.x * w.y) * inv;
+        }
         int ks = k + nchan / 2;
         if (ks >= nchan) ks -= nchan;
         fin.out[idx - k + ks] = o;
@@ -388,17 +423,26 @@ __device__ __forceinline__ XRange x_range(int64_t n_pts, int64_t n_chunks, int c
 #endif
 constexpr int kXU = 2;           // spectra per trip: kXU * A independent 8-byte loads in flight before the multiply-accumulates
 constexpr int kXThreads = 64;
-template <int A>
+// AUTOS (plans with autos, fxcorr.h fxc_products): A = 2 .. 8, the A power sums |z_a|^2 accumulate beside the cross products
+// and every raw row is [NB + A][nchan], the autos after the baselines with imaginary part 0; the spectra are read as
+// row i * frame_rows + a * ant_rows of a chunk (the plan's F stage alone writes [chunk][antenna][frame]: 1, n_pts).  Without
+// AUTOS the layout is the fixed [chunk][frame][antenna] above and the strides are not read.
+template <int A, bool AUTOS = false>
 __global__ __launch_bounds__(kXThreads) void xengine_kernel(const cf* __restrict__ spec, cf* __restrict__ raw, int64_t n_pts,
-                                                           int nchan, int64_t n_chunks, int cg, int n_ranges) {
+                                                           int nchan, int64_t n_chunks, int cg, int n_ranges,
+                                                           int64_t frame_rows = A, int64_t ant_rows = 1) {
     constexpr int NB = A * (A - 1) / 2;
+    constexpr int NP = NB + (AUTOS ? A : 0);
+    const int64_t fr = AUTOS ? frame_rows : A, ae = AUTOS ? ant_rows : 1;
     const int pos = blockIdx.x * blockDim.x + threadIdx.x;
     if (pos >= nchan) return;          // 16 and 32 channels: part of a wave
     const XRange xr = x_range(n_pts, n_chunks, cg, n_ranges);
     const int64_t grp = xr.grp;
-    float ar[NB], ai[NB];
+    float ar[NB], ai[NB], pw[AUTOS ? A : 1];
 #pragma unroll
     for (int p = 0; p < NB; ++p) ar[p] = ai[p] = 0.f;
+#pragma unroll
+    for (int a = 0; a < (AUTOS ? A : 1); ++a) pw[a] = 0.f;
     const int64_t c_end = (grp + 1) * cg < n_chunks ? (grp + 1) * cg : n_chunks;
     for (int64_t c = grp * cg; c < c_end; ++c) {
         const cf* base = spec + (c * A * n_pts) * nchan + pos;
@@ -408,9 +452,13 @@ __global__ __launch_bounds__(kXThreads) void xengine_kernel(const cf* __restrict
 #pragma unroll
             for (int u = 0; u < kXU; ++u)
 #pragma unroll
-                for (int a = 0; a < A; ++a) z[u][a] = FXC_X_LOAD(base + ((i + u) * A + a) * nchan);
+                for (int a = 0; a < A; ++a) z[u][a] = FXC_X_LOAD(base + ((i + u) * fr + a * ae) * nchan);
 #pragma unroll
             for (int u = 0; u < kXU; ++u) {
+                if constexpr (AUTOS) {
+#pragma unroll
+                    for (int a = 0; a < A; ++a) pw[a] += z[u][a].x * z[u][a].x + z[u][a].y * z[u][a].y;
+                }
                 int p = 0;
 #pragma unroll
                 for (int a = 0; a < A; ++a)
@@ -424,7 +472,11 @@ __global__ __launch_bounds__(kXThreads) void xengine_kernel(const cf* __restrict
         for (; i < xr.i1; ++i) {
             cf z[A];
 #pragma unroll
-            for (int a = 0; a < A; ++a) z[a] = FXC_X_LOAD(base + (i * A + a) * nchan);
+            for (int a = 0; a < A; ++a) z[a] = FXC_X_LOAD(base + (i * fr + a * ae) * nchan);
+            if constexpr (AUTOS) {
+#pragma unroll
+                for (int a = 0; a < A; ++a) pw[a] += z[a].x * z[a].x + z[a].y * z[a].y;
+            }
             int p = 0;
 #pragma unroll
             for (int a = 0; a < A; ++a)
@@ -436,7 +488,11 @@ __global__ __launch_bounds__(kXThreads) void xengine_kernel(const cf* __restrict
         }
     }
 #pragma unroll
-    for (int p = 0; p < NB; ++p) raw[(xr.row * NB + p) * nchan + pos] = fxc::mk(ar[p], ai[p]);
+    for (int p = 0; p < NB; ++p) raw[(xr.row * NP + p) * nchan + pos] = fxc::mk(ar[p], ai[p]);
+    if constexpr (AUTOS) {
+#pragma unroll
+        for (int a = 0; a < A; ++a) raw[(xr.row * NP + NB + a) * nchan + pos] = fxc::mk(pw[a], 0.f);
+    }
 }
 
 // More than 8 antennas: the same X-engine over blocks of kXB antennas.  A workgroup (one wave, as above) takes a column of
@@ -509,17 +565,23 @@ __global__ __launch_bounds__(kXThreads) void xengine_block_kernel(const cf* __re
 
 // out[p][(k + N/2) % N] = sums[p][k] * conj(rot[k]) / count      (effex.py:520-521, integrated)
 __global__ void finalize_spectrum_kernel(const cd* __restrict__ sums, cd* __restrict__ out, const cd* __restrict__ rot,
-                                         int nchan, int n_base) {
+                                         int nchan, int n_base, int n_cross) {   // (n_base: rows in all; autos from n_cross on)
     const int64_t n = (int64_t)n_base * nchan;
     const double inv = 1.0 / sums[n].x;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += stride) {
         const int k = (int)(idx % nchan);
         const int64_t p = idx / nchan;
-        const cd a = sums[idx], w = rot[k];
+        const cd a = sums[idx];
         cd o;
-        o.x = (a.x * w.x + a.y * w.y) * inv;
-        o.y = (a.y * w.x - a.x * w.y) * inv;
+        if (p >= n_cross) {
+            o.x = a.x * inv;
+            o.y = 0.0;
+        } else {
+            const cd w = rot[k];
+            o.x = (a.x * w.x + a.y * w.y) * inv;
+            o.y = (a.y * w.x - a.x * w.y) * inv;
+        }
         int ks = k + nchan / 2;
         if (ks >= nchan) ks -= nchan;
         out[p * nchan + ks] = o;
@@ -528,13 +590,18 @@ __global__ void finalize_spectrum_kernel(const cd* __restrict__ sums, cd* __rest
 
 __global__ __launch_bounds__(256) void finalize_continuum_kernel(const cd* __restrict__ sums, cd* __restrict__ out,
                                                                 const cd* __restrict__ rot, int nchan, int n_base,
-                                                                double inv_bw) {
+                                                                double inv_bw, int n_cross) {
     __shared__ double red[256];
     const int64_t n = (int64_t)n_base * nchan;
     const double scale = inv_bw / (sums[n].x * (double)nchan);
     for (int p = blockIdx.x; p < n_base; p += gridDim.x) {
+        const bool au = p >= n_cross;
         double ar = 0.0, ai = 0.0;
         for (int k = threadIdx.x; k < nchan; k += blockDim.x) {
+            if (au) {
+                ar += sums[(int64_t)p * nchan + k].x;
+                continue;
+            }
             const cd a = sums[(int64_t)p * nchan + k], w = rot[k];
             ar += a.x * w.x + a.y * w.y;
             ai += a.y * w.x - a.x * w.y;

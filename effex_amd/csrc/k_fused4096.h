@@ -82,6 +82,7 @@ __device__ __forceinline__ void convert_frame_u8(cf (&h)[16], cf off) {
 #endif
 constexpr int kStampSegs = 12;
 constexpr int kDckLdsBytes = 64;       // DCK launches: the waves' byte sums, behind the carve
+constexpr int kAutoLdsBytes = fxc::fused::kAccPerThread * fxc::fused::kThreads * 4;   // AUTOS launches: antenna 1's power sums
 #if FXC_STAMPS
 #define FXC_STAMP(k)                                                              \
     do {                                                                          \
@@ -233,8 +234,8 @@ __device__ __forceinline__ cf dck_offset(unsigned* acc, unsigned* red, int tid, 
 #ifndef FXC_SPEC_STORE_AUX
 #define FXC_SPEC_STORE_AUX 2      // cache policy of the F-only spectra stores: nt (written once, read by the X pass: 8 antennas 2.35 -> 2.19 ms)
 #endif
-template <int PH, bool SPEC_OUT, bool U8, bool DCK>
-__device__ __forceinline__ void fused_step(fxc::fused::State& s, U8State& u8, const cf* dc, const f4* win, cf* region,
+template <int PH, bool SPEC_OUT, bool U8, bool DCK, bool AUTOS>
+__device__ __forceinline__ void fused_step(fxc::fused::State& s, float (&pw)[fxc::fused::kAccPerThread], float* pw_lds, U8State& u8, const cf* dc, const f4* win, cf* region,
                                            const cf* tw2, int tid, const cf* x, int64_t num_samp, unsigned chunk_bytes,
                                            unsigned voff, fxc::fused::RangeWalk& pos, cf* rows_raw, int hp, v4u32_t* dck_stage,
                                            unsigned* dck_acc, unsigned* dck_red,
@@ -256,7 +257,7 @@ __device__ __forceinline__ void fused_step(fxc::fused::State& s, U8State& u8, co
     const unsigned char* dck_base = reinterpret_cast<const unsigned char*>(x) + (int64_t)(c + (dck_next ? 1 + pos.seg_jump : 0)) * 4 * num_samp;
     if (U8) convert_frame_u8(s.h[PH], u8.off);   // the byte pairs fetched a step ago become the samples of slot PH
     cf v[16];
-    phase1_fir<PH>(s, win, tid, v);      // first use of this frame: waits for its loads (issued a step ago)
+    phase1_fir<PH, AUTOS ? 2 : kFirGroup>(s, win, tid, v);      // first use of this frame: waits for its loads (issued a step ago)
     FXC_STAMP(2);
     // The oldest ring slot is dead now: refill it with the next frame of this workgroup's range (next frame of
     // the chunk, or frame 0 of the next chunk; at the very end the current frame again, never used).  The 16
@@ -278,7 +279,7 @@ __device__ __forceinline__ void fused_step(fxc::fused::State& s, U8State& u8, co
     // second half of the radix-16 with the twiddle w4096^(j k1) and the exchange-1 store of every output as it forms:
     // the stores are bound by the LDS write path, the butterflies and twiddles run in its shadow (B0 in front of the
     // whole radix-16 instead: +7 %; exchange 2 streamed the same way: spills, +6 %)
-    phase1_finish_store(s, v, region, tid);
+    phase1_finish_store<AUTOS>(s, v, region, tid);
 #endif
     FXC_STAMP(5);
 #if !(FXC_ABL & 2)
@@ -337,6 +338,11 @@ __device__ __forceinline__ void fused_step(fxc::fused::State& s, U8State& u8, co
             cf a = v[q], b = v[q + 8];
             permlane32_swap(a, b);
             xacc(s, q, a, b);
+            if (AUTOS) {      // the same bin of both antennas: |a|^2 in registers, |b|^2 in the lane's own LDS slots
+                pw[q] = __builtin_fmaf(a.y, a.y, __builtin_fmaf(a.x, a.x, pw[q]));
+                float* p1 = pw_lds + q * kThreads + tid;
+                *p1 = __builtin_fmaf(b.y, b.y, __builtin_fmaf(b.x, b.x, *p1));
+            }
         }
         FXC_STAMP(10);
     }
@@ -365,11 +371,17 @@ __device__ __forceinline__ void fused_step(fxc::fused::State& s, U8State& u8, co
                 s.acc[q] = fxc::mk(0.f, 0.f);
             }
         } else {
-            cf* row = rows_raw + (int64_t)pos.row * kN + tid;
+            // AUTOS: a raw row is three kN-rows in slot order -- the cross sums, antenna 0's and antenna 1's power sums
+            cf* row = rows_raw + (int64_t)pos.row * (AUTOS ? 3 : 1) * kN + tid;
 #pragma unroll
             for (int q = 0; q < kAccPerThread; ++q) {
                 row[q * kThreads] = s.acc[q];
                 s.acc[q] = fxc::mk(0.f, 0.f);
+                if (AUTOS) {
+                    row[kN + q * kThreads] = fxc::mk(pw[q], 0.f);
+                    row[2 * kN + q * kThreads] = fxc::mk(pw_lds[q * kThreads + tid], 0.f);
+                    pw[q] = pw_lds[q * kThreads + tid] = 0.f;
+                }
             }
         }
     }
@@ -387,7 +399,12 @@ __device__ __forceinline__ void fused_step(fxc::fused::State& s, U8State& u8, co
 // conversion offsets (-mean_byte / 127.5, or -1 without DC removal) of each stream; DCK: of the first chunk of every
 // workgroup's round-robin share and of the tail chunks only, the kernel sums the others itself.  stamps: diagnostic
 // builds only.
-template <bool SPEC_OUT, bool U8 = false, bool DCK = false>
+// AUTOS (complex64 F+X only, plans with autos): the two antennas' power spectra accumulate beside the cross product in the same
+// pass, and every raw row is [3][kN] in slot order: cross, |f_0|^2, |f_1|^2 (imaginary parts 0).  Register budget (the default
+// instantiation holds 248 of 256 VGPRs): antenna 0's 8 sums per lane in VGPRs, freed by the lean twiddles (phase1_finish_store
+// LEAN_TW) and a FIR group of 2; antenna 1's in the lane's own LDS slots behind the carve (kAutoLdsBytes, no barrier: nobody
+// else reads them).
+template <bool SPEC_OUT, bool U8 = false, bool DCK = false, bool AUTOS = false>
 __global__ __launch_bounds__(fxc::fused::kThreads, 2) void fx_fused4096_kernel(
     const cf* __restrict__ x, int64_t num_samp, int64_t n_pts, int64_t n_chunks, const f4* __restrict__ win_g,
     const cf* __restrict__ tw1_g, const cf* __restrict__ tw2_g, cf* __restrict__ rows_raw,
@@ -406,6 +423,14 @@ __global__ __launch_bounds__(fxc::fused::kThreads, 2) void fx_fused4096_kernel(
     state_load_twiddles(s, tw1_g, tid);
 #pragma unroll
     for (int q = 0; q < kAccPerThread; ++q) s.acc[q] = fxc::mk(0.f, 0.f);
+    static_assert(!AUTOS || (!SPEC_OUT && !U8), "autos: the complex64 F+X variant only");
+    float pw[kAccPerThread];
+    float* pw_lds = reinterpret_cast<float*>(smem + kLdsBytes);
+#pragma unroll
+    for (int q = 0; q < kAccPerThread; ++q) {
+        pw[q] = 0.f;
+        if (AUTOS) pw_lds[q * kThreads + tid] = 0.f;
+    }
     __syncthreads();
 
     constexpr int64_t kSampleBytes = U8 ? sizeof(unsigned short) : sizeof(cf);
@@ -445,9 +470,9 @@ __global__ __launch_bounds__(fxc::fused::kThreads, 2) void fx_fused4096_kernel(
             const RangeSplit sp = range_split(gridDim.x, (int)n_chunks, seg, walk_unit, rows_are_chunks != 0);
             int t_lead = tid;
             if (DCK) asm volatile("" : "+v"(t_lead));     // (formed here: as an invariant of the part loop the pointer is spilled)
-            cf* lead_row = rows_raw + (int64_t)(sp.rows_rounds + sp.n_tail + blockIdx.x) * kN + t_lead;
+            cf* lead_row = rows_raw + (int64_t)(sp.rows_rounds + sp.n_tail + blockIdx.x) * (AUTOS ? 3 : 1) * kN + t_lead;
 #pragma unroll
-            for (int q = 0; q < kAccPerThread; ++q) lead_row[q * kThreads] = fxc::mk(0.f, 0.f);
+            for (int q = 0; q < (AUTOS ? 3 : 1) * kAccPerThread; ++q) lead_row[q * kThreads] = fxc::mk(0.f, 0.f);
         }
         if (total == 0) continue;
         if (U8) u8.off = dc[(int64_t)pos.c * 2 + __builtin_amdgcn_readfirstlane(ant)];
@@ -476,13 +501,13 @@ __global__ __launch_bounds__(fxc::fused::kThreads, 2) void fx_fused4096_kernel(
         // frame g of the part sits in ring slot g & 3: unrolled by four so the ring rotates by register renaming
 #pragma unroll 1
         for (int g = 0; g < total; g += 4) {
-            fused_step<0, SPEC_OUT, U8, DCK>(s, u8, dc, win, region, tw2, tid, x, num_samp, chunk_bytes, voff, pos, rows_raw, SPEC_OUT ? unit : 0, dck_stage, dck_acc, dck_red, seg_t, t_prev);
+            fused_step<0, SPEC_OUT, U8, DCK, AUTOS>(s, pw, pw_lds, u8, dc, win, region, tw2, tid, x, num_samp, chunk_bytes, voff, pos, rows_raw, SPEC_OUT ? unit : 0, dck_stage, dck_acc, dck_red, seg_t, t_prev);
             if (g + 1 < total)
-                fused_step<1, SPEC_OUT, U8, DCK>(s, u8, dc, win, region, tw2, tid, x, num_samp, chunk_bytes, voff, pos, rows_raw, SPEC_OUT ? unit : 0, dck_stage, dck_acc, dck_red, seg_t, t_prev);
+                fused_step<1, SPEC_OUT, U8, DCK, AUTOS>(s, pw, pw_lds, u8, dc, win, region, tw2, tid, x, num_samp, chunk_bytes, voff, pos, rows_raw, SPEC_OUT ? unit : 0, dck_stage, dck_acc, dck_red, seg_t, t_prev);
             if (g + 2 < total)
-                fused_step<2, SPEC_OUT, U8, DCK>(s, u8, dc, win, region, tw2, tid, x, num_samp, chunk_bytes, voff, pos, rows_raw, SPEC_OUT ? unit : 0, dck_stage, dck_acc, dck_red, seg_t, t_prev);
+                fused_step<2, SPEC_OUT, U8, DCK, AUTOS>(s, pw, pw_lds, u8, dc, win, region, tw2, tid, x, num_samp, chunk_bytes, voff, pos, rows_raw, SPEC_OUT ? unit : 0, dck_stage, dck_acc, dck_red, seg_t, t_prev);
             if (g + 3 < total)
-                fused_step<3, SPEC_OUT, U8, DCK>(s, u8, dc, win, region, tw2, tid, x, num_samp, chunk_bytes, voff, pos, rows_raw, SPEC_OUT ? unit : 0, dck_stage, dck_acc, dck_red, seg_t, t_prev);
+                fused_step<3, SPEC_OUT, U8, DCK, AUTOS>(s, pw, pw_lds, u8, dc, win, region, tw2, tid, x, num_samp, chunk_bytes, voff, pos, rows_raw, SPEC_OUT ? unit : 0, dck_stage, dck_acc, dck_red, seg_t, t_prev);
         }
         frames_done += total;
     }

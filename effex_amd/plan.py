@@ -64,7 +64,7 @@ def rot_table(nbins, bandwidth, frequency, calibrated_delay):
 
 
 class FxPlan(object):
-    def __init__(self, n_ant, nchan, ntaps, num_samp, window=None, device=0, stream=None, path=None, dev=False):
+    def __init__(self, n_ant, nchan, ntaps, num_samp, window=None, device=0, stream=None, path=None, dev=False, autos=False):
         self._lib = _lib.load(dev=dev)          # dev: the developer build with the reference kernels (tests, tools/soak.py)
         self._h = ctypes.c_void_p()
         if window is None:
@@ -94,6 +94,20 @@ class FxPlan(object):
         self.num_samp, self.n_pts = info.num_samp, info.n_pts
         self.device = info.device
         self.path = PATH_NAMES[info.path]
+        self.autos, self.n_rows = False, self.n_baselines
+        if autos:
+            self.set_autos(True)
+
+    def set_autos(self, autos):
+        """``fxc_set_products``: results of ``n_rows = n_baselines + n_ant`` rows -- the cross rows, then each antenna's
+        autocorrelation (no rot, imaginary part 0) -- or back to the cross rows alone.  Only while nothing is accumulated,
+        no finalize result is outstanding and no pipe uses the plan."""
+        self._sync_stream()
+        want = _lib.FXC_PRODUCTS_CROSS_AUTO if autos else _lib.FXC_PRODUCTS_CROSS
+        self._check(self._lib.fxc_set_products(self._h, want))
+        products, n_rows = ctypes.c_int(), ctypes.c_int()
+        self._check(self._lib.fxc_plan_products(self._h, ctypes.byref(products), ctypes.byref(n_rows)))
+        self.autos, self.n_rows = products.value == _lib.FXC_PRODUCTS_CROSS_AUTO, n_rows.value
 
     # -- plumbing ---------------------------------------------------------------------------
     def _check(self, rc):
@@ -241,7 +255,7 @@ class FxPlan(object):
     def fx_rows(self, x, mode="SPECTRUM", bandwidth=1.0, remove_dc=False, out=None, c128=False):
         """One visibility row per chunk (the reference's ``_run_task`` result, effex.py:490-527).
 
-        SPECTRUM -> [n_chunks, n_baselines, nchan] complex64; CONTINUUM/TEST -> [n_chunks, n_baselines]
+        SPECTRUM -> [n_chunks, n_rows, nchan] complex64; CONTINUUM/TEST -> [n_chunks, n_rows]
         complex128.  ``remove_dc``: the per-chunk, per-antenna mean is removed on the device first (effex.py:394-395;
         ``fxc_fx_rows_iq``).  ``c128``: complex128 input crosses to the device as it is and is narrowed there (after the
         DC removal) instead of on the host.  ``out``: an array / tensor of the result's shape to receive the rows -- a
@@ -250,9 +264,9 @@ class FxPlan(object):
         m = MODES[mode.upper()]
         ptr, kind, n, keep = self._in(x, (self.n_ant, self.num_samp), c128)
         if m == _lib.FXC_MODE_SPECTRUM:
-            out, optr = self._out(x, (n, self.n_baselines, self.nchan), np.complex64, out)
+            out, optr = self._out(x, (n, self.n_rows, self.nchan), np.complex64, out)
         else:
-            out, optr = self._out(x, (n, self.n_baselines), np.complex128, out)
+            out, optr = self._out(x, (n, self.n_rows), np.complex128, out)
         if self._to_pinned:
             kind = _lib.FXC_MEM_DEVICE_TO_PINNED
         if remove_dc or self._fmt != _lib.FXC_IQ_C64:
@@ -267,24 +281,24 @@ class FxPlan(object):
         self._check(self._lib.fxc_acc_reset(self._h))
 
     def acc_export(self, sums):
-        """sums: CUDA complex128 tensor [n_baselines*nchan + 1] (raw sums + {spectra count})."""
+        """sums: CUDA complex128 tensor [n_rows*nchan + 1] (raw sums + {spectra count})."""
         import torch
-        if sums.dtype != torch.complex128 or sums.numel() != self.n_baselines * self.nchan + 1 \
+        if sums.dtype != torch.complex128 or sums.numel() != self.n_rows * self.nchan + 1 \
                 or not sums.is_contiguous() or not sums.is_cuda:
-            raise ValueError("sums must be a contiguous CUDA complex128 tensor of n_baselines*nchan + 1 elements")
+            raise ValueError("sums must be a contiguous CUDA complex128 tensor of n_rows*nchan + 1 elements")
         self._sync_stream()
         self._check(self._lib.fxc_acc_export(self._h, sums.data_ptr()))
         return sums
 
     def new_sums(self):
         import torch
-        return torch.empty(self.n_baselines * self.nchan + 1, dtype=torch.complex128,
+        return torch.empty(self.n_rows * self.nchan + 1, dtype=torch.complex128,
                            device=torch.device("cuda", self.device))
 
     def finalize_sums(self, sums=None, mode="SPECTRUM", bandwidth=1.0):
         """Visibilities from exported (and reduced) sums; ``sums=None``: the plan's own copy, as ``reduce`` leaves it."""
         m = MODES[mode.upper()]
-        shape = (self.n_baselines, self.nchan) if m == _lib.FXC_MODE_SPECTRUM else (self.n_baselines,)
+        shape = (self.n_rows, self.nchan) if m == _lib.FXC_MODE_SPECTRUM else (self.n_rows,)
         out = np.empty(shape, dtype=np.complex128)
         self._sync_stream()
         ptr = sums.data_ptr() if sums is not None else None
@@ -302,13 +316,13 @@ class FxPlan(object):
         """Mean over everything accumulated, times conj(rot), fft-shifted -> numpy complex128."""
         self._sync_stream()
         m = MODES[mode.upper()]
-        shape = (self.n_baselines, self.nchan) if m == _lib.FXC_MODE_SPECTRUM else (self.n_baselines,)
+        shape = (self.n_rows, self.nchan) if m == _lib.FXC_MODE_SPECTRUM else (self.n_rows,)
         out = np.empty(shape, dtype=np.complex128)
         self._check(self._lib.fxc_finalize(self._h, out.ctypes.data, m, float(bandwidth), int(bool(reset))))
         return out
 
     def _result(self, mode_code):
-        shape = (self.n_baselines, self.nchan) if mode_code == _lib.FXC_MODE_SPECTRUM else (self.n_baselines,)
+        shape = (self.n_rows, self.nchan) if mode_code == _lib.FXC_MODE_SPECTRUM else (self.n_rows,)
         return np.empty(shape, dtype=np.complex128)
 
     def finalize_async(self, mode="SPECTRUM", bandwidth=1.0, reset=True, out=None):
@@ -413,9 +427,9 @@ class FxPlan(object):
         m = MODES[mode.upper()]
         ptr, kind, n, keep = self._in_u8(iq_u8)
         if m == _lib.FXC_MODE_SPECTRUM:
-            out, optr = self._out(iq_u8, (n, self.n_baselines, self.nchan), np.complex64, out)
+            out, optr = self._out(iq_u8, (n, self.n_rows, self.nchan), np.complex64, out)
         else:
-            out, optr = self._out(iq_u8, (n, self.n_baselines), np.complex128, out)
+            out, optr = self._out(iq_u8, (n, self.n_rows), np.complex128, out)
         if self._to_pinned:
             kind = _lib.FXC_MEM_DEVICE_TO_PINNED
         self._check(self._lib.fxc_fx_rows_u8(self._h, ptr, optr, n, kind, m, float(bandwidth), int(bool(remove_dc))))
@@ -516,9 +530,9 @@ class FxPipeline(object):
         e.g. a window of a memory-mapped row file (``effex_amd.rowsink.BinSink.reserve``): the rows then go from the pinned
         result slot straight into the page cache."""
         if self.mode == _lib.FXC_MODE_SPECTRUM:
-            shape, dtype = (self.chunks, self.plan.n_baselines, self.plan.nchan), np.complex64
+            shape, dtype = (self.chunks, self.plan.n_rows, self.plan.nchan), np.complex64
         else:
-            shape, dtype = (self.chunks, self.plan.n_baselines), np.complex128
+            shape, dtype = (self.chunks, self.plan.n_rows), np.complex128
         if out is None:
             out = np.empty(shape, dtype=dtype)
         elif out.dtype != dtype or out.size != int(np.prod(shape)) or not out.flags.c_contiguous or not out.flags.writeable:

@@ -3,7 +3,7 @@
 Chunks are independent (``channelize_poly`` starts every chunk with zero PFB history and the reference
 processes chunk pairs one at a time with no carried state, effex/effex.py:391-410), so each rank
 integrates a contiguous range of the global chunk index on its own GPU with no data-path collective.
-The only exchange is one sum-reduction of the exported accumulators — ``n_baselines*nchan + 1``
+The only exchange is one sum-reduction of the exported accumulators — ``n_rows*nchan + 1``
 complex128 (raw cross-spectra sums + the spectra count; 64 KiB for 2 antennas) — once per integration,
 then ``fxc_finalize_sums`` on the root.  Two transports:
 
@@ -204,14 +204,15 @@ class ShardedRows(object):
         import numpy as np
         from . import rowsink
         spectrum = mode.upper() == "SPECTRUM"
-        row_len = self.plan.n_baselines * (self.plan.nchan if spectrum else 1)
+        n_rows = getattr(self.plan, "n_rows", self.plan.n_baselines)      # (plan-like objects without products: the baselines)
+        row_len = n_rows * (self.plan.nchan if spectrum else 1)
         dtype = np.complex64 if spectrum else np.complex128
         lo, hi = self.my_range(n_chunks)
         to_file = consumer is None
         if self.rank == 0 and to_file:
             rowsink.create_shared(path, header, freqs if spectrum else None, row_len, dtype, n_chunks)
         self._barrier()
-        shape_tail = (self.plan.n_baselines, self.plan.nchan) if spectrum else (self.plan.n_baselines,)
+        shape_tail = (n_rows, self.plan.nchan) if spectrum else (n_rows,)
         # every batch is read exactly once (a reader may be sequential -- a file, a socket): the first one says where the samples live
         first = read_chunks(lo, min(hi, lo + self.batch)) if hi > lo else None
         if first is not None and type(first).__module__.startswith("torch"):

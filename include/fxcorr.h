@@ -131,6 +131,27 @@ int fxc_plan_get_info(const fxc_plan* plan, fxc_info* info);
 int fxc_spec_probe(int nchan, int ntaps, int variant, const char* arch, char* report, int report_bytes);
 const char* fxc_last_error(const fxc_plan* plan);
 
+/* Products.  A plan makes cross products only (FXC_PRODUCTS_CROSS, the default) or cross products and the autocorrelation of
+ * every antenna (FXC_PRODUCTS_CROSS_AUTO).  With autos a result has n_rows = n_baselines + n_ant rows: the cross rows first, in
+ * the order and with the meaning they have without autos, then one row per antenna a = 0 .. n_ant-1:
+ *   SPECTRUM : fftshift(mean_i |f_a[i,k]|^2) over the same spectra the cross rows average;
+ *   CONTINUUM: the mean over the bins of that, divided by `bandwidth` (the cross formula, effex.py:523-524);
+ *   rot (fxc_set_rot) is not applied to them (it is a per-baseline phase) and their imaginary part is an exact 0.
+ * The autos are those of the samples the cross rows see: after the byte conversion and the DC removal of the *_u8 / *_iq calls.
+ * Everything sized by n_baselines without autos is sized by n_rows with them: the rows of fxc_fx_rows (_u8, _iq) and of the
+ * pipes, the results of every finalize call, the accumulator and its export (n_rows*nchan + 1 complex128).  Two antennas at
+ * nchan 4096 / ntaps 4 (FXC_PATH_FUSED) sum the autos inside the fused F+X kernel, one pass over the samples; other plans with autos
+ * take the plan's F stage alone (what fxc_channelize runs) into the workspace and then the X-engine that also sums |f_a|^2 --
+ * streaming plans (nchan 1) pay about 30 x their cross-only time for that and should not ask for autos yet.  Plans without autos
+ * run exactly the kernels they run without this call.
+ * fxc_set_products: FXC_OK, FXC_ERR_ARG (NULL plan, unknown value), FXC_ERR_UNSUPPORTED (autos for more than 8 antennas),
+ * FXC_ERR_STATE unless the accumulator is empty (nothing accumulated since the last reset or resetting finalize), no finalize
+ * result is outstanding and no fxc_pipe uses the plan.  fxc_plan_products: the current products and rows per result (either
+ * pointer may be NULL). */
+enum fxc_products { FXC_PRODUCTS_CROSS = 0, FXC_PRODUCTS_CROSS_AUTO = 1 };
+int fxc_set_products(fxc_plan* plan, int products);
+int fxc_plan_products(const fxc_plan* plan, int* products, int* n_rows);
+
 /* rot[k] = exp(+2*pi*i*f_k*tau), natural bin order — effex.py:516,519.  Formed by the caller in
  * float64 (phase ~ 9e3 rad), complex128[nchan] host memory, copied.  Default: all ones. */
 int fxc_set_rot(fxc_plan* plan, const double* rot_re_im);
