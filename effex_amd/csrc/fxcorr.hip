@@ -5,7 +5,9 @@
 //                                           g++ for the host emulation under tests/emul)
 //   k_generic.h k_finish.h k_fused4096.h k_tiled.h k_small.h k_prepass.h k_stream.h k_conditioning.h k_delay.h k_synth.h
 //                                           the __global__ kernels, one file per path / step
-//   h_plan.h h_launch.h h_run.h h_rccl.h    fxc_plan, the per-path launchers and workspace passes, the device-resident
+//   h_plan.h h_rtc.h h_launch.h h_build.h h_run.h h_rccl.h
+//                                           fxc_plan, the kernels compiled per channel count, the per-path launchers and
+//                                           workspace passes, plan construction (route, tables), the device-resident
 //                                           fx_accumulate / fx_rows, the run-time binding of librccl
 //
 // Replaces, for effex's hot path:
@@ -137,6 +139,7 @@ int64_t ws_target() {
 #include "h_plan.h"
 #include "h_rtc.h"
 #include "h_launch.h"
+#include "h_build.h"
 #include "h_run.h"
 #include "h_rccl.h"
 
@@ -186,7 +189,7 @@ int fxc_plan_destroy(fxc_plan* p) {
     }
     void* bufs[] = {p->d_win, p->d_tw, p->d_rot, p->d_win4, p->d_tw1, p->d_tw2, p->d_tw0, p->d_tw_small, p->d_stamps,
                     p->d_acc, p->d_sums, p->d_cont, p->d_rowpart, p->d_ws, p->d_stage[0], p->d_stage[1], p->d_stage[2], p->d_dc, p->d_hpre,
-                    p->d_ones, p->d_pre, p->d_tw8192, p->d_chirp, p->d_blud};
+                    p->d_ones, p->d_pre, p->d_tw8192, p->d_unit4, p->d_chirp, p->d_blud};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (p->ev_t0) (void)hipEventDestroy(p->ev_t0);
@@ -204,513 +207,6 @@ int fxc_plan_destroy(fxc_plan* p) {
     if (p->ev_fin) (void)hipEventDestroy(p->ev_fin);
     if (p->own_stream && p->stream) (void)hipStreamDestroy(p->stream);
     delete p;
-    return FXC_OK;
-}
-
-// float64 transform of any length on the host, kernel exp(+2 pi i j k / n): decimation in time over the smallest prime factor,
-// a direct sum for a prime length (the chirp-z table: 7-smooth lengths up to 8192, built once per plan)
-static std::vector<cd> host_dft(const std::vector<cd>& x) {
-    const int n = (int)x.size();
-    if (n == 1) return x;
-    int p1 = n;
-    for (int q = 2; q * q <= n; ++q)
-        if (n % q == 0) {
-            p1 = q;
-            break;
-        }
-    std::vector<cd> out((size_t)n);
-    if (p1 == n) {
-        for (int k = 0; k < n; ++k) {
-            double ar = 0.0, ai = 0.0;
-            for (int j = 0; j < n; ++j) {
-                const double ph = kTwoPi * (double)(((int64_t)j * k) % n) / (double)n;
-                const double wr = std::cos(ph), wi = std::sin(ph);
-                ar += x[j].x * wr - x[j].y * wi;
-                ai += x[j].x * wi + x[j].y * wr;
-            }
-            out[k].x = ar;
-            out[k].y = ai;
-        }
-        return out;
-    }
-    const int m = n / p1;                                   // x[p1 j + r] -> p1 transforms of m points
-    std::vector<std::vector<cd>> sub((size_t)p1);
-    for (int r = 0; r < p1; ++r) {
-        std::vector<cd> part((size_t)m);
-        for (int j = 0; j < m; ++j) part[j] = x[(size_t)p1 * j + r];
-        sub[r] = host_dft(part);
-    }
-    for (int k = 0; k < n; ++k) {
-        double ar = 0.0, ai = 0.0;
-        for (int r = 0; r < p1; ++r) {
-            const double ph = kTwoPi * (double)(((int64_t)r * k) % n) / (double)n;
-            const double wr = std::cos(ph), wi = std::sin(ph);
-            const cd v = sub[r][k % m];
-            ar += v.x * wr - v.y * wi;
-            ai += v.x * wi + v.y * wr;
-        }
-        out[k].x = ar;
-        out[k].y = ai;
-    }
-    return out;
-}
-
-static int plan_build(fxc_plan* p, const double* window, int force_path) {
-    hipDeviceProp_t prop;
-    FXC_HIP(p, hipGetDeviceProperties(&prop, p->device));
-    p->cu_count = prop.multiProcessorCount;
-    if (p->own_stream) FXC_HIP(p, hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-    FXC_HIP(p, hipEventCreate(&p->ev_t0));
-    FXC_HIP(p, hipEventCreate(&p->ev_t1));
-    FXC_HIP(p, hipEventCreateWithFlags(&p->ev_order, hipEventDisableTiming));
-
-    const int N = p->nchan, T = p->ntaps;
-    // the fused kernel channelises pairs of antenna streams: 2 antennas (X fused in) or 4 / 6 / 8 (F-only +
-    // xengine_kernel); num_samp is bounded by the 32-bit buffer-descriptor range of one stream pair
-    const bool fused_shape = ((p->n_ant == 2 || p->n_ant == 4 || p->n_ant == 6 || p->n_ant == 8) && N == fxc::fused::kN &&
-                              T == fxc::fused::kT && p->num_samp <= (1ll << 27));
-    if (force_path == FXC_PATH_FUSED && !fused_shape)
-        return fail(p, FXC_ERR_UNSUPPORTED, "no fused kernel for n_ant=%d nchan=%d ntaps=%d", p->n_ant, N, T);
-    const bool stream_shape = (p->n_ant == 2 && N == 1);
-    if (force_path == FXC_PATH_STREAM && !stream_shape)
-        return fail(p, FXC_ERR_UNSUPPORTED, "the streaming kernel needs n_ant=2, nchan=1");
-    // 2 antennas: X fused into the tiled kernel; 3 .. 8: F-only tiled kernel (an odd stream count leaves the last pair
-    // half empty) + X-engine
-    // 16 .. 256 channels, up to four taps: the wave-local variant of the tiled design (k_small.h) -- 2 antennas in one
-    // F+X kernel, 3 .. 64 through its F-only variant + X-engine
-    // (32-bit frame counters in the kernel; more than four taps: behind the pre-filter pass, whose buffer descriptors bound the stream)
-    const bool small_n = small_nchan(N) && p->num_samp / N < (1ll << 31) && (T <= 4 || p->num_samp <= (1ll << 27));
-    const bool small_shape = small_n && p->n_ant >= 2 && p->n_ant <= kMaxXAnt;
-    const bool tiled_shape = small_shape || (p->n_ant >= 2 && p->n_ant <= kMaxXAnt && tiled_nchan(N) && p->num_samp <= (1ll << 27));
-    if (force_path == FXC_PATH_TILED && !tiled_shape)
-        return fail(p, FXC_ERR_UNSUPPORTED, "no tiled kernel for n_ant=%d nchan=%d", p->n_ant, N);
-    p->path = FXC_PATH_GENERIC;
-    if (tiled_shape && (force_path == -1 || force_path == FXC_PATH_TILED)) p->path = FXC_PATH_TILED;
-    if (fused_shape && (force_path == -1 || force_path == FXC_PATH_FUSED)) p->path = FXC_PATH_FUSED;
-    if (stream_shape && (force_path == -1 || force_path == FXC_PATH_STREAM)) p->path = FXC_PATH_STREAM;
-    for (int t = 0; t < kMaxTaps; ++t) p->taps.h[t] = t < T ? (float)window[t] : 0.f;
-
-    // window: float32 copy of the float64 design (both layouts)
-    std::vector<float> wf((size_t)T * N);
-    for (size_t n = 0; n < wf.size(); ++n) wf[n] = (float)window[n];
-    FXC_HIP(p, hipMalloc(&p->d_win, wf.size() * sizeof(float)));
-    FXC_HIP(p, hipMemcpy(p->d_win, wf.data(), wf.size() * sizeof(float), hipMemcpyHostToDevice));
-
-    // generic F stage: every channel count that is not a power of two (and fits two LDS rows) takes the mixed-radix kernel;
-    // FXC_GENERIC_FFT=mixed|radix2 moves the powers of two onto it / everything off it (developer knob)
-    {
-        const char* gf = FXC_DEV_ENV("FXC_GENERIC_FFT");
-        const bool force_mixed = gf && !std::strcmp(gf, "mixed");
-        // (off the powers of two "radix2" means the direct DFT, a kernel only the developer build has)
-        const bool force_old = gf && !std::strcmp(gf, "radix2") && (p->pow2 || FXC_DEV_KERNELS);
-        // powers of two on the automatic path that no tuned kernel takes -- 4, 8 and 16384 channels -- ride along; a forced
-        // generic path keeps the radix-2 kernels (the tests' independent reference)
-        const bool auto_pow2 = force_path == -1 && (N == 4 || N == 8 || N == 16384);
-        p->mixed = N > 1 && N <= kMaxLdsFftN && !force_old && (!p->pow2 || force_mixed || auto_pow2);
-        if (p->mixed) {
-            p->mixed_plan = fxc::mixed_factor(N);
-            // (512 threads per row beyond 1320 channels, where three 256-thread workgroups stop fitting a CU's LDS: two antennas
-            // 1350 ... 2000 channels 18 - 20 % faster, F only with two frames per slot 10 - 25 %; 1120 ... 1300 slower)
-            p->mixed_tpr = fxc::mixed_threads_per_row(N, FXC_DEV_ENV_INT("FXC_MIXED_TPR", 1024), p->n_ant == 2, FXC_DEV_ENV_INT("FXC_MIXED_WIDE_FROM", 1320));
-            if (p->mixed_plan.n_stages < 0) p->mixed = false;
-        }
-        if (p->mixed) {
-            // a large prime factor costs more as an O(N p) stage than the whole transform as a chirp-z convolution
-            int pmax = 1;
-            for (int st = 0; st < p->mixed_plan.n_stages; ++st) pmax = std::max(pmax, p->mixed_plan.radix[st]);
-            // the convolution length: any 7-smooth number from 2 N - 1 up to the next power of two -- the one whose stages cost
-            // least (points x a weight per stage from the measured stage times), not the power of two itself (2049 channels:
-            // 4116 = 4 3 7 7 7 points instead of 8192)
-            int m_pow2 = 1;
-            while (m_pow2 < 2 * N - 1) m_pow2 <<= 1;
-            int m = m_pow2;
-            if (FXC_DEV_ENV_INT("FXC_BLU_SMOOTH", 1)) {
-                double best = 1e300;
-                for (int cand = 2 * N - 1; cand <= std::min(m_pow2, kBluMaxNfft); ++cand) {
-                    int rest = cand;
-                    double w = 0.0;
-                    for (int q : {4, 2, 3, 5, 7}) {
-                        const double wq = q == 4 ? 1.0 : q == 2 ? 0.8 : q == 3 ? 1.0 : q == 5 ? 1.5 : 2.0;
-                        while (rest % q == 0) {
-                            rest /= q;
-                            w += wq;
-                        }
-                    }
-                    if (rest == 1 && w * cand < best) {
-                        best = w * cand;
-                        m = cand;
-                    }
-                }
-            }
-            // measured (profiles/r04/experiments.md §7): the stage costs ~p, the chirp-z rows ~nfft / N; they cross near p = 45 nfft / N
-            const int p_min = FXC_DEV_ENV_INT("FXC_BLU_MIN_PRIME", (int)((int64_t)kBluPrimePerRatio * m / N));
-            if (pmax > p_min && m <= kBluMaxNfft) {
-                p->mixed_blu = true;
-                p->blu_nfft = m;
-                p->mixed_plan = fxc::mixed_factor(m);
-                p->mixed_tpr = fxc::mixed_threads_per_row(m, 1024);
-            }
-        }
-        p->rtc = env_int("FXC_RTC", 1) != 0;      // (read once, when the plan is made)
-        if (p->mixed && p->rtc && N <= 8192 && T <= 4 && !p->d_win4) {
-            // the lean builds of fx_spec.h (above 2048 channels, or with a prime factor of 17 ... 23) read a point's taps as one quad from
-            // L2: [N][4], zeros beyond T
-            std::vector<f4> w4((size_t)N);
-            for (int m = 0; m < N; ++m) {
-                f4 w;
-                w.x = wf[m];
-                w.y = T > 1 ? wf[(size_t)1 * N + m] : 0.f;
-                w.z = T > 2 ? wf[(size_t)2 * N + m] : 0.f;
-                w.w = T > 3 ? wf[(size_t)3 * N + m] : 0.f;
-                w4[(size_t)m] = w;
-            }
-            FXC_HIP(p, hipMalloc(&p->d_win4, w4.size() * sizeof(f4)));
-            FXC_HIP(p, hipMemcpy(p->d_win4, w4.data(), w4.size() * sizeof(f4), hipMemcpyHostToDevice));
-        }
-        p->mixed_xeng = p->mixed && p->n_ant >= 3 && FXC_DEV_ENV_INT("FXC_MIXED_XENGINE", 1);
-        if (p->mixed && !p->mixed_blu && p->n_ant == 2 && FXC_DEV_ENV_INT("FXC_MIXED_XF", 1)) {
-            const size_t rpw = (size_t)(std::max(256, p->mixed_tpr) / p->mixed_tpr);
-            // four rows (two antennas x ping-pong) must fit the LDS, with the twiddle table beside them (up to 4096 channels) or
-            // without (up to 5120)
-            p->mixed_xf = rpw * 4 * (size_t)N * sizeof(cf) <= (size_t)(160 * 1024) && N <= kMixedXPoints * p->mixed_tpr;
-            p->mixed_xf_twl = (rpw * 4 + 1) * (size_t)N * sizeof(cf) <= (size_t)(160 * 1024) && FXC_DEV_ENV_INT("FXC_MIXED_TWLDS", 1);
-            // (without the table in LDS that kernel has no register butterflies for 11 / 13: such channel counts go through the
-            // F-only kernel, which has, and xmul_kernel)
-            if (!p->mixed_xf_twl && fxc::mixed_rows_per_slot_cap(p->mixed_plan) == 1) p->mixed_xf = false;
-            // the kernel built for exactly this channel count (fx_spec.h through hiprtc, h_rtc.h): every sample fetched once,
-            // strides and trip counts compile-time constants.  FXC_RTC=0 keeps the any-shape kernel (developer knob, and what
-            // a box without hiprtc runs)
-            if (p->mixed_xf && p->rtc && p->num_samp < (1ll << 28)) {       // (32-bit byte offsets inside a chunk)
-                if (!spec_first_radices(N, T).empty()) {
-                    const SpecKernel* k = spec_kernel(p->device, N, T, kSpecC64);
-                    if (k->fn)
-                        p->spec = k;
-                    else if (env_int("FXC_RTC_VERBOSE", 0))
-                        std::fprintf(stderr, "libfxcorr: no specialised kernel for %d channels: %s\n", N, k->error.c_str());
-                }
-            }
-            // above 4096 channels there is no such kernel (sixteen points of two antennas: 256 registers of ring), but the F stage
-            // alone has one: complex64 input takes it, and xmul_kernel (h_launch.h::mixed_one_pass)
-            if (p->mixed_xf && !p->spec && N > 4096 && T <= 4 && p->rtc && p->num_samp < (1ll << 28) && FXC_DEV_ENV_INT("FXC_MIXED_XF_BYTES_ONLY", 1) &&
-                !spec_first_radices(N, T, spec_rows(N, kSpecFOnly)).empty()) {
-                const SpecKernel* k = spec_kernel(p->device, N, T, kSpecFOnly);
-                p->spec_f_tried = true;
-                p->spec_f = k->fn ? k : nullptr;
-                p->xf_bytes_only = p->spec_f != nullptr;
-            }
-        }
-    }
-    // generic FFT twiddles exp(+2 pi i j / N): [N/2] for the radix-2 kernel, [N] for the mixed-radix kernel and the direct DFT
-    if (N > 1) {
-        const int tn = p->mixed_blu ? p->blu_nfft : N;         // the chirp-z rows transform blu_nfft points
-        const int cnt = (p->pow2 && !p->mixed) ? N / 2 : tn;
-        std::vector<cf> tw((size_t)cnt);
-        for (int jx = 0; jx < cnt; ++jx) {
-            const double ph = kTwoPi * (double)jx / (double)tn;
-            tw[jx] = fxc::mk((float)std::cos(ph), (float)std::sin(ph));
-        }
-        FXC_HIP(p, hipMalloc(&p->d_tw, tw.size() * sizeof(cf)));
-        FXC_HIP(p, hipMemcpy(p->d_tw, tw.data(), tw.size() * sizeof(cf), hipMemcpyHostToDevice));
-    }
-
-    if (p->mixed_blu) {
-        // chirp c[n] = exp(+i pi n^2 / N) with n^2 reduced mod 2N (exact), and D = FFT_M(d) / M for d[m] = d[M - m] = conj(c[m]),
-        // m < N, zero elsewhere; kernel exp(+2 pi i j k / M), float64 radix-2 on the host
-        const int M = p->blu_nfft;
-        std::vector<cd> c((size_t)N);
-        for (int n = 0; n < N; ++n) {
-            const double ph = kTwoPi / 2.0 * (double)(((int64_t)n * n) % (2 * (int64_t)N)) / (double)N;
-            c[n].x = std::cos(ph);
-            c[n].y = std::sin(ph);
-        }
-        std::vector<cd> d((size_t)M);
-        for (auto& v : d) v.x = v.y = 0.0;
-        for (int m = 0; m < N; ++m) {
-            d[m].x = c[m].x;
-            d[m].y = -c[m].y;
-            if (m) d[M - m] = d[m];
-        }
-        d = host_dft(d);
-        std::vector<cf> cfl((size_t)N), dfl((size_t)M);
-        for (int n = 0; n < N; ++n) cfl[n] = fxc::mk((float)c[n].x, (float)c[n].y);
-        for (int k = 0; k < M; ++k) dfl[k] = fxc::mk((float)(d[k].x / M), (float)(d[k].y / M));
-        FXC_HIP(p, hipMalloc(&p->d_chirp, cfl.size() * sizeof(cf)));
-        FXC_HIP(p, hipMemcpy(p->d_chirp, cfl.data(), cfl.size() * sizeof(cf), hipMemcpyHostToDevice));
-        FXC_HIP(p, hipMalloc(&p->d_blud, dfl.size() * sizeof(cf)));
-        FXC_HIP(p, hipMemcpy(p->d_blud, dfl.data(), dfl.size() * sizeof(cf), hipMemcpyHostToDevice));
-    }
-
-    std::vector<cd> rot((size_t)N);
-    for (auto& r : rot) {
-        r.x = 1.0;
-        r.y = 0.0;
-    }
-    FXC_HIP(p, hipMalloc(&p->d_rot, rot.size() * sizeof(cd)));
-    FXC_HIP(p, hipMemcpy(p->d_rot, rot.data(), rot.size() * sizeof(cd), hipMemcpyHostToDevice));
-
-    const size_t acc_n = (size_t)acc_capacity(p);
-    FXC_HIP(p, hipMalloc(&p->d_acc, acc_n * sizeof(cd)));
-    FXC_HIP(p, hipMemset(p->d_acc, 0, acc_n * sizeof(cd)));
-    FXC_HIP(p, hipMalloc(&p->d_sums, (acc_n + 1) * sizeof(cd)));
-    FXC_HIP(p, hipMemset(p->d_sums, 0, (acc_n + 1) * sizeof(cd)));
-    // finalize results: pinned host memory the finishing kernels write through the device's mapping of it (coherent,
-    // so the host sees the bytes once the slot's event has completed)
-    for (int k = 0; k < fxc_plan::kResSlots; ++k) {
-        FXC_HIP(p, hipHostMalloc(reinterpret_cast<void**>(&p->h_res[k]), std::max<size_t>(acc_n, 16) * sizeof(cd),
-                                 hipHostMallocMapped | hipHostMallocCoherent));
-        FXC_HIP(p, hipHostGetDevicePointer(reinterpret_cast<void**>(&p->d_res[k]), p->h_res[k], 0));
-        FXC_HIP(p, hipEventCreateWithFlags(&p->ev_res[k], hipEventReleaseToSystem));
-    }
-
-    if (p->path == FXC_PATH_FUSED) {
-        using namespace fxc::fused;
-        std::vector<f4> w4((size_t)kN);
-        for (int r = 0; r < 16; ++r)
-            for (int jx = 0; jx < 256; ++jx) {
-                const int m = jx + 256 * r;
-                f4 w;
-                w.x = wf[0 * kN + m];
-                w.y = wf[1 * kN + m];
-                w.z = wf[2 * kN + m];
-                w.w = wf[3 * kN + m];
-                w4[r * 256 + jx] = w;
-            }
-        std::vector<cf> tw1((size_t)16 * 256), tw2((size_t)256);
-        for (int k1 = 0; k1 < 16; ++k1)
-            for (int jx = 0; jx < 256; ++jx) {
-                const double ph = kTwoPi * (double)((jx * k1) % kN) / (double)kN;
-                tw1[k1 * 256 + jx] = fxc::mk((float)std::cos(ph), (float)std::sin(ph));
-            }
-        for (int q1 = 0; q1 < 16; ++q1)
-            for (int j0 = 0; j0 < 16; ++j0) {
-                const double ph = kTwoPi * (double)(j0 * q1) / 256.0;
-                tw2[q1 * 16 + j0] = fxc::mk((float)std::cos(ph), (float)std::sin(ph));
-            }
-        FXC_HIP(p, hipMalloc(&p->d_win4, w4.size() * sizeof(f4)));
-        FXC_HIP(p, hipMemcpy(p->d_win4, w4.data(), w4.size() * sizeof(f4), hipMemcpyHostToDevice));
-        FXC_HIP(p, hipMalloc(&p->d_tw1, tw1.size() * sizeof(cf)));
-        FXC_HIP(p, hipMemcpy(p->d_tw1, tw1.data(), tw1.size() * sizeof(cf), hipMemcpyHostToDevice));
-        FXC_HIP(p, hipMalloc(&p->d_tw2, tw2.size() * sizeof(cf)));
-        FXC_HIP(p, hipMemcpy(p->d_tw2, tw2.data(), tw2.size() * sizeof(cf), hipMemcpyHostToDevice));
-        p->fused_grid_max = p->cu_count;   // one 512-thread workgroup (136 KiB LDS) per CU
-        if (const char* e = FXC_DEV_ENV("FXC_FUSED_SEG")) p->fused_seg = std::max<int64_t>(1, std::atoll(e));   // developer knob
-        FXC_HIP(p, hipFuncSetAttribute(reinterpret_cast<const void*>(&fx_fused4096_kernel<false, false>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
-        FXC_HIP(p, hipFuncSetAttribute(reinterpret_cast<const void*>(&fx_fused4096_kernel<true, false>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
-        FXC_HIP(p, hipFuncSetAttribute(reinterpret_cast<const void*>(&fx_fused4096_kernel<false, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
-        FXC_HIP(p, hipFuncSetAttribute(reinterpret_cast<const void*>(&fx_fused4096_kernel<false, true, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes + kDckLdsBytes));
-        FXC_HIP(p, hipFuncSetAttribute(reinterpret_cast<const void*>(&fx_fused4096_kernel<false, false, false, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes + kAutoLdsBytes));
-    }
-    p->small = small_shape && p->n_ant == 2 && p->path == FXC_PATH_TILED;
-    p->small_f = small_n && force_path != FXC_PATH_GENERIC;
-    if (p->small || p->small_f) {
-        const int P = N / 16;
-        // more than four taps: pfb_prefilter_kernel applies the FIR first (k_prepass.h), the wave-local kernel then runs with
-        // one unit tap -- the route the tiled channel counts take (FXC_PREFILTER=1: developer knob, the same at <= 4 taps)
-        const char* pre_env_s = FXC_DEV_ENV("FXC_PREFILTER");
-        p->prefilter = (T > 4 || (pre_env_s && std::atoi(pre_env_s) == 1));
-        if (p->prefilter) {
-            p->pre_tp = T <= 8 ? 8 : (T <= 16 ? 16 : 32);
-            std::vector<float> hp((size_t)p->pre_tp * N, 0.f);
-            for (int t = 0; t < T; ++t)
-                for (int n = 0; n < N; ++n) hp[(size_t)t * N + n] = wf[(size_t)t * N + (N - 1 - n)];
-            FXC_HIP(p, hipMalloc(&p->d_hpre, hp.size() * sizeof(float)));
-            FXC_HIP(p, hipMemcpy(p->d_hpre, hp.data(), hp.size() * sizeof(float), hipMemcpyHostToDevice));
-        }
-        std::vector<f4> w4((size_t)N);          // window quads [r P + u] = h[t N + u + P r], t = x, y, z, w (zero beyond ntaps)
-        for (int r = 0; r < 16; ++r)
-            for (int u = 0; u < P; ++u) {
-                const int m = u + P * r;
-                f4 w;
-                w.x = p->prefilter ? 1.f : wf[m];
-                w.y = (T > 1 && !p->prefilter) ? wf[(size_t)1 * N + m] : 0.f;
-                w.z = (T > 2 && !p->prefilter) ? wf[(size_t)2 * N + m] : 0.f;
-                w.w = (T > 3 && !p->prefilter) ? wf[(size_t)3 * N + m] : 0.f;
-                w4[(size_t)r * P + u] = w;
-            }
-        FXC_HIP(p, hipMalloc(&p->d_win4, w4.size() * sizeof(f4)));
-        FXC_HIP(p, hipMemcpy(p->d_win4, w4.data(), w4.size() * sizeof(f4), hipMemcpyHostToDevice));
-        std::vector<cf> tw((size_t)N);
-        for (int u = 0; u < P; ++u)
-            for (int k1 = 0; k1 < 16; ++k1) {
-                const double ph = kTwoPi * (double)((u * k1) % N) / (double)N;
-                tw[(size_t)u * 16 + k1] = fxc::mk((float)std::cos(ph), (float)std::sin(ph));
-            }
-        FXC_HIP(p, hipMalloc(&p->d_tw_small, tw.size() * sizeof(cf)));
-        FXC_HIP(p, hipMemcpy(p->d_tw_small, tw.data(), tw.size() * sizeof(cf), hipMemcpyHostToDevice));
-        const int rc = small_setup(p);
-        if (rc) return rc;
-    }
-    p->tiled_f = p->small_f || (tiled_nchan(N) && p->num_samp <= (1ll << 27) && force_path != FXC_PATH_GENERIC);
-    if (!small_nchan(N) && (p->path == FXC_PATH_TILED || p->tiled_f)) {
-        // pre-stage twiddles wN^((u + P g) k) at [g + G k][u]; stage tables as on the fused path
-        const int P = N / 16, R0 = N >= 4096 ? N / 4096 : N / 256, G = 16 / R0;
-        std::vector<cf> tw0((size_t)16 * P);
-        for (int r = 0; r < 16; ++r)
-            for (int u = 0; u < P; ++u) {
-                const int g = r % G, k = r / G;
-                const double ph = kTwoPi * (double)(((int64_t)(u + P * g) * k) % N) / (double)N;
-                tw0[(size_t)r * P + u] = fxc::mk((float)std::cos(ph), (float)std::sin(ph));
-            }
-        FXC_HIP(p, hipMalloc(&p->d_tw0, tw0.size() * sizeof(cf)));
-        FXC_HIP(p, hipMemcpy(p->d_tw0, tw0.data(), tw0.size() * sizeof(cf), hipMemcpyHostToDevice));
-        if (!p->d_tw1) {
-            std::vector<cf> tw1((size_t)16 * 256), tw2((size_t)256);
-            for (int k1 = 0; k1 < 16; ++k1)
-                for (int jx = 0; jx < 256; ++jx) {
-                    const double ph = kTwoPi * (double)((jx * k1) % 4096) / 4096.0;
-                    tw1[k1 * 256 + jx] = fxc::mk((float)std::cos(ph), (float)std::sin(ph));
-                }
-            for (int q1 = 0; q1 < 16; ++q1)
-                for (int j0 = 0; j0 < 16; ++j0) {
-                    const double ph = kTwoPi * (double)(j0 * q1) / 256.0;
-                    tw2[q1 * 16 + j0] = fxc::mk((float)std::cos(ph), (float)std::sin(ph));
-                }
-            FXC_HIP(p, hipMalloc(&p->d_tw1, tw1.size() * sizeof(cf)));
-            FXC_HIP(p, hipMemcpy(p->d_tw1, tw1.data(), tw1.size() * sizeof(cf), hipMemcpyHostToDevice));
-            FXC_HIP(p, hipMalloc(&p->d_tw2, tw2.size() * sizeof(cf)));
-            FXC_HIP(p, hipMemcpy(p->d_tw2, tw2.data(), tw2.size() * sizeof(cf), hipMemcpyHostToDevice));
-        }
-        // more than four taps (or FXC_PREFILTER=1, a developer knob to compare at <= 4): the FIR runs as its own pass
-        const char* pre_env = FXC_DEV_ENV("FXC_PREFILTER");
-        p->prefilter = (T > 4 || (pre_env && std::atoi(pre_env) == 1));
-        if (p->prefilter) {
-            p->pre_tp = T <= 8 ? 8 : (T <= 16 ? 16 : 32);
-            std::vector<float> hp((size_t)p->pre_tp * N, 0.f), ones((size_t)N, 1.f);
-            for (int t = 0; t < T; ++t)
-                for (int n = 0; n < N; ++n) hp[(size_t)t * N + n] = wf[(size_t)t * N + (N - 1 - n)];
-            FXC_HIP(p, hipMalloc(&p->d_hpre, hp.size() * sizeof(float)));
-            FXC_HIP(p, hipMemcpy(p->d_hpre, hp.data(), hp.size() * sizeof(float), hipMemcpyHostToDevice));
-            FXC_HIP(p, hipMalloc(&p->d_ones, ones.size() * sizeof(float)));
-            FXC_HIP(p, hipMemcpy(p->d_ones, ones.data(), ones.size() * sizeof(float), hipMemcpyHostToDevice));
-        }
-        // nchan 8192, two antennas, up to 16 taps: the split into two 4096-channel problems (FXC_SPLIT8192=0: off)
-        const char* split_env = FXC_DEV_ENV("FXC_SPLIT8192");
-        // ... up to four taps: two passes instead (f8192_ring_kernel and its XM form, h_launch.h::tiled_raw_sums; FXC_X8192=0: off)
-        const bool want_x8192 = N == 8192 && p->n_ant == 2 && T <= 4 && p->path == FXC_PATH_TILED && p->num_samp < (1ll << 28) &&
-                                FXC_DEV_ENV_INT("FXC_X8192", 1) && FXC_DEV_ENV_INT("FXC_F8192", 1);
-        p->split8192 = (N == 8192 && p->n_ant == 2 && T <= 16 && p->path == FXC_PATH_TILED && p->num_samp <= (1ll << 27) &&
-                        !(split_env && std::atoi(split_env) == 0) && !want_x8192);
-        if (p->split8192) {
-            p->prefilter = false;
-            p->pre_tp = T <= 4 ? 4 : (T <= 8 ? 8 : 16);
-            std::vector<float> hp((size_t)p->pre_tp * N, 0.f);
-            for (int t = 0; t < T; ++t)
-                for (int n = 0; n < N; ++n) hp[(size_t)t * N + n] = wf[(size_t)t * N + (N - 1 - n)];
-            if (p->d_hpre) (void)hipFree(p->d_hpre);
-            FXC_HIP(p, hipMalloc(&p->d_hpre, hp.size() * sizeof(float)));
-            FXC_HIP(p, hipMemcpy(p->d_hpre, hp.data(), hp.size() * sizeof(float), hipMemcpyHostToDevice));
-            std::vector<cf> tw((size_t)4096);
-            for (int n = 0; n < 4096; ++n) {
-                const double ph = kTwoPi * (double)(4095 - n) / 8192.0;
-                tw[n] = fxc::mk((float)std::cos(ph), (float)std::sin(ph));
-            }
-            FXC_HIP(p, hipMalloc(&p->d_tw8192, tw.size() * sizeof(cf)));
-            FXC_HIP(p, hipMemcpy(p->d_tw8192, tw.data(), tw.size() * sizeof(cf), hipMemcpyHostToDevice));
-            std::vector<f4> unit_taps((size_t)fxc::fused::kN);
-            for (auto& q : unit_taps) {
-                q.x = 1.f;
-                q.y = q.z = q.w = 0.f;
-            }
-            FXC_HIP(p, hipMalloc(&p->d_win4, unit_taps.size() * sizeof(f4)));
-            FXC_HIP(p, hipMemcpy(p->d_win4, unit_taps.data(), unit_taps.size() * sizeof(f4), hipMemcpyHostToDevice));
-            p->fused_grid_max = p->cu_count;
-            FXC_HIP(p, hipFuncSetAttribute(reinterpret_cast<const void*>(&fx_fused4096_kernel<false, false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, fxc::fused::kLdsBytes));
-        }
-        p->tiled_ring = ((T <= 4 || p->prefilter) && N <= 4096);
-        // 8192 channels, up to four taps: the F stage alone has a ring kernel of its own (k_tiled.h::f8192_ring_kernel), fed with the
-        // same window quads from L2.  FXC_F8192=0: the pair kernel (developer knob)
-        p->f8192 = N == 8192 && T <= 4 && !p->prefilter && FXC_DEV_ENV_INT("FXC_F8192", 1);
-        p->x8192 = want_x8192 && p->f8192;
-        if ((p->tiled_ring || p->f8192) && (!p->d_win4 || p->prefilter)) {
-            std::vector<f4> w4((size_t)N);
-            for (int r = 0; r < 16; ++r)
-                for (int u = 0; u < P; ++u) {
-                    const int m = u + P * r;
-                    f4 w;
-                    w.x = p->prefilter ? 1.f : wf[m];      // behind the pre-filter: one unit tap
-                    w.y = (T > 1 && !p->prefilter) ? wf[(size_t)1 * N + m] : 0.f;
-                    w.z = (T > 2 && !p->prefilter) ? wf[(size_t)2 * N + m] : 0.f;
-                    w.w = (T > 3 && !p->prefilter) ? wf[(size_t)3 * N + m] : 0.f;
-                    w4[(size_t)r * P + u] = w;
-                }
-            if (p->d_win4) {
-                (void)hipFree(p->d_win4);
-                p->d_win4 = nullptr;
-            }
-            FXC_HIP(p, hipMalloc(&p->d_win4, w4.size() * sizeof(f4)));
-            FXC_HIP(p, hipMemcpy(p->d_win4, w4.data(), w4.size() * sizeof(f4), hipMemcpyHostToDevice));
-        }
-        int rc = FXC_OK;
-        FXC_TILED_DISPATCH(p, rc = tiled_setup<G>(p));
-        if (rc) return rc;
-    }
-    if (p->n_ant >= 3 && p->n_ant <= kMaxXAnt) {
-        const void* xfn = nullptr;
-        switch (p->n_ant) {
-            case 3: xfn = reinterpret_cast<const void*>(&xengine_kernel<3>); break;
-            case 4: xfn = reinterpret_cast<const void*>(&xengine_kernel<4>); break;
-            case 5: xfn = reinterpret_cast<const void*>(&xengine_kernel<5>); break;
-            case 6: xfn = reinterpret_cast<const void*>(&xengine_kernel<6>); break;
-            case 7: xfn = reinterpret_cast<const void*>(&xengine_kernel<7>); break;
-            case 8: xfn = reinterpret_cast<const void*>(&xengine_kernel<8>); break;
-            default: xfn = reinterpret_cast<const void*>(&xengine_block_kernel); break;
-        }
-        // more than 8 antennas: the matrix-core X-engine (k_xmfma.h) unless FXC_XENGINE=block (developer knob: the vector
-        // kernel over blocks of 8 antennas it replaced)
-        const char* xe = FXC_DEV_ENV("FXC_XENGINE");
-        p->x_mfma = p->n_ant > kXB && !(FXC_DEV_KERNELS && xe && std::string(xe) == "block");
-        if (p->x_mfma) {
-            int per_cu = 0, threads = 0, lds = 0;
-            FXC_XMFMA_DISPATCH(p, {
-                xfn = reinterpret_cast<const void*>(&xengine_mfma_kernel<XT>);
-                threads = XMfmaGeo<XT>::kThreads;
-                lds = XMfmaGeo<XT>::kLdsBytes;
-            });
-            FXC_HIP(p, hipFuncSetAttribute(xfn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            FXC_HIP(p, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, xfn, threads, lds));
-            p->x_resident = (int64_t)std::max(per_cu, 1) * p->cu_count;
-        } else {
-        // one-wave workgroups resident per CU: the occupancy API, bounded by the register file (512 VGPRs per SIMD lane in
-        // granules of 8, at most 8 waves per SIMD) -- the API has been seen one block per CU high (MI355X_MICROARCH.md),
-        // and a launch sized one wave per CU too large would run a second round for that sliver
-        int per_cu = 0;
-        FXC_HIP(p, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, xfn, kXThreads, 0));
-        hipFuncAttributes fa;
-        FXC_HIP(p, hipFuncGetAttributes(&fa, xfn));
-        const int regs = std::max(8, (fa.numRegs + 7) / 8 * 8);
-        per_cu = std::min(per_cu, 4 * std::min(8, 512 / regs));
-        p->x_resident = (int64_t)std::max(per_cu, 1) * p->cu_count;
-        }
-    }
-    if (p->mixed) {
-        const int lds_max = 160 * 1024;
-        FXC_HIP(p, hipFuncSetAttribute(reinterpret_cast<const void*>(&pfb_fft_mixed_kernel<true, 1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-        FXC_HIP(p, hipFuncSetAttribute(reinterpret_cast<const void*>(&pfb_fft_mixed_kernel<true, 2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-        FXC_HIP(p, hipFuncSetAttribute(reinterpret_cast<const void*>(&pfb_fft_mixed_kernel<false, 1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-        FXC_HIP(p, hipFuncSetAttribute(reinterpret_cast<const void*>(&pfb_fft_mixed_kernel<true, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-        FXC_HIP(p, hipFuncSetAttribute(reinterpret_cast<const void*>(&pfb_fft_mixed_kernel<true, 2, true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-        FXC_HIP(p, hipFuncSetAttribute(reinterpret_cast<const void*>(&pfb_fft_mixed_kernel<false, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-        FXC_HIP(p, hipFuncSetAttribute(reinterpret_cast<const void*>(&pfb_fft_mixed_kernel<false, 2, true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-        FXC_HIP(p, hipFuncSetAttribute(reinterpret_cast<const void*>(&pfb_fft_mixed_kernel<false, 1, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-        FXC_HIP(p, hipFuncSetAttribute(reinterpret_cast<const void*>(&pfb_fft_mixed_kernel<true, 1, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-        FXC_HIP(p, hipFuncSetAttribute(reinterpret_cast<const void*>(&pfb_fft_mixed_kernel<false, 1, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    } else if (N > 1) {
-        const int lds = N * (int)sizeof(cf);
-        if (p->pow2)
-            FXC_HIP(p, hipFuncSetAttribute(reinterpret_cast<const void*>(&fft_pow2_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-#if FXC_DEV_KERNELS
-        else
-            FXC_HIP(p, hipFuncSetAttribute(reinterpret_cast<const void*>(&dft_any_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-#endif
-    }
     return FXC_OK;
 }
 
@@ -751,7 +247,11 @@ int fxc_plan_create(fxc_plan** out, int device, int n_ant, int nchan, int ntaps,
     while ((1 << p->lg2n) < nchan) ++p->lg2n;
     p->own_stream = (stream == FXC_STREAM_OWNED);
     p->stream = p->own_stream ? nullptr : static_cast<hipStream_t>(stream);
-    const int rc = plan_build(p, window, force_path);
+    int rc = plan_route(p, force_path);
+    if (rc == FXC_OK) {
+        plan_spec(p);
+        rc = plan_build(p, window);
+    }
     if (rc != FXC_OK) {
         g_lib_error = p->error;
         fxc_plan_destroy(p);
@@ -868,24 +368,8 @@ int fxc_set_products(fxc_plan* p, int products) {
     if (autos == p->autos) return FXC_OK;
     FXC_DEVICE(p, p->device);
     if (autos && !p->x_resident_auto) {
-        // one-wave workgroups resident per CU, bounded by the register file as for the cross-only X-engines (plan_build)
-        const void* xfn = nullptr;
-        switch (p->n_ant) {
-            case 2: xfn = reinterpret_cast<const void*>(&xengine_kernel<2, true>); break;
-            case 3: xfn = reinterpret_cast<const void*>(&xengine_kernel<3, true>); break;
-            case 4: xfn = reinterpret_cast<const void*>(&xengine_kernel<4, true>); break;
-            case 5: xfn = reinterpret_cast<const void*>(&xengine_kernel<5, true>); break;
-            case 6: xfn = reinterpret_cast<const void*>(&xengine_kernel<6, true>); break;
-            case 7: xfn = reinterpret_cast<const void*>(&xengine_kernel<7, true>); break;
-            default: xfn = reinterpret_cast<const void*>(&xengine_kernel<8, true>); break;
-        }
-        int per_cu = 0;
-        FXC_HIP(p, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, xfn, kXThreads, 0));
-        hipFuncAttributes fa;
-        FXC_HIP(p, hipFuncGetAttributes(&fa, xfn));
-        const int regs = std::max(8, (fa.numRegs + 7) / 8 * 8);
-        per_cu = std::min(per_cu, 4 * std::min(8, 512 / regs));
-        p->x_resident_auto = (int64_t)std::max(per_cu, 1) * p->cu_count;
+        const int rc = xengine_resident(p, xengine_fn<true>(p->n_ant), &p->x_resident_auto);
+        if (rc) return rc;
     }
     // the rows past the cross rows start from zero (they were never written, or an earlier autos plan cleared them)
     FXC_HIP(p, hipMemsetAsync(p->d_acc, 0, (size_t)acc_capacity(p) * sizeof(cd), p->stream));

@@ -20,17 +20,30 @@ int mixed_wave_local(const fxc_plan* p, bool fused_x) {
     return v && (fused_x || p->mixed_tpr >= 16);
 }
 
+// may this plan take the kernels built for its channel count (fx_spec.h through hiprtc, h_rtc.h)?  Mixed-radix plans of up to four taps
+// (the frame ring lives in registers) with 32-bit byte offsets inside a chunk, unless FXC_RTC=0; spec_first_radices then says which
+// builds the channel count has
+bool spec_eligible(const fxc_plan* p) { return p->mixed && p->rtc && p->ntaps <= 4 && p->num_samp < (1ll << 28); }
+
+// the build `variant` of the kernel for this plan's channel count, compiled (or found) on the first call only: *slot keeps it, or
+// nullptr where there is none (FXC_RTC_VERBOSE says why)
+const SpecKernel* spec_once(fxc_plan* p, const SpecKernel** slot, bool* tried, int variant) {
+    if (!*tried) {
+        *tried = true;
+        const SpecKernel* k = spec_kernel(p->device, p->nchan, p->ntaps, variant);
+        *slot = k->fn ? k : nullptr;
+        if (!k->fn && env_int("FXC_RTC_VERBOSE", 0))
+            std::fprintf(stderr, "libfxcorr: %d channels: no build %d of the kernel per channel count (%s): the any-shape kernels take its calls\n",
+                         p->nchan, variant, k->error.c_str());
+    }
+    return *slot;
+}
+
 // the F stage built for exactly this channel count (fx_spec.h, FXM_FONLY), compiled (or found) on first use; nullptr: the shape has none
 const SpecKernel* spec_f_kernel(fxc_plan* p) {
-    if (!p->spec_f_tried) {
+    if (!p->spec_f_tried && !(spec_eligible(p) && !spec_first_radices(p->nchan, p->ntaps, spec_rows(p->nchan, kSpecFOnly)).empty()))
         p->spec_f_tried = true;
-        if (p->mixed && p->ntaps <= 4 && p->num_samp < (1ll << 28) && p->rtc &&
-            !spec_first_radices(p->nchan, p->ntaps, spec_rows(p->nchan, kSpecFOnly)).empty()) {
-            const SpecKernel* k = spec_kernel(p->device, p->nchan, p->ntaps, kSpecFOnly);
-            p->spec_f = k->fn ? k : nullptr;
-        }
-    }
-    return p->spec_f;
+    return spec_once(p, &p->spec_f, &p->spec_f_tried, kSpecFOnly);
 }
 
 int run_channelize(fxc_plan* p, const cf* x, cf* spec, int64_t n_streams, int ant = 1) {
@@ -56,19 +69,17 @@ int run_channelize(fxc_plan* p, const cf* x, cf* spec, int64_t n_streams, int an
         FXC_HIP(p, hipGetLastError());
         return FXC_OK;
     }
-    if (p->mixed && p->ntaps <= 4 && p->num_samp < (1ll << 28) && p->rtc) {
-        // the F stage built for exactly this channel count (fx_spec.h, FXM_FONLY: a workgroup carries two streams through the
-        // stages, the last butterfly stores the spectra); compiled on first use
-        if (const SpecKernel* k = spec_f_kernel(p)) {
-            const int64_t pairs = (n_streams + k->shape.rows - 1) / k->shape.rows;      // (groups of streams: a workgroup's rows)
-            const int64_t ws = spec_wg_splits(p, k, pairs, false);
-            if (pairs * ws > (1ll << 30)) return fail(p, FXC_ERR_ARG, "too many streams for one launch");
-            SpecArgs a = {x, p->d_win, spec, p->d_tw, nullptr, (long long)p->num_samp, (long long)p->n_pts, (long long)n_streams, (int)ws, ant,
-                          reinterpret_cast<const float*>(p->d_win4), k->d_tw1, 0, nullptr};
-            void* params[] = {&a};
-            FXC_HIP(p, hipModuleLaunchKernel(k->fn, (unsigned)(pairs * ws), 1, 1, (unsigned)k->shape.threads(), 1, 1, 0, p->stream, params, nullptr));
-            return FXC_OK;
-        }
+    // the F stage built for exactly this channel count (fx_spec.h, FXM_FONLY: a workgroup carries two streams through the
+    // stages, the last butterfly stores the spectra); compiled on first use
+    if (const SpecKernel* k = spec_f_kernel(p)) {
+        const int64_t pairs = (n_streams + k->shape.rows - 1) / k->shape.rows;      // (groups of streams: a workgroup's rows)
+        const int64_t ws = spec_wg_splits(p, k, pairs, false);
+        if (pairs * ws > (1ll << 30)) return fail(p, FXC_ERR_ARG, "too many streams for one launch");
+        SpecArgs a = {x, p->d_win, spec, p->d_tw, nullptr, (long long)p->num_samp, (long long)p->n_pts, (long long)n_streams, (int)ws, ant,
+                      reinterpret_cast<const float*>(p->d_win4), k->d_tw1, 0, nullptr};
+        void* params[] = {&a};
+        FXC_HIP(p, hipModuleLaunchKernel(k->fn, (unsigned)(pairs * ws), 1, 1, (unsigned)k->shape.threads(), 1, 1, 0, p->stream, params, nullptr));
+        return FXC_OK;
     }
     if (p->mixed && p->nchan > kMixedMaxN) {
         // one LDS row, the other in the output (pfb_fft_mixed_kernel, BIG): one frame per workgroup pass, 1024 threads
@@ -145,14 +156,7 @@ bool two_pass_xm(fxc_plan* p, bool bytes_in) {
     if (bytes_in || p->n_ant != 2 || !p->mixed || p->mixed_blu || p->nchan <= 4096 || p->mixed_xeng) return false;
     if (!spec_f_kernel(p) || p->spec_f->shape.rows != 1) return false;
     if (!FXC_DEV_ENV_INT("FXC_XM", 1)) return false;
-    if (!p->spec_xm_tried) {
-        p->spec_xm_tried = true;
-        const SpecKernel* k = spec_kernel(p->device, p->nchan, p->ntaps, kSpecXM);
-        p->spec_xm = k->fn ? k : nullptr;
-        if (!k->fn && env_int("FXC_RTC_VERBOSE", 0))
-            std::fprintf(stderr, "libfxcorr: %d channels: no second-pass kernel (%s): both antennas' spectra + xmul_kernel\n", p->nchan, k->error.c_str());
-    }
-    return p->spec_xm != nullptr;
+    return spec_once(p, &p->spec_xm, &p->spec_xm_tried, kSpecXM) != nullptr;      // (none: both antennas' spectra + xmul_kernel)
 }
 int two_pass_raw_sums(fxc_plan* p, const cf* x, int64_t n_chunks, int n_splits, cf* spec, cf* raw) {
     const SpecKernel* kf = p->spec_f;
@@ -178,14 +182,7 @@ int mixed_fx_raw_sums(fxc_plan* p, const cf* x, int64_t n_chunks, int n_splits, 
     if (p->spec) {
         // the build of fx_spec.h made for this channel count (h_rtc.h); its byte-ingest twin is compiled on first use
         const SpecKernel* k = p->spec;
-        if (dc_u8) {
-            if (!p->spec_u8_tried) {
-                p->spec_u8_tried = true;
-                const SpecKernel* k8 = spec_kernel(p->device, p->nchan, p->ntaps, kSpecU8);
-                p->spec_u8 = k8->fn ? k8 : nullptr;
-            }
-            k = p->spec_u8;
-        }
+        if (dc_u8) k = spec_once(p, &p->spec_u8, &p->spec_u8_tried, kSpecU8);
         if (k && n_splits % k->shape.slots == 0 && n_splits / k->shape.slots >= 1) {
             const int wg_splits = n_splits / k->shape.slots;
             const int64_t grid = n_chunks * wg_splits;
@@ -427,6 +424,7 @@ int launch_fused(fxc_plan* p, const cf* x, int64_t n_pairs, cf* out, bool spec_o
                  bool rows_are_chunks, int64_t num_samp, bool dck) {
     using namespace fxc::fused;
     if (num_samp == 0) num_samp = p->num_samp;      // (the 8192-channel split runs on half-size streams)
+    const f4* win4 = p->split8192 ? p->d_unit4 : p->d_win4;      // (the split's own pass has applied the FIR: one unit tap)
     const int grid = fused_grid(p, n_pairs);
     const int seg = (int)p->fused_seg;
     if (n_pairs * p->n_pts >= (1ll << 31)) return fail(p, FXC_ERR_ARG, "more than 2^31 frames in one launch");
@@ -446,18 +444,18 @@ int launch_fused(fxc_plan* p, const cf* x, int64_t n_pairs, cf* out, bool spec_o
     hipExtLaunchKernelGGL(KERNEL, dim3(grid), dim3(kThreads), LDS, p->stream, ev_a, ev_b, 0, __VA_ARGS__)
     if (dc_u8 && dck)
         FXC_FUSED_LAUNCH((fx_fused4096_kernel<false, true, true>), kLdsBytes + kDckLdsBytes, x, num_samp, p->n_pts, n_pairs,
-                         p->d_win4, p->d_tw1, p->d_tw2, out, stamps, dc_u8, seg, (int)unit, rows_are_chunks ? 1 : 0);
+                         win4, p->d_tw1, p->d_tw2, out, stamps, dc_u8, seg, (int)unit, rows_are_chunks ? 1 : 0);
     else if (dc_u8)
-        FXC_FUSED_LAUNCH((fx_fused4096_kernel<false, true>), kLdsBytes, x, num_samp, p->n_pts, n_pairs, p->d_win4, p->d_tw1,
+        FXC_FUSED_LAUNCH((fx_fused4096_kernel<false, true>), kLdsBytes, x, num_samp, p->n_pts, n_pairs, win4, p->d_tw1,
                          p->d_tw2, out, stamps, dc_u8, seg, (int)unit, rows_are_chunks ? 1 : 0);
     else if (spec_out)      // (`unit` carries the stream pairs per chunk here)
-        FXC_FUSED_LAUNCH((fx_fused4096_kernel<true, false>), kLdsBytes, x, num_samp, p->n_pts, n_pairs, p->d_win4, p->d_tw1,
+        FXC_FUSED_LAUNCH((fx_fused4096_kernel<true, false>), kLdsBytes, x, num_samp, p->n_pts, n_pairs, win4, p->d_tw1,
                          p->d_tw2, out, stamps, (const cf*)nullptr, seg, p->n_ant / 2, 1);
     else if (p->autos && p->nchan == kN)      // (plans with autos: rows of [3][kN], fx_fused4096_kernel AUTOS)
-        FXC_FUSED_LAUNCH((fx_fused4096_kernel<false, false, false, true>), kLdsBytes + kAutoLdsBytes, x, num_samp, p->n_pts, n_pairs, p->d_win4,
+        FXC_FUSED_LAUNCH((fx_fused4096_kernel<false, false, false, true>), kLdsBytes + kAutoLdsBytes, x, num_samp, p->n_pts, n_pairs, win4,
                          p->d_tw1, p->d_tw2, out, stamps, (const cf*)nullptr, seg, (int)unit, rows_are_chunks ? 1 : 0);
     else
-        FXC_FUSED_LAUNCH((fx_fused4096_kernel<false, false>), kLdsBytes, x, num_samp, p->n_pts, n_pairs, p->d_win4, p->d_tw1,
+        FXC_FUSED_LAUNCH((fx_fused4096_kernel<false, false>), kLdsBytes, x, num_samp, p->n_pts, n_pairs, win4, p->d_tw1,
                          p->d_tw2, out, stamps, (const cf*)nullptr, seg, (int)unit, rows_are_chunks ? 1 : 0);
 #undef FXC_FUSED_LAUNCH
     if (ev_a) p->kev.emplace_back(ev_a, ev_b);

@@ -63,7 +63,7 @@ struct fxc_plan {
     bool mixed = false;            // generic F stage = pfb_fft_mixed_kernel (FIR + mixed-radix FFT in one pass)
     fxc::MixedPlan mixed_plan{};
     int mixed_tpr = 256;           // threads per row
-    bool mixed_blu = false;        // a large prime factor (plan_build): chirp-z rows of blu_nfft points (F only)
+    bool mixed_blu = false;        // a large prime factor (plan_route): chirp-z rows of blu_nfft points (F only)
     int blu_nfft = 0;
     cf* d_chirp = nullptr;         // [nchan] exp(+i pi n^2 / nchan)
     cf* d_blud = nullptr;          // [blu_nfft] FFT of the wrapped conjugate chirp / blu_nfft
@@ -74,6 +74,7 @@ struct fxc_plan {
     // ... and, where the shape allows, in the build of fx_spec.h made for exactly this channel count (h_rtc.h); spec_u8: its
     // byte-ingest twin, compiled when bytes first arrive
     const SpecKernel* spec = nullptr;
+    bool spec_tried = false;
     const SpecKernel* spec_u8 = nullptr;
     bool spec_u8_tried = false;
     const SpecKernel* spec_f = nullptr;      // the F stage alone (fxc_channelize, 3 + antennas), built on first use
@@ -89,7 +90,7 @@ struct fxc_plan {
     float* d_win = nullptr;        // [ntaps*nchan] float (generic)
     cf* d_tw = nullptr;            // generic FFT twiddles
     cd* d_rot = nullptr;           // [nchan]
-    f4* d_win4 = nullptr;          // fused
+    f4* d_win4 = nullptr;          // [nchan] window quads (one unit tap behind the pre-filter): fused, tiled ring, wave-local, lean fx_spec.h
     cf* d_tw1 = nullptr;
     cf* d_tw2 = nullptr;
     cf* d_tw0 = nullptr;           // tiled: pre-stage twiddles [16][nchan/16]
@@ -111,6 +112,7 @@ struct fxc_plan {
     bool x8192 = false;            // nchan 8192, 2 antennas, ntaps <= 4: two passes (f8192_ring_kernel, then its XM form); FXC_X8192=0: off
     bool split8192 = false;        // nchan 8192, 2 antennas: pfb_split8192_kernel + the 4096-channel fused kernel
     cf* d_tw8192 = nullptr;        // [4096] w8192^(4095 - n')
+    f4* d_unit4 = nullptr;         // [4096] unit-tap window quads of the fused kernel behind pfb_split8192_kernel
     unsigned long long* d_stamps = nullptr;   // diagnostic builds only
     int fused_grid_max = 0;
     int64_t x_resident = 0;        // workgroups of the X-engine kernel the device holds at once
