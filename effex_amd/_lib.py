@@ -78,6 +78,7 @@ SIGNATURES = {
     "fxc_spec_probe": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_char_p, _c.c_char_p, _c.c_int]),
     "fxc_last_error": (_c.c_char_p, [_vp]),
     "fxc_set_rot": (_c.c_int, [_vp, _vp]),
+    "fxc_set_rot_ant": (_c.c_int, [_vp, _vp]),
     "fxc_set_products": (_c.c_int, [_vp, _c.c_int]),
     "fxc_plan_products": (_c.c_int, [_vp, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
     "fxc_channelize": (_c.c_int, [_vp, _vp, _vp, _c.c_int64, _c.c_int]),
@@ -109,6 +110,7 @@ SIGNATURES = {
     "fxc_host_alloc": (_c.c_int, [_c.POINTER(_vp), _c.c_int64]),
     "fxc_host_free": (_c.c_int, [_vp]),
     "fxc_estimate_delay": (_c.c_int, [_vp, _vp, _vp, _c.c_int64, _c.c_int, _c.c_double, _c.POINTER(_c.c_double)]),
+    "fxc_estimate_delays": (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int, _c.c_double, _c.c_int, _vp]),
     "fxc_pipe_create": (_c.c_int, [_c.POINTER(_vp), _vp, _c.c_int64, _c.c_int, _c.c_int, _c.c_double]),
     "fxc_pipe_create_u8": (_c.c_int, [_c.POINTER(_vp), _vp, _c.c_int64, _c.c_int, _c.c_int, _c.c_double, _c.c_int]),
     "fxc_pipe_create_iq": (_c.c_int, [_c.POINTER(_vp), _vp, _c.c_int64, _c.c_int, _c.c_int, _c.c_double, _c.c_int,

@@ -67,6 +67,7 @@ ncclResult_t ncclCommGetAsyncError(ncclComm_t comm, ncclResult_t* asyncError);
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/fxcorr.h"
@@ -189,7 +190,7 @@ int fxc_plan_destroy(fxc_plan* p) {
     }
     void* bufs[] = {p->d_win, p->d_tw, p->d_rot, p->d_win4, p->d_tw1, p->d_tw2, p->d_tw0, p->d_tw_small, p->d_stamps,
                     p->d_acc, p->d_sums, p->d_cont, p->d_rowpart, p->d_ws, p->d_stage[0], p->d_stage[1], p->d_stage[2], p->d_dc, p->d_hpre,
-                    p->d_ones, p->d_pre, p->d_tw8192, p->d_unit4, p->d_chirp, p->d_blud};
+                    p->d_ones, p->d_pre, p->d_tw8192, p->d_unit4, p->d_chirp, p->d_blud, p->d_rot_ant, p->d_pair};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (p->ev_t0) (void)hipEventDestroy(p->ev_t0);
@@ -352,6 +353,32 @@ int fxc_set_rot(fxc_plan* p, const double* rot_re_im) {
     // ordered after any queued finish kernel that still reads the old table
     FXC_HIP(p, hipStreamSynchronize(p->stream));
     FXC_HIP(p, hipMemcpy(p->d_rot, rot_re_im, (size_t)p->nchan * sizeof(cd), hipMemcpyHostToDevice));
+    p->rot_ant = false;
+    return FXC_OK;
+}
+
+int fxc_set_rot_ant(fxc_plan* p, const double* rot_ant_re_im) {
+    if (!p || !rot_ant_re_im) return fail(p, FXC_ERR_ARG, "NULL argument");
+    if (p->n_ant < 2) return fail(p, FXC_ERR_ARG, "per-antenna rot needs 2 or more antennas, the plan has %d", p->n_ant);
+    FXC_DEVICE(p, p->device);
+    FXC_HIP(p, hipStreamSynchronize(p->stream));
+    const size_t N = (size_t)p->nchan;
+    const cd* r = reinterpret_cast<const cd*>(rot_ant_re_im);
+    if (p->n_ant == 2) {
+        // the one baseline's w = r_1 conj(r_0), in float64, into the shared table: every 2-antenna route runs as it is
+        std::vector<cd> w(N);
+        for (size_t k = 0; k < N; ++k) {
+            const cd ra = r[k], rb = r[N + k];
+            w[k].x = rb.x * ra.x + rb.y * ra.y;
+            w[k].y = rb.y * ra.x - rb.x * ra.y;
+        }
+        FXC_HIP(p, hipMemcpy(p->d_rot, w.data(), N * sizeof(cd), hipMemcpyHostToDevice));
+        p->rot_ant = false;
+        return FXC_OK;
+    }
+    if (!p->d_rot_ant) FXC_HIP(p, hipMalloc(&p->d_rot_ant, (size_t)p->n_ant * N * sizeof(cd)));
+    FXC_HIP(p, hipMemcpy(p->d_rot_ant, r, (size_t)p->n_ant * N * sizeof(cd), hipMemcpyHostToDevice));
+    p->rot_ant = true;
     return FXC_OK;
 }
 
@@ -708,13 +735,23 @@ int finalize_enqueue(fxc_plan* p, const cd* sums_src, int mode, double bandwidth
     } else if (mode == FXC_MODE_SPECTRUM) {
         const int rc = flush_pending(p);
         if (rc) return rc;
-        hipExtLaunchKernelGGL(finalize_spectrum_kernel, dim3(grid_for(n, 256, p->cu_count)), dim3(256), 0, p->stream, nullptr,
-                              big ? nullptr : p->ev_res[slot], 0, sums_src, out, p->d_rot, p->nchan, p->n_prod, p->n_base);
+        if (p->rot_ant)
+            hipExtLaunchKernelGGL(finalize_spectrum_kernel<true>, dim3(grid_for(n, 256, p->cu_count)), dim3(256), 0, p->stream, nullptr,
+                                  big ? nullptr : p->ev_res[slot], 0, sums_src, out, ant_rot_arg(p), p->nchan, p->n_prod, p->n_base);
+        else
+            hipExtLaunchKernelGGL(finalize_spectrum_kernel<false>, dim3(grid_for(n, 256, p->cu_count)), dim3(256), 0, p->stream, nullptr,
+                                  big ? nullptr : p->ev_res[slot], 0, sums_src, out, p->d_rot, p->nchan, p->n_prod, p->n_base);
     }
-    if (mode == FXC_MODE_CONTINUUM)
-        hipExtLaunchKernelGGL(finalize_continuum_kernel, dim3(p->n_prod), dim3(256), 0, p->stream, nullptr,
-                              big ? nullptr : p->ev_res[slot], 0, sums_src, out, p->d_rot, p->nchan, p->n_prod, 1.0 / bandwidth,
-                              p->n_base);
+    if (mode == FXC_MODE_CONTINUUM) {
+        if (p->rot_ant)
+            hipExtLaunchKernelGGL(finalize_continuum_kernel<true>, dim3(p->n_prod), dim3(256), 0, p->stream, nullptr,
+                                  big ? nullptr : p->ev_res[slot], 0, sums_src, out, ant_rot_arg(p), p->nchan, p->n_prod,
+                                  1.0 / bandwidth, p->n_base);
+        else
+            hipExtLaunchKernelGGL(finalize_continuum_kernel<false>, dim3(p->n_prod), dim3(256), 0, p->stream, nullptr,
+                                  big ? nullptr : p->ev_res[slot], 0, sums_src, out, p->d_rot, p->nchan, p->n_prod, 1.0 / bandwidth,
+                                  p->n_base);
+    }
     FXC_HIP(p, hipGetLastError());
     if (big) {
         FXC_HIP(p, hipEventRecord(p->ev_fin, p->stream));
@@ -1086,78 +1123,136 @@ int fxc_fx_accumulate_u8(fxc_plan* p, const void* iq_u8, int64_t n_chunks, int m
     return fx_u8_entry(p, iq_u8, nullptr, n_chunks, mem_kind, FXC_MODE_SPECTRUM, 1.0, remove_dc, false);
 }
 
-int fxc_estimate_delay(fxc_plan* p, const void* iq0, const void* iq1, int64_t n, int mem_kind, double rate,
-                       double* delay_s) {
-    if (!p || !iq0 || !iq1 || !delay_s) return fail(p, FXC_ERR_ARG, "NULL argument");
+namespace {
+
+// Delays of n_streams equal-length streams against streams[ref] (effex.py:583-627 for each pair (ref, s)): delays_s[s] is
+// (n - (imax + delta)) / rate of the correlation f_ref * conj(f_s), delays_s[ref] = 0.  The reference's spectrum is formed once;
+// the other streams go through in batches (k_delay.h) of as many as fit the workspace target (FXC_WS_MB), every batch's
+// arg-max words into one result block: one copy to the host and one synchronisation for the whole call.
+int estimate_delays_batch(fxc_plan* p, const cf* const* streams, int n_streams, int ref, int64_t n, int mem_kind, double rate,
+                          double* delays_s) {
     if (n < 2 || n > (1ll << 28)) return fail(p, FXC_ERR_ARG, "n=%lld out of range", (long long)n);
     if (!(rate > 0.0)) return fail(p, FXC_ERR_ARG, "rate must be > 0");
     if (mem_kind != FXC_MEM_HOST && mem_kind != FXC_MEM_DEVICE) return fail(p, FXC_ERR_ARG, "bad mem_kind %d", mem_kind);
+    if (n_streams < 2 || ref < 0 || ref >= n_streams) return fail(p, FXC_ERR_ARG, "ref=%d outside [0, %d)", ref, n_streams);
     FXC_DEVICE(p, p->device);
     int lg = 1;
     while ((1ll << lg) < 2 * n) ++lg;
     const int64_t len = 1ll << lg;
-    // workspace: 4 transform buffers + staging for host inputs + result words
+    // workspace: the reference's two transform buffers, two per stream of a batch, staging for host inputs (the reference
+    // and a batch), the result words of every stream (best[n_streams], then out3[n_streams][3])
     const int64_t buf_bytes = len * (int64_t)sizeof(cf);
-    const int64_t stage_bytes = mem_kind == FXC_MEM_HOST ? 2 * n * (int64_t)sizeof(cf) : 0;
-    int rc = ensure_ws(p, 4 * buf_bytes + stage_bytes + 256);
+    const int64_t stage_one = mem_kind == FXC_MEM_HOST ? (n * (int64_t)sizeof(cf) + 255) / 256 * 256 : 0;
+    const int64_t res_bytes = ((int64_t)n_streams * (8 + 3 * (int64_t)sizeof(cf)) + 255) / 256 * 256;
+    const int64_t fixed = 2 * buf_bytes + stage_one + res_bytes, per_stream = 2 * buf_bytes + stage_one;
+    const int n_other = n_streams - 1;
+    const int64_t fit = (ws_target() - fixed) / per_stream;
+    const int batch = (int)std::max<int64_t>(1, std::min<int64_t>(fit, std::min(n_other, kDelayBatch)));
+    int rc = ensure_ws(p, fixed + batch * per_stream);
     if (rc) return rc;
     char* ws = static_cast<char*>(p->d_ws);
-    cf* a[2] = {reinterpret_cast<cf*>(ws), reinterpret_cast<cf*>(ws + buf_bytes)};
-    cf* b[2] = {reinterpret_cast<cf*>(ws + 2 * buf_bytes), reinterpret_cast<cf*>(ws + 3 * buf_bytes)};
-    const cf *x0 = static_cast<const cf*>(iq0), *x1 = static_cast<const cf*>(iq1);
-    if (mem_kind == FXC_MEM_HOST) {
-        cf* st = reinterpret_cast<cf*>(ws + 4 * buf_bytes);
-        FXC_HIP(p, hipMemcpyAsync(st, iq0, (size_t)n * sizeof(cf), hipMemcpyHostToDevice, p->stream));
-        FXC_HIP(p, hipMemcpyAsync(st + n, iq1, (size_t)n * sizeof(cf), hipMemcpyHostToDevice, p->stream));
-        x0 = st;
-        x1 = st + n;
-    }
-    unsigned long long* best = reinterpret_cast<unsigned long long*>(ws + 4 * buf_bytes + stage_bytes);
-    cf* out3 = reinterpret_cast<cf*>(ws + 4 * buf_bytes + stage_bytes + 16);
-    const int g_len = grid_for(len, 256, p->cu_count);
-    hipLaunchKernelGGL(delay_pad_kernel, dim3(g_len), dim3(256), 0, p->stream, x0, a[0], n, len);
-    hipLaunchKernelGGL(delay_pad_kernel, dim3(g_len), dim3(256), 0, p->stream, x1, b[0], n, len);
-    // one transform = radix-16 passes, then one radix-8 / 4 / 2 pass for the remaining bits of lg
-    auto transform = [&](cf* (&buf)[2], int& cur, double sign) {
+    cf* rbuf[2] = {reinterpret_cast<cf*>(ws), reinterpret_cast<cf*>(ws + buf_bytes)};
+    cf* sbuf[2] = {reinterpret_cast<cf*>(ws + 2 * buf_bytes), reinterpret_cast<cf*>(ws + (2 + batch) * buf_bytes)};
+    cf* stage = reinterpret_cast<cf*>(ws + (2 + 2 * (int64_t)batch) * buf_bytes);      // [1 + batch][stage_one]
+    char* res = ws + fixed + batch * per_stream - res_bytes;
+    unsigned long long* best = reinterpret_cast<unsigned long long*>(res);
+    cf* out3 = reinterpret_cast<cf*>(res + 8 * (int64_t)n_streams);
+    const int64_t stage_elems = stage_one / (int64_t)sizeof(cf);
+    // stream s as the device sees it: staged into row `row` of the staging block when it is host memory
+    auto device_stream = [&](int s, int row) -> const cf* {
+        if (mem_kind == FXC_MEM_DEVICE) return streams[s];
+        cf* st = stage + row * stage_elems;
+        const hipError_t e = hipMemcpyAsync(st, streams[s], (size_t)n * sizeof(cf), hipMemcpyHostToDevice, p->stream);
+        return e == hipSuccess ? st : nullptr;
+    };
+    // forward (sign -1, kernel exp(-2 pi i ...) like cp.fft.fft) or inverse (+1, un-normalised: the peak fit is scale free)
+    // transform of `nb` buffers = radix-16 passes, then one radix-8 / 4 / 2 pass for the remaining bits of lg
+    auto transform = [&](cf* (&buf)[2], int nb, double sign) {
+        int cur = 0;
         int64_t pp = 1;
         for (int bits = lg; bits > 0;) {
             const int r = bits >= 4 ? 4 : bits;
-            const int grid = grid_for(len >> r, 256, p->cu_count);
-            if (r == 4) hipLaunchKernelGGL(stockham_stage_kernel<16>, dim3(grid), dim3(256), 0, p->stream, buf[cur], buf[cur ^ 1], len, pp, sign);
-            else if (r == 3) hipLaunchKernelGGL(stockham_stage_kernel<8>, dim3(grid), dim3(256), 0, p->stream, buf[cur], buf[cur ^ 1], len, pp, sign);
-            else if (r == 2) hipLaunchKernelGGL(stockham_stage_kernel<4>, dim3(grid), dim3(256), 0, p->stream, buf[cur], buf[cur ^ 1], len, pp, sign);
-            else hipLaunchKernelGGL(stockham_stage_kernel<2>, dim3(grid), dim3(256), 0, p->stream, buf[cur], buf[cur ^ 1], len, pp, sign);
+            const dim3 grid(grid_for(len >> r, 256, p->cu_count), nb);
+            if (r == 4) hipLaunchKernelGGL(stockham_stage_kernel<16>, grid, dim3(256), 0, p->stream, buf[cur], buf[cur ^ 1], len, pp, sign);
+            else if (r == 3) hipLaunchKernelGGL(stockham_stage_kernel<8>, grid, dim3(256), 0, p->stream, buf[cur], buf[cur ^ 1], len, pp, sign);
+            else if (r == 2) hipLaunchKernelGGL(stockham_stage_kernel<4>, grid, dim3(256), 0, p->stream, buf[cur], buf[cur ^ 1], len, pp, sign);
+            else hipLaunchKernelGGL(stockham_stage_kernel<2>, grid, dim3(256), 0, p->stream, buf[cur], buf[cur ^ 1], len, pp, sign);
             pp <<= r;
             bits -= r;
             cur ^= 1;
         }
+        return cur;
     };
-    int cur = 0, cur_b = 0;
-    transform(a, cur, -1.0);       // forward transforms, kernel exp(-2 pi i ...) like cp.fft.fft
-    transform(b, cur_b, -1.0);
-    hipLaunchKernelGGL(mul_conj_kernel, dim3(g_len), dim3(256), 0, p->stream, a[cur], b[cur_b], len);   // f0 * conj(f1)
-    transform(a, cur, 1.0);        // inverse transform (un-normalised: the peak fit is scale free)
-    FXC_HIP(p, hipMemsetAsync(best, 0, 8, p->stream));
-    hipLaunchKernelGGL(delay_argmax_kernel, dim3(grid_for(2 * n, 256, p->cu_count)), dim3(256), 0, p->stream, a[cur], best,
-                       n, len);
-    hipLaunchKernelGGL(delay_fetch_kernel, dim3(1), dim3(64), 0, p->stream, a[cur], best, out3, n, len);
-    FXC_HIP(p, hipGetLastError());
-    unsigned long long h_best = 0;
-    cf h3[3];
-    FXC_HIP(p, hipMemcpyAsync(&h_best, best, 8, hipMemcpyDeviceToHost, p->stream));
-    FXC_HIP(p, hipMemcpyAsync(h3, out3, sizeof h3, hipMemcpyDeviceToHost, p->stream));
+    const int g_len = grid_for(len, 256, p->cu_count);
+    FXC_HIP(p, hipMemsetAsync(best, 0, 8 * (size_t)n_streams, p->stream));
+    DelayStreams xs{};
+    xs.x[0] = device_stream(ref, 0);
+    if (!xs.x[0]) return fail(p, FXC_ERR_HIP, "host staging copy failed");
+    hipLaunchKernelGGL(delay_pad_kernel, dim3(g_len, 1), dim3(256), 0, p->stream, xs, rbuf[0], n, len);
+    const cf* f_ref = rbuf[transform(rbuf, 1, -1.0)];
+    std::vector<int> others;
+    for (int s = 0; s < n_streams; ++s)
+        if (s != ref) others.push_back(s);
+    for (int b0 = 0; b0 < n_other; b0 += batch) {
+        const int nb = std::min(batch, n_other - b0);
+        for (int q = 0; q < nb; ++q) {
+            xs.x[q] = device_stream(others[b0 + q], 1 + q);
+            if (!xs.x[q]) return fail(p, FXC_ERR_HIP, "host staging copy failed");
+        }
+        hipLaunchKernelGGL(delay_pad_kernel, dim3(g_len, nb), dim3(256), 0, p->stream, xs, sbuf[0], n, len);
+        const int cur = transform(sbuf, nb, -1.0);
+        hipLaunchKernelGGL(mul_conj_kernel, dim3(g_len, nb), dim3(256), 0, p->stream, f_ref, sbuf[cur], len);   // f_ref * conj(f_s)
+        cf* const xc = sbuf[cur];
+        cf* inv[2] = {xc, sbuf[cur ^ 1]};
+        cf* const r = inv[transform(inv, nb, 1.0)];
+        // the batch's streams are consecutive in `others`, so their result words are too
+        hipLaunchKernelGGL(delay_argmax_kernel, dim3(grid_for(2 * n, 256, p->cu_count), nb), dim3(256), 0, p->stream, r, best + b0, n,
+                           len);
+        hipLaunchKernelGGL(delay_fetch_kernel, dim3(nb), dim3(64), 0, p->stream, r, best + b0, out3 + 3 * (int64_t)b0, n, len);
+        FXC_HIP(p, hipGetLastError());
+    }
+    std::vector<char> h_res((size_t)res_bytes);
+    FXC_HIP(p, hipMemcpyAsync(h_res.data(), res, (size_t)res_bytes, hipMemcpyDeviceToHost, p->stream));
     FXC_HIP(p, hipStreamSynchronize(p->stream));
-    const int64_t imax = (int64_t)(0xFFFFFFFFull - (h_best & 0xFFFFFFFFull));
-    if (imax + 1 >= 2 * n)
-        return fail(p, FXC_ERR_STATE, "correlation peak at the last lag (the reference raises IndexError here)");
-    // effex.py:619-625
-    const double xprev = std::hypot((double)h3[0].x, (double)h3[0].y);
-    const double xbest = std::hypot((double)h3[1].x, (double)h3[1].y);
-    const double xnext = std::hypot((double)h3[2].x, (double)h3[2].y);
-    const double delta = 0.5 * (std::log(xprev) - std::log(xnext)) /
-                         (std::log(xprev) - 2.0 * std::log(xbest) + std::log(xnext));
-    *delay_s = ((double)n - ((double)imax + delta)) / rate;
+    const unsigned long long* h_best = reinterpret_cast<const unsigned long long*>(h_res.data());
+    const cf* h3_all = reinterpret_cast<const cf*>(h_res.data() + 8 * (int64_t)n_streams);
+    for (int q = 0; q < n_other; ++q) {
+        const cf* h3 = h3_all + 3 * q;
+        const int64_t imax = (int64_t)(0xFFFFFFFFull - (h_best[q] & 0xFFFFFFFFull));
+        if (imax + 1 >= 2 * n)
+            return fail(p, FXC_ERR_STATE, "correlation peak at the last lag (the reference raises IndexError here)");
+        // effex.py:619-625
+        const double xprev = std::hypot((double)h3[0].x, (double)h3[0].y);
+        const double xbest = std::hypot((double)h3[1].x, (double)h3[1].y);
+        const double xnext = std::hypot((double)h3[2].x, (double)h3[2].y);
+        const double delta = 0.5 * (std::log(xprev) - std::log(xnext)) /
+                             (std::log(xprev) - 2.0 * std::log(xbest) + std::log(xnext));
+        delays_s[others[q]] = ((double)n - ((double)imax + delta)) / rate;
+    }
+    delays_s[ref] = 0.0;
     return FXC_OK;
+}
+
+}  // namespace
+
+int fxc_estimate_delay(fxc_plan* p, const void* iq0, const void* iq1, int64_t n, int mem_kind, double rate,
+                       double* delay_s) {
+    if (!p || !iq0 || !iq1 || !delay_s) return fail(p, FXC_ERR_ARG, "NULL argument");
+    const cf* streams[2] = {static_cast<const cf*>(iq0), static_cast<const cf*>(iq1)};
+    double d[2];
+    const int rc = estimate_delays_batch(p, streams, 2, 0, n, mem_kind, rate, d);
+    if (rc == FXC_OK) *delay_s = d[1];
+    return rc;
+}
+
+int fxc_estimate_delays(fxc_plan* p, const void* x, int64_t n, int mem_kind, double rate, int ref, double* delays_s) {
+    if (!p || !x || !delays_s) return fail(p, FXC_ERR_ARG, "NULL argument");
+    if (p->n_ant < 2) return fail(p, FXC_ERR_ARG, "delays need 2 or more antennas, the plan has %d", p->n_ant);
+    if (ref < 0 || ref >= p->n_ant) return fail(p, FXC_ERR_ARG, "ref=%d outside [0, %d)", ref, p->n_ant);
+    if (n < 2 || n > (1ll << 28)) return fail(p, FXC_ERR_ARG, "n=%lld out of range", (long long)n);
+    std::vector<const cf*> streams((size_t)p->n_ant);
+    for (int a = 0; a < p->n_ant; ++a) streams[(size_t)a] = static_cast<const cf*>(x) + (int64_t)a * n;
+    return estimate_delays_batch(p, streams.data(), p->n_ant, ref, n, mem_kind, rate, delays_s);
 }
 
 int fxc_pipe_destroy(fxc_pipe* q) {

@@ -385,6 +385,13 @@ int plan_build(fxc_plan* p, const double* window) {
     one.x = 1.0;
     one.y = 0.0;
     if (int rc = upload(p, &p->d_rot, std::vector<cd>((size_t)N, one))) return rc;
+    // baseline -> (a, b) for per-antenna rot (fxc_set_rot_ant), in the order of the X-engines: (0,1),(0,2)..(A-2,A-1)
+    if (p->n_ant >= 3) {
+        std::vector<int2> pair;
+        for (int a = 0; a < p->n_ant; ++a)
+            for (int b = a + 1; b < p->n_ant; ++b) pair.push_back(make_int2(a, b));
+        if (int rc = upload(p, &p->d_pair, pair)) return rc;
+    }
 
     const size_t acc_n = (size_t)acc_capacity(p);
     FXC_HIP(p, hipMalloc(&p->d_acc, acc_n * sizeof(cd)));

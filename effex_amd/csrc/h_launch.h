@@ -337,22 +337,38 @@ FoldFinish with_autos(const fxc_plan* p, const FoldFinish& fin) {
     return f;
 }
 
+// the plan's per-antenna tables (fxc_set_rot_ant) as the finish kernels' ANT operand
+AntRot ant_rot_arg(const fxc_plan* p) { return {p->d_rot_ant, p->d_pair}; }
+
+// `fin` for the ANT instantiations: it finalises (out != nullptr) on a plan with per-antenna tables
+bool ant_finish(const fxc_plan* p, const FoldFinish& fin) { return p->rot_ant && fin.out; }
+FinishT<true> with_ant_rot(const fxc_plan* p, const FoldFinish& f) { return {f.sums, f.out, ant_rot_arg(p), f.count, f.reset, f.auto_from}; }
+
 // acc[p][bin] += sum of the raw rows [n_prod][nchan], and `fin` for every element: two launches, one when the rows are few
 // `done`: an event to complete with the last kernel (it rides on that dispatch: no packet of its own in the stream)
 int fold_rows(fxc_plan* p, const cf* raw, cd* part, int64_t n_rows, int layout, const FoldFinish& fin_in, hipEvent_t done = nullptr) {
     const FoldFinish fin = with_autos(p, fin_in);
+    const bool ant = ant_finish(p, fin);
     const int64_t row_len = (int64_t)p->n_prod * p->nchan;
     const unsigned cols = (unsigned)((row_len + 255) / 256);
     const int splits = fold_splits(n_rows, row_len);
     if (splits == 1) {
-        hipExtLaunchKernelGGL(fold_finish_kernel<cf>, dim3(cols), dim3(256 * kFoldPhases), 0, p->stream, nullptr, done, 0, raw,
-                              n_rows, p->d_acc, p->nchan, p->n_prod, layout, fin);
+        if (ant)
+            hipExtLaunchKernelGGL(fold_finish_kernel<cf, true>, dim3(cols), dim3(256 * kFoldPhases), 0, p->stream, nullptr, done, 0,
+                                  raw, n_rows, p->d_acc, p->nchan, p->n_prod, layout, with_ant_rot(p, fin));
+        else
+            hipExtLaunchKernelGGL(fold_finish_kernel<cf>, dim3(cols), dim3(256 * kFoldPhases), 0, p->stream, nullptr, done, 0, raw,
+                                  n_rows, p->d_acc, p->nchan, p->n_prod, layout, fin);
     } else {
         hipLaunchKernelGGL(fold_partial_kernel, dim3(cols, splits), dim3(256 * kFoldPhases), 0, p->stream, raw, part, row_len,
                            n_rows, splits);
         // the partials are in the rows' own layout
-        hipExtLaunchKernelGGL(fold_finish_kernel<cd>, dim3(cols), dim3(256 * kFoldPhases), 0, p->stream, nullptr, done, 0,
-                              (const cd*)part, (int64_t)splits, p->d_acc, p->nchan, p->n_prod, layout, fin);
+        if (ant)
+            hipExtLaunchKernelGGL(fold_finish_kernel<cd, true>, dim3(cols), dim3(256 * kFoldPhases), 0, p->stream, nullptr, done, 0,
+                                  (const cd*)part, (int64_t)splits, p->d_acc, p->nchan, p->n_prod, layout, with_ant_rot(p, fin));
+        else
+            hipExtLaunchKernelGGL(fold_finish_kernel<cd>, dim3(cols), dim3(256 * kFoldPhases), 0, p->stream, nullptr, done, 0,
+                                  (const cd*)part, (int64_t)splits, p->d_acc, p->nchan, p->n_prod, layout, fin);
     }
     FXC_HIP(p, hipGetLastError());
     return FXC_OK;
@@ -367,8 +383,13 @@ int flush_pending(fxc_plan* p, const FoldFinish* fin, hipEvent_t done) {
     }
     if (fin) {
         const int64_t n = (int64_t)p->n_prod * p->nchan;
-        hipExtLaunchKernelGGL(acc_finish_kernel, dim3(grid_for(n, 256, p->cu_count)), dim3(256), 0, p->stream, nullptr, done, 0,
-                              p->d_acc, p->nchan, p->n_prod, with_autos(p, *fin));
+        const FoldFinish f = with_autos(p, *fin);
+        if (ant_finish(p, f))
+            hipExtLaunchKernelGGL(acc_finish_kernel<true>, dim3(grid_for(n, 256, p->cu_count)), dim3(256), 0, p->stream, nullptr, done,
+                                  0, p->d_acc, p->nchan, p->n_prod, with_ant_rot(p, f));
+        else
+            hipExtLaunchKernelGGL(acc_finish_kernel<false>, dim3(grid_for(n, 256, p->cu_count)), dim3(256), 0, p->stream, nullptr, done,
+                                  0, p->d_acc, p->nchan, p->n_prod, f);
         FXC_HIP(p, hipGetLastError());
     } else if (done) {
         FXC_HIP(p, hipEventRecord(done, p->stream));

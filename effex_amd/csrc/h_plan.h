@@ -90,6 +90,11 @@ struct fxc_plan {
     float* d_win = nullptr;        // [ntaps*nchan] float (generic)
     cf* d_tw = nullptr;            // generic FFT twiddles
     cd* d_rot = nullptr;           // [nchan]
+    // per-antenna rot (fxc_set_rot_ant, 3 and more antennas; 2 antennas fold theirs into d_rot): the finish kernels' ANT
+    // instantiations read r_a[k] from d_rot_ant[n_ant][nchan] (allocated by the first call) and baseline p's (a, b) from d_pair
+    bool rot_ant = false;
+    cd* d_rot_ant = nullptr;
+    int2* d_pair = nullptr;        // [n_base] (plan_build)
     f4* d_win4 = nullptr;          // [nchan] window quads (one unit tap behind the pre-filter): fused, tiled ring, wave-local, lean fx_spec.h
     cf* d_tw1 = nullptr;
     cf* d_tw2 = nullptr;

@@ -220,22 +220,51 @@ int fx_accumulate_dev(fxc_plan* p, const cf* x, int64_t n_chunks, const cf* dc_u
     return FXC_OK;
 }
 
+// Rows of a plan with per-antenna tables (fxc_set_rot_ant: 3 and more antennas) go to the rows kernels' ANT instantiations.
+// Every route of those plans lays its rows out as [chunk][n_prod] with the n_base cross rows first, so the kernels take
+// n_prod and n_cross from the plan then.  The streaming, 8192-channel and 2-antenna tiled routes serve two antennas only
+// (fxc_set_rot_ant folds those into the shared table) and launch the shared-rot kernels themselves.
+
+// SPECTRUM rows
+void launch_rows_spectrum(fxc_plan* p, const cf* raw, cf* out, int nchan, int64_t rows, int n_splits, int64_t split_stride,
+                          float inv_pts, int slots, LeadRows lead, int n_prod, int n_cross) {
+    const dim3 grid(grid_for(rows * nchan, 256, p->cu_count));
+    if (p->rot_ant)
+        hipLaunchKernelGGL(rows_spectrum_kernel<true>, grid, dim3(256), 0, p->stream, raw, out, ant_rot_arg(p), nchan, rows, n_splits,
+                           split_stride, inv_pts, slots, lead, p->n_prod, p->n_base);
+    else
+        hipLaunchKernelGGL(rows_spectrum_kernel<false>, grid, dim3(256), 0, p->stream, raw, out, p->d_rot, nchan, rows, n_splits,
+                           split_stride, inv_pts, slots, lead, n_prod, n_cross);
+}
+
 // CONTINUUM rows: one workgroup per row when there are rows enough to fill the chip, else bin slices + a second small kernel
 int launch_rows_continuum(fxc_plan* p, const cf* raw, cd* out, int nchan, int64_t rows, int n_splits, int64_t split_stride,
                           double scale, int slots, LeadRows lead, int n_prod = 1, int n_cross = 1) {
+    if (p->rot_ant) {
+        n_prod = p->n_prod;
+        n_cross = p->n_base;
+    }
     const int slices = (int)std::min<int64_t>(32, nchan / 128);
     if (slices >= 2 && rows * 2 <= p->cu_count && rows <= 65535) {
         const int rg = grow(p, &p->d_rowpart, &p->rowpart_bytes, (size_t)rows * slices * sizeof(cd));
         if (rg) return rg;
         cd* part = static_cast<cd*>(p->d_rowpart);
-        hipLaunchKernelGGL(rows_continuum_part_kernel, dim3(slices, (unsigned)rows), dim3(256), 0, p->stream, raw, part, p->d_rot, nchan,
-                           rows, n_splits, split_stride, slots, lead, slices, n_prod, n_cross);
+        if (p->rot_ant)
+            hipLaunchKernelGGL(rows_continuum_part_kernel<true>, dim3(slices, (unsigned)rows), dim3(256), 0, p->stream, raw, part,
+                               ant_rot_arg(p), nchan, rows, n_splits, split_stride, slots, lead, slices, n_prod, n_cross);
+        else
+            hipLaunchKernelGGL(rows_continuum_part_kernel<false>, dim3(slices, (unsigned)rows), dim3(256), 0, p->stream, raw, part,
+                               p->d_rot, nchan, rows, n_splits, split_stride, slots, lead, slices, n_prod, n_cross);
         hipLaunchKernelGGL(rows_continuum_fin_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, p->stream, part, out, rows, slices,
                            scale);
     } else {
-        hipLaunchKernelGGL(rows_continuum_kernel, dim3((int)std::min<int64_t>(rows, (int64_t)p->cu_count * 8)),
-                           dim3(continuum_threads(nchan)), 0, p->stream, raw, out, p->d_rot, nchan, rows, n_splits, split_stride, scale,
-                           slots, lead, n_prod, n_cross);
+        const dim3 grid((int)std::min<int64_t>(rows, (int64_t)p->cu_count * 8));
+        if (p->rot_ant)
+            hipLaunchKernelGGL(rows_continuum_kernel<true>, grid, dim3(continuum_threads(nchan)), 0, p->stream, raw, out, ant_rot_arg(p),
+                               nchan, rows, n_splits, split_stride, scale, slots, lead, n_prod, n_cross);
+        else
+            hipLaunchKernelGGL(rows_continuum_kernel<false>, grid, dim3(continuum_threads(nchan)), 0, p->stream, raw, out, p->d_rot,
+                               nchan, rows, n_splits, split_stride, scale, slots, lead, n_prod, n_cross);
     }
     return FXC_OK;
 }
@@ -253,9 +282,8 @@ int autos_rows_dev(fxc_plan* p, const cf* x, void* out, int64_t n_chunks, int mo
         if (rc) return rc;
         const int64_t rows = nc * p->n_prod;
         if (mode == FXC_MODE_SPECTRUM)
-            hipLaunchKernelGGL(rows_spectrum_kernel, dim3(grid_for(rows * p->nchan, 256, p->cu_count)), dim3(256), 0, p->stream, raw,
-                               static_cast<cf*>(out) + c0 * p->n_prod * p->nchan, p->d_rot, p->nchan, rows, a.xr, rows * p->nchan,
-                               inv_pts, 0, kNoLead, p->n_prod, p->n_base);
+            launch_rows_spectrum(p, raw, static_cast<cf*>(out) + c0 * p->n_prod * p->nchan, p->nchan, rows, a.xr, rows * p->nchan,
+                                 inv_pts, 0, kNoLead, p->n_prod, p->n_base);
         else {
             rc = launch_rows_continuum(p, raw, static_cast<cd*>(out) + c0 * p->n_prod, p->nchan, rows, a.xr, rows * p->nchan, cscale, 0,
                                        kNoLead, p->n_prod, p->n_base);
@@ -285,7 +313,7 @@ int fx_rows_dev(fxc_plan* p, const cf* x, void* out, int64_t n_chunks, int mode,
             if (rc) return rc;
             // raw[block][chunk]: the blocks play the role of the generic path's splits (nchan = n_base = 1)
             if (mode == FXC_MODE_SPECTRUM)
-                hipLaunchKernelGGL(rows_spectrum_kernel, dim3(grid_for(nc, 256, p->cu_count)), dim3(256), 0, p->stream, raw,
+                hipLaunchKernelGGL(rows_spectrum_kernel<false>, dim3(grid_for(nc, 256, p->cu_count)), dim3(256), 0, p->stream, raw,
                                    static_cast<cf*>(out) + c0, p->d_rot, 1, nc, nb, nc, inv_pts, 0, kNoLead, 1, 1);
             else {
                 rc = launch_rows_continuum(p, raw, static_cast<cd*>(out) + c0, 1, nc, nb, nc, cscale, 0, kNoLead);
@@ -314,9 +342,8 @@ int fx_rows_dev(fxc_plan* p, const cf* x, void* out, int64_t n_chunks, int mode,
             const int xr = x_ranges(p, 1);
             const int64_t xr_stride = rows * p->nchan;
             if (mode == FXC_MODE_SPECTRUM)
-                hipLaunchKernelGGL(rows_spectrum_kernel, dim3(grid_for(rows * p->nchan, 256, p->cu_count)), dim3(256), 0,
-                                   p->stream, raw, static_cast<cf*>(out) + c0 * p->n_prod * p->nchan, p->d_rot, p->nchan,
-                                   rows, xr, xr_stride, inv_pts, fused_layout(p), lead, p->n_prod, p->n_base);
+                launch_rows_spectrum(p, raw, static_cast<cf*>(out) + c0 * p->n_prod * p->nchan, p->nchan, rows, xr, xr_stride, inv_pts,
+                                     fused_layout(p), lead, p->n_prod, p->n_base);
             else {
                 rc = launch_rows_continuum(p, raw, static_cast<cd*>(out) + c0 * p->n_prod, p->nchan, rows, xr, xr_stride, cscale, fused_layout(p), lead,
                                            p->n_prod, p->n_base);
@@ -338,7 +365,7 @@ int fx_rows_dev(fxc_plan* p, const cf* x, void* out, int64_t n_chunks, int mode,
             if (rc) return rc;
             const LeadRows lead = fused_lead(p, 2 * nc);
             if (mode == FXC_MODE_SPECTRUM)
-                hipLaunchKernelGGL(rows_spectrum_kernel, dim3(grid_for(nc * N, 256, p->cu_count)), dim3(256), 0, p->stream,
+                hipLaunchKernelGGL(rows_spectrum_kernel<false>, dim3(grid_for(nc * N, 256, p->cu_count)), dim3(256), 0, p->stream,
                                    raw, static_cast<cf*>(out) + c0 * N, p->d_rot, N, nc, 1, (int64_t)0, inv_pts, 3, lead, 1, 1);
             else {
                 rc = launch_rows_continuum(p, raw, static_cast<cd*>(out) + c0, N, nc, 1, (int64_t)0, cscale, 3, lead);
@@ -364,7 +391,7 @@ int fx_rows_dev(fxc_plan* p, const cf* x, void* out, int64_t n_chunks, int mode,
                                 raw, dc_u8 ? dc_u8 + c0 * 2 : nullptr);
             if (rc) return rc;
             if (mode == FXC_MODE_SPECTRUM)
-                hipLaunchKernelGGL(rows_spectrum_kernel, dim3(grid_for(nc * N, 256, p->cu_count)), dim3(256), 0, p->stream,
+                hipLaunchKernelGGL(rows_spectrum_kernel<false>, dim3(grid_for(nc * N, 256, p->cu_count)), dim3(256), 0, p->stream,
                                    raw, static_cast<cf*>(out) + c0 * N, p->d_rot, N, nc, n_splits, nc * N, inv_pts, 0, kNoLead, 1, 1);
             else {
                 rc = launch_rows_continuum(p, raw, static_cast<cd*>(out) + c0, N, nc, n_splits, nc * N, cscale, 0, kNoLead);
@@ -411,9 +438,8 @@ int fx_rows_dev(fxc_plan* p, const cf* x, void* out, int64_t n_chunks, int mode,
         const int64_t rows = nc * p->n_base;
         const int64_t split_stride = rows * p->nchan;
         if (mode == FXC_MODE_SPECTRUM)
-            hipLaunchKernelGGL(rows_spectrum_kernel, dim3(grid_for(rows * p->nchan, 256, p->cu_count)), dim3(256), 0,
-                               p->stream, raw, static_cast<cf*>(out) + c0 * p->n_base * p->nchan, p->d_rot, p->nchan,
-                               rows, g.n_splits, split_stride, inv_pts, 0, kNoLead, 1, 1);
+            launch_rows_spectrum(p, raw, static_cast<cf*>(out) + c0 * p->n_base * p->nchan, p->nchan, rows, g.n_splits, split_stride,
+                                 inv_pts, 0, kNoLead, 1, 1);
         else {
             rc = launch_rows_continuum(p, raw, static_cast<cd*>(out) + c0 * p->n_base, p->nchan, rows, g.n_splits, split_stride, cscale, 0, kNoLead);
             if (rc) return rc;

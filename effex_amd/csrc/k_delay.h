@@ -10,8 +10,18 @@ namespace {
 // and one radix-8 / 4 / 2 pass for what is left of log2 L -- 5 passes for the reference's 2 x 262144 points
 // (19 with the radix-2 passes of rounds 1-2); the linear correlation is the same for any padded length
 // L >= 2n, so L is the next power of two and lags are re-indexed to the reference's 2n layout.
+// Every kernel takes a batch of streams in blockIdx.y (fxc_estimate_delays: all antennas against one reference in a few
+// launches); the transform buffers are [batch][len].  Each element's arithmetic is that of a batch of one, so the batched
+// delays are bit for bit the pairwise ones.
 // ------------------------------------------------------------------------------------------
-__global__ void delay_pad_kernel(const cf* __restrict__ x, cf* __restrict__ out, int64_t n, int64_t len) {
+constexpr int kDelayBatch = 64;      // streams per batch at most (a plan has up to 64 antennas)
+struct DelayStreams {
+    const cf* x[kDelayBatch];
+};
+
+__global__ void delay_pad_kernel(DelayStreams xs, cf* __restrict__ out, int64_t n, int64_t len) {
+    const cf* __restrict__ x = xs.x[blockIdx.y];
+    out += blockIdx.y * len;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < len; idx += stride)
         out[idx] = idx < n ? x[idx] : fxc::mk(0.f, 0.f);
@@ -23,6 +33,8 @@ __global__ void delay_pad_kernel(const cf* __restrict__ x, cf* __restrict__ out,
 // the kernel exp(+2 pi i ..) (fx_math.h, fx_tiled.h); the forward transform (sign = -1) runs them on conjugated data.
 template <int R>
 __global__ void stockham_stage_kernel(const cf* __restrict__ in, cf* __restrict__ out, int64_t len, int64_t p, double sign) {
+    in += blockIdx.y * len;
+    out += blockIdx.y * len;
     const int64_t sub = len / R;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < sub; j += stride) {
@@ -53,16 +65,20 @@ __global__ void stockham_stage_kernel(const cf* __restrict__ in, cf* __restrict_
     }
 }
 
-__global__ void mul_conj_kernel(cf* __restrict__ a, const cf* __restrict__ b, int64_t len) {
+// b[s] = f_ref * conj(b[s]): the reference's spectrum against each stream's of the batch
+__global__ void mul_conj_kernel(const cf* __restrict__ ref, cf* __restrict__ b, int64_t len) {
+    b += blockIdx.y * len;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < len; idx += stride)
-        a[idx] = fxc::cmulc(a[idx], b[idx]);
+        b[idx] = fxc::cmulc(ref[idx], b[idx]);
 }
 
 // arg-max of |r| over the reference's index i = 0..2n-1 (lag i - n, stored at (i - n) mod len); first maximum
-// wins like numpy.argmax.  best[0] = packed (|r|^2 as ordered bits << 32 | ~i) maximised with atomicMax.
+// wins like numpy.argmax.  best[s] = packed (|r|^2 as ordered bits << 32 | ~i) maximised with atomicMax.
 __global__ void delay_argmax_kernel(const cf* __restrict__ r, unsigned long long* __restrict__ best, int64_t n,
                                     int64_t len) {
+    r += blockIdx.y * len;
+    best += blockIdx.y;
     unsigned long long loc = 0;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < 2 * n; i += stride) {
@@ -79,9 +95,12 @@ __global__ void delay_argmax_kernel(const cf* __restrict__ r, unsigned long long
     if ((threadIdx.x & 63) == 0) atomicMax(best, loc);
 }
 
-// out3 = r at reference indices imax-1 (python wrap for -1), imax, imax+1
+// out3 = r at reference indices imax-1 (python wrap for -1), imax, imax+1; one workgroup per stream of the batch
 __global__ void delay_fetch_kernel(const cf* __restrict__ r, const unsigned long long* __restrict__ best,
                                    cf* __restrict__ out3, int64_t n, int64_t len) {
+    r += blockIdx.x * len;
+    best += blockIdx.x;
+    out3 += 3 * blockIdx.x;
     const int64_t imax = (int64_t)(0xFFFFFFFFull - (best[0] & 0xFFFFFFFFull));
     const int d = threadIdx.x;
     if (d < 3) {

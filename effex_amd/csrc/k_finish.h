@@ -63,8 +63,28 @@ __device__ __forceinline__ bool auto_row(int64_t row, int n_prod, int n_cross) {
     return n_cross < n_prod && (int)(row % n_prod) >= n_cross;
 }
 
+// Per-antenna rot (fxc_set_rot_ant, 3 and more antennas): cross row p, baseline (a, b) = pair[p], takes
+// w[k] = r_b[k] conj(r_a[k]) from the antennas' tables tab[n_ant][nchan], formed in float64; the kernels then multiply by
+// conj(w) exactly as they do by conj(rot[k]).  ANT = false: the plan's one shared table, the code of the shared-rot plans.
+struct AntRot {
+    const cd* tab;
+    const int2* pair;
+};
+template <bool ANT> using RotArg = std::conditional_t<ANT, AntRot, const cd* __restrict__>;
+
+__device__ __forceinline__ cd ant_rot(const AntRot& r, int64_t p, int k, int nchan) {
+    const int2 ab = r.pair[p];
+    const cd ra = r.tab[(int64_t)ab.x * nchan + k], rb = r.tab[(int64_t)ab.y * nchan + k];
+    cd w;
+    w.x = rb.x * ra.x + rb.y * ra.y;
+    w.y = rb.y * ra.x - rb.x * ra.y;
+    return w;
+}
+
 // SPECTRUM rows: out[c][p][(k + N/2) % N] = (sum_split raw) * conj(rot[k]) / n_pts   (effex.py:520-521)
-__global__ void rows_spectrum_kernel(const cf* __restrict__ raw, cf* __restrict__ out, const cd* __restrict__ rot,
+// ANT: the rows are [chunk][n_prod] (baseline p = row % n_prod)
+template <bool ANT = false>
+__global__ void rows_spectrum_kernel(const cf* __restrict__ raw, cf* __restrict__ out, RotArg<ANT> rot,
                                      int nchan, int64_t rows, int n_splits, int64_t split_stride, float inv_pts,
                                      int slots, LeadRows lead, int n_prod, int n_cross) {
     const int64_t total = rows * nchan;
@@ -99,7 +119,15 @@ __global__ void rows_spectrum_kernel(const cf* __restrict__ raw, cf* __restrict_
             out[row * nchan + ks] = fxc::mk(ar * inv_pts, 0.f);
             continue;
         }
-        const float cr = (float)rot[k].x, ci = (float)rot[k].y;
+        float cr, ci;
+        if constexpr (ANT) {
+            const cd w = ant_rot(rot, row % n_prod, k, nchan);
+            cr = (float)w.x;
+            ci = (float)w.y;
+        } else {
+            cr = (float)rot[k].x;
+            ci = (float)rot[k].y;
+        }
         // (ar + i ai) * (cr - i ci)
         const float orr = (ar * cr + ai * ci) * inv_pts;
         const float oi = (ai * cr - ar * ci) * inv_pts;
@@ -144,8 +172,9 @@ __device__ __forceinline__ void sum_splits(const cf* src, int n_splits, int64_t 
 // so each bin gathers up to grid - 1 leading-part rows -- 72 us with 256 threads, the largest item of that call
 constexpr int kContinuumThreads = 1024;
 inline int continuum_threads(int nchan) { return nchan >= kContinuumThreads ? kContinuumThreads : 256; }
+template <bool ANT = false>
 __global__ __launch_bounds__(kContinuumThreads) void rows_continuum_kernel(const cf* __restrict__ raw, cd* __restrict__ out,
-                                                            const cd* __restrict__ rot, int nchan, int64_t rows,
+                                                            RotArg<ANT> rot, int nchan, int64_t rows,
                                                             int n_splits, int64_t split_stride, double scale,
                                                             int slots, LeadRows lead, int n_prod, int n_cross) {
     __shared__ double red[kContinuumThreads];
@@ -163,7 +192,11 @@ __global__ __launch_bounds__(kContinuumThreads) void rows_continuum_kernel(const
                 ar += xr;
                 continue;
             }
-            const cd w = rot[k];
+            cd w;
+            if constexpr (ANT)
+                w = ant_rot(rot, row % n_prod, k, nchan);
+            else
+                w = rot[k];
             ar += xr * w.x + xi * w.y;
             ai += xi * w.x - xr * w.y;
         }
@@ -182,8 +215,9 @@ __global__ __launch_bounds__(kContinuumThreads) void rows_continuum_kernel(const
 // workgroups (grid = slices x rows) that leave float64 partial sums, and rows_continuum_fin_kernel adds them in slice
 // order -- one workgroup per row gathered a chunk pair's up to 255 leading-part rows for all 4096 bins in 33 us, the largest
 // item of that call.
+template <bool ANT = false>
 __global__ __launch_bounds__(256) void rows_continuum_part_kernel(const cf* __restrict__ raw, cd* __restrict__ part,
-                                                                 const cd* __restrict__ rot, int nchan, int64_t rows, int n_splits,
+                                                                 RotArg<ANT> rot, int nchan, int64_t rows, int n_splits,
                                                                  int64_t split_stride, int slots, LeadRows lead, int slices,
                                                                  int n_prod, int n_cross) {
     __shared__ double red[256];
@@ -203,7 +237,11 @@ __global__ __launch_bounds__(256) void rows_continuum_part_kernel(const cf* __re
             ar += xr;
             continue;
         }
-        const cd w = rot[k];
+        cd w;
+        if constexpr (ANT)
+            w = ant_rot(rot, row % n_prod, k, nchan);
+        else
+            w = rot[k];
         ar += xr * w.x + xi * w.y;
         ai += xi * w.x - xr * w.y;
     }
@@ -234,21 +272,24 @@ __global__ void rows_continuum_fin_kernel(const cd* __restrict__ part, cd* __res
 // What the kernel that finishes an integration does with an accumulator element besides updating it: export it for the
 // cross-rank reduce, finalise it, clear it -- in the same launch instead of export + finalize + device-to-host copy +
 // memset (round 2: four commands and 50 us of gaps per integration).
-struct FoldFinish {
+template <bool ANT>
+struct FinishT {
     cd* sums;         // != nullptr: sums[idx] = acc[idx] (raw float64 sums) and sums[n] = {count, 0} -- fxc_acc_export
     cd* out;          // != nullptr: out[p][(k + N/2) % N] = acc * conj(rot[k]) / count (effex.py:520-521, integrated);
                       //             device memory or host memory mapped into the device (the plan's pinned result
                       //             slots).  Every kernel that fills it does so with consecutive lanes on consecutive
                       //             bins: single 16-byte stores scattered over mapped host memory cost ~45 ns each
                       //             (180 us per 4096-bin spectrum, measured), wave-wide runs go out at the copy rate
-    const cd* rot;
+    std::conditional_t<ANT, AntRot, const cd*> rot;   // ANT: per-antenna tables, baseline p = idx / nchan
     double count;     // spectra accumulated so far
     int reset;        // clear the accumulator afterwards
     int64_t auto_from = 0;   // > 0: elements from this index on are auto rows (no rot, imaginary part 0 in `out`)
 };
+using FoldFinish = FinishT<false>;
 
+template <bool ANT>
 __device__ __forceinline__ void finish_element(cd a, cd* __restrict__ acc, int64_t idx, int k, int nchan, int64_t n,
-                                               const FoldFinish& fin) {
+                                               const FinishT<ANT>& fin) {
     if (fin.sums) {
         fin.sums[idx] = a;
         if (idx == 0) {
@@ -265,7 +306,11 @@ __device__ __forceinline__ void finish_element(cd a, cd* __restrict__ acc, int64
             o.x = a.x * inv;
             o.y = 0.0;
         } else {
-            const cd w = fin.rot[k];
+            cd w;
+            if constexpr (ANT)
+                w = ant_rot(fin.rot, idx / nchan, k, nchan);
+            else
+                w = fin.rot[k];
             o.x = (a.x * w.x + a.y * w.y) * inv;
             o.y = (a.y * w.x - a.x * w.y) * inv;
         }
@@ -334,9 +379,9 @@ __global__ __launch_bounds__(1024) void fold_partial_kernel(const cf* __restrict
     }
 }
 
-template <class RowT>
+template <class RowT, bool ANT = false>
 __global__ __launch_bounds__(1024) void fold_finish_kernel(const RowT* __restrict__ rows, int64_t n_rows, cd* __restrict__ acc,
-                                                          int nchan, int n_base, int slots, FoldFinish fin) {
+                                                          int nchan, int n_base, int slots, FinishT<ANT> fin) {
     __shared__ cd sub[kFoldPhases][256];
     const int kl = threadIdx.x & 255, ph = threadIdx.x >> 8;
     const int64_t n = (int64_t)n_base * nchan;
@@ -379,7 +424,8 @@ __global__ __launch_bounds__(1024) void fold_finish_kernel(const RowT* __restric
 }
 
 // FoldFinish alone, on the accumulator as it stands (paths that update it themselves, or nothing pending)
-__global__ void acc_finish_kernel(cd* __restrict__ acc, int nchan, int n_base, FoldFinish fin) {
+template <bool ANT = false>
+__global__ void acc_finish_kernel(cd* __restrict__ acc, int nchan, int n_base, FinishT<ANT> fin) {
     const int64_t n = (int64_t)n_base * nchan;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += stride)
@@ -564,7 +610,8 @@ __global__ __launch_bounds__(kXThreads) void xengine_block_kernel(const cf* __re
 }
 
 // out[p][(k + N/2) % N] = sums[p][k] * conj(rot[k]) / count      (effex.py:520-521, integrated)
-__global__ void finalize_spectrum_kernel(const cd* __restrict__ sums, cd* __restrict__ out, const cd* __restrict__ rot,
+template <bool ANT = false>
+__global__ void finalize_spectrum_kernel(const cd* __restrict__ sums, cd* __restrict__ out, RotArg<ANT> rot,
                                          int nchan, int n_base, int n_cross) {   // (n_base: rows in all; autos from n_cross on)
     const int64_t n = (int64_t)n_base * nchan;
     const double inv = 1.0 / sums[n].x;
@@ -578,7 +625,11 @@ __global__ void finalize_spectrum_kernel(const cd* __restrict__ sums, cd* __rest
             o.x = a.x * inv;
             o.y = 0.0;
         } else {
-            const cd w = rot[k];
+            cd w;
+            if constexpr (ANT)
+                w = ant_rot(rot, p, k, nchan);
+            else
+                w = rot[k];
             o.x = (a.x * w.x + a.y * w.y) * inv;
             o.y = (a.y * w.x - a.x * w.y) * inv;
         }
@@ -588,8 +639,9 @@ __global__ void finalize_spectrum_kernel(const cd* __restrict__ sums, cd* __rest
     }
 }
 
+template <bool ANT = false>
 __global__ __launch_bounds__(256) void finalize_continuum_kernel(const cd* __restrict__ sums, cd* __restrict__ out,
-                                                                const cd* __restrict__ rot, int nchan, int n_base,
+                                                                RotArg<ANT> rot, int nchan, int n_base,
                                                                 double inv_bw, int n_cross) {
     __shared__ double red[256];
     const int64_t n = (int64_t)n_base * nchan;
@@ -602,7 +654,12 @@ __global__ __launch_bounds__(256) void finalize_continuum_kernel(const cd* __res
                 ar += sums[(int64_t)p * nchan + k].x;
                 continue;
             }
-            const cd a = sums[(int64_t)p * nchan + k], w = rot[k];
+            const cd a = sums[(int64_t)p * nchan + k];
+            cd w;
+            if constexpr (ANT)
+                w = ant_rot(rot, p, k, nchan);
+            else
+                w = rot[k];
             ar += a.x * w.x + a.y * w.y;
             ai += a.y * w.x - a.x * w.y;
         }

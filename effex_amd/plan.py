@@ -63,6 +63,11 @@ def rot_table(nbins, bandwidth, frequency, calibrated_delay):
     return np.exp(2j * np.pi * freqs * calibrated_delay)
 
 
+def rot_tables(nbins, bandwidth, frequency, delays):
+    """Per-antenna rot tables [n_ant, nbins] complex128 for ``FxPlan.set_rot_ant``: row a is ``rot_table(..., delays[a])``."""
+    return np.stack([rot_table(nbins, bandwidth, frequency, d) for d in np.asarray(delays, dtype=np.float64).reshape(-1)])
+
+
 class FxPlan(object):
     def __init__(self, n_ant, nchan, ntaps, num_samp, window=None, device=0, stream=None, path=None, dev=False, autos=False):
         self._lib = _lib.load(dev=dev)          # dev: the developer build with the reference kernels (tests, tools/soak.py)
@@ -232,6 +237,18 @@ class FxPlan(object):
 
     def set_delay(self, bandwidth, frequency, calibrated_delay):
         self.set_rot(rot_table(self.nchan, bandwidth, frequency, calibrated_delay))
+
+    def set_rot_ant(self, tables):
+        """Per-antenna rot: ``tables`` [n_ant, nchan] complex128; cross row (a, b) is then multiplied by r_a conj(r_b)
+        (fxcorr.h fxc_set_rot_ant).  Replaces the shared table of ``set_rot`` until the next ``set_rot``."""
+        tables = np.ascontiguousarray(tables, dtype=np.complex128)
+        if tables.shape != (self.n_ant, self.nchan):
+            raise ValueError("tables must have shape ({}, {})".format(self.n_ant, self.nchan))
+        self._check(self._lib.fxc_set_rot_ant(self._h, tables.ctypes.data))
+
+    def set_delays(self, delays_s, bandwidth, frequency):
+        """Phase every baseline for the per-antenna delays ``delays_s`` [n_ant] (seconds, e.g. from ``estimate_delays``)."""
+        self.set_rot_ant(rot_tables(self.nchan, bandwidth, frequency, delays_s))
 
     # -- F stage ----------------------------------------------------------------------------
     def channelize(self, x):
@@ -463,6 +480,27 @@ class FxPlan(object):
         out = ctypes.c_double()
         self._check(self._lib.fxc_estimate_delay(self._h, pa, pb, n, kind, float(rate), ctypes.byref(out)))
         return out.value
+
+    def estimate_delays(self, x, rate, ref=0):
+        """Delays of every antenna against antenna ``ref`` in one call: x = [n_ant, n] complex64 (numpy, or a CUDA tensor on
+        the plan's device) -> float64 [n_ant]; entry a is ``estimate_delay(x[ref], x[a], rate)`` bit for bit, entry ref 0."""
+        self._sync_stream()
+        if _is_torch(x):
+            import torch
+            if x.dtype != torch.complex64 or not x.is_cuda or x.dim() != 2 or x.device.index != self.device:
+                raise ValueError("device input must be a 2-D complex64 CUDA tensor on device {}".format(self.device))
+            keep = x.contiguous()
+            ptr, kind = keep.data_ptr(), _lib.FXC_MEM_DEVICE
+        else:
+            keep = np.ascontiguousarray(x, dtype=np.complex64)
+            if keep.ndim != 2:
+                raise ValueError("x must have shape (n_ant, n)")
+            ptr, kind = keep.ctypes.data, _lib.FXC_MEM_HOST
+        if tuple(keep.shape)[0] != self.n_ant:
+            raise ValueError("x must have shape ({}, n), got {}".format(self.n_ant, tuple(keep.shape)))
+        out = np.zeros(self.n_ant, dtype=np.float64)
+        self._check(self._lib.fxc_estimate_delays(self._h, ptr, int(keep.shape[1]), kind, float(rate), int(ref), out.ctypes.data))
+        return out
 
     # -- measurement ------------------------------------------------------------------------
     def timer_start(self):

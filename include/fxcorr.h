@@ -156,6 +156,16 @@ int fxc_plan_products(const fxc_plan* plan, int* products, int* n_rows);
  * float64 (phase ~ 9e3 rad), complex128[nchan] host memory, copied.  Default: all ones. */
 int fxc_set_rot(fxc_plan* plan, const double* rot_re_im);
 
+/* Per-antenna rot: rot_ant = [n_ant][nchan] complex128 host memory, copied; row a is antenna a's table
+ * r_a[k] = exp(+2*pi*i*f_k*tau_a), natural bin order.  Cross row (a,b), a < b, in the baseline order of the results is then
+ *   fftshift( raw_ab[k] * r_a[k] * conj(r_b[k]) / count )
+ * (with r_0 = 1 and r_1 = rot: exactly fxc_set_rot(rot), effex.py:516-521).  The kernels form w[k] = r_b[k] * conj(r_a[k]) in
+ * float64 and multiply by conj(w) as they do by conj(rot).  Auto rows (FXC_PRODUCTS_CROSS_AUTO) take no rot.  Two antennas: the
+ * one w is formed here and becomes the shared table.  Like fxc_set_rot it synchronises the plan's stream first and applies to
+ * every finishing kernel queued afterwards (rows, every finalize form, fxc_finalize_sums, pipes); of the two calls the last one
+ * wins.  FXC_ERR_ARG: a NULL argument, n_ant < 2. */
+int fxc_set_rot_ant(fxc_plan* plan, const double* rot_ant_re_im);
+
 /* F-stage only — replaces cusignal.filtering.channelize_poly + .T at effex.py:553 (and the
  * complex128 copy at :551).  x = [n_streams][num_samp] complex64, out = [n_streams][n_pts][nchan]
  * complex64, natural (un-shifted) bin order; trailing num_samp mod nchan samples ignored; zero
@@ -290,6 +300,14 @@ int fxc_host_free(void* ptr);
  * Uses the plan's device, stream and workspace; synchronises. */
 int fxc_estimate_delay(fxc_plan* plan, const void* iq0, const void* iq1, int64_t n, int mem_kind, double rate,
                        double* delay_s);
+
+/* Delay calibration of the whole array in one call: x = [n_ant][n] complex64 (host or device, mem_kind as above), delays_s[n_ant]
+ * out.  delays_s[a] is bit for bit fxc_estimate_delay(plan, x[ref], x[a], n, mem_kind, rate) and delays_s[ref] = 0.0, so
+ * per-antenna tables of these delays (fxc_set_rot_ant) remove the delay slope of every baseline.  The reference stream is
+ * transformed once and the others in batches as large as the workspace target allows; one copy to the host, one
+ * synchronisation.  FXC_ERR_ARG: a NULL argument, n_ant < 2, ref outside [0, n_ant), n or rate outside the ranges of
+ * fxc_estimate_delay. */
+int fxc_estimate_delays(fxc_plan* plan, const void* x, int64_t n, int mem_kind, double rate, int ref, double* delays_s);
 
 /* Host-fed front end: replaces the reference's blocking per-chunk copies
  * (effex.py:391-392, 508-509, 693).  A pipe owns `depth` slots of pinned host staging + device buffers.
