@@ -79,6 +79,10 @@ SIGNATURES = {
     "fxc_last_error": (_c.c_char_p, [_vp]),
     "fxc_set_rot": (_c.c_int, [_vp, _vp]),
     "fxc_set_rot_ant": (_c.c_int, [_vp, _vp]),
+    "fxc_set_delay_track": (_c.c_int, [_vp, _vp, _vp, _c.c_double, _c.c_double, _c.c_int64]),
+    "fxc_delay_track_chunk": (_c.c_int, [_vp, _c.POINTER(_c.c_int64)]),
+    "fxc_delay_track_seek": (_c.c_int, [_vp, _c.c_int64]),
+    "fxc_delay_track_tables": (_c.c_int, [_vp, _c.c_int64, _vp]),
     "fxc_set_products": (_c.c_int, [_vp, _c.c_int]),
     "fxc_plan_products": (_c.c_int, [_vp, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
     "fxc_channelize": (_c.c_int, [_vp, _vp, _vp, _c.c_int64, _c.c_int]),

@@ -305,7 +305,7 @@ class Correlator(object):
     def __init__(self, run_time=1, bandwidth=2.4e6, frequency=1.4204e9, num_samp=2 ** 18, nbins=2 ** 12,
                  gain=49.6, mode='SPECTRUM', loglevel='INFO',
                  source=None, device=0, max_num_samp=None, output_file=None, remove_dc=True, calibrate=True,
-                 output_format='csv', batch=1, autos=False):
+                 output_format='csv', batch=1, autos=False, device_sweep=False):
         self.logger = logging.getLogger(__name__)
         self.logger.setLevel(getattr(logging, loglevel))
         self._max_num_samp = int(max_num_samp) if max_num_samp else Correlator._MAX_NUM_SAMP
@@ -318,6 +318,10 @@ class Correlator(object):
         if int(batch) < 1:
             raise ValueError("batch must be >= 1")
         self.batch = int(batch)
+        # device_sweep=True: mode 'TEST' with batch > 1 takes the batched RUN state too -- its delay sweep (one
+        # test_delay_sweep_step more before every chunk pair, effex.py:403-404) becomes a delay track evaluated on the
+        # device (FxPlan.set_delay_track) instead of one host-built table per chunk pair.  Off: TEST runs pair by pair.
+        self.device_sweep = bool(device_sweep)
         # autos=True: each antenna's autocorrelation beside the cross product -- `last_autos` after every row / integration,
         # and in RUN one more file per antenna, <stem>_auto<a><ext>, in the output file's format.  They come from a plan of
         # their own (fxc_set_products): the cross rows, and so the output file, stay exactly those of a run without autos.
@@ -745,8 +749,13 @@ class Correlator(object):
         plan = self._plan()
         n, K = int(self.num_samp), self.batch
         u8 = np.asarray(first_pair[0]).dtype == np.uint8
-        mode = 'CONTINUUM' if 'CONTINUUM' == self.mode else 'SPECTRUM'
+        mode = 'CONTINUUM' if self.mode in ('CONTINUUM', 'TEST') else 'SPECTRUM'
         rows = 0
+        if 'TEST' == self.mode:
+            # row j of the sweep is phased for calibrated_delay + (j + 1) steps: the loop adds the step before the first row too
+            plan.set_delay_track(self.calibrated_delay + self.test_delay_sweep_step, self.test_delay_sweep_step,
+                                 self.bandwidth, self.frequency)
+            self._rot_key = None          # (the next _plan() sets a static table again, which ends the track)
 
         def emit(out):          # out: [k, 1, nchan] complex64 or [k, 1] complex128
             for row in out[:, 0]:
@@ -827,6 +836,9 @@ class Correlator(object):
                 else:
                     emit(out)
                 rows += k
+        if 'TEST' == self.mode:
+            for _ in range(rows):         # where the pair-by-pair loop leaves it, addition by addition
+                self.calibrated_delay += self.test_delay_sweep_step
         return rows
 
     def run_state_machine(self):
@@ -854,7 +866,7 @@ class Correlator(object):
                     if pair is None:
                         self.state = 'SHUTDOWN'
                         continue
-                    if 'RUN' == self.state and self.batch > 1 and self.mode not in ['TEST']:
+                    if 'RUN' == self.state and self.batch > 1 and (self.mode not in ['TEST'] or self.device_sweep):
                         rows += self._run_batched(pair, sink, fh, auto_sinks)      # to the end of the stream
                         self.state = 'SHUTDOWN'
                         continue

@@ -3,7 +3,7 @@
 // One translation unit.  This file holds the ABI entry points; it includes
 //   fx_math.h, fx_fused4096.h, fx_tiled.h, fx_small.h, fx_mixed.h   index maps, butterflies and kernel phases (also compiled by
 //                                           g++ for the host emulation under tests/emul)
-//   k_generic.h k_finish.h k_fused4096.h k_tiled.h k_small.h k_prepass.h k_stream.h k_conditioning.h k_delay.h k_synth.h
+//   k_generic.h k_finish.h (+ k_finish_rows.h) k_fused4096.h k_tiled.h k_small.h k_prepass.h k_stream.h k_conditioning.h k_track.h k_delay.h k_synth.h
 //                                           the __global__ kernels, one file per path / step
 //   h_plan.h h_rtc.h h_launch.h h_build.h h_run.h h_rccl.h
 //                                           fxc_plan, the kernels compiled per channel count, the per-path launchers and
@@ -135,6 +135,7 @@ int64_t ws_target() {
 #include "k_prepass.h"
 #include "k_stream.h"
 #include "k_conditioning.h"
+#include "k_track.h"
 #include "k_delay.h"
 #include "k_synth.h"
 #include "h_plan.h"
@@ -190,7 +191,7 @@ int fxc_plan_destroy(fxc_plan* p) {
     }
     void* bufs[] = {p->d_win, p->d_tw, p->d_rot, p->d_win4, p->d_tw1, p->d_tw2, p->d_tw0, p->d_tw_small, p->d_stamps,
                     p->d_acc, p->d_sums, p->d_cont, p->d_rowpart, p->d_ws, p->d_stage[0], p->d_stage[1], p->d_stage[2], p->d_dc, p->d_hpre,
-                    p->d_ones, p->d_pre, p->d_tw8192, p->d_unit4, p->d_chirp, p->d_blud, p->d_rot_ant, p->d_pair};
+                    p->d_ones, p->d_pre, p->d_tw8192, p->d_unit4, p->d_chirp, p->d_blud, p->d_rot_ant, p->d_pair, p->d_track_par, p->d_track, p->d_one};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (p->ev_t0) (void)hipEventDestroy(p->ev_t0);
@@ -347,8 +348,91 @@ int fxc_spec_probe(int nchan, int ntaps, int variant, const char* arch, char* re
     return FXC_OK;
 }
 
+namespace {
+bool acc_empty(const fxc_plan* p) { return !(p->spectra_count > 0.0) && !p->pend.valid; }
+
+// fxc_set_rot / fxc_set_rot_ant end a delay track -- unless the accumulator holds tracked chunks: their sums are rotated already,
+// a static table at finalize would rotate them again
+int end_track(fxc_plan* p) {
+    if (p->track && p->acc_track && !acc_empty(p))
+        return fail(p, FXC_ERR_STATE, "the accumulator holds chunks accumulated under the delay track: finalize or reset it first");
+    p->track = false;
+    return FXC_OK;
+}
+
+// the finalize kernels' rot: a tracked integration's sums are rotated already
+const cd* finalize_rot(const fxc_plan* p) { return p->track ? p->d_one : p->d_rot; }
+}  // namespace
+
+int fxc_set_delay_track(fxc_plan* p, const double* tau0_s, const double* rate_s_per_chunk, double bandwidth, double frequency,
+                        int64_t first_chunk) {
+    if (!p || !tau0_s || !rate_s_per_chunk) return fail(p, FXC_ERR_ARG, "NULL argument");
+    if (p->n_ant < 2) return fail(p, FXC_ERR_ARG, "a delay track needs 2 or more antennas, the plan has %d", p->n_ant);
+    if (!(bandwidth > 0.0) || !std::isfinite(bandwidth) || !std::isfinite(frequency))
+        return fail(p, FXC_ERR_ARG, "bandwidth must be > 0 and finite, frequency finite");
+    if (first_chunk < 0) return fail(p, FXC_ERR_ARG, "first_chunk < 0");
+    for (int a = 0; a < p->n_ant; ++a)
+        if (!std::isfinite(tau0_s[a]) || !std::isfinite(rate_s_per_chunk[a]))
+            return fail(p, FXC_ERR_ARG, "delay or rate of antenna %d is not finite", a);
+    if (p->live_pipes) return fail(p, FXC_ERR_STATE, "an fxc_pipe uses the plan");
+    if (!acc_empty(p) && !p->acc_track)
+        return fail(p, FXC_ERR_STATE, "the accumulator holds chunks accumulated without a delay track: finalize or reset it first");
+    FXC_DEVICE(p, p->device);
+    // ordered after any queued kernel that still reads the old parameters
+    FXC_HIP(p, hipStreamSynchronize(p->stream));
+    const size_t A = (size_t)p->n_ant, N = (size_t)p->nchan;
+    if (!p->d_track_par) FXC_HIP(p, hipMalloc(reinterpret_cast<void**>(&p->d_track_par), 2 * A * sizeof(double)));
+    if (!p->d_one) {
+        FXC_HIP(p, hipMalloc(reinterpret_cast<void**>(&p->d_one), N * sizeof(cd)));
+        cd one;
+        one.x = 1.0;
+        one.y = 0.0;
+        const std::vector<cd> ones(N, one);
+        FXC_HIP(p, hipMemcpy(p->d_one, ones.data(), N * sizeof(cd), hipMemcpyHostToDevice));
+    }
+    FXC_HIP(p, hipMemcpy(p->d_track_par, tau0_s, A * sizeof(double), hipMemcpyHostToDevice));
+    FXC_HIP(p, hipMemcpy(p->d_track_par + A, rate_s_per_chunk, A * sizeof(double), hipMemcpyHostToDevice));
+    p->track_df = 1.0 / ((double)p->nchan * (1.0 / bandwidth));      // np.fft.fftfreq(nchan, d = 1 / bandwidth), step by step
+    p->track_freq = frequency;
+    p->track_t = first_chunk;
+    p->track = true;
+    p->rot_ant = false;
+    return FXC_OK;
+}
+
+int fxc_delay_track_chunk(const fxc_plan* p, int64_t* next_chunk) {
+    if (!p || !next_chunk) return fail(p, FXC_ERR_ARG, "NULL argument");
+    if (!p->track) return fail(p, FXC_ERR_STATE, "the plan has no delay track");
+    *next_chunk = p->track_t;
+    return FXC_OK;
+}
+
+int fxc_delay_track_seek(fxc_plan* p, int64_t chunk) {
+    if (!p) return fail(p, FXC_ERR_ARG, "NULL plan");
+    if (chunk < 0) return fail(p, FXC_ERR_ARG, "chunk < 0");
+    if (!p->track) return fail(p, FXC_ERR_STATE, "the plan has no delay track");
+    p->track_t = chunk;
+    return FXC_OK;
+}
+
+int fxc_delay_track_tables(fxc_plan* p, int64_t chunk, double* out_re_im) {
+    if (!p || !out_re_im) return fail(p, FXC_ERR_ARG, "NULL argument");
+    if (chunk < 0) return fail(p, FXC_ERR_ARG, "chunk < 0");
+    if (!p->track) return fail(p, FXC_ERR_STATE, "the plan has no delay track");
+    FXC_DEVICE(p, p->device);
+    const size_t bytes = (size_t)p->n_ant * p->nchan * sizeof(cd);
+    const int rg = grow(p, &p->d_stage[1], &p->stage_bytes[1], bytes);
+    if (rg) return rg;
+    const int rc = track_tables(p, chunk, 1, static_cast<cd*>(p->d_stage[1]), false);
+    if (rc) return rc;
+    FXC_HIP(p, hipMemcpyAsync(out_re_im, p->d_stage[1], bytes, hipMemcpyDeviceToHost, p->stream));
+    FXC_HIP(p, hipStreamSynchronize(p->stream));
+    return FXC_OK;
+}
+
 int fxc_set_rot(fxc_plan* p, const double* rot_re_im) {
     if (!p || !rot_re_im) return fail(p, FXC_ERR_ARG, "NULL argument");
+    if (const int rs = end_track(p)) return rs;
     FXC_DEVICE(p, p->device);
     // ordered after any queued finish kernel that still reads the old table
     FXC_HIP(p, hipStreamSynchronize(p->stream));
@@ -360,6 +444,7 @@ int fxc_set_rot(fxc_plan* p, const double* rot_re_im) {
 int fxc_set_rot_ant(fxc_plan* p, const double* rot_ant_re_im) {
     if (!p || !rot_ant_re_im) return fail(p, FXC_ERR_ARG, "NULL argument");
     if (p->n_ant < 2) return fail(p, FXC_ERR_ARG, "per-antenna rot needs 2 or more antennas, the plan has %d", p->n_ant);
+    if (const int rs = end_track(p)) return rs;
     FXC_DEVICE(p, p->device);
     FXC_HIP(p, hipStreamSynchronize(p->stream));
     const size_t N = (size_t)p->nchan;
@@ -680,7 +765,7 @@ int fxc_acc_reset(fxc_plan* p) {
 int fxc_acc_export(fxc_plan* p, void* sums_dev) {
     if (!p || !sums_dev) return fail(p, FXC_ERR_ARG, "NULL argument");
     FXC_DEVICE(p, p->device);
-    const FoldFinish fin = {static_cast<cd*>(sums_dev), nullptr, p->d_rot, p->spectra_count, 0};
+    const FoldFinish fin = {static_cast<cd*>(sums_dev), nullptr, finalize_rot(p), p->spectra_count, 0};
     return flush_pending(p, &fin);
 }
 
@@ -718,7 +803,7 @@ int finalize_enqueue(fxc_plan* p, const cd* sums_src, int mode, double bandwidth
     p->res_dst[slot] = user_out;
     if (!sums_src) {
         // SPECTRUM: one kernel.  CONTINUUM needs the mean over the bins of the finished accumulator: export, then reduce
-        FoldFinish fin = {nullptr, out, p->d_rot, p->spectra_count, reset ? 1 : 0};
+        FoldFinish fin = {nullptr, out, finalize_rot(p), p->spectra_count, reset ? 1 : 0};
         if (mode == FXC_MODE_CONTINUUM) {
             // into a buffer of its own: d_sums may hold reduced sums (fxc_reduce) that fxc_finalize_sums(plan, NULL) has yet
             // to read, and only fxc_reduce makes that copy valid
@@ -740,7 +825,7 @@ int finalize_enqueue(fxc_plan* p, const cd* sums_src, int mode, double bandwidth
                                   big ? nullptr : p->ev_res[slot], 0, sums_src, out, ant_rot_arg(p), p->nchan, p->n_prod, p->n_base);
         else
             hipExtLaunchKernelGGL(finalize_spectrum_kernel<false>, dim3(grid_for(n, 256, p->cu_count)), dim3(256), 0, p->stream, nullptr,
-                                  big ? nullptr : p->ev_res[slot], 0, sums_src, out, p->d_rot, p->nchan, p->n_prod, p->n_base);
+                                  big ? nullptr : p->ev_res[slot], 0, sums_src, out, finalize_rot(p), p->nchan, p->n_prod, p->n_base);
     }
     if (mode == FXC_MODE_CONTINUUM) {
         if (p->rot_ant)
@@ -749,7 +834,7 @@ int finalize_enqueue(fxc_plan* p, const cd* sums_src, int mode, double bandwidth
                                   1.0 / bandwidth, p->n_base);
         else
             hipExtLaunchKernelGGL(finalize_continuum_kernel<false>, dim3(p->n_prod), dim3(256), 0, p->stream, nullptr,
-                                  big ? nullptr : p->ev_res[slot], 0, sums_src, out, p->d_rot, p->nchan, p->n_prod, 1.0 / bandwidth,
+                                  big ? nullptr : p->ev_res[slot], 0, sums_src, out, finalize_rot(p), p->nchan, p->n_prod, 1.0 / bandwidth,
                                   p->n_base);
     }
     FXC_HIP(p, hipGetLastError());
@@ -913,11 +998,11 @@ int fx_u8_dev(fxc_plan* p, const unsigned char* x8, void* out, int64_t n_chunks,
         // The fused 4096-channel kernel can sum the bytes of a workgroup's next chunk while it channelises the current one
         // (k_fused4096.h, DCK): the pre-pass then only covers the first chunk of every workgroup's round-robin share and
         // the tail chunks -- 272 of 10 000 chunk pairs.  Needs whole frames (num_samp % 4096 == 0), 16-byte aligned
-        // streams, the default work split, one launch for the pass and at least two rounds of chunks.
+        // streams, the default work split (so no delay track), one launch for the pass and at least two rounds of chunks.
         int64_t spec_b, raw_b;
         const int64_t g = p->fused_grid_max;
         // (num_samp <= 2^26: a wave's byte sums are reduced in 32 bits, 16384 frames x 4080 x 64 lanes < 2^32)
-        const bool dck = remove_dc && fused_ingest && p->path == FXC_PATH_FUSED && p->fused_seg == 1 &&
+        const bool dck = remove_dc && fused_ingest && !p->track && p->path == FXC_PATH_FUSED && p->fused_seg == 1 &&
                          (p->num_samp % fxc::fused::kN) == 0 && p->num_samp <= (1ll << 26) &&
                          (reinterpret_cast<uintptr_t>(xb) % 16) == 0 &&
                          fused_chunks_per_pass(p, nc, &spec_b, &raw_b) >= nc && nc >= 2 * g;

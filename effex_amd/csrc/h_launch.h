@@ -6,11 +6,17 @@
 namespace {
 
 int launch_fused(fxc_plan* p, const cf* x, int64_t n_pairs, cf* out, bool spec_out, const cf* dc_u8 = nullptr,
-                 int64_t unit = 1, bool rows_are_chunks = true, int64_t num_samp = 0, bool dck = false);
+                 int64_t unit = 1, bool rows_are_chunks = true, int64_t num_samp = 0, bool dck = false, int whole_grid = 0);
 
 // F-stage of `n_streams` streams: x -> spec (both device, natural bin order)
 int tiled_channelize(fxc_plan* p, const cf* x, cf* spec, int64_t n_streams, int spec_a = 0);
 int64_t spec_wg_splits(const fxc_plan* p, const SpecKernel* k, int64_t n_groups, bool sums);
+
+// Every route cuts a chunk's frames into runs (float32 partial sums) by the size of the call: more runs for few chunks, to fill the
+// device.  Under a delay track the rows of a chunk must not depend on the call that brought it (fxcorr.h), so the routes then ask
+// for the split of a call of very many chunks -- the fewest runs; the fused kernel: whole chunks (fused_raw_sums) -- whatever the
+// call's size.  A tracked call of a few chunks leaves part of the device idle for that.
+int64_t split_basis(const fxc_plan* p, int64_t n_chunks) { return p->track ? (int64_t)1 << 20 : n_chunks; }
 
 // Slots of one wave (tpr <= 64) go without the workgroup barrier between their steps: measured on one box, two antennas
 // 7 - 16 % faster at 8 ... 250 channels, F only 5 - 7 % faster at 96 ... 250 but 17 % slower at 12 (slots of 4 threads) -- so F
@@ -426,6 +432,7 @@ int64_t fused_rows(const fxc_plan* p, int64_t nc, int64_t unit, bool rows_are_ch
 }
 
 LeadRows fused_lead(const fxc_plan* p, int64_t nc) {
+    if (p->track) return LeadRows{0, 0, 0, 0, 0};      // (whole chunks only: fused_raw_sums)
     const fxc::fused::RangeSplit sp = fxc::fused::range_split(fused_grid(p, nc), (int)nc, (int)p->fused_seg, 1, true);
     LeadRows lr;
     lr.first_chunk = sp.n_full;
@@ -441,13 +448,14 @@ const LeadRows kNoLead = {0, 0, 0, 0, 0};
 // n_pairs = pairs of consecutive antenna streams to channelise; spec_out: write spectra instead of X sums
 // dc_u8 != nullptr: x is the uint8 I,Q stream and dc_u8 its per-stream conversion offsets (2 antennas, X fused in)
 // unit / rows_are_chunks: the raw-row layout (fx_fused4096.h::RangeWalk)
+// whole_grid > 0: that many workgroups, one chunk pair at a time each (n_pairs a multiple of it: no frame ranges)
 int launch_fused(fxc_plan* p, const cf* x, int64_t n_pairs, cf* out, bool spec_out, const cf* dc_u8, int64_t unit,
-                 bool rows_are_chunks, int64_t num_samp, bool dck) {
+                 bool rows_are_chunks, int64_t num_samp, bool dck, int whole_grid) {
     using namespace fxc::fused;
     if (num_samp == 0) num_samp = p->num_samp;      // (the 8192-channel split runs on half-size streams)
     const f4* win4 = p->split8192 ? p->d_unit4 : p->d_win4;      // (the split's own pass has applied the FIR: one unit tap)
-    const int grid = fused_grid(p, n_pairs);
-    const int seg = (int)p->fused_seg;
+    const int grid = whole_grid > 0 ? whole_grid : fused_grid(p, n_pairs);
+    const int seg = whole_grid > 0 ? 1 : (int)p->fused_seg;
     if (n_pairs * p->n_pts >= (1ll << 31)) return fail(p, FXC_ERR_ARG, "more than 2^31 frames in one launch");
     unsigned long long* stamps = nullptr;
 #if FXC_STAMPS
@@ -537,11 +545,33 @@ int64_t fused_chunks_per_pass(const fxc_plan* p, int64_t n_chunks, int64_t* spec
 
 int launch_xengine(fxc_plan* p, const cf* spec, cf* raw, int64_t nc, int cg, int xr);
 
+// Two antennas under a delay track: every chunk pair is summed whole, frame after frame by one workgroup, so its row is the same
+// bits in any call (the kernel's frame ranges would cut the last chunks of a launch by the launch's size).  Two launches of the
+// unchanged kernel: full rounds over fused_grid_max workgroups, then the rest with one workgroup per chunk pair.  Row c = chunk c;
+// the second launch's rows start where the first one's (empty) leading-part rows lie, and its own end within the nc +
+// fused_grid_max rows of the pass.
+int fused_whole_chunks(fxc_plan* p, const cf* x, int64_t nc, cf* raw, const cf* dc_u8, int64_t num_samp) {
+    const int64_t samp = num_samp ? num_samp : p->num_samp;
+    const int64_t in_bytes = 2 * samp * (dc_u8 ? 2 : (int64_t)sizeof(cf));      // per chunk pair
+    const int64_t row = (int64_t)fxc::fused::kN * (p->autos && p->nchan == fxc::fused::kN ? p->n_prod : 1);
+    const int64_t g = p->fused_grid_max;
+    const int64_t n1 = nc / g * g;
+    if (n1 > 0) {
+        const int rc = launch_fused(p, x, n1, raw, false, dc_u8, 1, true, num_samp, false, (int)g);
+        if (rc) return rc;
+    }
+    if (nc > n1)
+        return launch_fused(p, reinterpret_cast<const cf*>(reinterpret_cast<const char*>(x) + n1 * in_bytes), nc - n1, raw + n1 * row, false,
+                            dc_u8 ? dc_u8 + n1 * 2 : nullptr, 1, true, num_samp, false, (int)(nc - n1));
+    return FXC_OK;
+}
+
 // raw[c][p][layout] for nc chunks starting at x; spec = scratch for the multi-antenna path.  2 antennas: rows of
 // `unit` chunks + leading-part rows (fused_rows() of them in all)
 int fused_raw_sums(fxc_plan* p, const cf* x, int64_t nc, cf* spec, cf* raw, const cf* dc_u8 = nullptr, int64_t unit = 1,
                    bool rows_are_chunks = true, bool dck = false) {
     using namespace fxc::fused;
+    if (p->n_ant == 2 && p->track) return fused_whole_chunks(p, x, nc, raw, dc_u8, 0);
     if (p->n_ant == 2) return launch_fused(p, x, nc, raw, false, dc_u8, unit, rows_are_chunks, 0, dck);
     // 3 .. 64 antennas: spectra to HBM as [chunk][frame][antenna] rows (the F-only fused kernel in its own position order
     // at nchan 4096 / ntaps 4, the F-only tiled kernel in natural order otherwise), then the register-resident X-engine
@@ -935,6 +965,7 @@ int split_raw_sums(fxc_plan* p, const cf* x, int64_t nc, cf* raw) {
 #undef FXC_SPLIT_LAUNCH
     FXC_HIP(p, hipGetLastError());
     kt.stop();
+    if (p->track) return fused_whole_chunks(p, y, 2 * nc, raw, nullptr, half_samp);
     return launch_fused(p, y, 2 * nc, raw, false, nullptr, 1, true, half_samp);
 }
 

@@ -95,6 +95,16 @@ struct fxc_plan {
     bool rot_ant = false;
     cd* d_rot_ant = nullptr;
     int2* d_pair = nullptr;        // [n_base] (plan_build)
+    // delay track (fxc_set_delay_track): chunk t of every rows / accumulate call takes the rot of tau0 + t rate, written by
+    // track_tables_kernel (k_track.h) for the chunks of a pass into d_track; track_t is the next chunk's index
+    bool track = false;
+    int64_t track_t = 0;
+    double track_df = 0.0, track_freq = 0.0;     // bin spacing as numpy forms it, centre frequency
+    double* d_track_par = nullptr;   // [2][n_ant] tau0, rate
+    void* d_track = nullptr;         // the tables of one pass
+    size_t track_bytes = 0;
+    cd* d_one = nullptr;             // [nchan] of 1: a tracked integration's accumulator holds rotated sums, the finalize kernels' rot
+    bool acc_track = false;          // the chunks in the accumulator (spectra_count > 0) were folded under a track
     f4* d_win4 = nullptr;          // [nchan] window quads (one unit tap behind the pre-filter): fused, tiled ring, wave-local, lean fx_spec.h
     cf* d_tw1 = nullptr;
     cf* d_tw2 = nullptr;

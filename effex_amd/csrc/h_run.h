@@ -88,11 +88,24 @@ int autos_accumulate_dev(fxc_plan* p, const cf* x, int64_t n_chunks) {
     return FXC_OK;
 }
 
+// (fx_rows_dev, below) the mode of a tracked fx_accumulate: its passes fold their rows into the accumulator
+constexpr int kModeTrackFold = -1;
+int fx_rows_dev(fxc_plan* p, const cf* x, void* out, int64_t n_chunks, int mode, double bandwidth, const cf* dc_u8 = nullptr);
+
 // device-resident implementation of fx_accumulate
 // dc_u8 != nullptr (fused 2-antenna plans only): x is the uint8 I,Q stream [n_chunks][2][num_samp][2] and dc_u8 its
 // per-stream conversion offsets
 int fx_accumulate_dev(fxc_plan* p, const cf* x, int64_t n_chunks, const cf* dc_u8 = nullptr) {
     if (n_chunks == 0) return FXC_OK;
+    p->acc_track = p->track;
+    if (p->track) {
+        // rot changes from chunk to chunk, so it is applied before the sum over chunks: the rows routes' raw rows (one set per
+        // chunk), folded by track_fold_kernel
+        const int rc = fx_rows_dev(p, x, nullptr, n_chunks, kModeTrackFold, 1.0, dc_u8);
+        if (rc) return rc;
+        p->spectra_count += (double)n_chunks * (double)p->n_pts;
+        return FXC_OK;
+    }
     if (p->autos && !fused_autos(p, n_chunks)) return autos_accumulate_dev(p, x, n_chunks);
     if (p->path == FXC_PATH_STREAM) {
         const int64_t blocks = stream_blocks(p);
@@ -222,14 +235,46 @@ int fx_accumulate_dev(fxc_plan* p, const cf* x, int64_t n_chunks, const cf* dc_u
 
 // Rows of a plan with per-antenna tables (fxc_set_rot_ant: 3 and more antennas) go to the rows kernels' ANT instantiations.
 // Every route of those plans lays its rows out as [chunk][n_prod] with the n_base cross rows first, so the kernels take
-// n_prod and n_cross from the plan then.  The streaming, 8192-channel and 2-antenna tiled routes serve two antennas only
-// (fxc_set_rot_ant folds those into the shared table) and launch the shared-rot kernels themselves.
+// n_prod and n_cross from the plan then.  Every route of fx_rows_dev ends in launch_rows below.
+//
+// Plans with a delay track (fxc_set_delay_track) go to the tracked instantiations: the pass's rows are [chunk][p->n_prod] on
+// every route (two antennas: 1 row, or cross + 2 autos), its chunks take the plan's counter onwards, and track_pass writes
+// their tables first.  The counter advances here, pass by pass; fx_rows_dev puts it back when a call fails half way.
+int track_tables(fxc_plan* p, int64_t t0, int64_t n_t, cd* out, bool pair) {
+    const TrackPar tp = {p->d_track_par, p->d_track_par + p->n_ant, p->track_df, p->track_freq};
+    const dim3 grid(grid_for(n_t * (pair ? 1 : p->n_ant) * p->nchan, 256, p->cu_count));
+    if (pair)
+        hipLaunchKernelGGL(track_tables_kernel<true>, grid, dim3(256), 0, p->stream, tp, out, p->n_ant, p->nchan, t0, n_t);
+    else
+        hipLaunchKernelGGL(track_tables_kernel<false>, grid, dim3(256), 0, p->stream, tp, out, p->n_ant, p->nchan, t0, n_t);
+    FXC_HIP(p, hipGetLastError());
+    return FXC_OK;
+}
+
+int64_t track_stride(const fxc_plan* p) { return (int64_t)(p->n_ant == 2 ? 1 : p->n_ant) * p->nchan; }
+TrackRot<false> track_rot_arg(const fxc_plan* p) { return {static_cast<const cd*>(p->d_track), track_stride(p)}; }
+TrackRot<true> track_ant_rot_arg(const fxc_plan* p) { return {{static_cast<const cd*>(p->d_track), p->d_pair}, track_stride(p)}; }
+
+int track_pass(fxc_plan* p, int64_t n_chunks) {
+    const int rg = grow(p, &p->d_track, &p->track_bytes, (size_t)(n_chunks * track_stride(p)) * sizeof(cd));
+    if (rg) return rg;
+    const int rc = track_tables(p, p->track_t, n_chunks, static_cast<cd*>(p->d_track), p->n_ant == 2);
+    if (rc) return rc;
+    p->track_t += n_chunks;
+    return FXC_OK;
+}
 
 // SPECTRUM rows
 void launch_rows_spectrum(fxc_plan* p, const cf* raw, cf* out, int nchan, int64_t rows, int n_splits, int64_t split_stride,
                           float inv_pts, int slots, LeadRows lead, int n_prod, int n_cross) {
     const dim3 grid(grid_for(rows * nchan, 256, p->cu_count));
-    if (p->rot_ant)
+    if (p->track && p->n_ant > 2)
+        hipLaunchKernelGGL(rows_spectrum_track_kernel<true>, grid, dim3(256), 0, p->stream, raw, out, track_ant_rot_arg(p), nchan, rows,
+                           n_splits, split_stride, inv_pts, slots, lead, p->n_prod, p->n_base);
+    else if (p->track)
+        hipLaunchKernelGGL(rows_spectrum_track_kernel<false>, grid, dim3(256), 0, p->stream, raw, out, track_rot_arg(p), nchan, rows,
+                           n_splits, split_stride, inv_pts, slots, lead, p->n_prod, p->n_base);
+    else if (p->rot_ant)
         hipLaunchKernelGGL(rows_spectrum_kernel<true>, grid, dim3(256), 0, p->stream, raw, out, ant_rot_arg(p), nchan, rows, n_splits,
                            split_stride, inv_pts, slots, lead, p->n_prod, p->n_base);
     else
@@ -240,16 +285,23 @@ void launch_rows_spectrum(fxc_plan* p, const cf* raw, cf* out, int nchan, int64_
 // CONTINUUM rows: one workgroup per row when there are rows enough to fill the chip, else bin slices + a second small kernel
 int launch_rows_continuum(fxc_plan* p, const cf* raw, cd* out, int nchan, int64_t rows, int n_splits, int64_t split_stride,
                           double scale, int slots, LeadRows lead, int n_prod = 1, int n_cross = 1) {
-    if (p->rot_ant) {
+    if (p->rot_ant || p->track) {
         n_prod = p->n_prod;
         n_cross = p->n_base;
     }
+    const bool track_ant = p->track && p->n_ant > 2;
     const int slices = (int)std::min<int64_t>(32, nchan / 128);
     if (slices >= 2 && rows * 2 <= p->cu_count && rows <= 65535) {
         const int rg = grow(p, &p->d_rowpart, &p->rowpart_bytes, (size_t)rows * slices * sizeof(cd));
         if (rg) return rg;
         cd* part = static_cast<cd*>(p->d_rowpart);
-        if (p->rot_ant)
+        if (track_ant)
+            hipLaunchKernelGGL(rows_continuum_part_track_kernel<true>, dim3(slices, (unsigned)rows), dim3(256), 0, p->stream, raw, part,
+                               track_ant_rot_arg(p), nchan, rows, n_splits, split_stride, slots, lead, slices, n_prod, n_cross);
+        else if (p->track)
+            hipLaunchKernelGGL(rows_continuum_part_track_kernel<false>, dim3(slices, (unsigned)rows), dim3(256), 0, p->stream, raw, part,
+                               track_rot_arg(p), nchan, rows, n_splits, split_stride, slots, lead, slices, n_prod, n_cross);
+        else if (p->rot_ant)
             hipLaunchKernelGGL(rows_continuum_part_kernel<true>, dim3(slices, (unsigned)rows), dim3(256), 0, p->stream, raw, part,
                                ant_rot_arg(p), nchan, rows, n_splits, split_stride, slots, lead, slices, n_prod, n_cross);
         else
@@ -259,7 +311,13 @@ int launch_rows_continuum(fxc_plan* p, const cf* raw, cd* out, int nchan, int64_
                            scale);
     } else {
         const dim3 grid((int)std::min<int64_t>(rows, (int64_t)p->cu_count * 8));
-        if (p->rot_ant)
+        if (track_ant)
+            hipLaunchKernelGGL(rows_continuum_track_kernel<true>, grid, dim3(continuum_threads(nchan)), 0, p->stream, raw, out,
+                               track_ant_rot_arg(p), nchan, rows, n_splits, split_stride, scale, slots, lead, n_prod, n_cross);
+        else if (p->track)
+            hipLaunchKernelGGL(rows_continuum_track_kernel<false>, grid, dim3(continuum_threads(nchan)), 0, p->stream, raw, out,
+                               track_rot_arg(p), nchan, rows, n_splits, split_stride, scale, slots, lead, n_prod, n_cross);
+        else if (p->rot_ant)
             hipLaunchKernelGGL(rows_continuum_kernel<true>, grid, dim3(continuum_threads(nchan)), 0, p->stream, raw, out, ant_rot_arg(p),
                                nchan, rows, n_splits, split_stride, scale, slots, lead, n_prod, n_cross);
         else
@@ -269,8 +327,43 @@ int launch_rows_continuum(fxc_plan* p, const cf* raw, cd* out, int nchan, int64_
     return FXC_OK;
 }
 
+// What a pass of fx_rows_dev does with its raw rows: SPECTRUM or CONTINUUM rows into `out` from row `row0` on, or -- a tracked
+// fx_accumulate, which runs the rows routes -- the fold of the pass's chunks into the accumulator (track_fold_kernel)
+struct RowsOut {
+    int mode;
+    void* out;
+    float inv_pts;
+    double cscale;
+};
+
+int launch_rows(fxc_plan* p, const RowsOut& o, int64_t row0, const cf* raw, int nchan, int64_t rows, int n_splits,
+                int64_t split_stride, int slots, LeadRows lead, int n_prod = 1, int n_cross = 1) {
+    if (p->track) {
+        const int rc = track_pass(p, rows / p->n_prod);
+        if (rc) return rc;
+    }
+    if (o.mode == FXC_MODE_SPECTRUM) {
+        launch_rows_spectrum(p, raw, static_cast<cf*>(o.out) + row0 * nchan, nchan, rows, n_splits, split_stride, o.inv_pts, slots, lead,
+                             n_prod, n_cross);
+    } else if (o.mode == FXC_MODE_CONTINUUM) {
+        const int rc = launch_rows_continuum(p, raw, static_cast<cd*>(o.out) + row0, nchan, rows, n_splits, split_stride, o.cscale, slots,
+                                             lead, n_prod, n_cross);
+        if (rc) return rc;
+    } else {
+        const dim3 grid(grid_for((int64_t)p->n_prod * nchan, 256, p->cu_count));
+        if (p->n_ant > 2)
+            hipLaunchKernelGGL(track_fold_kernel<true>, grid, dim3(256), 0, p->stream, raw, p->d_acc, track_ant_rot_arg(p), nchan,
+                               rows / p->n_prod, n_splits, split_stride, slots, lead, p->n_prod, p->n_base);
+        else
+            hipLaunchKernelGGL(track_fold_kernel<false>, grid, dim3(256), 0, p->stream, raw, p->d_acc, track_rot_arg(p), nchan,
+                               rows / p->n_prod, n_splits, split_stride, slots, lead, p->n_prod, p->n_base);
+    }
+    FXC_HIP(p, hipGetLastError());
+    return FXC_OK;
+}
+
 // fx_rows of a plan with autos: one raw row per chunk and frame range, the ranges as the rows kernels' splits
-int autos_rows_dev(fxc_plan* p, const cf* x, void* out, int64_t n_chunks, int mode, float inv_pts, double cscale) {
+int autos_rows_dev(fxc_plan* p, const cf* x, const RowsOut& o, int64_t n_chunks) {
     const AutoPass a = autos_pass(p, n_chunks, true);
     int rc = ensure_ws(p, a.spec_bytes + a.raw_bytes);
     if (rc) return rc;
@@ -281,26 +374,15 @@ int autos_rows_dev(fxc_plan* p, const cf* x, void* out, int64_t n_chunks, int mo
         rc = autos_raw_sums(p, x + c0 * p->n_ant * p->num_samp, nc, spec, raw, 1, a.xr);
         if (rc) return rc;
         const int64_t rows = nc * p->n_prod;
-        if (mode == FXC_MODE_SPECTRUM)
-            launch_rows_spectrum(p, raw, static_cast<cf*>(out) + c0 * p->n_prod * p->nchan, p->nchan, rows, a.xr, rows * p->nchan,
-                                 inv_pts, 0, kNoLead, p->n_prod, p->n_base);
-        else {
-            rc = launch_rows_continuum(p, raw, static_cast<cd*>(out) + c0 * p->n_prod, p->nchan, rows, a.xr, rows * p->nchan, cscale, 0,
-                                       kNoLead, p->n_prod, p->n_base);
-            if (rc) return rc;
-        }
-        FXC_HIP(p, hipGetLastError());
+        rc = launch_rows(p, o, c0 * p->n_prod, raw, p->nchan, rows, a.xr, rows * p->nchan, 0, kNoLead, p->n_prod, p->n_base);
+        if (rc) return rc;
     }
     return FXC_OK;
 }
 
-// device-resident implementation of fx_rows; out = cf[n_chunks][n_prod][nchan] or cd[n_chunks][n_prod]
-int fx_rows_dev(fxc_plan* p, const cf* x, void* out, int64_t n_chunks, int mode, double bandwidth,
-                const cf* dc_u8 = nullptr) {
-    if (n_chunks == 0) return FXC_OK;
-    const float inv_pts = (float)(1.0 / (double)p->n_pts);
-    const double cscale = 1.0 / ((double)p->n_pts * (double)p->nchan * bandwidth);
-    if (p->autos && !fused_autos(p, n_chunks)) return autos_rows_dev(p, x, out, n_chunks, mode, inv_pts, cscale);
+// the routes of fx_rows_dev: raw rows pass by pass, each pass finished by launch_rows
+int rows_routes(fxc_plan* p, const cf* x, const RowsOut& o, int64_t n_chunks, const cf* dc_u8) {
+    if (p->autos && !fused_autos(p, n_chunks)) return autos_rows_dev(p, x, o, n_chunks);
     if (p->path == FXC_PATH_STREAM) {
         const int nb = (int)stream_blocks(p);
         const int64_t cb = std::min<int64_t>(n_chunks, 65535);
@@ -312,14 +394,8 @@ int fx_rows_dev(fxc_plan* p, const cf* x, void* out, int64_t n_chunks, int mode,
             rc = stream_raw_sums(p, x + c0 * 2 * p->num_samp, nc, raw);
             if (rc) return rc;
             // raw[block][chunk]: the blocks play the role of the generic path's splits (nchan = n_base = 1)
-            if (mode == FXC_MODE_SPECTRUM)
-                hipLaunchKernelGGL(rows_spectrum_kernel<false>, dim3(grid_for(nc, 256, p->cu_count)), dim3(256), 0, p->stream, raw,
-                                   static_cast<cf*>(out) + c0, p->d_rot, 1, nc, nb, nc, inv_pts, 0, kNoLead, 1, 1);
-            else {
-                rc = launch_rows_continuum(p, raw, static_cast<cd*>(out) + c0, 1, nc, nb, nc, cscale, 0, kNoLead);
-                if (rc) return rc;
-            }
-            FXC_HIP(p, hipGetLastError());
+            rc = launch_rows(p, o, c0, raw, 1, nc, nb, nc, 0, kNoLead);
+            if (rc) return rc;
         }
         return FXC_OK;
     }
@@ -341,15 +417,8 @@ int fx_rows_dev(fxc_plan* p, const cf* x, void* out, int64_t n_chunks, int mode,
             // 3 and more antennas: the frame ranges of a chunk are the rows kernels' splits (range-major raw rows)
             const int xr = x_ranges(p, 1);
             const int64_t xr_stride = rows * p->nchan;
-            if (mode == FXC_MODE_SPECTRUM)
-                launch_rows_spectrum(p, raw, static_cast<cf*>(out) + c0 * p->n_prod * p->nchan, p->nchan, rows, xr, xr_stride, inv_pts,
-                                     fused_layout(p), lead, p->n_prod, p->n_base);
-            else {
-                rc = launch_rows_continuum(p, raw, static_cast<cd*>(out) + c0 * p->n_prod, p->nchan, rows, xr, xr_stride, cscale, fused_layout(p), lead,
-                                           p->n_prod, p->n_base);
-                if (rc) return rc;
-            }
-            FXC_HIP(p, hipGetLastError());
+            rc = launch_rows(p, o, c0 * p->n_prod, raw, p->nchan, rows, xr, xr_stride, fused_layout(p), lead, p->n_prod, p->n_base);
+            if (rc) return rc;
         }
         return FXC_OK;
     }
@@ -363,22 +432,15 @@ int fx_rows_dev(fxc_plan* p, const cf* x, void* out, int64_t n_chunks, int mode,
             const int64_t nc = std::min(cb, n_chunks - c0);
             rc = split_raw_sums(p, x + c0 * 2 * p->num_samp, nc, raw);
             if (rc) return rc;
-            const LeadRows lead = fused_lead(p, 2 * nc);
-            if (mode == FXC_MODE_SPECTRUM)
-                hipLaunchKernelGGL(rows_spectrum_kernel<false>, dim3(grid_for(nc * N, 256, p->cu_count)), dim3(256), 0, p->stream,
-                                   raw, static_cast<cf*>(out) + c0 * N, p->d_rot, N, nc, 1, (int64_t)0, inv_pts, 3, lead, 1, 1);
-            else {
-                rc = launch_rows_continuum(p, raw, static_cast<cd*>(out) + c0, N, nc, 1, (int64_t)0, cscale, 3, lead);
-                if (rc) return rc;
-            }
-            FXC_HIP(p, hipGetLastError());
+            rc = launch_rows(p, o, c0, raw, N, nc, 1, (int64_t)0, 3, fused_lead(p, 2 * nc));
+            if (rc) return rc;
         }
         return FXC_OK;
     }
     if (use_tiled(p, n_chunks)) {
         const int N = p->nchan;
         const int64_t in_bytes = (int64_t)2 * p->num_samp * (dc_u8 ? 2 : (int64_t)sizeof(cf));   // per chunk
-        const int n_splits = tiled_splits(p, n_chunks);
+        const int n_splits = tiled_splits(p, split_basis(p, n_chunks));
         const int64_t row_bytes = (int64_t)N * (int64_t)sizeof(cf);
         const int64_t cb = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_chunks, tiled_streams_per_pass(p) / 2),
                                                                   ws_target() / (row_bytes * n_splits)));
@@ -390,20 +452,14 @@ int fx_rows_dev(fxc_plan* p, const cf* x, void* out, int64_t n_chunks, int mode,
             rc = tiled_raw_sums(p, reinterpret_cast<const cf*>(reinterpret_cast<const char*>(x) + c0 * in_bytes), nc, n_splits,
                                 raw, dc_u8 ? dc_u8 + c0 * 2 : nullptr);
             if (rc) return rc;
-            if (mode == FXC_MODE_SPECTRUM)
-                hipLaunchKernelGGL(rows_spectrum_kernel<false>, dim3(grid_for(nc * N, 256, p->cu_count)), dim3(256), 0, p->stream,
-                                   raw, static_cast<cf*>(out) + c0 * N, p->d_rot, N, nc, n_splits, nc * N, inv_pts, 0, kNoLead, 1, 1);
-            else {
-                rc = launch_rows_continuum(p, raw, static_cast<cd*>(out) + c0, N, nc, n_splits, nc * N, cscale, 0, kNoLead);
-                if (rc) return rc;
-            }
-            FXC_HIP(p, hipGetLastError());
+            rc = launch_rows(p, o, c0, raw, N, nc, n_splits, nc * N, 0, kNoLead);
+            if (rc) return rc;
         }
         return FXC_OK;
     }
     const bool xf = mixed_one_pass(p, dc_u8 != nullptr);
     const bool xm = !xf && two_pass_xm(p, dc_u8 != nullptr);
-    const XGeom g = x_geometry(p, n_chunks, xf, xm);
+    const XGeom g = x_geometry(p, split_basis(p, n_chunks), xf, xm);
     int64_t spec_bytes, raw_bytes;
     const int64_t cb = generic_chunks_per_pass(p, n_chunks, g, &spec_bytes, &raw_bytes, xf, xm);
     int rc = ensure_ws(p, spec_bytes + raw_bytes);
@@ -437,16 +493,22 @@ int fx_rows_dev(fxc_plan* p, const cf* x, void* out, int64_t n_chunks, int mode,
         kt.stop();
         const int64_t rows = nc * p->n_base;
         const int64_t split_stride = rows * p->nchan;
-        if (mode == FXC_MODE_SPECTRUM)
-            launch_rows_spectrum(p, raw, static_cast<cf*>(out) + c0 * p->n_base * p->nchan, p->nchan, rows, g.n_splits, split_stride,
-                                 inv_pts, 0, kNoLead, 1, 1);
-        else {
-            rc = launch_rows_continuum(p, raw, static_cast<cd*>(out) + c0 * p->n_base, p->nchan, rows, g.n_splits, split_stride, cscale, 0, kNoLead);
-            if (rc) return rc;
-        }
         FXC_HIP(p, hipGetLastError());
+        rc = launch_rows(p, o, c0 * p->n_base, raw, p->nchan, rows, g.n_splits, split_stride, 0, kNoLead);
+        if (rc) return rc;
     }
     return FXC_OK;
+}
+
+// device-resident implementation of fx_rows; out = cf[n_chunks][n_prod][nchan] or cd[n_chunks][n_prod].  Under a delay track
+// the call's chunks are the plan's chunks track_t .. track_t + n_chunks - 1 (launch_rows counts them pass by pass).
+int fx_rows_dev(fxc_plan* p, const cf* x, void* out, int64_t n_chunks, int mode, double bandwidth, const cf* dc_u8) {
+    if (n_chunks == 0) return FXC_OK;
+    const RowsOut o = {mode, out, (float)(1.0 / (double)p->n_pts), 1.0 / ((double)p->n_pts * (double)p->nchan * bandwidth)};
+    const int64_t t0 = p->track_t;
+    const int rc = rows_routes(p, x, o, n_chunks, dc_u8);
+    if (rc) p->track_t = t0;
+    return rc;
 }
 
 // host-buffer helper: stage in, run, stage out (synchronous)

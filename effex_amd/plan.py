@@ -100,6 +100,7 @@ class FxPlan(object):
         self.device = info.device
         self.path = PATH_NAMES[info.path]
         self.autos, self.n_rows = False, self.n_baselines
+        self.tracked = False                              # a delay track is set (set_delay_track)
         if autos:
             self.set_autos(True)
 
@@ -234,6 +235,7 @@ class FxPlan(object):
         if rot.shape != (self.nchan,):
             raise ValueError("rot must have shape ({},)".format(self.nchan))
         self._check(self._lib.fxc_set_rot(self._h, rot.ctypes.data))
+        self.tracked = False
 
     def set_delay(self, bandwidth, frequency, calibrated_delay):
         self.set_rot(rot_table(self.nchan, bandwidth, frequency, calibrated_delay))
@@ -245,10 +247,46 @@ class FxPlan(object):
         if tables.shape != (self.n_ant, self.nchan):
             raise ValueError("tables must have shape ({}, {})".format(self.n_ant, self.nchan))
         self._check(self._lib.fxc_set_rot_ant(self._h, tables.ctypes.data))
+        self.tracked = False
 
     def set_delays(self, delays_s, bandwidth, frequency):
         """Phase every baseline for the per-antenna delays ``delays_s`` [n_ant] (seconds, e.g. from ``estimate_delays``)."""
         self.set_rot_ant(rot_tables(self.nchan, bandwidth, frequency, delays_s))
+
+    def _per_antenna(self, v, name):
+        v = np.asarray(v, dtype=np.float64)
+        if v.ndim == 0 and self.n_ant == 2:
+            v = np.array([0.0, float(v)])          # a scalar: antenna 1 against antenna 0, as set_delay
+        v = np.ascontiguousarray(v.reshape(-1))
+        if v.shape != (self.n_ant,):
+            raise ValueError("{} must have {} entries".format(name, self.n_ant))
+        return v
+
+    def set_delay_track(self, delays_s, rates_s_per_chunk, bandwidth, frequency, first_chunk=0):
+        """Delays that move: chunk t is phased for ``delays_s[a] + t * rates_s_per_chunk[a]`` (fxcorr.h fxc_set_delay_track).
+        Every ``fx_rows`` / ``fx_accumulate`` call and every pipe batch takes the next chunk indices, from ``first_chunk`` on.
+        A scalar delay / rate on a two-antenna plan means antenna 1 against antenna 0.  Ends at the next ``set_rot*``."""
+        tau0 = self._per_antenna(delays_s, "delays_s")
+        rate = self._per_antenna(rates_s_per_chunk, "rates_s_per_chunk")
+        self._check(self._lib.fxc_set_delay_track(self._h, tau0.ctypes.data, rate.ctypes.data, float(bandwidth), float(frequency),
+                                                  int(first_chunk)))
+        self.tracked = True
+
+    @property
+    def track_chunk(self):
+        """The chunk index the next chunk takes under the delay track."""
+        t = ctypes.c_int64()
+        self._check(self._lib.fxc_delay_track_chunk(self._h, ctypes.byref(t)))
+        return t.value
+
+    def track_seek(self, chunk):
+        self._check(self._lib.fxc_delay_track_seek(self._h, int(chunk)))
+
+    def track_tables(self, chunk):
+        """The per-antenna rot tables [n_ant, nchan] complex128 the device applies to chunk ``chunk``."""
+        out = np.empty((self.n_ant, self.nchan), dtype=np.complex128)
+        self._check(self._lib.fxc_delay_track_tables(self._h, int(chunk), out.ctypes.data))
+        return out
 
     # -- F stage ----------------------------------------------------------------------------
     def channelize(self, x):

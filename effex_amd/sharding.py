@@ -95,7 +95,10 @@ class ShardedIntegrator(object):
     def my_range(self, n_chunks):
         return chunk_range(self.rank, self.world_size, n_chunks)
 
-    def accumulate(self, x_local):
+    def accumulate(self, x_local, first_chunk=None):
+        """``first_chunk``: the global index of ``x_local``'s first chunk, for a plan with a delay track (``FxPlan.track_seek``)."""
+        if first_chunk is not None:
+            self.plan.track_seek(first_chunk)
         return self.plan.fx_accumulate(x_local)
 
     def reduce(self, root=0, to_all=False):
@@ -208,6 +211,8 @@ class ShardedRows(object):
         row_len = n_rows * (self.plan.nchan if spectrum else 1)
         dtype = np.complex64 if spectrum else np.complex128
         lo, hi = self.my_range(n_chunks)
+        if getattr(self.plan, "tracked", False):      # a delay track counts global chunks: this rank's rows start at `lo`
+            self.plan.track_seek(lo)
         to_file = consumer is None
         if self.rank == 0 and to_file:
             rowsink.create_shared(path, header, freqs if spectrum else None, row_len, dtype, n_chunks)

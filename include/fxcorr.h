@@ -166,6 +166,34 @@ int fxc_set_rot(fxc_plan* plan, const double* rot_re_im);
  * wins.  FXC_ERR_ARG: a NULL argument, n_ant < 2. */
 int fxc_set_rot_ant(fxc_plan* plan, const double* rot_ant_re_im);
 
+/* Delay track: delays that move with the chunk index (fringe stopping; the reference's TEST sweep, effex.py:403-404).  The plan
+ * keeps a chunk counter t, set to first_chunk here.  Chunk t is phased with the per-antenna tables of
+ *   tau_a(t) = tau0_s[a] + t * rate_s_per_chunk[a],   r_a[k](t) = exp(+2*pi*i*f_k*tau_a(t)),
+ *   f_k = fftfreq(nchan, 1/bandwidth)[k] + frequency
+ * exactly as fxc_set_rot_ant would phase it with the tables of that chunk (two antennas with tau0 = (0, tau) and rate 0:
+ * fxc_set_rot of rot(tau)); auto rows take no rot.  The tables are formed on the device, in float64 (f_k*tau in turns, rounded
+ * once, reduced, sincospi), from (a, k, t) alone: the rows of a chunk do not depend on how calls and passes batch the chunks.
+ * Every call that consumes chunks takes t, t+1, ... for them and advances the counter by their number: fxc_fx_rows (_u8, _iq),
+ * fxc_fx_accumulate (_u8, _iq), and the batches of a pipe in submit order.  A tracked fxc_fx_accumulate applies rot chunk by
+ * chunk before it sums: it runs the raw rows of fxc_fx_rows (one row set per chunk) and folds raw * conj(w_t) into the float64
+ * accumulator in chunk order, so the accumulator (and fxc_acc_export, fxc_reduce) holds rotated sums and every finalize form
+ * multiplies by 1 instead of conj(rot) while the track is set; count, fftshift and continuum scaling are unchanged.  Chunks
+ * accumulated with and without a track do not mix in one integration: fxc_set_delay_track answers FXC_ERR_STATE while the
+ * accumulator holds chunks accumulated without one, fxc_set_rot / fxc_set_rot_ant while it holds tracked ones (fxc_acc_reset or
+ * a finalize with reset empties it).  fxc_set_rot and fxc_set_rot_ant end the track; the last of the three calls wins.  Plans
+ * without a track run exactly the kernels they run without these calls.
+ * fxc_set_delay_track synchronises the plan's stream.  FXC_ERR_ARG: a NULL argument, n_ant < 2, a non-finite value,
+ * bandwidth <= 0, first_chunk < 0.  FXC_ERR_STATE: as above, or an fxc_pipe uses the plan (create the pipe after the track).
+ * fxc_delay_track_chunk: the counter (the index the next chunk takes); fxc_delay_track_seek moves it (a sharded run starts each
+ * rank at the first chunk of its range); both FXC_ERR_STATE without a track, seek FXC_ERR_ARG for chunk < 0.
+ * fxc_delay_track_tables: the tables r_a[k](chunk) as the device forms them, out_re_im = [n_ant][nchan] complex128 host memory,
+ * computed by the same device code and copied out; synchronises. */
+int fxc_set_delay_track(fxc_plan* plan, const double* tau0_s, const double* rate_s_per_chunk, double bandwidth, double frequency,
+                        int64_t first_chunk);
+int fxc_delay_track_chunk(const fxc_plan* plan, int64_t* next_chunk);
+int fxc_delay_track_seek(fxc_plan* plan, int64_t chunk);
+int fxc_delay_track_tables(fxc_plan* plan, int64_t chunk, double* out_re_im);
+
 /* F-stage only — replaces cusignal.filtering.channelize_poly + .T at effex.py:553 (and the
  * complex128 copy at :551).  x = [n_streams][num_samp] complex64, out = [n_streams][n_pts][nchan]
  * complex64, natural (un-shifted) bin order; trailing num_samp mod nchan samples ignored; zero
