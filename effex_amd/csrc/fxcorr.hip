@@ -3,7 +3,7 @@
 // One translation unit.  This file holds the ABI entry points; it includes
 //   fx_math.h, fx_fused4096.h, fx_tiled.h, fx_small.h, fx_mixed.h   index maps, butterflies and kernel phases (also compiled by
 //                                           g++ for the host emulation under tests/emul)
-//   k_generic.h k_finish.h (+ k_finish_rows.h) k_fused4096.h k_tiled.h k_small.h k_prepass.h k_stream.h k_conditioning.h k_track.h k_delay.h k_synth.h
+//   k_generic.h k_finish.h (+ k_finish_rows.h) k_fused4096.h k_tiled.h k_small.h k_prepass.h k_stream.h k_conditioning.h k_track.h k_delay.h k_fringe.h k_synth.h
 //                                           the __global__ kernels, one file per path / step
 //   h_plan.h h_rtc.h h_launch.h h_build.h h_run.h h_rccl.h
 //                                           fxc_plan, the kernels compiled per channel count, the per-path launchers and
@@ -137,6 +137,7 @@ int64_t ws_target() {
 #include "k_conditioning.h"
 #include "k_track.h"
 #include "k_delay.h"
+#include "k_fringe.h"
 #include "k_synth.h"
 #include "h_plan.h"
 #include "h_rtc.h"
@@ -1338,6 +1339,155 @@ int fxc_estimate_delays(fxc_plan* p, const void* x, int64_t n, int mem_kind, dou
     std::vector<const cf*> streams((size_t)p->n_ant);
     for (int a = 0; a < p->n_ant; ++a) streams[(size_t)a] = static_cast<const cf*>(x) + (int64_t)a * n;
     return estimate_delays_batch(p, streams.data(), p->n_ant, ref, n, mem_kind, rate, delays_s);
+}
+
+namespace {
+
+// The fringe fit of the baselines (ref, b), b != ref (fxcorr.h fxc_fringe_fit; kernels in k_fringe.h).  The baselines go
+// through in batches of as many as fit the workspace target (FXC_WS_MB): gather, frequency transform, time transform + peak,
+// stencil; every batch's result words go into one block: one copy to the host and one synchronisation for the whole call.
+int fringe_fit_batch(fxc_plan* p, const cf* rows, int64_t n_chunks, int mem_kind, double bandwidth, double frequency, int ref,
+                     int lk_log, int lt_log, double* delay_s, double* rate_s_per_chunk, double* snr) {
+    FXC_DEVICE(p, p->device);
+    const int n_ant = p->n_ant, nchan = p->nchan, n_other = n_ant - 1;
+    const int64_t lk = 1ll << lk_log, lt = 1ll << lt_log;
+    const int64_t n_rows = p->n_prod;
+    // the time-axis tile: as many adjacent columns (a power of two, 64 at most) as fit the LDS budget beside the twiddles
+    int tm_log = 0, pad = 1;
+    for (int cand = 6; cand >= 0; --cand) {
+        const int64_t tm = 1ll << cand, pd = tm < 32 ? tm : 0;
+        if (tm <= lk && (lt * tm + (lt >> 4) * pd + lt) * (int64_t)sizeof(cf) <= kFringeLdsBytes) {
+            tm_log = cand;
+            pad = (int)pd;
+            break;
+        }
+    }
+    const int64_t lds = (lt * (1ll << tm_log) + (lt >> 4) * pad + lt) * (int64_t)sizeof(cf);
+    const int first_log = lt_log % 4 ? lt_log % 4 : 4;
+    // workspace: two transform buffers [n_chunks][Lk] per baseline of a batch, its rows staged when they are host memory,
+    // and the result words of every baseline (best[n_other], stencil[n_other][5] complex128, part[n_other][kFringeParts])
+    const int64_t buf_one = n_chunks * lk * (int64_t)sizeof(cf);
+    const int64_t stage_one = mem_kind == FXC_MEM_HOST ? (n_chunks * nchan * (int64_t)sizeof(cf) + 255) / 256 * 256 : 0;
+    const int64_t res_bytes = ((int64_t)n_other * (8 + 80 + 8 * kFringeParts) + 255) / 256 * 256;
+    const int64_t per_base = 2 * buf_one + stage_one;
+    const int64_t fit = (ws_target() - res_bytes) / per_base;
+    const int batch = (int)std::max<int64_t>(1, std::min<int64_t>(fit, std::min(n_other, kFringeBatch)));
+    int rc = ensure_ws(p, res_bytes + batch * per_base);
+    if (rc) return rc;
+    FXC_HIP(p, hipFuncSetAttribute(reinterpret_cast<const void*>(&fringe_time_peak_kernel),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, kFringeLdsBytes));
+    char* ws = static_cast<char*>(p->d_ws);
+    cf* gbuf[2] = {reinterpret_cast<cf*>(ws), reinterpret_cast<cf*>(ws + batch * buf_one)};
+    cf* stage = reinterpret_cast<cf*>(ws + 2 * batch * buf_one);
+    char* res = ws + batch * per_base;
+    unsigned long long* best = reinterpret_cast<unsigned long long*>(res);
+    double* stencil = reinterpret_cast<double*>(res + 8 * (int64_t)n_other);
+    double* part = stencil + 10 * (int64_t)n_other;
+    std::vector<int> others;
+    for (int b = 0; b < n_ant; ++b)
+        if (b != ref) others.push_back(b);
+    FXC_HIP(p, hipMemsetAsync(best, 0, 8 * (size_t)n_other, p->stream));
+    for (int b0 = 0; b0 < n_other; b0 += batch) {
+        const int nb = std::min(batch, n_other - b0);
+        FringeRows br{};
+        for (int q = 0; q < nb; ++q) {
+            const int b = others[(size_t)(b0 + q)], lo = std::min(ref, b), hi = std::max(ref, b);
+            const int64_t row = (int64_t)lo * (2 * n_ant - lo - 1) / 2 + (hi - lo - 1);     // the baseline order of the results
+            br.conj[q] = b < ref;
+            if (mem_kind == FXC_MEM_HOST) {
+                cf* st = stage + q * (stage_one / (int64_t)sizeof(cf));
+                FXC_HIP(p, hipMemcpy2DAsync(st, (size_t)nchan * sizeof(cf), rows + row * nchan, (size_t)(n_rows * nchan) * sizeof(cf),
+                                            (size_t)nchan * sizeof(cf), (size_t)n_chunks, hipMemcpyHostToDevice, p->stream));
+                br.off[q] = st - stage;
+            } else {
+                br.off[q] = row * nchan;
+            }
+        }
+        const cf* src = mem_kind == FXC_MEM_HOST ? stage : rows;
+        const int64_t t_stride = mem_kind == FXC_MEM_HOST ? nchan : n_rows * nchan;
+        hipLaunchKernelGGL(fringe_gather_kernel, dim3(kFringeParts, nb), dim3(kFringeThreads), 0, p->stream, src, br, t_stride, gbuf[0],
+                           part + (int64_t)b0 * kFringeParts, (int)n_chunks, nchan, lk_log);
+        // frequency axis: forward Stockham stages over the nb n_chunks rows, at most 65535 rows (gridDim.y) a launch
+        int cur = 0;
+        int64_t pp = 1;
+        const int64_t n_lines = (int64_t)nb * n_chunks;
+        for (int bits = lk_log; bits > 0;) {
+            const int r = bits >= 4 ? 4 : bits;
+            for (int64_t l0 = 0; l0 < n_lines; l0 += 65535) {
+                const dim3 grid(grid_for(lk >> r, 256, p->cu_count), (unsigned)std::min<int64_t>(65535, n_lines - l0));
+                const cf* in = gbuf[cur] + l0 * lk;
+                cf* out = gbuf[cur ^ 1] + l0 * lk;
+                if (r == 4) hipLaunchKernelGGL(stockham_stage_kernel<16>, grid, dim3(256), 0, p->stream, in, out, lk, pp, -1.0);
+                else if (r == 3) hipLaunchKernelGGL(stockham_stage_kernel<8>, grid, dim3(256), 0, p->stream, in, out, lk, pp, -1.0);
+                else if (r == 2) hipLaunchKernelGGL(stockham_stage_kernel<4>, grid, dim3(256), 0, p->stream, in, out, lk, pp, -1.0);
+                else hipLaunchKernelGGL(stockham_stage_kernel<2>, grid, dim3(256), 0, p->stream, in, out, lk, pp, -1.0);
+            }
+            pp <<= r;
+            bits -= r;
+            cur ^= 1;
+        }
+        const cf* g = gbuf[cur];
+        hipLaunchKernelGGL(fringe_time_peak_kernel, dim3((unsigned)(lk >> tm_log), nb), dim3(kFringeThreads), (size_t)lds, p->stream, g,
+                           best + b0, (int)n_chunks, lk_log, lt_log, tm_log, pad, first_log);
+        hipLaunchKernelGGL(fringe_stencil_kernel, dim3(nb), dim3(kFringeThreads), 0, p->stream, g, best + b0,
+                           stencil + 10 * (int64_t)b0, (int)n_chunks, lk_log, lt_log);
+        FXC_HIP(p, hipGetLastError());
+    }
+    std::vector<char> h_res((size_t)res_bytes);
+    FXC_HIP(p, hipMemcpyAsync(h_res.data(), res, (size_t)res_bytes, hipMemcpyDeviceToHost, p->stream));
+    FXC_HIP(p, hipStreamSynchronize(p->stream));
+    const unsigned long long* h_best = reinterpret_cast<const unsigned long long*>(h_res.data());
+    const double* h_st = reinterpret_cast<const double*>(h_res.data() + 8 * (int64_t)n_other);
+    const double* h_part = h_st + 10 * (int64_t)n_other;
+    auto sub = [](double a, double b, double c) {      // effex.py:619-625
+        const double la = std::log(a), lb = std::log(b), lc = std::log(c);
+        return 0.5 * (la - lc) / (la - 2.0 * lb + lc);
+    };
+    for (int i = 0; i < n_other; ++i) {
+        const unsigned lin = (unsigned)(0xFFFFFFFFull - (h_best[i] & 0xFFFFFFFFull));
+        int64_t q = (int64_t)(lin >> lk_log) & (lt - 1), m = (int64_t)lin & (lk - 1);
+        double a[5];
+        for (int k = 0; k < 5; ++k) a[k] = std::hypot(h_st[(i * 5 + k) * 2], h_st[(i * 5 + k) * 2 + 1]);
+        const double dm = sub(a[1], a[0], a[2]), dq = sub(a[3], a[0], a[4]);
+        if (m >= lk / 2) m -= lk;
+        if (q >= lt / 2) q -= lt;
+        double power = 0.0;
+        for (int k = 0; k < kFringeParts; ++k) power += h_part[(int64_t)i * kFringeParts + k];
+        const int b = others[(size_t)i];
+        delay_s[b] = ((double)m + dm) * (double)nchan / ((double)lk * bandwidth);
+        rate_s_per_chunk[b] = ((double)q + dq) / ((double)lt * frequency);
+        if (snr) snr[b] = a[0] / std::sqrt(power);
+    }
+    delay_s[ref] = 0.0;
+    rate_s_per_chunk[ref] = 0.0;
+    if (snr) snr[ref] = 0.0;
+    return FXC_OK;
+}
+
+}  // namespace
+
+int fxc_fringe_fit(fxc_plan* p, const void* rows, int64_t n_chunks, int mem_kind, double bandwidth, double frequency, int ref,
+                   int pad, double* delay_s, double* rate_s_per_chunk, double* snr) {
+    if (!p || !rows || !delay_s || !rate_s_per_chunk) return fail(p, FXC_ERR_ARG, "NULL argument");
+    if (p->n_ant < 2) return fail(p, FXC_ERR_ARG, "a fringe fit needs 2 or more antennas, the plan has %d", p->n_ant);
+    if (ref < 0 || ref >= p->n_ant) return fail(p, FXC_ERR_ARG, "ref=%d outside [0, %d)", ref, p->n_ant);
+    if (n_chunks < 2) return fail(p, FXC_ERR_ARG, "n_chunks=%lld: a fringe fit needs 2 or more chunks", (long long)n_chunks);
+    if (pad != 1 && pad != 2 && pad != 4 && pad != 8) return fail(p, FXC_ERR_ARG, "pad=%d is not 1, 2, 4 or 8", pad);
+    if (!std::isfinite(bandwidth) || !(bandwidth > 0.0)) return fail(p, FXC_ERR_ARG, "bandwidth must be finite and > 0");
+    if (!std::isfinite(frequency) || !(frequency > 0.0)) return fail(p, FXC_ERR_ARG, "frequency must be finite and > 0");
+    if (mem_kind != FXC_MEM_HOST && mem_kind != FXC_MEM_DEVICE) return fail(p, FXC_ERR_ARG, "bad mem_kind %d", mem_kind);
+    if (p->nchan == 1) return fail(p, FXC_ERR_UNSUPPORTED, "a fringe fit needs a frequency axis: nchan is 1");
+    int lk_log = 0, lt_log = 0;
+    while ((1ll << lk_log) < (int64_t)pad * p->nchan) ++lk_log;
+    while (lt_log < 13 && (1ll << lt_log) < (int64_t)pad * n_chunks) ++lt_log;
+    if (lt_log > 12)
+        return fail(p, FXC_ERR_UNSUPPORTED, "Lt = pad * n_chunks rounded up to a power of two exceeds 4096 (pad %d, %lld chunks)", pad,
+                    (long long)n_chunks);
+    if (lk_log > 16)
+        return fail(p, FXC_ERR_UNSUPPORTED, "Lk = pad * nchan rounded up to a power of two exceeds 65536 (pad %d, %d channels)", pad,
+                    p->nchan);
+    return fringe_fit_batch(p, static_cast<const cf*>(rows), n_chunks, mem_kind, bandwidth, frequency, ref, lk_log, lt_log, delay_s,
+                            rate_s_per_chunk, snr);
 }
 
 int fxc_pipe_destroy(fxc_pipe* q) {

@@ -540,6 +540,31 @@ class FxPlan(object):
         self._check(self._lib.fxc_estimate_delays(self._h, ptr, int(keep.shape[1]), kind, float(rate), int(ref), out.ctypes.data))
         return out
 
+    def fringe_fit(self, rows, bandwidth, frequency, ref=0, pad=2):
+        """Residual delay and delay rate of every antenna against antenna ``ref`` from SPECTRUM rows (fxcorr.h fxc_fringe_fit):
+        ``rows`` = [n_chunks, n_rows, nchan] complex64 as ``fx_rows(x)`` returns them (numpy, or a CUDA tensor on the plan's
+        device) -> (delays_s, rates_s_per_chunk, snr), float64 [n_ant] each, entry ``ref`` 0.  Added to what
+        ``set_delay_track`` was given they stop the fringes."""
+        self._sync_stream()
+        if _is_torch(rows):
+            import torch
+            if rows.dtype != torch.complex64 or not rows.is_cuda or rows.device.index != self.device:
+                raise ValueError("device input must be a complex64 CUDA tensor on device {}".format(self.device))
+            keep = rows.contiguous()
+            ptr, kind = keep.data_ptr(), _lib.FXC_MEM_DEVICE
+        else:
+            keep = np.ascontiguousarray(rows, dtype=np.complex64)
+            ptr, kind = keep.ctypes.data, _lib.FXC_MEM_HOST
+        shape = tuple(keep.shape)
+        if len(shape) != 3 or shape[1:] != (self.n_rows, self.nchan):
+            raise ValueError("rows must have shape (n_chunks, {}, {}), got {}".format(self.n_rows, self.nchan, shape))
+        delays = np.zeros(self.n_ant, dtype=np.float64)
+        rates = np.zeros(self.n_ant, dtype=np.float64)
+        snr = np.zeros(self.n_ant, dtype=np.float64)
+        self._check(self._lib.fxc_fringe_fit(self._h, ptr, int(shape[0]), kind, float(bandwidth), float(frequency), int(ref),
+                                             int(pad), delays.ctypes.data, rates.ctypes.data, snr.ctypes.data))
+        return delays, rates, snr
+
     # -- measurement ------------------------------------------------------------------------
     def timer_start(self):
         self._check(self._lib.fxc_timer_start(self._h))

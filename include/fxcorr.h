@@ -337,6 +337,40 @@ int fxc_estimate_delay(fxc_plan* plan, const void* iq0, const void* iq1, int64_t
  * fxc_estimate_delay. */
 int fxc_estimate_delays(fxc_plan* plan, const void* x, int64_t n, int mem_kind, double rate, int ref, double* delays_s);
 
+/* Fringe fit: the residual delay and delay rate of every antenna against antenna `ref`, from the SPECTRUM rows of n_chunks
+ * consecutive chunks -- the measurement that fxc_set_delay_track's rate_s_per_chunk needs.
+ * rows = [n_chunks][n_rows][nchan] complex64, host or device (mem_kind), exactly what fxc_fx_rows(.., FXC_MODE_SPECTRUM) writes:
+ * fftshifted bins, n_rows as fxc_plan_products reports; auto rows are ignored.  For every antenna b != ref:
+ *   R[t][j]  = row (ref, b) of chunk t if ref < b, else the complex conjugate of row (b, ref); bin j has the frequency
+ *              frequency + fftshift(fftfreq(nchan, 1/bandwidth))[j]: monotonic, spacing bandwidth / nchan;
+ *   Lk, Lt   = the smallest powers of two >= pad * nchan, >= pad * n_chunks;
+ *   F[q][m]  = sum_t sum_j R[t][j] exp(-2*pi*i*(j*m/Lk + t*q/Lt)), the zero-padded forward 2-D DFT;
+ *   (q0, m0) = arg-max of |F|, the first maximum in row-major (q, m) order (numpy.argmax);
+ *   dm, dq   = 0.5 (ln a - ln c) / (ln a - 2 ln b + ln c), a, b, c = |F| at index -1, 0, +1 along m and along q, indices
+ *              wrapping (the three-point log-parabola of fxc_estimate_delay, effex.py:619-625);
+ *   with m, q = m0, q0 as signed indices (m0 - Lk for m0 >= Lk/2, likewise q0):
+ *   delay_s[b]          = (m + dm) * nchan / (Lk * bandwidth)
+ *   rate_s_per_chunk[b] = (q + dq) / (Lt * frequency)
+ *   snr[b]              = |F[q0][m0]| / sqrt(sum_t sum_j |R[t][j]|^2): the peak over the root-mean-square of |F| on the whole
+ *                         padded grid (Parseval); pure noise gives about sqrt(ln(n_chunks * nchan)).
+ * delay_s[ref] = rate_s_per_chunk[ref] = snr[ref] = 0.  The three outputs are host double[n_ant]; snr may be NULL.
+ * Sign: rows made with the delays tau_used of a signal whose true delays are tau_true have R_ab[t][k] proportional to
+ * exp(+2*pi*i*f_k*(D_b(t) - D_a(t))), D = tau_true - tau_used (row (a,b) is raw_ab r_a conj(r_b)).  The fit returns D_b - D_ref:
+ * fxc_set_delay_track(tau0 + delay_s, rate + rate_s_per_chunk, ..) stops the fringes.
+ * Limits: |delay| < nchan / (2 bandwidth) and |rate| < 1 / (2 frequency) per chunk are the unambiguous ranges.  The search takes
+ * the fringe rate to be the same in every bin (f_k ~ frequency in the time term), which neglects the delay drift over the scan,
+ * |rate| * n_chunks * bandwidth samples: n_chunks * bandwidth / (2 frequency) at the rate limit, 0.2 sample for 256 chunks at
+ * 2.4 MHz / 1.4204 GHz.  Only the n_ant - 1 baselines to `ref` are used.
+ * The |F|^2 of the search is formed in float32 and never written out; the five values of the two parabolas are summed again in
+ * float64.  The baselines go through in batches as large as the workspace target allows, and no value depends on the batching.
+ * Uses the plan's device, stream and workspace; synchronises like fxc_estimate_delays; neither reads nor changes the rot tables,
+ * the track or its counter.
+ * FXC_ERR_ARG, before any device work: a NULL plan / rows / delay_s / rate_s_per_chunk, n_ant < 2, ref outside [0, n_ant),
+ * n_chunks < 2, pad not 1, 2, 4 or 8, bandwidth or frequency <= 0 or not finite, an unknown mem_kind.
+ * FXC_ERR_UNSUPPORTED: Lt > 4096, Lk > 65536, nchan == 1.  The outputs are written on FXC_OK only. */
+int fxc_fringe_fit(fxc_plan* plan, const void* rows, int64_t n_chunks, int mem_kind, double bandwidth, double frequency,
+                   int ref, int pad, double* delay_s, double* rate_s_per_chunk, double* snr);
+
 /* Host-fed front end: replaces the reference's blocking per-chunk copies
  * (effex.py:391-392, 508-509, 693).  A pipe owns `depth` slots of pinned host staging + device buffers.
  * fxc_pipe_acquire hands the producer the pinned input buffer of the next free slot
