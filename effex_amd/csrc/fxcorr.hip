@@ -3,7 +3,7 @@
 // One translation unit.  This file holds the ABI entry points; it includes
 //   fx_math.h, fx_fused4096.h, fx_tiled.h, fx_small.h, fx_mixed.h   index maps, butterflies and kernel phases (also compiled by
 //                                           g++ for the host emulation under tests/emul)
-//   k_generic.h k_finish.h (+ k_finish_rows.h) k_fused4096.h k_tiled.h k_small.h k_prepass.h k_stream.h k_conditioning.h k_track.h k_delay.h k_fringe.h k_synth.h
+//   k_generic.h k_finish.h (+ k_finish_rows.h) k_fused4096.h k_tiled.h k_small.h k_prepass.h k_stream.h k_conditioning.h k_track.h k_delay.h k_fringe.h k_gains.h k_synth.h
 //                                           the __global__ kernels, one file per path / step
 //   h_plan.h h_rtc.h h_launch.h h_build.h h_run.h h_rccl.h
 //                                           fxc_plan, the kernels compiled per channel count, the per-path launchers and
@@ -138,6 +138,7 @@ int64_t ws_target() {
 #include "k_track.h"
 #include "k_delay.h"
 #include "k_fringe.h"
+#include "k_gains.h"
 #include "k_synth.h"
 #include "h_plan.h"
 #include "h_rtc.h"
@@ -1488,6 +1489,90 @@ int fxc_fringe_fit(fxc_plan* p, const void* rows, int64_t n_chunks, int mem_kind
                     p->nchan);
     return fringe_fit_batch(p, static_cast<const cf*>(rows), n_chunks, mem_kind, bandwidth, frequency, ref, lk_log, lt_log, delay_s,
                             rate_s_per_chunk, snr);
+}
+
+namespace {
+
+// The gain solve (fxcorr.h fxc_solve_gains; kernels in k_gains.h).  The workspace holds the results of every interval (gains,
+// step), the averaged matrices V of a group of intervals and, for host rows, a staging block of cross rows; the intervals go
+// through in groups and a group's host chunks in batches, both sized by the workspace target (FXC_WS_MB).  A batch continues
+// the sums of the batch before it in V, so no bit depends on the sizes.  One copy to the host and one synchronisation.
+int solve_gains_batch(fxc_plan* p, const cf* rows, int64_t n_chunks, int mem_kind, int64_t interval, int ref, int iters,
+                      double* gains_re_im, double* step) {
+    FXC_DEVICE(p, p->device);
+    const int n_ant = p->n_ant, nchan = p->nchan, n_base = p->n_base;
+    const int64_t n_rows = p->n_prod;
+    const int64_t n_int = (n_chunks + interval - 1) / interval;
+    // the solve's tile: as many adjacent bins (a power of two) as give every (antenna, bin) a thread and fit the LDS budget
+    int tm_log = 0;
+    for (int cand = 6; cand >= 0; --cand) {
+        const int64_t tm = 1ll << cand;
+        if (tm <= kGainsMaxTile && n_ant * tm <= kGainsThreads && ((int64_t)n_base + 2 * n_ant) * tm * (int64_t)sizeof(cd) <= kGainsLdsBytes) {
+            tm_log = cand;
+            break;
+        }
+    }
+    const int64_t lds = ((int64_t)n_base + 2 * n_ant) * (int64_t)sizeof(cd) << tm_log;
+    const int64_t gains_bytes = n_int * n_ant * nchan * (int64_t)sizeof(cd);
+    const int64_t res_bytes = (gains_bytes + n_int * nchan * (int64_t)sizeof(double) + 255) / 256 * 256;
+    const int64_t v_one = (int64_t)n_base * nchan * (int64_t)sizeof(cd), stage_one = (int64_t)n_base * nchan * (int64_t)sizeof(cf);
+    const bool host = mem_kind == FXC_MEM_HOST;
+    const int64_t avail = std::max<int64_t>(0, ws_target() - res_bytes);
+    const int64_t group = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_int, 65535), (host ? avail / 2 : avail) / v_one));
+    const int64_t group_chunks = std::min(n_chunks, group * interval);
+    const int64_t batch = host ? std::max<int64_t>(1, std::min(group_chunks, (avail - group * v_one) / stage_one)) : 0;
+    int rc = ensure_ws(p, res_bytes + group * v_one + batch * stage_one);
+    if (rc) return rc;
+    FXC_HIP(p, hipFuncSetAttribute(reinterpret_cast<const void*>(&gains_solve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   kGainsLdsBytes));
+    char* ws = static_cast<char*>(p->d_ws);
+    cd* d_gains = reinterpret_cast<cd*>(ws);
+    double* d_step = reinterpret_cast<double*>(ws + gains_bytes);
+    cd* d_v = reinterpret_cast<cd*>(ws + res_bytes);
+    cf* stage = reinterpret_cast<cf*>(ws + res_bytes + group * v_one);
+    const dim3 block(kGainsThreads);
+    const unsigned gx = (unsigned)(((nchan + 1) / 2 + kGainsThreads - 1) / kGainsThreads);
+    for (int64_t s0 = 0; s0 < n_int; s0 += group) {
+        const int64_t s1 = std::min(n_int, s0 + group), c0 = s0 * interval, c1 = std::min(n_chunks, s1 * interval);
+        if (host) {
+            for (int64_t b0 = c0; b0 < c1; b0 += batch) {
+                const int64_t b1 = std::min(c1, b0 + batch), sa = b0 / interval, sb = (b1 - 1) / interval;
+                FXC_HIP(p, hipMemcpy2DAsync(stage, (size_t)stage_one, rows + b0 * n_rows * nchan, (size_t)(n_rows * nchan) * sizeof(cf),
+                                            (size_t)stage_one, (size_t)(b1 - b0), hipMemcpyHostToDevice, p->stream));
+                hipLaunchKernelGGL(gains_average_kernel, dim3(gx, n_base, (unsigned)(sb - sa + 1)), block, 0, p->stream, stage,
+                                   (int64_t)n_base * nchan, b0, b1, interval, n_chunks, sa, s0, d_v, n_base, nchan, (int)(nchan % 2 == 0));
+            }
+        } else {
+            const int vec = nchan % 2 == 0 && reinterpret_cast<uintptr_t>(rows) % 16 == 0;
+            hipLaunchKernelGGL(gains_average_kernel, dim3(gx, n_base, (unsigned)(s1 - s0)), block, 0, p->stream, rows + c0 * n_rows * nchan,
+                               n_rows * nchan, c0, c1, interval, n_chunks, s0, s0, d_v, n_base, nchan, vec);
+        }
+        hipLaunchKernelGGL(gains_solve_kernel, dim3((unsigned)((nchan + (1 << tm_log) - 1) >> tm_log), (unsigned)(s1 - s0)), block,
+                           (size_t)lds, p->stream, d_v, d_gains + s0 * n_ant * nchan, d_step + s0 * nchan, n_ant, nchan, tm_log, ref, iters);
+        FXC_HIP(p, hipGetLastError());
+    }
+    std::vector<char> h_res((size_t)res_bytes);
+    FXC_HIP(p, hipMemcpyAsync(h_res.data(), ws, (size_t)res_bytes, hipMemcpyDeviceToHost, p->stream));
+    FXC_HIP(p, hipStreamSynchronize(p->stream));
+    std::memcpy(gains_re_im, h_res.data(), (size_t)gains_bytes);
+    if (step) std::memcpy(step, h_res.data() + gains_bytes, (size_t)(n_int * nchan) * sizeof(double));
+    return FXC_OK;
+}
+
+}  // namespace
+
+int fxc_solve_gains(fxc_plan* p, const void* rows, int64_t n_chunks, int mem_kind, int64_t interval, int ref, int iters,
+                    double* gains_re_im, double* step) {
+    if (!p || !rows || !gains_re_im) return fail(p, FXC_ERR_ARG, "NULL argument");
+    if (n_chunks < 1) return fail(p, FXC_ERR_ARG, "n_chunks=%lld: a gain solve needs 1 or more chunks", (long long)n_chunks);
+    if (interval < 0) return fail(p, FXC_ERR_ARG, "interval=%lld is negative", (long long)interval);
+    if (ref < 0 || ref >= p->n_ant) return fail(p, FXC_ERR_ARG, "ref=%d outside [0, %d)", ref, p->n_ant);
+    if (iters < 1 || iters > 1000) return fail(p, FXC_ERR_ARG, "iters=%d outside 1 .. 1000", iters);
+    if (mem_kind != FXC_MEM_HOST && mem_kind != FXC_MEM_DEVICE) return fail(p, FXC_ERR_ARG, "bad mem_kind %d", mem_kind);
+    if (p->n_ant < 3)
+        return fail(p, FXC_ERR_UNSUPPORTED, "a gain solve needs 3 or more antennas, the plan has %d: one baseline closes nothing", p->n_ant);
+    if (interval == 0 || interval > n_chunks) interval = n_chunks;
+    return solve_gains_batch(p, static_cast<const cf*>(rows), n_chunks, mem_kind, interval, ref, iters, gains_re_im, step);
 }
 
 int fxc_pipe_destroy(fxc_pipe* q) {

@@ -68,6 +68,26 @@ def rot_tables(nbins, bandwidth, frequency, delays):
     return np.stack([rot_table(nbins, bandwidth, frequency, d) for d in np.asarray(delays, dtype=np.float64).reshape(-1)])
 
 
+def gain_tables(gains, n_ant, nchan, delays_s=None, bandwidth=None, frequency=None):
+    """Per-antenna tables [n_ant, nchan] complex128 for ``FxPlan.set_rot_ant`` that undo the gains ``gains`` [n_ant, nchan] of
+    ``FxPlan.solve_gains`` (bins in the rows' fftshifted order): ``ifftshift(1 / g_a)``, 0 where g_a is 0, times the rot table
+    of ``delays_s[a]`` when delays are given."""
+    gains = np.asarray(gains, dtype=np.complex128)
+    if gains.shape != (n_ant, nchan):
+        raise ValueError("gains must have shape ({}, {})".format(n_ant, nchan))
+    inv = np.zeros_like(gains)
+    np.divide(1.0, gains, out=inv, where=gains != 0)
+    tables = np.fft.ifftshift(inv, axes=1)
+    if delays_s is not None:
+        if bandwidth is None or frequency is None:
+            raise ValueError("delays_s needs bandwidth and frequency")
+        delays = np.asarray(delays_s, dtype=np.float64).reshape(-1)
+        if delays.shape != (n_ant,):
+            raise ValueError("delays_s must have {} entries".format(n_ant))
+        tables = tables * rot_tables(nchan, bandwidth, frequency, delays)
+    return tables
+
+
 class FxPlan(object):
     def __init__(self, n_ant, nchan, ntaps, num_samp, window=None, device=0, stream=None, path=None, dev=False, autos=False):
         self._lib = _lib.load(dev=dev)          # dev: the developer build with the reference kernels (tests, tools/soak.py)
@@ -564,6 +584,42 @@ class FxPlan(object):
         self._check(self._lib.fxc_fringe_fit(self._h, ptr, int(shape[0]), kind, float(bandwidth), float(frequency), int(ref),
                                              int(pad), delays.ctypes.data, rates.ctypes.data, snr.ctypes.data))
         return delays, rates, snr
+
+    def solve_gains(self, rows, interval=0, ref=0, iters=50):
+        """Every antenna's complex gain per bin from SPECTRUM rows of a calibrator (fxcorr.h fxc_solve_gains): ``rows`` =
+        [n_chunks, n_rows, nchan] complex64 as ``fx_rows(x)`` returns them (numpy, or a CUDA tensor on the plan's device; a 2-D
+        [n_rows, nchan] array such as an integration from ``finalize`` is one chunk) -> (gains [n_int, n_ant, nchan]
+        complex128, step [n_int, nchan] float64), one solution per ``interval`` chunks (0: one over all), bins in the rows'
+        order, antenna ``ref`` real.  ``set_gains(gains[s])`` applies a solution."""
+        self._sync_stream()
+        if _is_torch(rows):
+            import torch
+            if rows.dtype != torch.complex64 or not rows.is_cuda or rows.device.index != self.device:
+                raise ValueError("device input must be a complex64 CUDA tensor on device {}".format(self.device))
+            keep = rows.contiguous()
+            ptr, kind = keep.data_ptr(), _lib.FXC_MEM_DEVICE
+        else:
+            keep = np.ascontiguousarray(rows, dtype=np.complex64)
+            ptr, kind = keep.ctypes.data, _lib.FXC_MEM_HOST
+        shape = tuple(keep.shape)
+        if len(shape) == 2:
+            shape = (1,) + shape
+        if len(shape) != 3 or shape[0] < 1 or shape[1:] != (self.n_rows, self.nchan):
+            raise ValueError("rows must have shape (n_chunks, {}, {}), got {}".format(self.n_rows, self.nchan, tuple(keep.shape)))
+        interval = int(interval)
+        span = min(interval, shape[0]) if interval > 0 else shape[0]
+        n_int = -(-shape[0] // span)
+        gains = np.zeros((n_int, self.n_ant, self.nchan), dtype=np.complex128)
+        step = np.zeros((n_int, self.nchan), dtype=np.float64)
+        self._check(self._lib.fxc_solve_gains(self._h, ptr, int(shape[0]), kind, interval, int(ref), int(iters), gains.ctypes.data,
+                                              step.ctypes.data))
+        return gains, step
+
+    def set_gains(self, gains, delays_s=None, bandwidth=None, frequency=None):
+        """Correct the rows for the per-antenna gains ``gains`` [n_ant, nchan] (one solution of ``solve_gains``, bins in the
+        rows' order): antenna a's table is ``ifftshift(1 / g_a)``, 0 where g_a is 0 so that a dead channel stays zero, times
+        ``rot_tables(nchan, bandwidth, frequency, delays_s)[a]`` when delays are given, handed to ``set_rot_ant``."""
+        self.set_rot_ant(gain_tables(gains, self.n_ant, self.nchan, delays_s, bandwidth, frequency))
 
     # -- measurement ------------------------------------------------------------------------
     def timer_start(self):

@@ -163,7 +163,8 @@ int fxc_set_rot(fxc_plan* plan, const double* rot_re_im);
  * float64 and multiply by conj(w) as they do by conj(rot).  Auto rows (FXC_PRODUCTS_CROSS_AUTO) take no rot.  Two antennas: the
  * one w is formed here and becomes the shared table.  Like fxc_set_rot it synchronises the plan's stream first and applies to
  * every finishing kernel queued afterwards (rows, every finalize form, fxc_finalize_sums, pipes); of the two calls the last one
- * wins.  FXC_ERR_ARG: a NULL argument, n_ant < 2. */
+ * wins.  The tables need not have unit modulus: they are copied as they are, and r_a = 1 / g_a with the gains of
+ * fxc_solve_gains corrects the rows' amplitudes and phases.  FXC_ERR_ARG: a NULL argument, n_ant < 2. */
 int fxc_set_rot_ant(fxc_plan* plan, const double* rot_ant_re_im);
 
 /* Delay track: delays that move with the chunk index (fringe stopping; the reference's TEST sweep, effex.py:403-404).  The plan
@@ -370,6 +371,41 @@ int fxc_estimate_delays(fxc_plan* plan, const void* x, int64_t n, int mem_kind, 
  * FXC_ERR_UNSUPPORTED: Lt > 4096, Lk > 65536, nchan == 1.  The outputs are written on FXC_OK only. */
 int fxc_fringe_fit(fxc_plan* plan, const void* rows, int64_t n_chunks, int mem_kind, double bandwidth, double frequency,
                    int ref, int pad, double* delay_s, double* rate_s_per_chunk, double* snr);
+
+/* Gain solve: every antenna's complex gain per bin from the SPECTRUM rows of n_chunks consecutive chunks of a point source at
+ * the phase centre (a calibrator; model visibility 1), by least squares over ALL baselines -- what is left
+ * after fxc_estimate_delays / fxc_fringe_fit: the bandpass amplitudes and the residual phases.
+ * rows = [n_chunks][n_rows][nchan] complex64, host or device (mem_kind), exactly what fxc_fx_rows(.., FXC_MODE_SPECTRUM) writes:
+ * fftshifted bins, n_rows as fxc_plan_products reports.  Only the first n_baselines rows of a chunk are read: auto rows are
+ * skipped.  Row (a,b), a < b, in the baseline order of the results, is modelled as g_a conj(g_b).
+ * Solution intervals: with L = interval (0: L = n_chunks), interval s covers the chunks [s L, min((s + 1) L, n_chunks)) and
+ * n_int = ceil(n_chunks / L).  Per interval and per bin k:
+ *   V_ab     = the sum of the interval's rows (a,b), added in float64 one chunk after the other in ascending chunk order (plain
+ *              adds from 0, real and imaginary parts apart), then each part divided by the number of chunks; V_ba = conj(V_ab);
+ *              the diagonal is not used;
+ *   start      s = mean over b != ref (b ascending) of |V_b,ref|; g_ref = sqrt(s), g_a = V_a,ref / sqrt(s); all 0 where s == 0;
+ *   for it = 1 .. iters (Salvini & Wijnholds' StefCal with model visibility 1; every a from the g of the iteration before):
+ *              n_a = sum over b != a of V_ab g_b and d_a = sum over b != a of |g_b|^2, b ascending;
+ *              new_a = n_a / d_a, 0 where d_a == 0; on even it new = (new + g) / 2;
+ *              step = sqrt(sum_a |new_a - g_a|^2 / sum_a |new_a|^2), a ascending, 0 for a zero denominator; g = new;
+ *   end        with u = conj(g_ref) / |g_ref|: g_a = g_a u for a != ref and g_ref = |g_ref|, real and non-negative (nothing
+ *              changes where g_ref == 0).
+ * gains_re_im = [n_int][n_ant][nchan] complex128 and step = [n_int][nchan] float64 (the last iteration's value; may be NULL),
+ * host memory, bins in the rows' order.  iters is a count, not a convergence test: the map from rows to gains is fixed, and
+ * step says how far the iteration got (it converges fast from 8 antennas on, slowly at 3 .. 5).  Everything after the sum is
+ * float64.  fxc_set_rot_ant with r_a = ifftshift(1 / g_a) then makes the rows of the same signal 1.
+ * Host rows are staged through the workspace in batches and the intervals solved in groups, both sized by the workspace
+ * target; a batch continues the sums of the one before it, so no bit of the outputs depends on the sizes, and host and device
+ * rows give the same bits.  Uses the plan's device, stream and workspace; synchronises like fxc_fringe_fit (one copy to the
+ * host and one synchronisation end the call); neither reads nor changes the rot tables, the track or its counter.
+ * Not covered: gains under a delay track (fxc_set_rot_ant ends the track), a sky model other than a point source at the phase
+ * centre, weights or flags, two antennas.
+ * FXC_ERR_ARG, before any device work: a NULL plan / rows / gains_re_im, n_chunks < 1, interval < 0, ref outside [0, n_ant),
+ * iters outside 1 .. 1000, an unknown mem_kind.  FXC_ERR_UNSUPPORTED: fewer than 3 antennas (one baseline closes nothing).
+ * The outputs are written on FXC_OK only. */
+int fxc_solve_gains(fxc_plan* plan, const void* rows, int64_t n_chunks, int mem_kind, int64_t interval, int ref, int iters,
+                    double* gains_re_im /* [n_int][n_ant][nchan] complex128, bins in the rows' order */,
+                    double* step        /* [n_int][nchan], may be NULL */);
 
 /* Host-fed front end: replaces the reference's blocking per-chunk copies
  * (effex.py:391-392, 508-509, 693).  A pipe owns `depth` slots of pinned host staging + device buffers.
