@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import fx_oracle
+import spec_cover
 from effex_amd import synth
 from effex_amd.window import design_window
 
@@ -247,22 +248,11 @@ print("sanitized emulation ok")
 def _spec_shape(nchan, ntaps, u8=False, fonly=False, xm=False):
     """The library's own cut of fx_spec.h for this shape (fxc_spec_probe compiles it through hiprtc -- no GPU needed -- and
     reports threads per slot, slots and stage order), as the -D options the host emulation is built with."""
-    import re
-    from effex_amd import _lib
-    lib = _lib.load(dev=bool(os.environ.get("FXC_RTC_U")))      # (the knob that forces the frames per step exists in the developer library only)
-    buf = ctypes.create_string_buffer(1024)
-    rc = lib.fxc_spec_probe(nchan, ntaps, 3 if xm else (2 if fonly else int(u8)), b"gfx950", buf, len(buf))
+    rc, rep = spec_cover.probe_rc(nchan, ntaps, 3 if xm else (2 if fonly else int(u8)))
     if rc != 0:
         return rc, None
-    fonly = fonly or xm
-    rep = dict(kv.split("=") for kv in buf.value.decode().split())
-    stages = rep["stages"]
-    flags = ["-DFXM_N=%d" % nchan, "-DFXM_T=%d" % ntaps, "-DFXM_TPR=%s" % rep["tpr"], "-DFXM_SLOTS=%s" % rep["slots"],
-             "-DFXM_NST=%d" % len(stages.split(",")), "-DFXM_RADICES=%s" % stages, "-DFXM_U8=%d" % int(u8),
-             "-DFXM_U=%s" % rep["frames_per_step"], "-DFXM_FONLY=%d" % int(fonly), "-DFXM_LEAN=%s" % rep["lean"], "-DFXM_ROWS=%s" % rep["rows"],
-             "-DFXM_GROUPS=%s" % rep["groups"], "-DFXM_PADS=%s" % rep["pads"], "-DFXM_PLANE0=%s" % rep["plane0"], "-DFXM_TWFULL=%s" % rep["twfull"], "-DFXM_XM=%d" % int(xm)]
-    assert re.fullmatch(r"[0-9,]+", stages) and int(rep["code_bytes"]) > 1000
-    return 0, (flags, int(rep["tpr"]), int(rep["slots"]))
+    assert all(v >= 0 for v in rep["stages"]) and rep["code_bytes"] > 1000
+    return 0, (spec_cover.emul_flags(rep, u8=u8, fonly=fonly, xm=xm), rep["tpr"], rep["slots"])
 
 
 def test_specialised_kernel_shapes():
@@ -301,44 +291,7 @@ def test_specialised_kernel_matches_oracle(tmp_path, monkeypatch, nchan, ntaps, 
     flags, tpr, slots = shape
     if frames_per_step == 2 and "-DFXM_U=2" not in flags:
         pytest.skip("one frame per step for this shape (one stage only)")
-    lib_path = str(tmp_path / "libemul_spec.so")
-    subprocess.run(["g++", "-O1", "-std=c++17", "-shared", "-fPIC", "-pthread"] + flags +
-                   ["-o", lib_path, os.path.join(HERE, "emul", "emul_spec.cpp")], check=True)
-    lib = ctypes.CDLL(lib_path)
-    assert lib.emul_spec_threads() == tpr * slots and lib.emul_spec_slots() == slots
-    n_chunks, num_samp = 2, nchan * n_pts + min(3, nchan - 1)
-    rng = np.random.default_rng(nchan * 7 + n_pts)
-    window = rng.standard_normal(ntaps * nchan) if nchan < 16 else design_window(ntaps, nchan)
-    if u8:
-        xb = rng.integers(0, 256, size=(n_chunks, 2, num_samp, 2), dtype=np.uint8)
-        xb[:, 1, 2:] = xb[:, 0, :-2] // 2 + xb[:, 1, 2:] // 2
-        dc = (rng.standard_normal((n_chunks, 2, 2)) * 0.1).astype(np.float32)            # conversion offsets [chunk][antenna] (re, im)
-        x = (xb.astype(np.float32) / np.float32(127.5) + dc[:, :, None, :]).view(np.complex64)[..., 0]
-        x_in, dc_in = xb, dc
-    else:
-        x = synth.synth_iq(nchan, n_chunks, 2, num_samp)
-        x_in, dc_in = x, None
-    tw = np.exp(2j * np.pi * np.arange(nchan) / nchan).astype(np.complex64)
-    h32 = np.ascontiguousarray(window, dtype=np.float32)
-    E = wg_splits * slots
-    out = np.full((E, n_chunks, nchan), np.nan + 0j, dtype=np.complex64)
-    lib.emul_spec_run.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_longlong] * 3 + [ctypes.c_int] * 2
-    assert lib.emul_spec_run(x_in.ctypes.data, h32.ctypes.data, out.ctypes.data, tw.ctypes.data,
-                             dc_in.ctypes.data if u8 else None, num_samp, n_pts, n_chunks, wg_splits, 1) == 0
-    assert np.isfinite(out).all()
-    got = out.astype(np.complex128).sum(axis=0)
-    for c in range(n_chunks):
-        s0 = fx_oracle.spectrometer_poly(x[c, 0], ntaps, nchan, window)
-        s1 = fx_oracle.spectrometer_poly(x[c, 1], ntaps, nchan, window)
-        ref = (s0 * np.conj(s1)).sum(axis=0)
-        assert np.abs(got[c] - ref).max() <= 1e-5 * np.abs(ref).max(), (nchan, c)
-    # a slot's row is the sum over ITS run of frames: slot e of E takes frames [e n_pts / E, (e + 1) n_pts / E)
-    e = E - 1
-    lo, hi = e * n_pts // E, (e + 1) * n_pts // E
-    s0 = fx_oracle.spectrometer_poly(x[0, 0], ntaps, nchan, window)[lo:hi]
-    s1 = fx_oracle.spectrometer_poly(x[0, 1], ntaps, nchan, window)[lo:hi]
-    ref = (s0 * np.conj(s1)).sum(axis=0)
-    assert np.abs(out[e, 0] - ref).max() <= 1e-5 * max(np.abs(ref).max(), 1e-30)
+    spec_cover.check_fx_emulation(tmp_path, nchan, ntaps, n_pts, wg_splits, u8, flags, tpr, slots)
 
 
 @pytest.mark.parametrize("nchan,ntaps,n_pts,wg_splits,n_streams,ant", [
@@ -354,27 +307,7 @@ def test_specialised_f_stage_matches_oracle(tmp_path, nchan, ntaps, n_pts, wg_sp
     rc, shape = _spec_shape(nchan, ntaps, fonly=True)
     assert rc == 0
     flags, tpr, slots = shape
-    lib_path = str(tmp_path / "libemul_spec_f.so")
-    subprocess.run(["g++", "-O1", "-std=c++17", "-shared", "-fPIC", "-pthread"] + flags +
-                   ["-o", lib_path, os.path.join(HERE, "emul", "emul_spec.cpp")], check=True)
-    lib = ctypes.CDLL(lib_path)
-    assert lib.emul_spec_fonly() == 1
-    num_samp = nchan * n_pts + min(2, nchan - 1)
-    rng = np.random.default_rng(nchan + n_streams)
-    window = rng.standard_normal(ntaps * nchan) if nchan < 16 else design_window(ntaps, nchan)
-    x = synth.synth_iq(31 + nchan, n_streams, 1, num_samp)[:, 0]
-    tw = np.exp(2j * np.pi * np.arange(nchan) / nchan).astype(np.complex64)
-    h32 = np.ascontiguousarray(window, dtype=np.float32)
-    assert n_streams % ant == 0
-    out = np.full((n_streams // ant, n_pts, ant, nchan), np.nan + 0j, dtype=np.complex64)
-    lib.emul_spec_run.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_longlong] * 3 + [ctypes.c_int] * 2
-    assert lib.emul_spec_run(x.ctypes.data, h32.ctypes.data, out.ctypes.data, tw.ctypes.data, None, num_samp, n_pts, n_streams,
-                             wg_splits, ant) == 0
-    assert np.isfinite(out).all()
-    for s_ in range(n_streams):
-        ref = fx_oracle.spectrometer_poly(x[s_], ntaps, nchan, window)
-        got = out[s_ // ant, :, s_ % ant, :]
-        assert np.abs(got - ref).max() <= 2e-6 * np.abs(ref).max(), (nchan, s_)
+    spec_cover.check_f_emulation(tmp_path, nchan, ntaps, n_pts, wg_splits, n_streams, ant, flags)
 
 
 def test_specialised_kernels_are_cached_on_disk(tmp_path, monkeypatch):
@@ -439,39 +372,9 @@ def test_second_pass_kernel_matches_oracle(tmp_path, nchan, ntaps, n_pts, wg_spl
     antenna 0 of every chunk pair through the F-only build (streams two chunks apart: Args::stride), then antenna 1 through the
     second-pass build (FXM_XM) whose last butterfly multiplies with antenna 0's spectra -- the sums over the slots' runs are the
     oracle's sum_i spec0[i] conj(spec1[i]) (effex.py:508-521 before the mean)."""
-    libs = []
-    for tag, xm in (("f", False), ("x", True)):
+    shapes = []
+    for xm in (False, True):
         rc, shape = _spec_shape(nchan, ntaps, fonly=not xm, xm=xm)
         assert rc == 0
-        flags, tpr, slots = shape
-        assert "-DFXM_ROWS=1" in flags and slots == 1
-        lib_path = str(tmp_path / ("libemul_spec_%s.so" % tag))
-        subprocess.run(["g++", "-O1", "-std=c++17", "-shared", "-fPIC", "-pthread"] + flags +
-                       ["-o", lib_path, os.path.join(HERE, "emul", "emul_spec.cpp")], check=True)
-        lib = ctypes.CDLL(lib_path)
-        lib.emul_spec_run2.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_longlong] * 3 + [ctypes.c_int] * 2 + [ctypes.c_longlong, ctypes.c_void_p]
-        assert lib.emul_spec_xm() == int(xm)
-        libs.append(lib)
-    f_lib, x_lib = libs
-    n_chunks, num_samp = 3, nchan * n_pts + 11
-    window = design_window(ntaps, nchan)
-    x = synth.synth_iq(nchan + 1, n_chunks, 2, num_samp)
-    tw = np.exp(2j * np.pi * np.arange(nchan) / nchan).astype(np.complex64)
-    h32 = np.ascontiguousarray(window, dtype=np.float32)
-    spec0 = np.full((n_chunks, n_pts, nchan), np.nan + 0j, dtype=np.complex64)
-    assert f_lib.emul_spec_run2(x.ctypes.data, h32.ctypes.data, spec0.ctypes.data, tw.ctypes.data, None, num_samp, n_pts, n_chunks,
-                                wg_splits, 1, 2 * num_samp, None) == 0
-    for c in range(n_chunks):
-        ref = fx_oracle.spectrometer_poly(x[c, 0], ntaps, nchan, window)
-        assert np.abs(spec0[c] - ref).max() <= 1e-5 * np.abs(ref).max()
-    out = np.full((wg_splits, n_chunks, nchan), np.nan + 0j, dtype=np.complex64)
-    ant1 = x.reshape(-1)[num_samp:]
-    assert x_lib.emul_spec_run2(ant1.ctypes.data, h32.ctypes.data, out.ctypes.data, tw.ctypes.data, None, num_samp, n_pts, n_chunks,
-                                wg_splits, 1, 2 * num_samp, spec0.ctypes.data) == 0
-    assert np.isfinite(out).all()
-    got = out.astype(np.complex128).sum(axis=0)
-    for c in range(n_chunks):
-        s0 = fx_oracle.spectrometer_poly(x[c, 0], ntaps, nchan, window)
-        s1 = fx_oracle.spectrometer_poly(x[c, 1], ntaps, nchan, window)
-        ref = (s0 * np.conj(s1)).sum(axis=0)
-        assert np.abs(got[c] - ref).max() <= 1e-5 * np.abs(ref).max(), (nchan, c)
+        shapes.append(shape)
+    spec_cover.check_two_pass_emulation(tmp_path, nchan, ntaps, n_pts, wg_splits, shapes[0], shapes[1])
