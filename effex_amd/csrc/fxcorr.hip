@@ -193,7 +193,7 @@ int fxc_plan_destroy(fxc_plan* p) {
     }
     void* bufs[] = {p->d_win, p->d_tw, p->d_rot, p->d_win4, p->d_tw1, p->d_tw2, p->d_tw0, p->d_tw_small, p->d_stamps,
                     p->d_acc, p->d_sums, p->d_cont, p->d_rowpart, p->d_ws, p->d_stage[0], p->d_stage[1], p->d_stage[2], p->d_dc, p->d_hpre,
-                    p->d_ones, p->d_pre, p->d_tw8192, p->d_unit4, p->d_chirp, p->d_blud, p->d_rot_ant, p->d_pair, p->d_track_par, p->d_track, p->d_one};
+                    p->d_ones, p->d_pre, p->d_tw8192, p->d_unit4, p->d_chirp, p->d_blud, p->d_rot_ant, p->d_pair, p->d_track_par, p->d_track, p->d_one, p->d_gain_q};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (p->ev_t0) (void)hipEventDestroy(p->ev_t0);
@@ -359,7 +359,16 @@ int end_track(fxc_plan* p) {
     if (p->track && p->acc_track && !acc_empty(p))
         return fail(p, FXC_ERR_STATE, "the accumulator holds chunks accumulated under the delay track: finalize or reset it first");
     p->track = false;
+    p->gain_n = 0;      // the gains were solved under this track: they end with it (release_gain_q frees them once the stream is idle)
     return FXC_OK;
+}
+
+// frees the table of a gain track that has ended; the caller has synchronised the plan's stream
+void release_gain_q(fxc_plan* p) {
+    if (p->gain_n == 0 && p->d_gain_q) {
+        (void)hipFree(p->d_gain_q);
+        p->d_gain_q = nullptr;
+    }
 }
 
 // the finalize kernels' rot: a tracked integration's sums are rotated already
@@ -399,6 +408,74 @@ int fxc_set_delay_track(fxc_plan* p, const double* tau0_s, const double* rate_s_
     p->track_t = first_chunk;
     p->track = true;
     p->rot_ant = false;
+    p->gain_n = 0;      // gains were solved on rows made under one particular track: a new track drops them
+    release_gain_q(p);
+    return FXC_OK;
+}
+
+int fxc_set_track_gains(fxc_plan* p, const double* gains_re_im, int64_t n_solutions, int64_t interval, int64_t first_chunk) {
+    if (!p) return fail(p, FXC_ERR_ARG, "NULL plan");
+    if (n_solutions < 0) return fail(p, FXC_ERR_ARG, "n_solutions < 0");
+    if (n_solutions > 0 && !gains_re_im) return fail(p, FXC_ERR_ARG, "gains_re_im is NULL");
+    if (interval < 0 || (interval < 1 && n_solutions > 1))
+        return fail(p, FXC_ERR_ARG, "interval=%lld: %lld solutions need an interval of 1 chunk or more", (long long)interval, (long long)n_solutions);
+    if (first_chunk < 0) return fail(p, FXC_ERR_ARG, "first_chunk < 0");
+    const size_t per = (size_t)p->n_ant * (size_t)p->nchan;
+    if ((uint64_t)n_solutions > ((uint64_t)1 << 46) / (per * sizeof(cd)))
+        return fail(p, FXC_ERR_NOMEM, "%lld solutions of %zu gains do not fit the device", (long long)n_solutions, per);
+    const size_t count = (size_t)n_solutions * per;
+    for (size_t i = 0; i < count; ++i) {
+        const double x = gains_re_im[2 * i], y = gains_re_im[2 * i + 1];
+        if (!std::isfinite(x) || !std::isfinite(y)) return fail(p, FXC_ERR_ARG, "gain %zu is not finite", i);
+        const double m = std::hypot(x, y);
+        // d = x x + y y of the inverse must neither overflow nor underflow
+        if (m != 0.0 && (m < 1e-150 || m > 1e150)) return fail(p, FXC_ERR_ARG, "|gain %zu| = %g outside [1e-150, 1e150]", i, m);
+    }
+    if (!p->track) return fail(p, FXC_ERR_STATE, "the plan has no delay track");
+    if (!acc_empty(p)) return fail(p, FXC_ERR_STATE, "the accumulator holds chunks: finalize or reset it first");
+    if (p->live_pipes) return fail(p, FXC_ERR_STATE, "an fxc_pipe uses the plan");
+    FXC_DEVICE(p, p->device);
+    if (n_solutions == 0) {
+        FXC_HIP(p, hipStreamSynchronize(p->stream));
+        p->gain_n = p->gain_interval = p->gain_first = 0;
+        release_gain_q(p);
+        return FXC_OK;
+    }
+    // the new table is complete before the plan changes: a call that fails leaves an earlier gain track in force
+    const size_t bytes = count * sizeof(cd);
+    cd *g = nullptr, *q = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&q), bytes) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&g), bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        if (q) (void)hipFree(q);
+        return fail(p, FXC_ERR_NOMEM, "allocation of 2 x %zu bytes for the gain track failed", bytes);
+    }
+    hipError_t e = hipMemcpy(g, gains_re_im, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(track_gain_inverse_kernel, dim3(grid_for((int64_t)count, 256, p->cu_count)), dim3(256), 0, p->stream, g, q,
+                           p->nchan, (int64_t)count);
+        e = hipGetLastError();
+    }
+    // also ordered after any queued kernel that still reads the old table
+    if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
+    (void)hipFree(g);
+    if (e != hipSuccess) {
+        (void)hipFree(q);
+        return fail(p, FXC_ERR_HIP, "forming the gain track's table failed: %s", hipGetErrorString(e));
+    }
+    if (p->d_gain_q) (void)hipFree(p->d_gain_q);
+    p->d_gain_q = q;
+    p->gain_n = n_solutions;
+    p->gain_interval = interval;
+    p->gain_first = first_chunk;
+    return FXC_OK;
+}
+
+int fxc_track_gains_info(const fxc_plan* p, int64_t* n_solutions, int64_t* interval, int64_t* first_chunk) {
+    if (!p || !n_solutions || !interval || !first_chunk) return fail(p, FXC_ERR_ARG, "NULL argument");
+    if (!p->track) return fail(p, FXC_ERR_STATE, "the plan has no delay track");
+    *n_solutions = p->gain_n;
+    *interval = p->gain_n ? p->gain_interval : 0;
+    *first_chunk = p->gain_n ? p->gain_first : 0;
     return FXC_OK;
 }
 
@@ -438,6 +515,7 @@ int fxc_set_rot(fxc_plan* p, const double* rot_re_im) {
     FXC_DEVICE(p, p->device);
     // ordered after any queued finish kernel that still reads the old table
     FXC_HIP(p, hipStreamSynchronize(p->stream));
+    release_gain_q(p);
     FXC_HIP(p, hipMemcpy(p->d_rot, rot_re_im, (size_t)p->nchan * sizeof(cd), hipMemcpyHostToDevice));
     p->rot_ant = false;
     return FXC_OK;
@@ -449,6 +527,7 @@ int fxc_set_rot_ant(fxc_plan* p, const double* rot_ant_re_im) {
     if (const int rs = end_track(p)) return rs;
     FXC_DEVICE(p, p->device);
     FXC_HIP(p, hipStreamSynchronize(p->stream));
+    release_gain_q(p);
     const size_t N = (size_t)p->nchan;
     const cd* r = reinterpret_cast<const cd*>(rot_ant_re_im);
     if (p->n_ant == 2) {

@@ -105,6 +105,10 @@ struct fxc_plan {
     size_t track_bytes = 0;
     cd* d_one = nullptr;             // [nchan] of 1: a tracked integration's accumulator holds rotated sums, the finalize kernels' rot
     bool acc_track = false;          // the chunks in the accumulator (spectra_count > 0) were folded under a track
+    // gain track (fxc_set_track_gains) under the delay track: d_gain_q = 1 / g of every solution, [gain_n][n_ant][nchan] in
+    // natural bin order, written once by track_gain_inverse_kernel; gain_n == 0: none, track_tables_kernel runs as before
+    cd* d_gain_q = nullptr;
+    int64_t gain_n = 0, gain_interval = 0, gain_first = 0;
     f4* d_win4 = nullptr;          // [nchan] window quads (one unit tap behind the pre-filter): fused, tiled ring, wave-local, lean fx_spec.h
     cf* d_tw1 = nullptr;
     cf* d_tw2 = nullptr;

@@ -243,7 +243,13 @@ int fx_accumulate_dev(fxc_plan* p, const cf* x, int64_t n_chunks, const cf* dc_u
 int track_tables(fxc_plan* p, int64_t t0, int64_t n_t, cd* out, bool pair) {
     const TrackPar tp = {p->d_track_par, p->d_track_par + p->n_ant, p->track_df, p->track_freq};
     const dim3 grid(grid_for(n_t * (pair ? 1 : p->n_ant) * p->nchan, 256, p->cu_count));
-    if (pair)
+    if (p->gain_n > 0) {      // a gain track (fxc_set_track_gains): the same tables times 1 / g of the chunk's solution
+        const GainTrack gt = {p->d_gain_q, p->gain_n, p->gain_interval > 0 ? p->gain_interval : 1, p->gain_first};
+        if (pair)
+            hipLaunchKernelGGL(track_gain_tables_kernel<true>, grid, dim3(256), 0, p->stream, tp, gt, out, p->n_ant, p->nchan, t0, n_t);
+        else
+            hipLaunchKernelGGL(track_gain_tables_kernel<false>, grid, dim3(256), 0, p->stream, tp, gt, out, p->n_ant, p->nchan, t0, n_t);
+    } else if (pair)
         hipLaunchKernelGGL(track_tables_kernel<true>, grid, dim3(256), 0, p->stream, tp, out, p->n_ant, p->nchan, t0, n_t);
     else
         hipLaunchKernelGGL(track_tables_kernel<false>, grid, dim3(256), 0, p->stream, tp, out, p->n_ant, p->nchan, t0, n_t);

@@ -52,6 +52,84 @@ __global__ void track_tables_kernel(TrackPar tp, cd* __restrict__ out, int n_ant
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// gain track (fxc_set_track_gains): chunk t takes solution s(t) = clamp(floor((t - first_chunk) / interval), 0, n_solutions - 1)
+// and the table of antenna a becomes r_a[k](t) = phasor_a[k](t) * q[s(t)][a][k], q = 1 / g in natural bin order.  Both steps
+// are individually rounded float64 operations (no contraction), so a table still depends on (a, k, t) and the gain track alone,
+// and with every gain 1 it is the plain track's table.
+// ------------------------------------------------------------------------------------------
+struct GainTrack {
+    const cd* q;             // [n_solutions][n_ant][nchan], natural bin order
+    int64_t n_solutions;
+    int64_t interval;        // >= 1 (one solution for every chunk: n_solutions == 1)
+    int64_t first_chunk;
+};
+
+__device__ __forceinline__ int64_t gain_solution(const GainTrack& gt, int64_t t) {
+    const int64_t d = t - gt.first_chunk;
+    if (d <= 0 || gt.n_solutions == 1) return 0;
+    const int64_t s = d / gt.interval;
+    return s < gt.n_solutions ? s : gt.n_solutions - 1;
+}
+
+__device__ __forceinline__ cd gain_apply(cd r, cd q) {
+#pragma clang fp contract(off)
+    cd o;
+    o.x = r.x * q.x - r.y * q.y;
+    o.y = r.x * q.y + r.y * q.x;
+    return o;
+}
+
+// q[s][a][k] = 1 / g[s][a][(k + nchan / 2) % nchan]: the rows' fftshifted order back to natural order (numpy's ifftshift, odd
+// channel counts included) and the inverse (x / d, -y / d), d = x x + y y, 0 where g is 0 so that a dead channel stays zero.
+// Once per fxc_set_track_gains; total = n_solutions n_ant nchan.
+__global__ __launch_bounds__(256) void track_gain_inverse_kernel(const cd* __restrict__ g, cd* __restrict__ q, int nchan, int64_t total) {
+#pragma clang fp contract(off)
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int half = nchan / 2;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += stride) {
+        const int k = (int)(idx % nchan);
+        int j = k + half;
+        if (j >= nchan) j -= nchan;
+        const cd v = g[idx - k + j];
+        const double d = v.x * v.x + v.y * v.y;
+        cd o;
+        o.x = 0.0;
+        o.y = 0.0;
+        if (d != 0.0) {
+            o.x = v.x / d;
+            o.y = -v.y / d;
+        }
+        q[idx] = o;
+    }
+}
+
+// track_tables_kernel with the multiply by q[s(t)][a][k]: one coalesced 16-byte load per table element beside the store
+// PAIR = true: r_0, r_1 with their gains, then w = r_1 conj(r_0) as track_tables_kernel<true> forms it
+template <bool PAIR>
+__global__ void track_gain_tables_kernel(TrackPar tp, GainTrack gt, cd* __restrict__ out, int n_ant, int nchan, int64_t t0, int64_t n_t) {
+    const int rows = PAIR ? 1 : n_ant;
+    const int64_t total = n_t * rows * nchan;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += stride) {
+        const int k = (int)(idx % nchan);
+        const int64_t ta = idx / nchan;
+        const int64_t t = t0 + ta / rows;
+        const cd* q = gt.q + gain_solution(gt, t) * n_ant * nchan + k;
+        if constexpr (PAIR) {
+            const cd ra = gain_apply(track_phasor(tp, 0, k, nchan, t), q[0]);
+            const cd rb = gain_apply(track_phasor(tp, 1, k, nchan, t), q[nchan]);
+            cd w;
+            w.x = rb.x * ra.x + rb.y * ra.y;
+            w.y = rb.y * ra.x - rb.x * ra.y;
+            out[idx] = w;
+        } else {
+            const int a = (int)(ta % rows);
+            out[idx] = gain_apply(track_phasor(tp, a, k, nchan, t), q[(int64_t)a * nchan]);
+        }
+    }
+}
+
 // Tracked integration: acc[p][k] += (sum over the splits and leading parts of chunk c's raw row p) * conj(w_c[k]), chunk after
 // chunk in the order of the stream, in float64 with explicit fused multiply-adds -- so the accumulator after chunks t0 .. t1 is
 // the same bits whatever calls and passes brought them.  The accumulator is in natural bin order and holds rotated sums

@@ -88,6 +88,43 @@ def gain_tables(gains, n_ant, nchan, delays_s=None, bandwidth=None, frequency=No
     return tables
 
 
+def gain_track_solution(chunk, n_solutions, interval, first_chunk):
+    """The solution chunk ``chunk`` takes under a gain track (fxcorr.h fxc_set_track_gains):
+    ``clamp(floor((chunk - first_chunk) / interval), 0, n_solutions - 1)``; interval 0 (one solution) is solution 0."""
+    if int(interval) < 1:
+        return 0
+    return min(max((int(chunk) - int(first_chunk)) // int(interval), 0), int(n_solutions) - 1)
+
+
+def gain_track_tables(gains, interval, first_chunk, chunk, delays, rates, bandwidth, frequency):
+    """The numpy form of one chunk's tables under a delay track with a gain track (fxcorr.h fxc_set_track_gains): [n_ant, nchan]
+    complex128, ``rot_tables(nchan, bandwidth, frequency, delays + chunk * rates)`` times ``ifftshift(1 / g)`` of the chunk's
+    solution.  ``gains`` is [n_ant, nchan] or [n_solutions, n_ant, nchan] as ``FxPlan.solve_gains`` returns them (bins in the
+    rows' fftshifted order).  The inverse is (x / d, -y / d) with d = x x + y y, 0 where g is 0, and the product
+    (c qx - s qy, c qy + s qx), each operation rounded on its own, as the device forms them."""
+    gains = np.asarray(gains, dtype=np.complex128)
+    if gains.ndim == 2:
+        gains = gains[None]
+    if gains.ndim != 3 or gains.shape[0] < 1:
+        raise ValueError("gains must have shape (n_ant, nchan) or (n_solutions, n_ant, nchan)")
+    n_sol, n_ant, nchan = gains.shape
+    if n_sol > 1 and int(interval) < 1:
+        raise ValueError("{} solutions need an interval of 1 chunk or more".format(n_sol))
+    delays = np.asarray(delays, dtype=np.float64).reshape(-1)
+    rates = np.asarray(rates, dtype=np.float64).reshape(-1)
+    if delays.shape != (n_ant,) or rates.shape != (n_ant,):
+        raise ValueError("delays and rates must have {} entries".format(n_ant))
+    g = np.fft.ifftshift(gains[gain_track_solution(chunk, n_sol, interval, first_chunk)], axes=1)
+    x, y = g.real, g.imag
+    d = x * x + y * y
+    live = d != 0
+    safe = np.where(live, d, 1.0)
+    qx, qy = np.where(live, x / safe, 0.0), np.where(live, -y / safe, 0.0)
+    rot = rot_tables(nchan, bandwidth, frequency, delays + float(int(chunk)) * rates)
+    c, s = rot.real, rot.imag
+    return (c * qx - s * qy) + 1j * (c * qy + s * qx)
+
+
 class FxPlan(object):
     def __init__(self, n_ant, nchan, ntaps, num_samp, window=None, device=0, stream=None, path=None, dev=False, autos=False):
         self._lib = _lib.load(dev=dev)          # dev: the developer build with the reference kernels (tests, tools/soak.py)
@@ -285,7 +322,9 @@ class FxPlan(object):
     def set_delay_track(self, delays_s, rates_s_per_chunk, bandwidth, frequency, first_chunk=0):
         """Delays that move: chunk t is phased for ``delays_s[a] + t * rates_s_per_chunk[a]`` (fxcorr.h fxc_set_delay_track).
         Every ``fx_rows`` / ``fx_accumulate`` call and every pipe batch takes the next chunk indices, from ``first_chunk`` on.
-        A scalar delay / rate on a two-antenna plan means antenna 1 against antenna 0.  Ends at the next ``set_rot*``."""
+        A scalar delay / rate on a two-antenna plan means antenna 1 against antenna 0.  Ends at the next ``set_rot*``.
+        A new track drops the gains of ``set_track_gains``: they were solved on rows made under the earlier one, so solve or
+        send them again."""
         tau0 = self._per_antenna(delays_s, "delays_s")
         rate = self._per_antenna(rates_s_per_chunk, "rates_s_per_chunk")
         self._check(self._lib.fxc_set_delay_track(self._h, tau0.ctypes.data, rate.ctypes.data, float(bandwidth), float(frequency),
@@ -303,10 +342,34 @@ class FxPlan(object):
         self._check(self._lib.fxc_delay_track_seek(self._h, int(chunk)))
 
     def track_tables(self, chunk):
-        """The per-antenna rot tables [n_ant, nchan] complex128 the device applies to chunk ``chunk``."""
+        """The per-antenna tables [n_ant, nchan] complex128 the device applies to chunk ``chunk``, the gains of
+        ``set_track_gains`` included."""
         out = np.empty((self.n_ant, self.nchan), dtype=np.complex128)
         self._check(self._lib.fxc_delay_track_tables(self._h, int(chunk), out.ctypes.data))
         return out
+
+    def set_track_gains(self, gains, interval=0, first_chunk=0):
+        """Gains under the delay track (fxcorr.h fxc_set_track_gains): ``gains`` [n_ant, nchan] or [n_solutions, n_ant, nchan]
+        complex128, ``solve_gains``' output as it is; chunk t takes solution
+        ``clamp((t - first_chunk) // interval, 0, n_solutions - 1)`` and antenna a's table of that chunk is multiplied by
+        ``ifftshift(1 / g_a)`` (0 where g_a is 0), on the device.  ``interval`` may be 0 for one solution.  ``None`` removes
+        the gains and keeps the track.  Needs a delay track, an empty accumulator and no open pipe."""
+        if gains is None:
+            self._check(self._lib.fxc_set_track_gains(self._h, None, 0, 0, 0))
+            return
+        gains = np.asarray(gains, dtype=np.complex128)
+        if gains.ndim == 2:
+            gains = gains[None]
+        if gains.ndim != 3 or gains.shape[0] < 1 or gains.shape[1:] != (self.n_ant, self.nchan):
+            raise ValueError("gains must have shape ({0}, {1}) or (n_solutions, {0}, {1})".format(self.n_ant, self.nchan))
+        gains = np.ascontiguousarray(gains)
+        self._check(self._lib.fxc_set_track_gains(self._h, gains.ctypes.data, int(gains.shape[0]), int(interval), int(first_chunk)))
+
+    def track_gains_info(self):
+        """(n_solutions, interval, first_chunk) of the gain track; zeros when the delay track carries none."""
+        n, interval, first = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        self._check(self._lib.fxc_track_gains_info(self._h, ctypes.byref(n), ctypes.byref(interval), ctypes.byref(first)))
+        return n.value, interval.value, first.value
 
     # -- F stage ----------------------------------------------------------------------------
     def channelize(self, x):
@@ -590,7 +653,8 @@ class FxPlan(object):
         [n_chunks, n_rows, nchan] complex64 as ``fx_rows(x)`` returns them (numpy, or a CUDA tensor on the plan's device; a 2-D
         [n_rows, nchan] array such as an integration from ``finalize`` is one chunk) -> (gains [n_int, n_ant, nchan]
         complex128, step [n_int, nchan] float64), one solution per ``interval`` chunks (0: one over all), bins in the rows'
-        order, antenna ``ref`` real.  ``set_gains(gains[s])`` applies a solution."""
+        order, antenna ``ref`` real.  ``set_gains(gains[s])`` applies a solution; under a delay track ``set_track_gains(gains,
+        interval)`` applies all of them."""
         self._sync_stream()
         if _is_torch(rows):
             import torch

@@ -195,6 +195,43 @@ int fxc_delay_track_chunk(const fxc_plan* plan, int64_t* next_chunk);
 int fxc_delay_track_seek(fxc_plan* plan, int64_t chunk);
 int fxc_delay_track_tables(fxc_plan* plan, int64_t chunk, double* out_re_im);
 
+/* Gain track: per-interval gain corrections applied under a delay track.  A plan with a delay track may also carry a gain track:
+ *   - n_solutions sets of gains g[s][a][j], gains_re_im = [n_solutions][n_ant][nchan] complex128 host memory with the bins in the
+ *     rows' fftshifted order: exactly what fxc_solve_gains writes;
+ *   - interval >= 1 chunks per solution, and a first_chunk.
+ * Chunk t takes solution
+ *   s(t) = clamp(floor((t - first_chunk) / interval), 0, n_solutions - 1):
+ * chunks before the first interval use the first solution, chunks after the last interval the last one.  The solutions are
+ * piecewise constant; interpolation between solutions is out of scope.
+ * The correction of antenna a is
+ *   q[s][a][k] = 1 / g[s][a][(k + nchan/2) % nchan]
+ * (nchan/2 is integer division: numpy's ifftshift, odd channel counts included).  The inverse is (x/d, -y/d) with d = x*x + y*y,
+ * every operation rounded on its own, and 0 where g == 0, so a dead channel stays zero.
+ * The table of chunk t is
+ *   r_a[k](t) = phasor_a[k](t) * q[s(t)][a][k],
+ * phasor being the delay track's exp(+2*pi*i*f_k*tau_a(t)) above; the product is (c*qx - s*qy, c*qy + s*qx), without contraction
+ * to fused multiply-adds, as the phasor itself.  A table therefore depends on (a, k, t) and the gain track alone, and with every
+ * gain equal to 1 the tables are the plain track's tables, element for element.
+ * Everything downstream of the tables is unchanged (rows, tracked fxc_fx_accumulate and every finalize form, pipes, sharded runs
+ * with fxc_delay_track_seek): cross row (a,b) of chunk t is raw_ab * r_a * conj(r_b) / count, two antennas take w = r_1 conj(r_0),
+ * and auto rows take no rot and no gain, as under fxc_set_rot_ant.
+ * fxc_set_track_gains copies the gains to the device and forms q there, once (q stays resident in the plan and is freed with
+ * it); it synchronises the plan's stream, as fxc_set_delay_track does.  n_solutions == 0 (gains_re_im may be NULL) removes the
+ * gain track and keeps the delay track.  interval may be 0 only when n_solutions == 1: the one solution applies to every chunk.
+ * FXC_ERR_ARG: a NULL plan, NULL gains with n_solutions > 0, n_solutions < 0, interval < 1 with more than one solution (or
+ * < 0), first_chunk < 0, a non-finite gain, a non-zero gain with |g| outside [1e-150, 1e150] (d would overflow or underflow).
+ * FXC_ERR_STATE: the plan has no delay track, the accumulator holds chunks (finalize or reset first), an fxc_pipe uses the plan.
+ * FXC_ERR_NOMEM: the n_solutions * n_ant * nchan * 16 bytes of device memory (and as much again while the call runs) cannot be
+ * allocated.  A call that fails changes nothing: an earlier gain track stays in force.
+ * fxc_set_delay_track removes the gain track (gains were solved on rows made under one particular track: send them again after
+ * a new track); fxc_set_rot and fxc_set_rot_ant end both, under the accumulator rule they already have.  The last call wins.
+ * fxc_track_gains_info reports (n_solutions, interval, first_chunk), zeros when the plan has a delay track and no gain track;
+ * FXC_ERR_STATE when it has no delay track, FXC_ERR_ARG for a NULL argument.  fxc_delay_track_tables returns the tables as
+ * applied, gains included; fxc_delay_track_chunk and fxc_delay_track_seek are untouched.  Plans without a gain track launch
+ * exactly the kernels they launch without these calls. */
+int fxc_set_track_gains(fxc_plan* plan, const double* gains_re_im, int64_t n_solutions, int64_t interval, int64_t first_chunk);
+int fxc_track_gains_info(const fxc_plan* plan, int64_t* n_solutions, int64_t* interval, int64_t* first_chunk);
+
 /* F-stage only — replaces cusignal.filtering.channelize_poly + .T at effex.py:553 (and the
  * complex128 copy at :551).  x = [n_streams][num_samp] complex64, out = [n_streams][n_pts][nchan]
  * complex64, natural (un-shifted) bin order; trailing num_samp mod nchan samples ignored; zero
@@ -398,8 +435,8 @@ int fxc_fringe_fit(fxc_plan* plan, const void* rows, int64_t n_chunks, int mem_k
  * target; a batch continues the sums of the one before it, so no bit of the outputs depends on the sizes, and host and device
  * rows give the same bits.  Uses the plan's device, stream and workspace; synchronises like fxc_fringe_fit (one copy to the
  * host and one synchronisation end the call); neither reads nor changes the rot tables, the track or its counter.
- * Not covered: gains under a delay track (fxc_set_rot_ant ends the track), a sky model other than a point source at the phase
- * centre, weights or flags, two antennas.
+ * Under a delay track fxc_set_track_gains applies every solution, interval by interval.
+ * Not covered: a sky model other than a point source at the phase centre, weights or flags, two antennas.
  * FXC_ERR_ARG, before any device work: a NULL plan / rows / gains_re_im, n_chunks < 1, interval < 0, ref outside [0, n_ant),
  * iters outside 1 .. 1000, an unknown mem_kind.  FXC_ERR_UNSUPPORTED: fewer than 3 antennas (one baseline closes nothing).
  * The outputs are written on FXC_OK only. */
