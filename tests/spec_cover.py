@@ -141,7 +141,7 @@ def build_emul(lib_path, flags):
     return ctypes.CDLL(lib_path)
 
 
-def check_fx_emulation(tmp_path, nchan, ntaps, n_pts, wg_splits, u8, flags, tpr, slots):
+def check_fx_emulation(tmp_path, nchan, ntaps, n_pts, wg_splits, u8, flags, tpr, slots, window=None):
     """The F + X build on the host: the sums over each slot's run of frames, added up over the slots, against the oracle's
     sum_i spec0[i] conj(spec1[i]) of the chunk, and the last slot's row against the sum over ITS run (1e-5 of the largest)."""
     import fx_oracle
@@ -151,7 +151,8 @@ def check_fx_emulation(tmp_path, nchan, ntaps, n_pts, wg_splits, u8, flags, tpr,
     assert lib.emul_spec_threads() == tpr * slots and lib.emul_spec_slots() == slots
     n_chunks, num_samp = 2, nchan * n_pts + min(3, nchan - 1)
     rng = np.random.default_rng(nchan * 7 + n_pts)
-    window = rng.standard_normal(ntaps * nchan) if nchan < 16 else design_window(ntaps, nchan)
+    if window is None:
+        window = rng.standard_normal(ntaps * nchan) if nchan < 16 else design_window(ntaps, nchan)
     if u8:
         xb = rng.integers(0, 256, size=(n_chunks, 2, num_samp, 2), dtype=np.uint8)
         xb[:, 1, 2:] = xb[:, 0, :-2] // 2 + xb[:, 1, 2:] // 2
@@ -184,7 +185,7 @@ def check_fx_emulation(tmp_path, nchan, ntaps, n_pts, wg_splits, u8, flags, tpr,
     assert np.abs(out[e, 0] - ref).max() <= 1e-5 * max(np.abs(ref).max(), 1e-30)
 
 
-def check_f_emulation(tmp_path, nchan, ntaps, n_pts, wg_splits, n_streams, ant, flags, extra=None):
+def check_f_emulation(tmp_path, nchan, ntaps, n_pts, wg_splits, n_streams, ant, flags, extra=None, window=None):
     """The F-only build on the host: every stream's spectra, natural bin order, in the antenna-interleaved layout
     ([chunk][frame][antenna][nchan]), against the oracle's spectrometer_poly (2e-6 of the largest)."""
     import fx_oracle
@@ -194,7 +195,8 @@ def check_f_emulation(tmp_path, nchan, ntaps, n_pts, wg_splits, n_streams, ant, 
     assert lib.emul_spec_fonly() == 1
     num_samp = nchan * n_pts + (min(2, nchan - 1) if extra is None else extra)
     rng = np.random.default_rng(nchan + n_streams)
-    window = rng.standard_normal(ntaps * nchan) if nchan < 16 else design_window(ntaps, nchan)
+    if window is None:
+        window = rng.standard_normal(ntaps * nchan) if nchan < 16 else design_window(ntaps, nchan)
     x = synth.synth_iq(31 + nchan, n_streams, 1, num_samp)[:, 0]
     tw = np.exp(2j * np.pi * np.arange(nchan) / nchan).astype(np.complex64)
     h32 = np.ascontiguousarray(window, dtype=np.float32)

@@ -12,6 +12,7 @@ import fx_oracle
 import spec_cover
 from effex_amd import synth
 from effex_amd.window import design_window
+from window_cases import rough_window
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -41,9 +42,9 @@ def test_output_layouts_are_consistent(emul):
 
 
 @pytest.mark.parametrize("num_samp", [4096, 4096 * 3 + 17, 4096 * 9])
-def test_fused_phases_match_oracle(emul, num_samp):
+def test_fused_phases_match_oracle(emul, num_samp, w=None):
     x = synth.synth_iq(1234, 1, 2, num_samp)[0]
-    w = design_window(4, 4096)
+    w = design_window(4, 4096) if w is None else w
     out = np.zeros(4096, np.complex128)
     rc = emul.emul_fused4096(x.ctypes.data_as(ctypes.c_void_p), ctypes.c_int64(num_samp),
                              w.ctypes.data_as(ctypes.c_void_p), out.ctypes.data_as(ctypes.c_void_p))
@@ -52,6 +53,11 @@ def test_fused_phases_match_oracle(emul, num_samp):
     f1 = fx_oracle.spectrometer_poly(x[1], 4, 4096, w)
     ref = (f0 * np.conj(f1)).sum(axis=0)
     assert np.abs(out - ref).max() / np.abs(ref).max() < 1e-6
+
+
+def test_fused_phases_with_a_rough_window(emul):
+    """The window quads f4[16][256] with independent taps (tests/window_cases.py): a slip in the layout cannot hide in them."""
+    test_fused_phases_match_oracle(emul, 4096 * 7 + 5, rough_window(4, 4096))
 
 
 @pytest.fixture(scope="module")
@@ -67,12 +73,12 @@ def emul_tiled():
 @pytest.mark.parametrize("nchan,ntaps,frames,ring", [
     (512, 4, 9, 0), (512, 4, 9, 1), (1024, 4, 6, 1), (2048, 4, 5, 1), (2048, 3, 5, 1), (1024, 1, 3, 1), (4096, 8, 4, 0), (4096, 4, 6, 1),
     (8192, 4, 3, 0), (2048, 32, 3, 0), (512, 7, 12, 0)])
-def test_tiled_phases_match_oracle(emul_tiled, nchan, ntaps, frames, ring):
+def test_tiled_phases_match_oracle(emul_tiled, nchan, ntaps, frames, ring, w=None):
     """fx_tiled.h (the other --nfft values, effex.py:778): decomposition, padded exchange layout, bin mapping,
     and the ntaps <= 4 ring variant, on the host."""
     num_samp = nchan * frames + 13
     x = synth.synth_iq(99, 1, 2, num_samp)[0]
-    w = design_window(ntaps, nchan)
+    w = design_window(ntaps, nchan) if w is None else w
     out = np.zeros(nchan, np.complex128)
     rc = emul_tiled.emul_tiled(x.ctypes.data_as(ctypes.c_void_p), ctypes.c_int64(num_samp), nchan, ntaps,
                                w.ctypes.data_as(ctypes.c_void_p), out.ctypes.data_as(ctypes.c_void_p), ring)
@@ -81,6 +87,13 @@ def test_tiled_phases_match_oracle(emul_tiled, nchan, ntaps, frames, ring):
     f1 = fx_oracle.spectrometer_poly(x[1], ntaps, nchan, w)
     ref = (f0 * np.conj(f1)).sum(axis=0)
     assert np.abs(out - ref).max() / np.abs(ref).max() < 1e-6
+
+
+@pytest.mark.parametrize("nchan,ntaps,frames,ring", [(512, 4, 9, 1), (1024, 3, 7, 1), (2048, 1, 5, 1), (4096, 2, 6, 1), (8192, 4, 5, 0),
+                                                     (512, 7, 12, 0)])
+def test_tiled_phases_with_a_rough_window(emul_tiled, nchan, ntaps, frames, ring):
+    """Every zero-padded quad width of the ring variant, and the plain variant's [ntaps][nchan] taps, with independent taps."""
+    test_tiled_phases_match_oracle(emul_tiled, nchan, ntaps, frames, ring, rough_window(ntaps, nchan))
 
 
 @pytest.fixture(scope="module")
@@ -95,12 +108,12 @@ def emul_small():
 
 @pytest.mark.parametrize("nchan,ntaps,frames", [(16, 4, 40), (32, 4, 33), (64, 4, 21), (128, 4, 12), (256, 4, 9), (256, 3, 5),
                                                 (64, 1, 7), (32, 2, 6)])
-def test_small_phases_match_oracle(emul_small, nchan, ntaps, frames):
+def test_small_phases_match_oracle(emul_small, nchan, ntaps, frames, w=None):
     """fx_small.h (--nfft 16 ... 256 inside one wave): radix-16, twiddle, transposition rows inside the item's lanes,
     the transforms of P points and the bin mapping, on the host."""
     num_samp = nchan * frames + 5
     x = synth.synth_iq(77, 1, 2, num_samp)[0]
-    w = design_window(ntaps, nchan)
+    w = design_window(ntaps, nchan) if w is None else w
     out = np.zeros(nchan, np.complex128)
     rc = emul_small.emul_small(x.ctypes.data_as(ctypes.c_void_p), ctypes.c_int64(num_samp), nchan, ntaps,
                                w.ctypes.data_as(ctypes.c_void_p), out.ctypes.data_as(ctypes.c_void_p))
@@ -109,6 +122,11 @@ def test_small_phases_match_oracle(emul_small, nchan, ntaps, frames):
     f1 = fx_oracle.spectrometer_poly(x[1], ntaps, nchan, w)
     ref = (f0 * np.conj(f1)).sum(axis=0)
     assert np.abs(out - ref).max() / np.abs(ref).max() < 1e-6
+
+
+@pytest.mark.parametrize("nchan,ntaps,frames", [(16, 4, 9), (64, 3, 7), (256, 4, 8), (128, 1, 5), (32, 2, 6)])
+def test_small_phases_with_a_rough_window(emul_small, nchan, ntaps, frames):
+    test_small_phases_match_oracle(emul_small, nchan, ntaps, frames, rough_window(ntaps, nchan))
 
 
 @pytest.fixture(scope="module")
@@ -292,6 +310,21 @@ def test_specialised_kernel_matches_oracle(tmp_path, monkeypatch, nchan, ntaps, 
     if frames_per_step == 2 and "-DFXM_U=2" not in flags:
         pytest.skip("one frame per step for this shape (one stage only)")
     spec_cover.check_fx_emulation(tmp_path, nchan, ntaps, n_pts, wg_splits, u8, flags, tpr, slots)
+
+
+@pytest.mark.parametrize("nchan,ntaps,n_pts,wg_splits,fonly", [(1000, 4, 9, 2, False), (250, 2, 7, 1, False), (3000, 4, 6, 1, False),
+                                                             (3000, 4, 6, 1, True)])
+def test_specialised_kernels_with_a_rough_window(tmp_path, nchan, ntaps, n_pts, wg_splits, fonly):
+    """The tap tables of fx_spec.h -- in LDS, and read as quads in the lean build above 2048 channels -- with independent taps
+    (tests/window_cases.py), F + X and the F stage alone."""
+    rc, shape = _spec_shape(nchan, ntaps, fonly=fonly)
+    assert rc == 0
+    flags, tpr, slots = shape
+    window = rough_window(ntaps, nchan)
+    if fonly:
+        spec_cover.check_f_emulation(tmp_path, nchan, ntaps, n_pts, wg_splits, 3, 1, flags, window=window)
+    else:
+        spec_cover.check_fx_emulation(tmp_path, nchan, ntaps, n_pts, wg_splits, False, flags, tpr, slots, window=window)
 
 
 @pytest.mark.parametrize("nchan,ntaps,n_pts,wg_splits,n_streams,ant", [
