@@ -5,10 +5,11 @@
 //                                           g++ for the host emulation under tests/emul)
 //   k_generic.h k_finish.h (+ k_finish_rows.h) k_fused4096.h k_tiled.h k_small.h k_prepass.h k_stream.h k_conditioning.h k_track.h k_delay.h k_fringe.h k_gains.h k_synth.h
 //                                           the __global__ kernels, one file per path / step
-//   h_plan.h h_rtc.h h_launch.h h_build.h h_run.h h_rccl.h
+//   h_plan.h h_rtc.h h_launch.h h_build.h h_run.h h_ingest.h h_rccl.h
 //                                           fxc_plan, the kernels compiled per channel count, the per-path launchers and
 //                                           workspace passes, plan construction (route, tables), the device-resident
-//                                           fx_accumulate / fx_rows, the run-time binding of librccl
+//                                           fx_accumulate / fx_rows, the ingest front end of every entry point that takes
+//                                           samples (formats, DC removal, host / device dispatch), the run-time binding of librccl
 //
 // Replaces, for effex's hot path:
 //   cusignal.filtering.channelize_poly FIR half   effex/effex.py:553   -> pfb_fir_kernel / pfb_fft_mixed_kernel / fused phase 1
@@ -145,6 +146,7 @@ int64_t ws_target() {
 #include "h_launch.h"
 #include "h_build.h"
 #include "h_run.h"
+#include "h_ingest.h"
 #include "h_rccl.h"
 
 
@@ -783,55 +785,11 @@ int fxc_channelize(fxc_plan* p, const void* x, void* out, int64_t n_streams, int
 }
 
 int fxc_fx_accumulate(fxc_plan* p, const void* x, int64_t n_chunks, int mem_kind) {
-    if (!p) return fail(p, FXC_ERR_ARG, "NULL plan");
-    if (n_chunks < 0) return fail(p, FXC_ERR_ARG, "n_chunks < 0");
-    if (p->n_ant < 2) return fail(p, FXC_ERR_ARG, "cross-correlation needs n_ant >= 2");
-    if (n_chunks == 0) return FXC_OK;
-    if (!x) return fail(p, FXC_ERR_ARG, "NULL buffer");
-    FXC_DEVICE(p, p->device);
-    if (mem_kind == FXC_MEM_DEVICE) return fx_accumulate_dev(p, static_cast<const cf*>(x), n_chunks);
-    if (mem_kind != FXC_MEM_HOST) return fail(p, FXC_ERR_ARG, "bad mem_kind %d", mem_kind);
-    const size_t xb = (size_t)n_chunks * p->n_ant * p->num_samp * sizeof(cf);
-    return with_host_staging(p, x, xb, nullptr, 0,
-                             [&](const cf* dx, void*) { return fx_accumulate_dev(p, dx, n_chunks); });
+    return fx_call(p, {FXC_IQ_C64, false, false, FXC_MODE_SPECTRUM, 1.0}, x, nullptr, n_chunks, mem_kind);
 }
-
-namespace {
-// FXC_MEM_DEVICE_TO_PINNED: the rows of device-resident samples go straight into fxc_host_alloc memory -- the finishing
-// kernel writes them across PCIe through the device's mapping of the block, nothing is copied and nothing waits
-int pinned_rows_out(fxc_plan* p, void** out, int* mem_kind, int64_t n_chunks, int mode) {
-    if (*mem_kind != FXC_MEM_DEVICE_TO_PINNED) return FXC_OK;
-    if (!p || !*out || n_chunks <= 0) {
-        *mem_kind = FXC_MEM_DEVICE;         // (the entry's own argument checks answer)
-        return FXC_OK;
-    }
-    const size_t ob = mode == FXC_MODE_SPECTRUM ? (size_t)n_chunks * p->n_prod * p->nchan * sizeof(cf) : (size_t)n_chunks * p->n_prod * sizeof(cd);
-    void* d = pinned_device_ptr(*out, ob);
-    if (!d) return fail(p, FXC_ERR_ARG, "`out` of FXC_MEM_DEVICE_TO_PINNED (%zu bytes) is not inside memory from fxc_host_alloc", ob);
-    *out = d;
-    *mem_kind = FXC_MEM_DEVICE;
-    return FXC_OK;
-}
-}  // namespace
 
 int fxc_fx_rows(fxc_plan* p, const void* x, void* out, int64_t n_chunks, int mem_kind, int mode, double bandwidth) {
-    if (const int rp = pinned_rows_out(p, &out, &mem_kind, n_chunks, mode)) return rp;
-    if (!p) return fail(p, FXC_ERR_ARG, "NULL plan");
-    if (n_chunks < 0) return fail(p, FXC_ERR_ARG, "n_chunks < 0");
-    if (p->n_ant < 2) return fail(p, FXC_ERR_ARG, "cross-correlation needs n_ant >= 2");
-    if (mode != FXC_MODE_SPECTRUM && mode != FXC_MODE_CONTINUUM) return fail(p, FXC_ERR_ARG, "bad mode %d", mode);
-    if (mode == FXC_MODE_CONTINUUM && !(bandwidth > 0.0)) return fail(p, FXC_ERR_ARG, "bandwidth must be > 0");
-    if (n_chunks == 0) return FXC_OK;
-    if (!x || !out) return fail(p, FXC_ERR_ARG, "NULL buffer");
-    FXC_DEVICE(p, p->device);
-    if (mem_kind == FXC_MEM_DEVICE) return fx_rows_dev(p, static_cast<const cf*>(x), out, n_chunks, mode, bandwidth);
-    if (mem_kind != FXC_MEM_HOST) return fail(p, FXC_ERR_ARG, "bad mem_kind %d", mem_kind);
-    const size_t xb = (size_t)n_chunks * p->n_ant * p->num_samp * sizeof(cf);
-    const size_t ob = mode == FXC_MODE_SPECTRUM ? (size_t)n_chunks * p->n_prod * p->nchan * sizeof(cf)
-                                                : (size_t)n_chunks * p->n_prod * sizeof(cd);
-    return with_host_staging(p, x, xb, out, ob, [&](const cf* dx, void* dout) {
-        return fx_rows_dev(p, dx, dout, n_chunks, mode, bandwidth);
-    });
+    return fx_call(p, {FXC_IQ_C64, false, true, mode, bandwidth}, x, out, n_chunks, mem_kind);
 }
 
 int fxc_acc_reset(fxc_plan* p) {
@@ -986,17 +944,6 @@ int fxc_finalize(fxc_plan* p, void* out_host, int mode, double bandwidth, int re
     return fxc_finalize_wait(p, out_host);
 }
 
-// workgroups per stream of the subtract / narrow pass: enough to fill the chip when a call has few streams (one chunk
-// pair: the reference's own call), a handful when it has thousands
-static int cond_slices(const fxc_plan* p, int64_t n_streams) {
-    return (int)std::max<int64_t>(1, std::min<int64_t>(256, ((int64_t)p->cu_count * 8 + n_streams - 1) / n_streams));
-}
-// slice sums per stream (each a workgroup): 32 for batches, up to 256 when a call has a handful of streams (one chunk pair:
-// 64 workgroups of 32 sequential loads each took 7 us for 4 MiB)
-static int sum_slices(const fxc_plan* p, int64_t n_streams) {
-    return (int)std::max<int64_t>(32, std::min<int64_t>(256, (int64_t)p->cu_count * 4 / n_streams));
-}
-
 static int conditioning_common(fxc_plan* p, int64_t n_streams, const void* x, void* out) {
     if (!p) return fail(p, FXC_ERR_ARG, "NULL plan");
     if (n_streams < 0) return fail(p, FXC_ERR_ARG, "n_streams < 0");
@@ -1012,26 +959,10 @@ int fxc_remove_dc(fxc_plan* p, const void* x_dev, void* out_dev, int64_t n_strea
     const int n_slices = 32;
     rc = ensure_ws(p, n_streams * n_slices * 2 * (int64_t)sizeof(double));
     if (rc) return rc;
-    double* part = static_cast<double*>(p->d_ws);
-    hipLaunchKernelGGL(dc_sum_c64_kernel, dim3(n_slices, (unsigned)n_streams), dim3(256), 0, p->stream,
-                       static_cast<const cf*>(x_dev), part, p->num_samp, n_slices);
-    hipLaunchKernelGGL(dc_apply_c64_kernel, dim3(cond_slices(p, n_streams), (unsigned)n_streams), dim3(256), 0, p->stream,
-                       static_cast<const cf*>(x_dev), static_cast<cf*>(out_dev), part, p->num_samp, cond_slices(p, n_streams),
-                       n_slices, 1);
+    launch_remove_dc_c64(p, static_cast<const cf*>(x_dev), static_cast<cf*>(out_dev), static_cast<double*>(p->d_ws), n_streams, n_slices);
     FXC_HIP(p, hipGetLastError());
     return FXC_OK;
 }
-
-namespace {
-// bytes -> complex64 of n_streams streams: a few thousand workgroups, each on one slice of a stream at a time
-void launch_convert_u8(fxc_plan* p, const unsigned char* x8, cf* out, const double* part, int n_slices, int64_t n_streams, int remove_dc) {
-    const unsigned gy = (unsigned)std::min<int64_t>(n_streams, 65535);
-    const int64_t per_stream = std::max<int64_t>(1, ((int64_t)p->cu_count * 16 + gy - 1) / gy);
-    const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(per_stream, (p->num_samp + 1023) / 1024));
-    hipLaunchKernelGGL(convert_u8_kernel, dim3(gx, gy), dim3(256), 0, p->stream, x8, out, part, p->num_samp, n_slices, n_streams,
-                       remove_dc ? 1 : 0);
-}
-}  // namespace
 
 int fxc_convert_u8(fxc_plan* p, const void* iq_u8_dev, void* out_dev, int64_t n_streams, int remove_dc) {
     int rc = conditioning_common(p, n_streams, iq_u8_dev, out_dev);
@@ -1041,205 +972,19 @@ int fxc_convert_u8(fxc_plan* p, const void* iq_u8_dev, void* out_dev, int64_t n_
     rc = ensure_ws(p, n_streams * n_slices * 2 * (int64_t)sizeof(double));
     if (rc) return rc;
     double* part = static_cast<double*>(p->d_ws);
-    if (remove_dc)
-        hipLaunchKernelGGL(dc_sum_u8_stream_kernel, dim3((unsigned)std::min<int64_t>(n_streams * n_slices, (int64_t)p->cu_count * 16)),
-                           dim3(256), 0, p->stream, static_cast<const unsigned char*>(iq_u8_dev), part, p->num_samp, n_streams, n_slices);
-    launch_convert_u8(p, static_cast<const unsigned char*>(iq_u8_dev), static_cast<cf*>(out_dev), part, n_slices, n_streams, remove_dc);
+    if (remove_dc) launch_dc_sum_u8(p, static_cast<const unsigned char*>(iq_u8_dev), part, n_streams, n_slices);
+    launch_convert_u8(p, static_cast<const unsigned char*>(iq_u8_dev), static_cast<cf*>(out_dev), part, n_slices, n_streams, remove_dc != 0);
     FXC_HIP(p, hipGetLastError());
     return FXC_OK;
 }
 
-namespace {
-
-// uint8 I,Q in: fused plans (2 antennas: nchan 4096 / ntaps 4, the tiled ring and wave-local kernels, the mixed-radix F + X
-// kernel) read the bytes in the F+X kernel itself; every other plan
-// converts into a complex64 staging buffer first.  rows: fxc_fx_rows semantics (out != nullptr) or accumulate.
-int fx_u8_dev(fxc_plan* p, const unsigned char* x8, void* out, int64_t n_chunks, int mode, double bandwidth, int remove_dc,
-              bool rows) {
-    constexpr int kSlices = 32;
-    const size_t row_elems = mode == FXC_MODE_SPECTRUM ? (size_t)p->n_prod * p->nchan * sizeof(cf) : (size_t)p->n_prod * sizeof(cd);
-    // chunks per pass: at most 65535 streams (a grid dimension of the conditioning kernels), and plans without the
-    // fused ingest convert a pass into a complex64 staging buffer that stays within the workspace target
-    const bool fused_in = p->n_ant == 2 && !p->autos && !p->prefilter && (p->path == FXC_PATH_FUSED || (p->path == FXC_PATH_TILED && (p->tiled_ring || p->small || p->x8192)) ||
-                                                              (p->path == FXC_PATH_GENERIC && p->mixed_xf && FXC_DEV_ENV_INT("FXC_MIXED_U8", 1)));
-    int64_t per_pass = std::min<int64_t>(16384, 65535 / p->n_ant);
-    if (!fused_in) per_pass = std::min<int64_t>(per_pass, ws_target() / ((int64_t)p->n_ant * p->num_samp * (int64_t)sizeof(cf)));
-    per_pass = std::max<int64_t>(1, per_pass);
-    for (int64_t c0 = 0; c0 < n_chunks; c0 += per_pass) {
-        const int64_t nc = std::min<int64_t>(per_pass, n_chunks - c0);
-        const int64_t n_streams = nc * p->n_ant;
-        const unsigned char* xb = x8 + c0 * p->n_ant * p->num_samp * 2;
-        void* ob = rows ? static_cast<char*>(out) + (size_t)c0 * row_elems : nullptr;
-        const size_t part_bytes = (size_t)n_streams * kSlices * 2 * sizeof(double);
-        int rc = grow(p, &p->d_dc, &p->dc_bytes, part_bytes + (size_t)n_streams * sizeof(cf));
-        if (rc) return rc;
-        double* part = static_cast<double*>(p->d_dc);
-        cf* dc = reinterpret_cast<cf*>(static_cast<char*>(p->d_dc) + part_bytes);
-        const bool fused_ingest = fused_in;
-        // The fused 4096-channel kernel can sum the bytes of a workgroup's next chunk while it channelises the current one
-        // (k_fused4096.h, DCK): the pre-pass then only covers the first chunk of every workgroup's round-robin share and
-        // the tail chunks -- 272 of 10 000 chunk pairs.  Needs whole frames (num_samp % 4096 == 0), 16-byte aligned
-        // streams, the default work split (so no delay track), one launch for the pass and at least two rounds of chunks.
-        int64_t spec_b, raw_b;
-        const int64_t g = p->fused_grid_max;
-        // (num_samp <= 2^26: a wave's byte sums are reduced in 32 bits, 16384 frames x 4080 x 64 lanes < 2^32)
-        const bool dck = remove_dc && fused_ingest && !p->track && p->path == FXC_PATH_FUSED && p->fused_seg == 1 &&
-                         (p->num_samp % fxc::fused::kN) == 0 && p->num_samp <= (1ll << 26) &&
-                         (reinterpret_cast<uintptr_t>(xb) % 16) == 0 &&
-                         fused_chunks_per_pass(p, nc, &spec_b, &raw_b) >= nc && nc >= 2 * g;
-        if (remove_dc && fused_ingest) {
-            const int64_t n_full = dck ? nc / g * g : nc;
-            // chunk ranges the pre-pass sums: everything, or [0, g) and [n_full, nc)
-            const int64_t lo[2] = {0, n_full}, hi[2] = {dck ? g : nc, dck ? nc : n_full};
-            // a call of a few streams (one chunk pair: the reference's own call) is cut into slices to fill the chip
-            const int sl = dck ? 1 : (int)std::max<int64_t>(1, std::min<int64_t>(kSlices, (int64_t)p->cu_count * 2 / n_streams));
-            for (int r = 0; r < 2; ++r) {
-                const int64_t ns = (hi[r] - lo[r]) * p->n_ant;
-                if (ns <= 0) continue;
-                hipLaunchKernelGGL(dc_sum_u8_stream_kernel, dim3((unsigned)std::min<int64_t>(ns * sl, (int64_t)p->cu_count * 16)),
-                                   dim3(256), 0, p->stream, xb + lo[r] * p->n_ant * p->num_samp * 2,
-                                   part + lo[r] * p->n_ant * 2 * sl, p->num_samp, ns, sl);
-                hipLaunchKernelGGL(dc_offsets_u8_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, p->stream,
-                                   part + lo[r] * p->n_ant * 2 * sl, dc + lo[r] * p->n_ant, ns, sl, p->num_samp, 1);
-            }
-        } else if (remove_dc) {
-            hipLaunchKernelGGL(dc_sum_u8_stream_kernel, dim3((unsigned)std::min<int64_t>(n_streams * kSlices, (int64_t)p->cu_count * 16)),
-                               dim3(256), 0, p->stream, xb, part, p->num_samp, n_streams, kSlices);
-        }
-        if (fused_ingest) {
-            if (!remove_dc)
-                hipLaunchKernelGGL(dc_offsets_u8_kernel, dim3((unsigned)((n_streams + 255) / 256)), dim3(256), 0, p->stream, part,
-                                   dc, n_streams, 1, p->num_samp, 0);
-            FXC_HIP(p, hipGetLastError());
-            p->u8_dck = dck;
-            rc = rows ? fx_rows_dev(p, reinterpret_cast<const cf*>(xb), ob, nc, mode, bandwidth, dc)
-                      : fx_accumulate_dev(p, reinterpret_cast<const cf*>(xb), nc, dc);
-            p->u8_dck = false;
-        } else {
-            const int64_t total = n_streams * p->num_samp;
-            rc = grow(p, &p->d_stage[2], &p->stage_bytes[2], (size_t)total * sizeof(cf));
-            if (rc) return rc;
-            cf* xc = static_cast<cf*>(p->d_stage[2]);
-            launch_convert_u8(p, xb, xc, part, kSlices, n_streams, remove_dc);
-            FXC_HIP(p, hipGetLastError());
-            rc = rows ? fx_rows_dev(p, xc, ob, nc, mode, bandwidth) : fx_accumulate_dev(p, xc, nc);
-        }
-        if (rc) return rc;
-    }
-    return FXC_OK;
-}
-
-int fx_u8_entry(fxc_plan* p, const void* iq_u8, void* out, int64_t n_chunks, int mem_kind, int mode, double bandwidth,
-                int remove_dc, bool rows) {
-    if (rows)
-        if (const int rp = pinned_rows_out(p, &out, &mem_kind, n_chunks, mode)) return rp;
-    if (!p) return fail(p, FXC_ERR_ARG, "NULL plan");
-    if (p->n_ant < 2) return fail(p, FXC_ERR_ARG, "cross-correlation needs n_ant >= 2");
-    if (n_chunks < 0) return fail(p, FXC_ERR_ARG, "n_chunks < 0");
-    if (rows && mode != FXC_MODE_SPECTRUM && mode != FXC_MODE_CONTINUUM) return fail(p, FXC_ERR_ARG, "bad mode %d", mode);
-    if (rows && mode == FXC_MODE_CONTINUUM && !(bandwidth > 0.0)) return fail(p, FXC_ERR_ARG, "bandwidth must be > 0");
-    if (n_chunks == 0) return FXC_OK;
-    if (!iq_u8 || (rows && !out)) return fail(p, FXC_ERR_ARG, "NULL buffer");
-    FXC_DEVICE(p, p->device);
-    if (mem_kind == FXC_MEM_DEVICE)
-        return fx_u8_dev(p, static_cast<const unsigned char*>(iq_u8), out, n_chunks, mode, bandwidth, remove_dc, rows);
-    if (mem_kind != FXC_MEM_HOST) return fail(p, FXC_ERR_ARG, "bad mem_kind %d", mem_kind);
-    const size_t xb = (size_t)n_chunks * p->n_ant * p->num_samp * 2;
-    const size_t ob = !rows ? 0
-                            : (mode == FXC_MODE_SPECTRUM ? (size_t)n_chunks * p->n_prod * p->nchan * sizeof(cf)
-                                                         : (size_t)n_chunks * p->n_prod * sizeof(cd));
-    return with_host_staging(p, iq_u8, xb, out, ob, [&](const cf* dx, void* dout) {
-        return fx_u8_dev(p, reinterpret_cast<const unsigned char*>(dx), dout, n_chunks, mode, bandwidth, remove_dc, rows);
-    });
-}
-
-}  // namespace
-
-namespace {
-
-// complex64 with DC removal, or complex128 (narrowed on the device, after the DC removal when asked for): sums, then
-// subtract / narrow into a complex64 staging buffer -- or in place when x is the library's own complex64 staging copy of a
-// host buffer (x_is_scratch) -- then the plan's usual kernels.  The caller's device buffers are never written.
-int fx_cond_dev(fxc_plan* p, const void* x, void* out, int64_t n_chunks, int mode, double bandwidth, int fmt, int remove_dc,
-                bool rows, bool x_is_scratch) {
-    const size_t in_elem = fmt == FXC_IQ_C128 ? sizeof(cd) : sizeof(cf);
-    const size_t row_bytes = mode == FXC_MODE_SPECTRUM ? (size_t)p->n_prod * p->nchan * sizeof(cf) : (size_t)p->n_prod * sizeof(cd);
-    const bool in_place = x_is_scratch && fmt == FXC_IQ_C64;
-    // streams per pass: the stream index rides in grid.y, and the staging buffer stays within the workspace target
-    int64_t per_pass = 65535 / p->n_ant;
-    if (!in_place) per_pass = std::min<int64_t>(per_pass, ws_target() / ((int64_t)p->n_ant * p->num_samp * (int64_t)sizeof(cf)));
-    per_pass = std::max<int64_t>(1, std::min<int64_t>(per_pass, n_chunks));
-    for (int64_t c0 = 0; c0 < n_chunks; c0 += per_pass) {
-        const int64_t nc = std::min<int64_t>(per_pass, n_chunks - c0);
-        const int64_t n_streams = nc * p->n_ant;
-        const char* xb = static_cast<const char*>(x) + (size_t)c0 * p->n_ant * p->num_samp * in_elem;
-        void* ob = rows ? static_cast<char*>(out) + (size_t)c0 * row_bytes : nullptr;
-        const int kSlices = sum_slices(p, n_streams);
-        int rc = grow(p, &p->d_dc, &p->dc_bytes, (size_t)n_streams * kSlices * 2 * sizeof(double));
-        if (rc) return rc;
-        double* part = static_cast<double*>(p->d_dc);
-        cf* xc = in_place ? reinterpret_cast<cf*>(const_cast<char*>(xb)) : nullptr;
-        if (!in_place) {
-            rc = grow(p, &p->d_stage[2], &p->stage_bytes[2], (size_t)n_streams * p->num_samp * sizeof(cf));
-            if (rc) return rc;
-            xc = static_cast<cf*>(p->d_stage[2]);
-        }
-        const dim3 sum_grid(kSlices, (unsigned)n_streams), app_grid(cond_slices(p, n_streams), (unsigned)n_streams);
-        if (fmt == FXC_IQ_C128) {
-            if (remove_dc)
-                hipLaunchKernelGGL(dc_sum_c128_kernel, sum_grid, dim3(256), 0, p->stream, reinterpret_cast<const cd*>(xb), part,
-                                   p->num_samp, kSlices);
-            hipLaunchKernelGGL(narrow_c128_kernel, app_grid, dim3(256), 0, p->stream, reinterpret_cast<const cd*>(xb), xc, part,
-                               p->num_samp, (int)app_grid.x, kSlices, remove_dc ? 1 : 0);
-        } else {
-            hipLaunchKernelGGL(dc_sum_c64_kernel, sum_grid, dim3(256), 0, p->stream, reinterpret_cast<const cf*>(xb), part,
-                               p->num_samp, kSlices);
-            hipLaunchKernelGGL(dc_apply_c64_kernel, app_grid, dim3(256), 0, p->stream, reinterpret_cast<const cf*>(xb), xc, part,
-                               p->num_samp, (int)app_grid.x, kSlices, 1);
-        }
-        FXC_HIP(p, hipGetLastError());
-        rc = rows ? fx_rows_dev(p, xc, ob, nc, mode, bandwidth) : fx_accumulate_dev(p, xc, nc);
-        if (rc) return rc;
-    }
-    return FXC_OK;
-}
-
-int fx_iq_entry(fxc_plan* p, const void* x, void* out, int64_t n_chunks, int mem_kind, int mode, double bandwidth, int fmt,
-                int remove_dc, bool rows) {
-    if (fmt == FXC_IQ_U8) return fx_u8_entry(p, x, out, n_chunks, mem_kind, mode, bandwidth, remove_dc, rows);
-    if (fmt != FXC_IQ_C64 && fmt != FXC_IQ_C128) return fail(p, FXC_ERR_ARG, "bad iq_format %d", fmt);
-    if (fmt == FXC_IQ_C64 && !remove_dc)
-        return rows ? fxc_fx_rows(p, x, out, n_chunks, mem_kind, mode, bandwidth) : fxc_fx_accumulate(p, x, n_chunks, mem_kind);
-    if (rows)
-        if (const int rp = pinned_rows_out(p, &out, &mem_kind, n_chunks, mode)) return rp;
-    if (!p) return fail(p, FXC_ERR_ARG, "NULL plan");
-    if (p->n_ant < 2) return fail(p, FXC_ERR_ARG, "cross-correlation needs n_ant >= 2");
-    if (n_chunks < 0) return fail(p, FXC_ERR_ARG, "n_chunks < 0");
-    if (rows && mode != FXC_MODE_SPECTRUM && mode != FXC_MODE_CONTINUUM) return fail(p, FXC_ERR_ARG, "bad mode %d", mode);
-    if (rows && mode == FXC_MODE_CONTINUUM && !(bandwidth > 0.0)) return fail(p, FXC_ERR_ARG, "bandwidth must be > 0");
-    if (n_chunks == 0) return FXC_OK;
-    if (!x || (rows && !out)) return fail(p, FXC_ERR_ARG, "NULL buffer");
-    FXC_DEVICE(p, p->device);
-    if (mem_kind == FXC_MEM_DEVICE) return fx_cond_dev(p, x, out, n_chunks, mode, bandwidth, fmt, remove_dc, rows, false);
-    if (mem_kind != FXC_MEM_HOST) return fail(p, FXC_ERR_ARG, "bad mem_kind %d", mem_kind);
-    const size_t xb = (size_t)n_chunks * p->n_ant * p->num_samp * (fmt == FXC_IQ_C128 ? sizeof(cd) : sizeof(cf));
-    const size_t ob = !rows ? 0
-                            : (mode == FXC_MODE_SPECTRUM ? (size_t)n_chunks * p->n_prod * p->nchan * sizeof(cf)
-                                                         : (size_t)n_chunks * p->n_prod * sizeof(cd));
-    return with_host_staging(p, x, xb, out, ob, [&](const cf* dx, void* dout) {
-        return fx_cond_dev(p, dx, dout, n_chunks, mode, bandwidth, fmt, remove_dc, rows, true);
-    });
-}
-
-}  // namespace
-
 int fxc_fx_rows_iq(fxc_plan* p, const void* x, void* out, int64_t n_chunks, int mem_kind, int mode, double bandwidth,
                    int iq_format, int remove_dc) {
-    return fx_iq_entry(p, x, out, n_chunks, mem_kind, mode, bandwidth, iq_format, remove_dc, true);
+    return fx_call(p, {iq_format, remove_dc != 0, true, mode, bandwidth}, x, out, n_chunks, mem_kind);
 }
 
 int fxc_fx_accumulate_iq(fxc_plan* p, const void* x, int64_t n_chunks, int mem_kind, int iq_format, int remove_dc) {
-    return fx_iq_entry(p, x, nullptr, n_chunks, mem_kind, FXC_MODE_SPECTRUM, 1.0, iq_format, remove_dc, false);
+    return fx_call(p, {iq_format, remove_dc != 0, false, FXC_MODE_SPECTRUM, 1.0}, x, nullptr, n_chunks, mem_kind);
 }
 
 int fxc_host_alloc(void** out, int64_t bytes) {
@@ -1282,11 +1027,11 @@ int fxc_host_free(void* ptr) {
 
 int fxc_fx_rows_u8(fxc_plan* p, const void* iq_u8, void* out, int64_t n_chunks, int mem_kind, int mode, double bandwidth,
                    int remove_dc) {
-    return fx_u8_entry(p, iq_u8, out, n_chunks, mem_kind, mode, bandwidth, remove_dc, true);
+    return fx_call(p, {FXC_IQ_U8, remove_dc != 0, true, mode, bandwidth}, iq_u8, out, n_chunks, mem_kind);
 }
 
 int fxc_fx_accumulate_u8(fxc_plan* p, const void* iq_u8, int64_t n_chunks, int mem_kind, int remove_dc) {
-    return fx_u8_entry(p, iq_u8, nullptr, n_chunks, mem_kind, FXC_MODE_SPECTRUM, 1.0, remove_dc, false);
+    return fx_call(p, {FXC_IQ_U8, remove_dc != 0, false, FXC_MODE_SPECTRUM, 1.0}, iq_u8, nullptr, n_chunks, mem_kind);
 }
 
 namespace {
@@ -1690,10 +1435,7 @@ int fxc_pipe_create_iq(fxc_pipe** out, fxc_plan* p, int64_t chunks_per_batch, in
     if (!out || !p) return fail(p, FXC_ERR_ARG, "NULL argument");
     *out = nullptr;
     if (chunks_per_batch < 1 || depth < 1 || depth > 16) return fail(p, FXC_ERR_ARG, "bad batch size or depth");
-    if (p->n_ant < 2) return fail(p, FXC_ERR_ARG, "cross-correlation needs n_ant >= 2");
-    if (mode != FXC_MODE_SPECTRUM && mode != FXC_MODE_CONTINUUM) return fail(p, FXC_ERR_ARG, "bad mode %d", mode);
-    if (mode == FXC_MODE_CONTINUUM && !(bandwidth > 0.0)) return fail(p, FXC_ERR_ARG, "bandwidth must be > 0");
-    if (fmt != FXC_IQ_C64 && fmt != FXC_IQ_U8 && fmt != FXC_IQ_C128) return fail(p, FXC_ERR_ARG, "bad iq_format %d", fmt);
+    if (const int rc = check_call(p, {fmt, remove_dc != 0, true, mode, bandwidth})) return rc;
     FXC_DEVICE(p, p->device);
     fxc_pipe* q = new (std::nothrow) fxc_pipe();
     if (!q) return fail(p, FXC_ERR_NOMEM, "host allocation failed");
@@ -1704,9 +1446,8 @@ int fxc_pipe_create_iq(fxc_pipe** out, fxc_plan* p, int64_t chunks_per_batch, in
     q->bandwidth = bandwidth;
     q->fmt = fmt;
     q->remove_dc = remove_dc;
-    q->in_bytes = (size_t)chunks_per_batch * p->n_ant * p->num_samp * (fmt == FXC_IQ_U8 ? 2 : (fmt == FXC_IQ_C128 ? sizeof(cd) : sizeof(cf)));
-    q->out_bytes = mode == FXC_MODE_SPECTRUM ? (size_t)chunks_per_batch * p->n_prod * p->nchan * sizeof(cf)
-                                             : (size_t)chunks_per_batch * p->n_prod * sizeof(cd);
+    q->in_bytes = input_bytes(p, fmt, chunks_per_batch);
+    q->out_bytes = (size_t)chunks_per_batch * row_bytes(p, mode);
     q->slots.resize((size_t)depth);
     hipError_t e = hipStreamCreateWithFlags(&q->s_in, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&q->s_out, hipStreamNonBlocking);
@@ -1749,12 +1490,8 @@ int fxc_pipe_submit(fxc_pipe* q) {
     FXC_HIP(p, hipMemcpyAsync(sl.d_in, sl.h_in, q->in_bytes, hipMemcpyHostToDevice, q->s_in));
     FXC_HIP(p, hipEventRecord(sl.ev_in, q->s_in));
     FXC_HIP(p, hipStreamWaitEvent(p->stream, sl.ev_in, 0));
-    // the slot's device copy is the pipe's own: complex64 batches are de-meaned in place
-    int rc = q->fmt == FXC_IQ_U8 ? fx_u8_dev(p, static_cast<const unsigned char*>(sl.d_in), sl.d_out, q->chunks, q->mode,
-                                             q->bandwidth, q->remove_dc, true)
-             : (q->fmt == FXC_IQ_C128 || q->remove_dc)
-                 ? fx_cond_dev(p, sl.d_in, sl.d_out, q->chunks, q->mode, q->bandwidth, q->fmt, q->remove_dc, true, true)
-                 : fx_rows_dev(p, static_cast<const cf*>(sl.d_in), sl.d_out, q->chunks, q->mode, q->bandwidth);
+    // the slot's device copy is the pipe's own (x_is_scratch): complex64 batches are de-meaned in place
+    int rc = fx_call_dev(p, {q->fmt, q->remove_dc != 0, true, q->mode, q->bandwidth}, sl.d_in, sl.d_out, q->chunks, true);
     if (rc) return rc;
     FXC_HIP(p, hipEventRecord(sl.ev_compute, p->stream));
     FXC_HIP(p, hipStreamWaitEvent(q->s_out, sl.ev_compute, 0));

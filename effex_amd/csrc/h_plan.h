@@ -175,7 +175,6 @@ struct fxc_plan {
     void* d_rowpart = nullptr;                       // continuum rows of a few-row call: float64 partial sums per bin slice
     size_t rowpart_bytes = 0;
     void* d_dc = nullptr;                            // uint8 ingest: byte sums + conversion offsets per stream
-    bool u8_dck = false;                             // this uint8 call: the fused kernel sums its later chunks' bytes itself
     size_t dc_bytes = 0;
     // timing
     hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;

@@ -9,7 +9,7 @@ namespace {
 // [chunk][antenna][frame][nchan] in natural bin order, then xengine_kernel<A, true> reads every spectrum once and writes raw rows
 // [n_prod][nchan]: the n_base cross rows, then the A auto rows.  A raw row is a float32 sum of at most kRowSpectra spectra: up
 // to `unit` chunks (integrations), or one of `xr` frame ranges of a chunk (k_finish.h::x_range) -- the multi-antenna fused route's
-// rows.  Byte input reaches it through the conversion pass (fx_u8_dev).
+// rows.  Byte input reaches it through the conversion pass (condition_u8, h_ingest.h).
 struct AutoPass {
     int64_t cb;          // chunks per pass
     int64_t unit;        // chunks per raw row at most
@@ -90,18 +90,19 @@ int autos_accumulate_dev(fxc_plan* p, const cf* x, int64_t n_chunks) {
 
 // (fx_rows_dev, below) the mode of a tracked fx_accumulate: its passes fold their rows into the accumulator
 constexpr int kModeTrackFold = -1;
-int fx_rows_dev(fxc_plan* p, const cf* x, void* out, int64_t n_chunks, int mode, double bandwidth, const cf* dc_u8 = nullptr);
+int fx_rows_dev(fxc_plan* p, const cf* x, void* out, int64_t n_chunks, int mode, double bandwidth, const cf* dc_u8 = nullptr,
+                bool dck = false);
 
 // device-resident implementation of fx_accumulate
 // dc_u8 != nullptr (fused 2-antenna plans only): x is the uint8 I,Q stream [n_chunks][2][num_samp][2] and dc_u8 its
-// per-stream conversion offsets
-int fx_accumulate_dev(fxc_plan* p, const cf* x, int64_t n_chunks, const cf* dc_u8 = nullptr) {
+// per-stream conversion offsets; dck: the fused kernel sums its later chunks' bytes itself (never under a delay track)
+int fx_accumulate_dev(fxc_plan* p, const cf* x, int64_t n_chunks, const cf* dc_u8 = nullptr, bool dck = false) {
     if (n_chunks == 0) return FXC_OK;
     p->acc_track = p->track;
     if (p->track) {
         // rot changes from chunk to chunk, so it is applied before the sum over chunks: the rows routes' raw rows (one set per
         // chunk), folded by track_fold_kernel
-        const int rc = fx_rows_dev(p, x, nullptr, n_chunks, kModeTrackFold, 1.0, dc_u8);
+        const int rc = fx_rows_dev(p, x, nullptr, n_chunks, kModeTrackFold, 1.0, dc_u8, dck);
         if (rc) return rc;
         p->spectra_count += (double)n_chunks * (double)p->n_pts;
         return FXC_OK;
@@ -136,7 +137,7 @@ int fx_accumulate_dev(fxc_plan* p, const cf* x, int64_t n_chunks, const cf* dc_u
             // chunks per raw row: 2 antennas, rows of up to kRowSpectra spectra; more, the X-engine's chunk groups
             const int64_t unit = p->n_ant == 2 ? fused_unit(p) : xengine_group(p, nc, fused_unit(p));
             rc = fused_raw_sums(p, reinterpret_cast<const cf*>(reinterpret_cast<const char*>(x) + c0 * in_bytes), nc, spec, raw,
-                                dc_u8 ? dc_u8 + c0 * 2 : nullptr, unit, false, dc_u8 && p->u8_dck);
+                                dc_u8 ? dc_u8 + c0 * 2 : nullptr, unit, false, dc_u8 && dck);
             if (rc) return rc;
             // 2 antennas: all the raw rows, leading parts included; more: one row [n_base][nchan] per chunk group
             const int64_t n_rows = p->n_ant == 2 ? fused_rows(p, nc, unit, false) : (nc + unit - 1) / unit * x_ranges(p, unit);
@@ -387,7 +388,7 @@ int autos_rows_dev(fxc_plan* p, const cf* x, const RowsOut& o, int64_t n_chunks)
 }
 
 // the routes of fx_rows_dev: raw rows pass by pass, each pass finished by launch_rows
-int rows_routes(fxc_plan* p, const cf* x, const RowsOut& o, int64_t n_chunks, const cf* dc_u8) {
+int rows_routes(fxc_plan* p, const cf* x, const RowsOut& o, int64_t n_chunks, const cf* dc_u8, bool dck) {
     if (p->autos && !fused_autos(p, n_chunks)) return autos_rows_dev(p, x, o, n_chunks);
     if (p->path == FXC_PATH_STREAM) {
         const int nb = (int)stream_blocks(p);
@@ -416,7 +417,7 @@ int rows_routes(fxc_plan* p, const cf* x, const RowsOut& o, int64_t n_chunks, co
         for (int64_t c0 = 0; c0 < n_chunks; c0 += cb) {
             const int64_t nc = std::min(cb, n_chunks - c0);
             rc = fused_raw_sums(p, reinterpret_cast<const cf*>(reinterpret_cast<const char*>(x) + c0 * in_bytes), nc, spec, raw,
-                                dc_u8 ? dc_u8 + c0 * 2 : nullptr, 1, true, dc_u8 && p->u8_dck);
+                                dc_u8 ? dc_u8 + c0 * 2 : nullptr, 1, true, dc_u8 && dck);
             if (rc) return rc;
             const int64_t rows = nc * p->n_prod;
             const LeadRows lead = p->n_ant == 2 ? fused_lead(p, nc) : kNoLead;
@@ -508,11 +509,11 @@ int rows_routes(fxc_plan* p, const cf* x, const RowsOut& o, int64_t n_chunks, co
 
 // device-resident implementation of fx_rows; out = cf[n_chunks][n_prod][nchan] or cd[n_chunks][n_prod].  Under a delay track
 // the call's chunks are the plan's chunks track_t .. track_t + n_chunks - 1 (launch_rows counts them pass by pass).
-int fx_rows_dev(fxc_plan* p, const cf* x, void* out, int64_t n_chunks, int mode, double bandwidth, const cf* dc_u8) {
+int fx_rows_dev(fxc_plan* p, const cf* x, void* out, int64_t n_chunks, int mode, double bandwidth, const cf* dc_u8, bool dck) {
     if (n_chunks == 0) return FXC_OK;
     const RowsOut o = {mode, out, (float)(1.0 / (double)p->n_pts), 1.0 / ((double)p->n_pts * (double)p->nchan * bandwidth)};
     const int64_t t0 = p->track_t;
-    const int rc = rows_routes(p, x, o, n_chunks, dc_u8);
+    const int rc = rows_routes(p, x, o, n_chunks, dc_u8, dck);
     if (rc) p->track_t = t0;
     return rc;
 }

@@ -67,6 +67,18 @@ def test_argument_validation_needs_no_device(lib):
     assert lib.fxc_fx_rows_iq(None, None, None, 1, 0, 0, 1.0, 7, 0) == _lib.FXC_ERR_ARG          # no such sample format
     assert lib.fxc_fx_accumulate_iq(None, None, 1, 0, _lib.FXC_IQ_C64, 1) == _lib.FXC_ERR_ARG
     assert lib.fxc_pipe_create_iq(None, None, 1, 2, 0, 1.0, _lib.FXC_IQ_C64, 1) == _lib.FXC_ERR_ARG
+    # every entry point that takes samples, and the pipe, with a NULL plan: plain, then with a bad mode / sample format where
+    # the signature has one -- one argument check answers all of them (csrc/h_ingest.h)
+    pipe = ctypes.c_void_p()
+    for mode, fmt in ((0, _lib.FXC_IQ_C64), (9, _lib.FXC_IQ_C64), (0, 7), (9, 7)):
+        for mem in (_lib.FXC_MEM_DEVICE, _lib.FXC_MEM_HOST, _lib.FXC_MEM_DEVICE_TO_PINNED):
+            assert lib.fxc_fx_rows(None, None, None, 1, mem, mode, 1.0) == _lib.FXC_ERR_ARG
+            assert lib.fxc_fx_accumulate(None, None, 1, mem) == _lib.FXC_ERR_ARG
+            assert lib.fxc_fx_rows_u8(None, None, None, 1, mem, mode, 1.0, 1) == _lib.FXC_ERR_ARG
+            assert lib.fxc_fx_accumulate_u8(None, None, 1, mem, 1) == _lib.FXC_ERR_ARG
+            assert lib.fxc_fx_rows_iq(None, None, None, 1, mem, mode, 1.0, fmt, 1) == _lib.FXC_ERR_ARG
+            assert lib.fxc_fx_accumulate_iq(None, None, 1, mem, fmt, 0) == _lib.FXC_ERR_ARG
+        assert lib.fxc_pipe_create_iq(ctypes.byref(pipe), None, 1, 2, mode, 1.0, fmt, 1) == _lib.FXC_ERR_ARG and not pipe.value
     assert lib.fxc_host_alloc(None, 64) == _lib.FXC_ERR_ARG
     assert lib.fxc_host_free(None) == _lib.FXC_OK
 
