@@ -119,6 +119,8 @@ SIGNATURES = {
     "fxc_estimate_delays": (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int, _c.c_double, _c.c_int, _vp]),
     "fxc_fringe_fit": (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int, _c.c_double, _c.c_double, _c.c_int, _c.c_int, _vp, _vp, _vp]),
     "fxc_solve_gains": (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int, _c.c_int64, _c.c_int, _c.c_int, _vp, _vp]),
+    "fxc_solve_gains_weighted": (_c.c_int, [_vp, _vp, _vp, _c.c_int64, _c.c_int, _vp, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int, _vp,
+                                            _vp]),
     "fxc_pipe_create": (_c.c_int, [_c.POINTER(_vp), _vp, _c.c_int64, _c.c_int, _c.c_int, _c.c_double]),
     "fxc_pipe_create_u8": (_c.c_int, [_c.POINTER(_vp), _vp, _c.c_int64, _c.c_int, _c.c_int, _c.c_double, _c.c_int]),
     "fxc_pipe_create_iq": (_c.c_int, [_c.POINTER(_vp), _vp, _c.c_int64, _c.c_int, _c.c_int, _c.c_double, _c.c_int,

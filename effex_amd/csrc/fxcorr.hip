@@ -1383,7 +1383,119 @@ int solve_gains_batch(fxc_plan* p, const cf* rows, int64_t n_chunks, int mem_kin
     return FXC_OK;
 }
 
+// The weighted gain solve (fxcorr.h fxc_solve_gains_weighted): solve_gains_batch with a weight block beside every staged row
+// block, U and D (24 bytes per baseline and bin) for V, and the model of a group of intervals uploaded once per group (of all
+// intervals once when there is one model).  Batches continue the sums S, Sw in U, D, so no bit depends on the sizes.
+int solve_gains_weighted_batch(fxc_plan* p, const cf* rows, const float* weights, int64_t n_chunks, int mem_kind, const cf* model,
+                               int64_t n_model, int64_t interval, int ref, int iters, double* gains_re_im, double* step) {
+    FXC_DEVICE(p, p->device);
+    const int n_ant = p->n_ant, nchan = p->nchan, n_base = p->n_base;
+    const int64_t n_rows = p->n_prod;
+    const int64_t n_int = (n_chunks + interval - 1) / interval;
+    // the solve's tile: as many adjacent bins (a power of two) as give every (antenna, bin) a thread and fit the LDS budget
+    const int64_t lds_bin = (int64_t)n_base * kGainsWeightedTileBytes + (int64_t)n_ant * kGainsImageBytes;
+    int tm_log = 0;
+    for (int cand = 6; cand >= 0; --cand) {
+        const int64_t tm = 1ll << cand;
+        if (tm <= kGainsMaxTile && n_ant * tm <= kGainsThreads && lds_bin * tm <= kGainsLdsBytes) {
+            tm_log = cand;
+            break;
+        }
+    }
+    const int64_t lds = lds_bin << tm_log;
+    const int64_t elems = (int64_t)n_base * nchan;
+    const int64_t gains_bytes = n_int * n_ant * nchan * (int64_t)sizeof(cd);
+    const int64_t res_bytes = (gains_bytes + n_int * nchan * (int64_t)sizeof(double) + 255) / 256 * 256;
+    const int64_t model_one = elems * (int64_t)sizeof(cf);
+    // per interval: U + D, and the interval's own model where there is one per interval; a single model is a fixed part
+    const int64_t v_one = elems * kGainsWeightedTileBytes + (n_model > 1 ? model_one : 0);
+    const int64_t fixed = n_model == 1 ? model_one : 0;
+    const int64_t stage_one = elems * (int64_t)(sizeof(cf) + (weights ? sizeof(float) : 0));
+    const bool host = mem_kind == FXC_MEM_HOST;
+    const int64_t avail = std::max<int64_t>(0, ws_target() - res_bytes - fixed);
+    const int64_t group = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_int, 65535), (host ? avail / 2 : avail) / v_one));
+    const int64_t group_chunks = std::min(n_chunks, group * interval);
+    const int64_t batch = host ? std::max<int64_t>(1, std::min(group_chunks, (avail - group * v_one) / stage_one)) : 0;
+    const int64_t model_slots = n_model > 1 ? group : n_model;
+    int rc = ensure_ws(p, res_bytes + group * elems * kGainsWeightedTileBytes + model_slots * model_one + batch * stage_one);
+    if (rc) return rc;
+    FXC_HIP(p, hipFuncSetAttribute(reinterpret_cast<const void*>(&gains_weighted_solve_kernel),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, kGainsLdsBytes));
+    char* ws = static_cast<char*>(p->d_ws);
+    cd* d_gains = reinterpret_cast<cd*>(ws);
+    double* d_step = reinterpret_cast<double*>(ws + gains_bytes);
+    cd* d_u = reinterpret_cast<cd*>(ws + res_bytes);
+    double* d_d = reinterpret_cast<double*>(ws + res_bytes + group * elems * (int64_t)sizeof(cd));
+    cf* d_model = reinterpret_cast<cf*>(ws + res_bytes + group * elems * kGainsWeightedTileBytes);
+    cf* stage = d_model + model_slots * elems;
+    float* stage_w = reinterpret_cast<float*>(stage + batch * elems);
+    const dim3 block(kGainsThreads);
+    const dim3 solve_block((unsigned)(((n_ant << tm_log) + 63) / 64 * 64));
+    const unsigned gx = (unsigned)(((nchan + 1) / 2 + kGainsThreads - 1) / kGainsThreads);
+    const int64_t model_stride = n_model > 1 ? elems : 0;
+    if (n_model == 1) FXC_HIP(p, hipMemcpyAsync(d_model, model, (size_t)model_one, hipMemcpyHostToDevice, p->stream));
+    for (int64_t s0 = 0; s0 < n_int; s0 += group) {
+        const int64_t s1 = std::min(n_int, s0 + group), c0 = s0 * interval, c1 = std::min(n_chunks, s1 * interval);
+        if (n_model > 1)
+            FXC_HIP(p, hipMemcpyAsync(d_model, model + s0 * elems, (size_t)((s1 - s0) * model_one), hipMemcpyHostToDevice, p->stream));
+        const cf* d_m = n_model ? d_model : nullptr;
+        if (host) {
+            for (int64_t b0 = c0; b0 < c1; b0 += batch) {
+                const int64_t b1 = std::min(c1, b0 + batch), sa = b0 / interval, sb = (b1 - 1) / interval;
+                FXC_HIP(p, hipMemcpy2DAsync(stage, (size_t)elems * sizeof(cf), rows + b0 * n_rows * nchan, (size_t)(n_rows * nchan) * sizeof(cf),
+                                            (size_t)elems * sizeof(cf), (size_t)(b1 - b0), hipMemcpyHostToDevice, p->stream));
+                if (weights)
+                    FXC_HIP(p, hipMemcpyAsync(stage_w, weights + b0 * elems, (size_t)((b1 - b0) * elems) * sizeof(float),
+                                              hipMemcpyHostToDevice, p->stream));
+                hipLaunchKernelGGL(gains_weighted_average_kernel, dim3(gx, n_base, (unsigned)(sb - sa + 1)), block, 0, p->stream, stage, elems,
+                                   weights ? stage_w : nullptr, elems, d_m, model_stride, b0, b1, interval, n_chunks, sa, s0, d_u, d_d,
+                                   n_base, nchan, (int)(nchan % 2 == 0));
+            }
+        } else {
+            const int vec = nchan % 2 == 0 && reinterpret_cast<uintptr_t>(rows) % 16 == 0 && reinterpret_cast<uintptr_t>(weights) % 8 == 0;
+            hipLaunchKernelGGL(gains_weighted_average_kernel, dim3(gx, n_base, (unsigned)(s1 - s0)), block, 0, p->stream,
+                               rows + c0 * n_rows * nchan, n_rows * nchan, weights ? weights + c0 * elems : nullptr, elems, d_m, model_stride,
+                               c0, c1, interval, n_chunks, s0, s0, d_u, d_d, n_base, nchan, vec);
+        }
+        hipLaunchKernelGGL(gains_weighted_solve_kernel, dim3((unsigned)((nchan + (1 << tm_log) - 1) >> tm_log), (unsigned)(s1 - s0)),
+                           solve_block, (size_t)lds, p->stream, d_u, d_d, d_gains + s0 * n_ant * nchan, d_step + s0 * nchan, n_ant, nchan,
+                           tm_log, ref, iters);
+        FXC_HIP(p, hipGetLastError());
+    }
+    std::vector<char> h_res((size_t)res_bytes);
+    FXC_HIP(p, hipMemcpyAsync(h_res.data(), ws, (size_t)res_bytes, hipMemcpyDeviceToHost, p->stream));
+    FXC_HIP(p, hipStreamSynchronize(p->stream));
+    std::memcpy(gains_re_im, h_res.data(), (size_t)gains_bytes);
+    if (step) std::memcpy(step, h_res.data() + gains_bytes, (size_t)(n_int * nchan) * sizeof(double));
+    return FXC_OK;
+}
+
 }  // namespace
+
+int fxc_solve_gains_weighted(fxc_plan* p, const void* rows, const void* weights, int64_t n_chunks, int mem_kind, const void* model,
+                             int64_t n_model, int64_t interval, int ref, int iters, double* gains_re_im, double* step) {
+    if (!p || !rows || !gains_re_im) return fail(p, FXC_ERR_ARG, "NULL argument");
+    if (n_chunks < 1) return fail(p, FXC_ERR_ARG, "n_chunks=%lld: a gain solve needs 1 or more chunks", (long long)n_chunks);
+    if (interval < 0) return fail(p, FXC_ERR_ARG, "interval=%lld is negative", (long long)interval);
+    if (ref < 0 || ref >= p->n_ant) return fail(p, FXC_ERR_ARG, "ref=%d outside [0, %d)", ref, p->n_ant);
+    if (iters < 1 || iters > 1000) return fail(p, FXC_ERR_ARG, "iters=%d outside 1 .. 1000", iters);
+    if (mem_kind != FXC_MEM_HOST && mem_kind != FXC_MEM_DEVICE) return fail(p, FXC_ERR_ARG, "bad mem_kind %d", mem_kind);
+    if (interval == 0 || interval > n_chunks) interval = n_chunks;
+    const int64_t n_int = (n_chunks + interval - 1) / interval;
+    if ((model == nullptr) != (n_model == 0)) return fail(p, FXC_ERR_ARG, "model and n_model=%lld disagree", (long long)n_model);
+    if (model && n_model != 1 && n_model != n_int)
+        return fail(p, FXC_ERR_ARG, "n_model=%lld is neither 1 nor the number of intervals %lld", (long long)n_model, (long long)n_int);
+    if (p->n_ant < 3)
+        return fail(p, FXC_ERR_UNSUPPORTED, "a gain solve needs 3 or more antennas, the plan has %d: one baseline closes nothing", p->n_ant);
+    if (model) {
+        const float* m = static_cast<const float*>(model);
+        const int64_t n = 2 * n_model * (int64_t)p->n_base * p->nchan;
+        for (int64_t i = 0; i < n; ++i)
+            if (!std::isfinite(m[i])) return fail(p, FXC_ERR_ARG, "model value %lld is not finite", (long long)(i / 2));
+    }
+    return solve_gains_weighted_batch(p, static_cast<const cf*>(rows), static_cast<const float*>(weights), n_chunks, mem_kind,
+                                      static_cast<const cf*>(model), n_model, interval, ref, iters, gains_re_im, step);
+}
 
 int fxc_solve_gains(fxc_plan* p, const void* rows, int64_t n_chunks, int mem_kind, int64_t interval, int ref, int iters,
                     double* gains_re_im, double* step) {

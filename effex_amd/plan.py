@@ -88,6 +88,19 @@ def gain_tables(gains, n_ant, nchan, delays_s=None, bandwidth=None, frequency=No
     return tables
 
 
+def offset_source_model(n_ant, nchan, bandwidth, frequency, delays_s, flux=1.0):
+    """Model visibilities [n_baselines, nchan] complex64 for ``FxPlan.solve_gains(.., model=)``, bins in the rows' fftshifted
+    order, baselines in the rows' order: a point source of flux ``flux`` whose signal reaches antenna a ``delays_s[a]`` later than
+    the phase centre's would.  With r = ``rot_tables(nchan, bandwidth, frequency, delays_s)`` row (a, b) is
+    ``flux * fftshift(conj(r_a) r_b)``: the phase slopes the rows of such a source carry (row (a, b) is x_a conj(x_b))."""
+    delays = np.asarray(delays_s, dtype=np.float64).reshape(-1)
+    if delays.shape != (n_ant,):
+        raise ValueError("delays_s must have {} entries".format(n_ant))
+    rot = np.fft.fftshift(rot_tables(nchan, bandwidth, frequency, delays), axes=1)
+    out = [float(flux) * np.conj(rot[a]) * rot[b] for a in range(n_ant) for b in range(a + 1, n_ant)]
+    return np.stack(out).astype(np.complex64)
+
+
 def gain_track_solution(chunk, n_solutions, interval, first_chunk):
     """The solution chunk ``chunk`` takes under a gain track (fxcorr.h fxc_set_track_gains):
     ``clamp(floor((chunk - first_chunk) / interval), 0, n_solutions - 1)``; interval 0 (one solution) is solution 0."""
@@ -648,13 +661,19 @@ class FxPlan(object):
                                              int(pad), delays.ctypes.data, rates.ctypes.data, snr.ctypes.data))
         return delays, rates, snr
 
-    def solve_gains(self, rows, interval=0, ref=0, iters=50):
+    def solve_gains(self, rows, interval=0, ref=0, iters=50, weights=None, model=None):
         """Every antenna's complex gain per bin from SPECTRUM rows of a calibrator (fxcorr.h fxc_solve_gains): ``rows`` =
         [n_chunks, n_rows, nchan] complex64 as ``fx_rows(x)`` returns them (numpy, or a CUDA tensor on the plan's device; a 2-D
         [n_rows, nchan] array such as an integration from ``finalize`` is one chunk) -> (gains [n_int, n_ant, nchan]
         complex128, step [n_int, nchan] float64), one solution per ``interval`` chunks (0: one over all), bins in the rows'
         order, antenna ``ref`` real.  ``set_gains(gains[s])`` applies a solution; under a delay track ``set_track_gains(gains,
-        interval)`` applies all of them."""
+        interval)`` applies all of them.
+
+        ``weights`` and ``model`` (fxcorr.h fxc_solve_gains_weighted; with both None the call is fxc_solve_gains as it was):
+        ``weights`` = float32 [n_chunks, n_baselines, nchan] ([n_baselines, nchan] for 2-D rows), numpy for host rows or a
+        CUDA tensor on the plan's device for device rows; a sample counts iff its weight is > 0.  ``model`` = the model
+        visibilities, anything numpy casts to complex64, [n_baselines, nchan] or [n_int, n_baselines, nchan] (for instance
+        ``offset_source_model``)."""
         self._sync_stream()
         if _is_torch(rows):
             import torch
@@ -675,8 +694,40 @@ class FxPlan(object):
         n_int = -(-shape[0] // span)
         gains = np.zeros((n_int, self.n_ant, self.nchan), dtype=np.complex128)
         step = np.zeros((n_int, self.nchan), dtype=np.float64)
-        self._check(self._lib.fxc_solve_gains(self._h, ptr, int(shape[0]), kind, interval, int(ref), int(iters), gains.ctypes.data,
-                                              step.ctypes.data))
+        if weights is None and model is None:
+            self._check(self._lib.fxc_solve_gains(self._h, ptr, int(shape[0]), kind, interval, int(ref), int(iters), gains.ctypes.data,
+                                                  step.ctypes.data))
+            return gains, step
+        w_keep, w_ptr = None, None
+        if weights is not None:
+            if _is_torch(weights) != (kind == _lib.FXC_MEM_DEVICE):
+                raise ValueError("weights must be in the memory of rows: a CUDA tensor for device rows, numpy for host rows")
+            if kind == _lib.FXC_MEM_DEVICE:
+                import torch
+                if weights.dtype != torch.float32 or not weights.is_cuda or weights.device.index != self.device:
+                    raise ValueError("device weights must be a float32 CUDA tensor on device {}".format(self.device))
+                w_keep = weights.contiguous()
+                w_ptr = w_keep.data_ptr()
+            else:
+                w_keep = np.ascontiguousarray(weights, dtype=np.float32)
+                w_ptr = w_keep.ctypes.data
+            w_shape = tuple(w_keep.shape)
+            if len(w_shape) == 2 and len(tuple(keep.shape)) == 2:
+                w_shape = (1,) + w_shape
+            if w_shape != (shape[0], self.n_baselines, self.nchan):
+                raise ValueError("weights must have shape ({}, {}, {}), got {}".format(shape[0], self.n_baselines, self.nchan,
+                                                                                      tuple(w_keep.shape)))
+        m_keep, m_ptr, n_model = None, None, 0
+        if model is not None:
+            m_keep = np.ascontiguousarray(np.asarray(model).astype(np.complex64))
+            if m_keep.ndim == 2:
+                m_keep = m_keep[None]
+            if m_keep.ndim != 3 or m_keep.shape[0] not in (1, n_int) or m_keep.shape[1:] != (self.n_baselines, self.nchan):
+                raise ValueError("model must have shape ({1}, {2}) or ({0}, {1}, {2}), got {3}".format(
+                    n_int, self.n_baselines, self.nchan, tuple(np.shape(model))))
+            m_ptr, n_model = m_keep.ctypes.data, int(m_keep.shape[0])
+        self._check(self._lib.fxc_solve_gains_weighted(self._h, ptr, w_ptr, int(shape[0]), kind, m_ptr, n_model, interval, int(ref),
+                                                       int(iters), gains.ctypes.data, step.ctypes.data))
         return gains, step
 
     def set_gains(self, gains, delays_s=None, bandwidth=None, frequency=None):

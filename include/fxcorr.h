@@ -436,13 +436,54 @@ int fxc_fringe_fit(fxc_plan* plan, const void* rows, int64_t n_chunks, int mem_k
  * rows give the same bits.  Uses the plan's device, stream and workspace; synchronises like fxc_fringe_fit (one copy to the
  * host and one synchronisation end the call); neither reads nor changes the rot tables, the track or its counter.
  * Under a delay track fxc_set_track_gains applies every solution, interval by interval.
- * Not covered: a sky model other than a point source at the phase centre, weights or flags, two antennas.
+ * A sky model other than a point source at the phase centre, weights and flags: fxc_solve_gains_weighted below.  Not covered:
+ * two antennas.
  * FXC_ERR_ARG, before any device work: a NULL plan / rows / gains_re_im, n_chunks < 1, interval < 0, ref outside [0, n_ant),
  * iters outside 1 .. 1000, an unknown mem_kind.  FXC_ERR_UNSUPPORTED: fewer than 3 antennas (one baseline closes nothing).
  * The outputs are written on FXC_OK only. */
 int fxc_solve_gains(fxc_plan* plan, const void* rows, int64_t n_chunks, int mem_kind, int64_t interval, int ref, int iters,
                     double* gains_re_im /* [n_int][n_ant][nchan] complex128, bins in the rows' order */,
                     double* step        /* [n_int][nchan], may be NULL */);
+
+/* Weighted gain solve: fxc_solve_gains with a weight per sample (a weight that is not > 0 flags the sample) and a model
+ * visibility per baseline and bin -- for data with dropped chunks, narrow-band interference or a dead antenna,
+ * and for a calibrator that is resolved or away from the phase centre.
+ * rows = [n_chunks][n_rows][nchan] complex64 as for fxc_solve_gains; only the first n_baselines rows of a chunk are read.
+ * weights = [n_chunks][n_baselines][nchan] float32 in the memory kind of rows: cross rows only, with no room for auto rows also
+ * on a plan with autos, bins in the rows' fftshifted order; NULL: every weight is 1 (no buffer is read).  A sample counts iff
+ * w > 0: a zero, negative or NaN weight flags it.  Positive weights must be finite (stated, not checked).
+ * model = [n_model][n_baselines][nchan] complex64 HOST memory in the rows' order; n_model is 1 (one model for every interval) or
+ * n_int; NULL with n_model 0: model visibility 1.  Model values must be finite (checked on the host); a zero is allowed and takes
+ * that baseline out of that bin.
+ * Per interval (as in fxc_solve_gains; n chunks in the interval) and per bin:
+ *   S_ab     = sum over the chunks c of [w_c > 0 ? (double)w_c (double)v_c : 0] and Sw_ab = sum of [w_c > 0 ? (double)w_c : 0]:
+ *              real and imaginary parts apart, plain adds from 0 in ascending chunk order.  The product of two float32 values is
+ *              exact in float64, so the sums have one value whether or not the compiler contracts.  The VALUE of a flagged
+ *              sample is never used: NaN, Inf or 1e30 there changes no output bit;
+ *   A_ab     = S_ab / n and Wbar_ab = Sw_ab / n, each part divided;
+ *   U, D       without a model U_ab = A_ab and D_ab = Wbar_ab exactly; with a model M converted to float64
+ *              U_ab = A_ab conj(M_ab) and D_ab = Wbar_ab (Mx^2 + My^2); U_ba = conj(U_ab), D_ba = D_ab; the diagonal is not used;
+ *   start      Vhat_b = U_b,ref / D_b,ref where D_b,ref != 0; s = the mean of |Vhat_b| over those b != ref, b ascending;
+ *              g_ref = sqrt(s), g_a = Vhat_a / sqrt(s) where D_a,ref != 0, else 0; all 0 where s == 0 or no such b exists: a
+ *              bin whose reference antenna carries no weight is not solved;
+ *   for it = 1 .. iters (every a from the g of the iteration before, b != a ascending):
+ *              n_a = sum of U_ab g_b and d_a = sum of D_ab |g_b|^2; new_a = n_a / d_a, 0 where d_a == 0; on even it
+ *              new = (new + g) / 2; step, g = new and the final rotation to a real non-negative g_ref exactly as in
+ *              fxc_solve_gains.
+ * With unit weights and no model this is fxc_solve_gains' definition term for term.  An antenna whose baselines all carry
+ * zero weight gets g = 0 and takes no part in the other antennas' sums (fxc_set_track_gains then zeroes its rows).  Multiplying
+ * all weights by a power of two changes no output bit.
+ * Host rows and weights are staged through the workspace in batches, the intervals solved in groups and the model uploaded once
+ * per group, all sized by the workspace target; no output bit depends on the sizes, and host and device input give the same
+ * bits.  Uses the plan's device, stream and workspace; synchronises like fxc_solve_gains; neither reads nor changes the rot
+ * tables, the tracks or their counters.
+ * FXC_ERR_ARG, before any device work: every case of fxc_solve_gains; model and n_model disagree (one NULL / 0 without the
+ * other); n_model neither 1 nor n_int; a model value that is not finite.  FXC_ERR_UNSUPPORTED: fewer than 3 antennas.
+ * The outputs are written on FXC_OK only. */
+int fxc_solve_gains_weighted(fxc_plan* plan, const void* rows, const void* weights, int64_t n_chunks, int mem_kind,
+                             const void* model, int64_t n_model, int64_t interval, int ref, int iters,
+                             double* gains_re_im /* [n_int][n_ant][nchan] complex128, bins in the rows' order */,
+                             double* step        /* [n_int][nchan], may be NULL */);
 
 /* Host-fed front end: replaces the reference's blocking per-chunk copies
  * (effex.py:391-392, 508-509, 693).  A pipe owns `depth` slots of pinned host staging + device buffers.
