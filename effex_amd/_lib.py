@@ -121,6 +121,8 @@ SIGNATURES = {
     "fxc_solve_gains": (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int, _c.c_int64, _c.c_int, _c.c_int, _vp, _vp]),
     "fxc_solve_gains_weighted": (_c.c_int, [_vp, _vp, _vp, _c.c_int64, _c.c_int, _vp, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int, _vp,
                                             _vp]),
+    "fxc_flag_rows": (_c.c_int, [_vp, _vp, _vp, _c.c_int64, _c.c_int, _c.c_int64, _c.c_float, _c.c_float, _c.c_int, _c.c_int, _vp,
+                                 _vp]),
     "fxc_pipe_create": (_c.c_int, [_c.POINTER(_vp), _vp, _c.c_int64, _c.c_int, _c.c_int, _c.c_double]),
     "fxc_pipe_create_u8": (_c.c_int, [_c.POINTER(_vp), _vp, _c.c_int64, _c.c_int, _c.c_int, _c.c_double, _c.c_int]),
     "fxc_pipe_create_iq": (_c.c_int, [_c.POINTER(_vp), _vp, _c.c_int64, _c.c_int, _c.c_int, _c.c_double, _c.c_int,

@@ -140,6 +140,7 @@ int64_t ws_target() {
 #include "k_delay.h"
 #include "k_fringe.h"
 #include "k_gains.h"
+#include "k_flag.h"
 #include "k_synth.h"
 #include "h_plan.h"
 #include "h_rtc.h"
@@ -1470,7 +1471,109 @@ int solve_gains_weighted_batch(fxc_plan* p, const cf* rows, const float* weights
     return FXC_OK;
 }
 
+// The detector (fxcorr.h fxc_flag_rows; kernels in k_flag.h).  The workspace holds the counts of every window, the level and
+// scatter planes of the windows and baselines of one launch and, for host rows, a slab: the rows, the prior and the weights of
+// some whole baselines of one window (one strided copy each way).  Slabs and window groups are sized by the workspace target
+// (FXC_WS_MB); a column belongs to one launch and a baseline's bins to one slab, so no bit depends on the sizes.
+int flag_rows_batch(fxc_plan* p, const cf* rows, const float* prior, int64_t n_chunks, int mem_kind, int64_t window, float time_threshold,
+                    float freq_threshold, int half_width, int iters, float* weights, int64_t* counts) {
+    FXC_DEVICE(p, p->device);
+    const int nchan = p->nchan, n_base = p->n_base;
+    const int64_t n_rows = p->n_prod;
+    const int64_t n_win = (n_chunks + window - 1) / window;
+    // a wave's columns: as many (a power of two, 16 at most) as leave a lane 8 samples of the longest window -- short loops and
+    // little LDS a wave, so that many waves share a CU --, 2 where the window is longer than that allows (32 samples at 1024 chunks)
+    int q_log = 1;
+    for (int cand = kFlagMaxQLog; cand >= 1; --cand) {
+        if (((window << cand) + 63) / 64 <= kFlagTargetLaneSamples) {
+            q_log = cand;
+            break;
+        }
+    }
+    const int plane_stride = (int)(((window << q_log) + 63) / 64 * 64);
+    const size_t lds = (size_t)(kFlagThreads / 64) * 3 * plane_stride * sizeof(uint32_t);
+    const bool host = mem_kind == FXC_MEM_HOST;
+    const int64_t counts_bytes = (n_win * n_base * 3 * (int64_t)sizeof(unsigned long long) + 255) / 256 * 256;
+    const int64_t stats_base = (int64_t)nchan * 2 * (int64_t)sizeof(uint32_t);      // per window and baseline
+    const int64_t slab_base = host ? window * nchan * (int64_t)(sizeof(cf) + sizeof(float) + (prior ? sizeof(float) : 0)) : 0;
+    const int64_t avail = std::max<int64_t>(0, ws_target() - counts_bytes);
+    const int64_t nb_slab = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_base, 65535), avail / (stats_base + slab_base)));
+    const int64_t group = host || nb_slab < n_base ? 1
+                                                   : std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_win, 65535),
+                                                                                            avail / (stats_base * n_base)));
+    const int64_t slab_elems = nb_slab * window * nchan;      // samples of a host slab
+    int rc = ensure_ws(p, counts_bytes + group * nb_slab * stats_base + nb_slab * slab_base);
+    if (rc) return rc;
+    FXC_HIP(p, hipFuncSetAttribute(reinterpret_cast<const void*>(&flag_time_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)lds));
+    char* ws = static_cast<char*>(p->d_ws);
+    unsigned long long* d_counts = reinterpret_cast<unsigned long long*>(ws);
+    uint32_t* d_stats = reinterpret_cast<uint32_t*>(ws + counts_bytes);
+    cf* stage = reinterpret_cast<cf*>(ws + counts_bytes + group * nb_slab * stats_base);
+    float* stage_w = reinterpret_cast<float*>(stage + (host ? slab_elems : 0));
+    float* stage_p = stage_w + (host ? slab_elems : 0);
+    FXC_HIP(p, hipMemsetAsync(d_counts, 0, (size_t)counts_bytes, p->stream));
+    const dim3 block(kFlagThreads);
+    const unsigned gx_time = (unsigned)((nchan + (4 << q_log) - 1) / (4 << q_log)), gx_freq = (unsigned)((nchan + kFlagThreads - 1) / kFlagThreads);
+    for (int64_t s0 = 0; s0 < n_win; s0 += group) {
+        const int64_t s1 = std::min(n_win, s0 + group), c0 = s0 * window;
+        for (int64_t b0 = 0; b0 < n_base; b0 += nb_slab) {
+            const int64_t nb = std::min<int64_t>(nb_slab, n_base - b0);
+            unsigned long long* d_c = d_counts + (s0 * n_base + b0) * 3;
+            const dim3 grid_time(gx_time, (unsigned)nb, (unsigned)(s1 - s0)), grid_freq(gx_freq, (unsigned)nb, (unsigned)(s1 - s0));
+            if (host) {
+                const int64_t n = std::min(window, n_chunks - c0);
+                const size_t width = (size_t)(nb * nchan);
+                FXC_HIP(p, hipMemcpy2DAsync(stage, width * sizeof(cf), rows + (c0 * n_rows + b0) * nchan, (size_t)(n_rows * nchan) * sizeof(cf),
+                                            width * sizeof(cf), (size_t)n, hipMemcpyHostToDevice, p->stream));
+                if (prior)
+                    FXC_HIP(p, hipMemcpy2DAsync(stage_p, width * sizeof(float), prior + (c0 * n_base + b0) * nchan,
+                                                (size_t)n_base * nchan * sizeof(float), width * sizeof(float), (size_t)n,
+                                                hipMemcpyHostToDevice, p->stream));
+                hipLaunchKernelGGL(flag_time_kernel, grid_time, block, lds, p->stream, stage, (int64_t)width, prior ? stage_p : nullptr,
+                                   stage_w, (int64_t)width, window, n, time_threshold, iters, d_stats, d_c, n_base, nchan, q_log,
+                                   plane_stride);
+                hipLaunchKernelGGL(flag_freq_kernel, grid_freq, block, 0, p->stream, d_stats, stage_w, (int64_t)width, window, n,
+                                   freq_threshold, half_width, d_c, n_base, nchan);
+                FXC_HIP(p, hipMemcpy2DAsync(weights + (c0 * n_base + b0) * nchan, (size_t)n_base * nchan * sizeof(float), stage_w,
+                                            width * sizeof(float), width * sizeof(float), (size_t)n, hipMemcpyDeviceToHost, p->stream));
+            } else {
+                const int64_t w_stride = (int64_t)n_base * nchan, at = (c0 * n_base + b0) * nchan;
+                hipLaunchKernelGGL(flag_time_kernel, grid_time, block, lds, p->stream, rows + (c0 * n_rows + b0) * nchan, n_rows * nchan,
+                                   prior ? prior + at : nullptr, weights + at, w_stride, window, n_chunks - c0, time_threshold, iters, d_stats,
+                                   d_c, n_base, nchan, q_log, plane_stride);
+                hipLaunchKernelGGL(flag_freq_kernel, grid_freq, block, 0, p->stream, d_stats, weights + at, w_stride, window, n_chunks - c0,
+                                   freq_threshold, half_width, d_c, n_base, nchan);
+            }
+            FXC_HIP(p, hipGetLastError());
+        }
+    }
+    std::vector<int64_t> h_counts((size_t)(n_win * n_base * 3));
+    FXC_HIP(p, hipMemcpyAsync(h_counts.data(), d_counts, h_counts.size() * sizeof(int64_t), hipMemcpyDeviceToHost, p->stream));
+    FXC_HIP(p, hipStreamSynchronize(p->stream));
+    if (counts) std::memcpy(counts, h_counts.data(), h_counts.size() * sizeof(int64_t));
+    return FXC_OK;
+}
+
 }  // namespace
+
+int fxc_flag_rows(fxc_plan* p, const void* rows, const void* prior, int64_t n_chunks, int mem_kind, int64_t window, float time_threshold,
+                  float freq_threshold, int half_width, int iters, void* weights, int64_t* counts) {
+    if (!p || !rows || !weights) return fail(p, FXC_ERR_ARG, "NULL argument");
+    if (n_chunks < 1) return fail(p, FXC_ERR_ARG, "n_chunks=%lld: the detector needs 1 or more chunks", (long long)n_chunks);
+    if (window < 0) return fail(p, FXC_ERR_ARG, "window=%lld is negative", (long long)window);
+    if (!std::isfinite(time_threshold) || !(time_threshold > 0.f)) return fail(p, FXC_ERR_ARG, "time_threshold must be finite and > 0");
+    if (!std::isfinite(freq_threshold) || !(freq_threshold > 0.f)) return fail(p, FXC_ERR_ARG, "freq_threshold must be finite and > 0");
+    if (half_width < 0) return fail(p, FXC_ERR_ARG, "half_width=%d is negative", half_width);
+    if (iters < 1 || iters > 8) return fail(p, FXC_ERR_ARG, "iters=%d outside 1 .. 8", iters);
+    if (mem_kind != FXC_MEM_HOST && mem_kind != FXC_MEM_DEVICE) return fail(p, FXC_ERR_ARG, "bad mem_kind %d", mem_kind);
+    if (p->n_base < 1) return fail(p, FXC_ERR_ARG, "the detector needs 2 or more antennas, the plan has %d", p->n_ant);
+    if (window == 0 || window > n_chunks) window = n_chunks;
+    if (window > kFlagMaxChunks)
+        return fail(p, FXC_ERR_UNSUPPORTED, "%lld chunks in a window: a column lives in LDS, 1024 chunks at most", (long long)window);
+    return flag_rows_batch(p, static_cast<const cf*>(rows), static_cast<const float*>(prior), n_chunks, mem_kind, window, time_threshold,
+                           freq_threshold, std::min(half_width, p->nchan), iters, static_cast<float*>(weights), counts);
+}
 
 int fxc_solve_gains_weighted(fxc_plan* p, const void* rows, const void* weights, int64_t n_chunks, int mem_kind, const void* model,
                              int64_t n_model, int64_t interval, int ref, int iters, double* gains_re_im, double* step) {

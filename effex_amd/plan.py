@@ -730,6 +730,67 @@ class FxPlan(object):
                                                        int(iters), gains.ctypes.data, step.ctypes.data))
         return gains, step
 
+    def flag_rows(self, rows, window=0, time_threshold=20.0, freq_threshold=8.0, half_width=8, iters=2, prior=None,
+                  return_counts=False):
+        """The weights ``solve_gains(weights=)`` takes, from the rows alone (fxcorr.h fxc_flag_rows): ``rows`` = [n_chunks,
+        n_rows, nchan] complex64 as ``fx_rows(x)`` returns them, fringes stopped (numpy, or a CUDA tensor on the plan's device;
+        a 2-D [n_rows, nchan] array is one chunk) -> float32 [n_chunks, n_baselines, nchan] in the memory of rows: numpy for
+        host rows, a CUDA tensor for device rows, which goes into ``solve_gains`` without touching the host.  Per ``window``
+        chunks (0: all) a sample further than ``time_threshold`` median deviations from its (baseline, bin) column's complex
+        median gets weight 0 (``iters`` rounds), then a bin whose level or scatter stands ``freq_threshold`` median deviations
+        out of the bins within ``half_width`` loses its column.  The thresholds are multiples of the median deviation, not
+        sigmas.  ``prior`` = float32 weights in the memory of rows: a sample whose prior is not > 0 is ignored, a surviving one
+        keeps its prior.  With ``return_counts`` -> (weights, counts [n_win, n_baselines, 3] int64: not live at the start,
+        flagged in time, flagged in frequency)."""
+        self._sync_stream()
+        device = _is_torch(rows)
+        if device:
+            import torch
+            if rows.dtype != torch.complex64 or not rows.is_cuda or rows.device.index != self.device:
+                raise ValueError("device input must be a complex64 CUDA tensor on device {}".format(self.device))
+            keep = rows.contiguous()
+            ptr, kind = keep.data_ptr(), _lib.FXC_MEM_DEVICE
+        else:
+            keep = np.ascontiguousarray(rows, dtype=np.complex64)
+            ptr, kind = keep.ctypes.data, _lib.FXC_MEM_HOST
+        shape = tuple(keep.shape)
+        one = len(shape) == 2
+        if one:
+            shape = (1,) + shape
+        if len(shape) != 3 or shape[0] < 1 or shape[1:] != (self.n_rows, self.nchan):
+            raise ValueError("rows must have shape (n_chunks, {}, {}), got {}".format(self.n_rows, self.nchan, tuple(keep.shape)))
+        w_shape = (shape[0], self.n_baselines, self.nchan)
+        p_keep, p_ptr = None, None
+        if prior is not None:
+            if _is_torch(prior) != device:
+                raise ValueError("prior must be in the memory of rows: a CUDA tensor for device rows, numpy for host rows")
+            if device:
+                if prior.dtype != torch.float32 or not prior.is_cuda or prior.device.index != self.device:
+                    raise ValueError("device prior must be a float32 CUDA tensor on device {}".format(self.device))
+                p_keep = prior.contiguous()
+                p_ptr = p_keep.data_ptr()
+            else:
+                p_keep = np.ascontiguousarray(prior, dtype=np.float32)
+                p_ptr = p_keep.ctypes.data
+            if tuple(p_keep.shape) != (w_shape[1:] if one else w_shape):
+                raise ValueError("prior must have shape {}, got {}".format(w_shape[1:] if one else w_shape, tuple(p_keep.shape)))
+        window = int(window)
+        span = min(window, shape[0]) if window > 0 else shape[0]
+        counts = np.zeros((-(-shape[0] // span), self.n_baselines, 3), dtype=np.int64)
+        if device:
+            weights = torch.empty(w_shape, dtype=torch.float32, device=keep.device)      # the call writes every element
+            w_ptr = weights.data_ptr()
+            if not self._follow:      # a stream of the plan's own: torch's may still be using the block it handed out
+                torch.cuda.current_stream(keep.device).synchronize()
+        else:
+            weights = np.zeros(w_shape, dtype=np.float32)
+            w_ptr = weights.ctypes.data
+        self._check(self._lib.fxc_flag_rows(self._h, ptr, p_ptr, int(shape[0]), kind, window, float(time_threshold),
+                                            float(freq_threshold), int(half_width), int(iters), w_ptr, counts.ctypes.data))
+        if one:
+            weights = weights[0]
+        return (weights, counts) if return_counts else weights
+
     def set_gains(self, gains, delays_s=None, bandwidth=None, frequency=None):
         """Correct the rows for the per-antenna gains ``gains`` [n_ant, nchan] (one solution of ``solve_gains``, bins in the
         rows' order): antenna a's table is ``ifftshift(1 / g_a)``, 0 where g_a is 0 so that a dead channel stays zero, times

@@ -485,6 +485,52 @@ int fxc_solve_gains_weighted(fxc_plan* plan, const void* rows, const void* weigh
                              double* gains_re_im /* [n_int][n_ant][nchan] complex128, bins in the rows' order */,
                              double* step        /* [n_int][nchan], may be NULL */);
 
+/* Detector: the weights fxc_solve_gains_weighted takes, from the rows alone -- samples that stand out of their
+ * (baseline, bin) column in time, and bins that stand out of their neighbours in frequency, get weight 0.
+ * rows = [n_chunks][n_rows][nchan] complex64 as for fxc_solve_gains, exactly what fxc_fx_rows(.., FXC_MODE_SPECTRUM) writes, with
+ * the fringes stopped (a complex median means nothing on a rotating phasor); only the first n_baselines rows of a chunk are
+ * read: auto rows are skipped.  prior = [n_chunks][n_baselines][nchan] float32 in the memory kind of rows, or NULL.  weights has
+ * fxc_solve_gains_weighted's layout: cross rows only, no room for auto rows.
+ * Windows: with L = window (0: L = n_chunks), window s covers the chunks [s L, min((s + 1) L, n_chunks)) and n_win =
+ * ceil(n_chunks / L).  Everything below is per window, per baseline b and, where it says so, per bin k.
+ * Lower median of m values: the element at index (m - 1) / 2 (rounded down) of their ascending order -- an element of the set,
+ * no arithmetic.
+ * Live at the start: a sample (x, y) is live iff x and y are finite, not both zero (an exactly zero row is a dropped chunk), and
+ * prior is NULL or its value is > 0.  The VALUE of a sample that is not live is never used.
+ * Time stage, per column (b, k), `iters` times over the column's live samples (nothing happens once none is live):
+ *   mx, my   = the lower medians of x and of y;
+ *   dx, dy   = x - mx and y - my, each ONE float32 subtraction;
+ *   e        = (float)((double)dx (double)dx + (double)dy (double)dy): the products are exact in float64, so the sum has one value
+ *              whether or not the compiler contracts; then one rounding to float32;
+ *   d        = the lower median of e; where d > 0 a live sample is flagged iff e > time_threshold d (one float32 multiply and a
+ *              comparison; an infinite e compares like any value); where d == 0 nothing is flagged.
+ * Column statistics: after the iterations a column with a live sample is "defined" and gets, over its survivors, mx, my and e
+ * as above, level[k] = (float)((double)mx mx + (double)my my) and scatter[k] = the lower median of e.
+ * Frequency stage, per baseline, every decision from the level, scatter and defined-ness the time stage left, before any bin is
+ * cleared.  For a defined bin k take the defined bins j with |j - k| <= half_width, 0 <= j < nchan (k among them); for S in
+ * {level, scatter}: r = the lower median of S[j] and s = the lower median of |S[j] - r| (a float32 subtraction, then the absolute
+ * value).  Level test: k is an outlier iff s > 0 and |level[k] - r| > freq_threshold s (two-sided: a dead bin as well as a
+ * tone).  Scatter test: iff s > 0 and scatter[k] - r > freq_threshold s (the high side only).  An outlier bin has all its samples
+ * of the window flagged.  One pass: the neighbours' medians are not recomputed without the outliers.
+ * Output: a sample that is live at the end gets the prior's value where a prior was given, else 1.0f; every other sample
+ * +0.0f.  counts[s][b] = {not live at the start, flagged by the time stage, still live when the frequency stage flagged them}.
+ * The thresholds are multiples of the median deviation, not sigmas: for complex Gaussian scatter the median of e is ln 2 sigma^2,
+ * so time_threshold 20 is e > 13.9 sigma^2.
+ * No output depends on what a non-live sample holds; permuting the chunks of a window permutes the weights and changes nothing
+ * else; multiplying all rows by a power of two changes no output (barring overflow and underflow; float32 denormals are kept);
+ * no output depends on batching, the workspace size or host against device input.  Host rows and the prior are staged through
+ * the workspace in slabs of whole baselines of one window and a slab's weights copied back.  Uses the plan's device, stream and
+ * workspace; synchronises like fxc_solve_gains; neither reads nor changes the rot tables, the tracks or their counters.  Works
+ * from one baseline (2 antennas) up and at nchan 1 (where the frequency stage never fires: s is 0).
+ * FXC_ERR_ARG, before any device work: a NULL plan / rows / weights, n_chunks < 1, window < 0, a threshold that is not finite or
+ * not > 0, half_width < 0, iters outside 1 .. 8, an unknown mem_kind, a plan with fewer than 2 antennas.
+ * FXC_ERR_UNSUPPORTED: more than 1024 chunks in a window (a column lives in LDS; larger windows are out of scope).
+ * The outputs are written on FXC_OK only. */
+int fxc_flag_rows(fxc_plan* plan, const void* rows, const void* prior, int64_t n_chunks, int mem_kind, int64_t window,
+                  float time_threshold, float freq_threshold, int half_width, int iters,
+                  void* weights   /* [n_chunks][n_baselines][nchan] float32, in the memory kind of rows */,
+                  int64_t* counts /* [n_win][n_baselines][3], host, may be NULL */);
+
 /* Host-fed front end: replaces the reference's blocking per-chunk copies
  * (effex.py:391-392, 508-509, 693).  A pipe owns `depth` slots of pinned host staging + device buffers.
  * fxc_pipe_acquire hands the producer the pinned input buffer of the next free slot
