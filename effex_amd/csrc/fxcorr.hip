@@ -1318,83 +1318,22 @@ int fxc_fringe_fit(fxc_plan* p, const void* rows, int64_t n_chunks, int mem_kind
 
 namespace {
 
-// The gain solve (fxcorr.h fxc_solve_gains; kernels in k_gains.h).  The workspace holds the results of every interval (gains,
-// step), the averaged matrices V of a group of intervals and, for host rows, a staging block of cross rows; the intervals go
-// through in groups and a group's host chunks in batches, both sized by the workspace target (FXC_WS_MB).  A batch continues
-// the sums of the batch before it in V, so no bit depends on the sizes.  One copy to the host and one synchronisation.
-int solve_gains_batch(fxc_plan* p, const cf* rows, int64_t n_chunks, int mem_kind, int64_t interval, int ref, int iters,
-                      double* gains_re_im, double* step) {
+// The gain solve (fxcorr.h fxc_solve_gains and, `weighted`, fxc_solve_gains_weighted; kernels in k_gains.h).  The workspace holds
+// the results of every interval (gains, step), the averaged matrices of a group of intervals (V; weighted: U and D, 24 bytes per
+// baseline and bin) and, for host rows, a staging block of cross rows (weighted: with a weight block beside it where there are
+// weights); the model of a group of intervals is uploaded once per group (of all intervals once when there is one model).  The
+// intervals go through in groups and a group's host chunks in batches, both sized by the workspace target (FXC_WS_MB).  A batch
+// continues the sums of the batch before it in V (U, D), so no bit depends on the sizes.  One copy to the host and one
+// synchronisation.
+int solve_gains_batch(fxc_plan* p, bool weighted, const cf* rows, const float* weights, int64_t n_chunks, int mem_kind, const cf* model,
+                      int64_t n_model, int64_t interval, int ref, int iters, double* gains_re_im, double* step) {
     FXC_DEVICE(p, p->device);
     const int n_ant = p->n_ant, nchan = p->nchan, n_base = p->n_base;
     const int64_t n_rows = p->n_prod;
     const int64_t n_int = (n_chunks + interval - 1) / interval;
     // the solve's tile: as many adjacent bins (a power of two) as give every (antenna, bin) a thread and fit the LDS budget
-    int tm_log = 0;
-    for (int cand = 6; cand >= 0; --cand) {
-        const int64_t tm = 1ll << cand;
-        if (tm <= kGainsMaxTile && n_ant * tm <= kGainsThreads && ((int64_t)n_base + 2 * n_ant) * tm * (int64_t)sizeof(cd) <= kGainsLdsBytes) {
-            tm_log = cand;
-            break;
-        }
-    }
-    const int64_t lds = ((int64_t)n_base + 2 * n_ant) * (int64_t)sizeof(cd) << tm_log;
-    const int64_t gains_bytes = n_int * n_ant * nchan * (int64_t)sizeof(cd);
-    const int64_t res_bytes = (gains_bytes + n_int * nchan * (int64_t)sizeof(double) + 255) / 256 * 256;
-    const int64_t v_one = (int64_t)n_base * nchan * (int64_t)sizeof(cd), stage_one = (int64_t)n_base * nchan * (int64_t)sizeof(cf);
-    const bool host = mem_kind == FXC_MEM_HOST;
-    const int64_t avail = std::max<int64_t>(0, ws_target() - res_bytes);
-    const int64_t group = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_int, 65535), (host ? avail / 2 : avail) / v_one));
-    const int64_t group_chunks = std::min(n_chunks, group * interval);
-    const int64_t batch = host ? std::max<int64_t>(1, std::min(group_chunks, (avail - group * v_one) / stage_one)) : 0;
-    int rc = ensure_ws(p, res_bytes + group * v_one + batch * stage_one);
-    if (rc) return rc;
-    FXC_HIP(p, hipFuncSetAttribute(reinterpret_cast<const void*>(&gains_solve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   kGainsLdsBytes));
-    char* ws = static_cast<char*>(p->d_ws);
-    cd* d_gains = reinterpret_cast<cd*>(ws);
-    double* d_step = reinterpret_cast<double*>(ws + gains_bytes);
-    cd* d_v = reinterpret_cast<cd*>(ws + res_bytes);
-    cf* stage = reinterpret_cast<cf*>(ws + res_bytes + group * v_one);
-    const dim3 block(kGainsThreads);
-    const unsigned gx = (unsigned)(((nchan + 1) / 2 + kGainsThreads - 1) / kGainsThreads);
-    for (int64_t s0 = 0; s0 < n_int; s0 += group) {
-        const int64_t s1 = std::min(n_int, s0 + group), c0 = s0 * interval, c1 = std::min(n_chunks, s1 * interval);
-        if (host) {
-            for (int64_t b0 = c0; b0 < c1; b0 += batch) {
-                const int64_t b1 = std::min(c1, b0 + batch), sa = b0 / interval, sb = (b1 - 1) / interval;
-                FXC_HIP(p, hipMemcpy2DAsync(stage, (size_t)stage_one, rows + b0 * n_rows * nchan, (size_t)(n_rows * nchan) * sizeof(cf),
-                                            (size_t)stage_one, (size_t)(b1 - b0), hipMemcpyHostToDevice, p->stream));
-                hipLaunchKernelGGL(gains_average_kernel, dim3(gx, n_base, (unsigned)(sb - sa + 1)), block, 0, p->stream, stage,
-                                   (int64_t)n_base * nchan, b0, b1, interval, n_chunks, sa, s0, d_v, n_base, nchan, (int)(nchan % 2 == 0));
-            }
-        } else {
-            const int vec = nchan % 2 == 0 && reinterpret_cast<uintptr_t>(rows) % 16 == 0;
-            hipLaunchKernelGGL(gains_average_kernel, dim3(gx, n_base, (unsigned)(s1 - s0)), block, 0, p->stream, rows + c0 * n_rows * nchan,
-                               n_rows * nchan, c0, c1, interval, n_chunks, s0, s0, d_v, n_base, nchan, vec);
-        }
-        hipLaunchKernelGGL(gains_solve_kernel, dim3((unsigned)((nchan + (1 << tm_log) - 1) >> tm_log), (unsigned)(s1 - s0)), block,
-                           (size_t)lds, p->stream, d_v, d_gains + s0 * n_ant * nchan, d_step + s0 * nchan, n_ant, nchan, tm_log, ref, iters);
-        FXC_HIP(p, hipGetLastError());
-    }
-    std::vector<char> h_res((size_t)res_bytes);
-    FXC_HIP(p, hipMemcpyAsync(h_res.data(), ws, (size_t)res_bytes, hipMemcpyDeviceToHost, p->stream));
-    FXC_HIP(p, hipStreamSynchronize(p->stream));
-    std::memcpy(gains_re_im, h_res.data(), (size_t)gains_bytes);
-    if (step) std::memcpy(step, h_res.data() + gains_bytes, (size_t)(n_int * nchan) * sizeof(double));
-    return FXC_OK;
-}
-
-// The weighted gain solve (fxcorr.h fxc_solve_gains_weighted): solve_gains_batch with a weight block beside every staged row
-// block, U and D (24 bytes per baseline and bin) for V, and the model of a group of intervals uploaded once per group (of all
-// intervals once when there is one model).  Batches continue the sums S, Sw in U, D, so no bit depends on the sizes.
-int solve_gains_weighted_batch(fxc_plan* p, const cf* rows, const float* weights, int64_t n_chunks, int mem_kind, const cf* model,
-                               int64_t n_model, int64_t interval, int ref, int iters, double* gains_re_im, double* step) {
-    FXC_DEVICE(p, p->device);
-    const int n_ant = p->n_ant, nchan = p->nchan, n_base = p->n_base;
-    const int64_t n_rows = p->n_prod;
-    const int64_t n_int = (n_chunks + interval - 1) / interval;
-    // the solve's tile: as many adjacent bins (a power of two) as give every (antenna, bin) a thread and fit the LDS budget
-    const int64_t lds_bin = (int64_t)n_base * kGainsWeightedTileBytes + (int64_t)n_ant * kGainsImageBytes;
+    const int tile_bytes = weighted ? kGainsWeightedTileBytes : kGainsTileBytes;
+    const int64_t lds_bin = (int64_t)n_base * tile_bytes + (int64_t)n_ant * kGainsImageBytes;
     int tm_log = 0;
     for (int cand = 6; cand >= 0; --cand) {
         const int64_t tm = 1ll << cand;
@@ -1408,8 +1347,8 @@ int solve_gains_weighted_batch(fxc_plan* p, const cf* rows, const float* weights
     const int64_t gains_bytes = n_int * n_ant * nchan * (int64_t)sizeof(cd);
     const int64_t res_bytes = (gains_bytes + n_int * nchan * (int64_t)sizeof(double) + 255) / 256 * 256;
     const int64_t model_one = elems * (int64_t)sizeof(cf);
-    // per interval: U + D, and the interval's own model where there is one per interval; a single model is a fixed part
-    const int64_t v_one = elems * kGainsWeightedTileBytes + (n_model > 1 ? model_one : 0);
+    // per interval: V (U + D), and the interval's own model where there is one per interval; a single model is a fixed part
+    const int64_t v_one = elems * tile_bytes + (n_model > 1 ? model_one : 0);
     const int64_t fixed = n_model == 1 ? model_one : 0;
     const int64_t stage_one = elems * (int64_t)(sizeof(cf) + (weights ? sizeof(float) : 0));
     const bool host = mem_kind == FXC_MEM_HOST;
@@ -1418,22 +1357,35 @@ int solve_gains_weighted_batch(fxc_plan* p, const cf* rows, const float* weights
     const int64_t group_chunks = std::min(n_chunks, group * interval);
     const int64_t batch = host ? std::max<int64_t>(1, std::min(group_chunks, (avail - group * v_one) / stage_one)) : 0;
     const int64_t model_slots = n_model > 1 ? group : n_model;
-    int rc = ensure_ws(p, res_bytes + group * elems * kGainsWeightedTileBytes + model_slots * model_one + batch * stage_one);
+    int rc = ensure_ws(p, res_bytes + group * elems * tile_bytes + model_slots * model_one + batch * stage_one);
     if (rc) return rc;
-    FXC_HIP(p, hipFuncSetAttribute(reinterpret_cast<const void*>(&gains_weighted_solve_kernel),
+    FXC_HIP(p, hipFuncSetAttribute(weighted ? reinterpret_cast<const void*>(&gains_weighted_solve_kernel)
+                                            : reinterpret_cast<const void*>(&gains_solve_kernel),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, kGainsLdsBytes));
     char* ws = static_cast<char*>(p->d_ws);
     cd* d_gains = reinterpret_cast<cd*>(ws);
     double* d_step = reinterpret_cast<double*>(ws + gains_bytes);
-    cd* d_u = reinterpret_cast<cd*>(ws + res_bytes);
-    double* d_d = reinterpret_cast<double*>(ws + res_bytes + group * elems * (int64_t)sizeof(cd));
-    cf* d_model = reinterpret_cast<cf*>(ws + res_bytes + group * elems * kGainsWeightedTileBytes);
+    cd* d_v = reinterpret_cast<cd*>(ws + res_bytes);
+    double* d_d = reinterpret_cast<double*>(ws + res_bytes + group * elems * (int64_t)sizeof(cd));      // weighted only
+    cf* d_model = reinterpret_cast<cf*>(ws + res_bytes + group * elems * tile_bytes);
     cf* stage = d_model + model_slots * elems;
     float* stage_w = reinterpret_cast<float*>(stage + batch * elems);
     const dim3 block(kGainsThreads);
-    const dim3 solve_block((unsigned)(((n_ant << tm_log) + 63) / 64 * 64));
+    const dim3 solve_grid((unsigned)((nchan + (1 << tm_log) - 1) >> tm_log));
+    const dim3 solve_block((unsigned)(((n_ant << tm_log) + 63) / 64 * 64));      // weighted
     const unsigned gx = (unsigned)(((nchan + 1) / 2 + kGainsThreads - 1) / kGainsThreads);
     const int64_t model_stride = n_model > 1 ? elems : 0;
+    // rows [c_lo, c_hi) at src, c_stride elements a chunk (weights: elems a chunk), into the intervals sa .. sa + n_s - 1
+    auto average = [&](const cf* src, int64_t c_stride, const float* w, int64_t c_lo, int64_t c_hi, int64_t sa, int64_t n_s, int64_t s0,
+                       const cf* d_m, int vec) {
+        const dim3 grid(gx, n_base, (unsigned)n_s);
+        if (weighted)
+            hipLaunchKernelGGL(gains_weighted_average_kernel, grid, block, 0, p->stream, src, c_stride, w, elems, d_m, model_stride, c_lo, c_hi,
+                               interval, n_chunks, sa, s0, d_v, d_d, n_base, nchan, vec);
+        else
+            hipLaunchKernelGGL(gains_average_kernel, grid, block, 0, p->stream, src, c_stride, c_lo, c_hi, interval, n_chunks, sa, s0, d_v,
+                               n_base, nchan, vec);
+    };
     if (n_model == 1) FXC_HIP(p, hipMemcpyAsync(d_model, model, (size_t)model_one, hipMemcpyHostToDevice, p->stream));
     for (int64_t s0 = 0; s0 < n_int; s0 += group) {
         const int64_t s1 = std::min(n_int, s0 + group), c0 = s0 * interval, c1 = std::min(n_chunks, s1 * interval);
@@ -1448,19 +1400,19 @@ int solve_gains_weighted_batch(fxc_plan* p, const cf* rows, const float* weights
                 if (weights)
                     FXC_HIP(p, hipMemcpyAsync(stage_w, weights + b0 * elems, (size_t)((b1 - b0) * elems) * sizeof(float),
                                               hipMemcpyHostToDevice, p->stream));
-                hipLaunchKernelGGL(gains_weighted_average_kernel, dim3(gx, n_base, (unsigned)(sb - sa + 1)), block, 0, p->stream, stage, elems,
-                                   weights ? stage_w : nullptr, elems, d_m, model_stride, b0, b1, interval, n_chunks, sa, s0, d_u, d_d,
-                                   n_base, nchan, (int)(nchan % 2 == 0));
+                average(stage, elems, weights ? stage_w : nullptr, b0, b1, sa, sb - sa + 1, s0, d_m, (int)(nchan % 2 == 0));
             }
         } else {
             const int vec = nchan % 2 == 0 && reinterpret_cast<uintptr_t>(rows) % 16 == 0 && reinterpret_cast<uintptr_t>(weights) % 8 == 0;
-            hipLaunchKernelGGL(gains_weighted_average_kernel, dim3(gx, n_base, (unsigned)(s1 - s0)), block, 0, p->stream,
-                               rows + c0 * n_rows * nchan, n_rows * nchan, weights ? weights + c0 * elems : nullptr, elems, d_m, model_stride,
-                               c0, c1, interval, n_chunks, s0, s0, d_u, d_d, n_base, nchan, vec);
+            average(rows + c0 * n_rows * nchan, n_rows * nchan, weights ? weights + c0 * elems : nullptr, c0, c1, s0, s1 - s0, s0, d_m, vec);
         }
-        hipLaunchKernelGGL(gains_weighted_solve_kernel, dim3((unsigned)((nchan + (1 << tm_log) - 1) >> tm_log), (unsigned)(s1 - s0)),
-                           solve_block, (size_t)lds, p->stream, d_u, d_d, d_gains + s0 * n_ant * nchan, d_step + s0 * nchan, n_ant, nchan,
-                           tm_log, ref, iters);
+        const dim3 grid(solve_grid.x, (unsigned)(s1 - s0));
+        if (weighted)
+            hipLaunchKernelGGL(gains_weighted_solve_kernel, grid, solve_block, (size_t)lds, p->stream, d_v, d_d, d_gains + s0 * n_ant * nchan,
+                               d_step + s0 * nchan, n_ant, nchan, tm_log, ref, iters);
+        else
+            hipLaunchKernelGGL(gains_solve_kernel, grid, block, (size_t)lds, p->stream, d_v, d_gains + s0 * n_ant * nchan, d_step + s0 * nchan,
+                               n_ant, nchan, tm_log, ref, iters);
         FXC_HIP(p, hipGetLastError());
     }
     std::vector<char> h_res((size_t)res_bytes);
@@ -1575,16 +1527,18 @@ int fxc_flag_rows(fxc_plan* p, const void* rows, const void* prior, int64_t n_ch
                            freq_threshold, std::min(half_width, p->nchan), iters, static_cast<float*>(weights), counts);
 }
 
-int fxc_solve_gains_weighted(fxc_plan* p, const void* rows, const void* weights, int64_t n_chunks, int mem_kind, const void* model,
-                             int64_t n_model, int64_t interval, int ref, int iters, double* gains_re_im, double* step) {
+// The argument checks of both gain solves, in the order that gives each call its code and message; the plain call has no model.
+// Sets an interval of 0 or beyond the chunks to all of them.
+static int check_solve_gains(fxc_plan* p, const void* rows, int64_t n_chunks, int mem_kind, const void* model, int64_t n_model,
+                             int64_t* interval, int ref, int iters, const double* gains_re_im) {
     if (!p || !rows || !gains_re_im) return fail(p, FXC_ERR_ARG, "NULL argument");
     if (n_chunks < 1) return fail(p, FXC_ERR_ARG, "n_chunks=%lld: a gain solve needs 1 or more chunks", (long long)n_chunks);
-    if (interval < 0) return fail(p, FXC_ERR_ARG, "interval=%lld is negative", (long long)interval);
+    if (*interval < 0) return fail(p, FXC_ERR_ARG, "interval=%lld is negative", (long long)*interval);
     if (ref < 0 || ref >= p->n_ant) return fail(p, FXC_ERR_ARG, "ref=%d outside [0, %d)", ref, p->n_ant);
     if (iters < 1 || iters > 1000) return fail(p, FXC_ERR_ARG, "iters=%d outside 1 .. 1000", iters);
     if (mem_kind != FXC_MEM_HOST && mem_kind != FXC_MEM_DEVICE) return fail(p, FXC_ERR_ARG, "bad mem_kind %d", mem_kind);
-    if (interval == 0 || interval > n_chunks) interval = n_chunks;
-    const int64_t n_int = (n_chunks + interval - 1) / interval;
+    if (*interval == 0 || *interval > n_chunks) *interval = n_chunks;
+    const int64_t n_int = (n_chunks + *interval - 1) / *interval;
     if ((model == nullptr) != (n_model == 0)) return fail(p, FXC_ERR_ARG, "model and n_model=%lld disagree", (long long)n_model);
     if (model && n_model != 1 && n_model != n_int)
         return fail(p, FXC_ERR_ARG, "n_model=%lld is neither 1 nor the number of intervals %lld", (long long)n_model, (long long)n_int);
@@ -1596,22 +1550,21 @@ int fxc_solve_gains_weighted(fxc_plan* p, const void* rows, const void* weights,
         for (int64_t i = 0; i < n; ++i)
             if (!std::isfinite(m[i])) return fail(p, FXC_ERR_ARG, "model value %lld is not finite", (long long)(i / 2));
     }
-    return solve_gains_weighted_batch(p, static_cast<const cf*>(rows), static_cast<const float*>(weights), n_chunks, mem_kind,
-                                      static_cast<const cf*>(model), n_model, interval, ref, iters, gains_re_im, step);
+    return FXC_OK;
+}
+
+int fxc_solve_gains_weighted(fxc_plan* p, const void* rows, const void* weights, int64_t n_chunks, int mem_kind, const void* model,
+                             int64_t n_model, int64_t interval, int ref, int iters, double* gains_re_im, double* step) {
+    if (int rc = check_solve_gains(p, rows, n_chunks, mem_kind, model, n_model, &interval, ref, iters, gains_re_im)) return rc;
+    return solve_gains_batch(p, true, static_cast<const cf*>(rows), static_cast<const float*>(weights), n_chunks, mem_kind,
+                             static_cast<const cf*>(model), n_model, interval, ref, iters, gains_re_im, step);
 }
 
 int fxc_solve_gains(fxc_plan* p, const void* rows, int64_t n_chunks, int mem_kind, int64_t interval, int ref, int iters,
                     double* gains_re_im, double* step) {
-    if (!p || !rows || !gains_re_im) return fail(p, FXC_ERR_ARG, "NULL argument");
-    if (n_chunks < 1) return fail(p, FXC_ERR_ARG, "n_chunks=%lld: a gain solve needs 1 or more chunks", (long long)n_chunks);
-    if (interval < 0) return fail(p, FXC_ERR_ARG, "interval=%lld is negative", (long long)interval);
-    if (ref < 0 || ref >= p->n_ant) return fail(p, FXC_ERR_ARG, "ref=%d outside [0, %d)", ref, p->n_ant);
-    if (iters < 1 || iters > 1000) return fail(p, FXC_ERR_ARG, "iters=%d outside 1 .. 1000", iters);
-    if (mem_kind != FXC_MEM_HOST && mem_kind != FXC_MEM_DEVICE) return fail(p, FXC_ERR_ARG, "bad mem_kind %d", mem_kind);
-    if (p->n_ant < 3)
-        return fail(p, FXC_ERR_UNSUPPORTED, "a gain solve needs 3 or more antennas, the plan has %d: one baseline closes nothing", p->n_ant);
-    if (interval == 0 || interval > n_chunks) interval = n_chunks;
-    return solve_gains_batch(p, static_cast<const cf*>(rows), n_chunks, mem_kind, interval, ref, iters, gains_re_im, step);
+    if (int rc = check_solve_gains(p, rows, n_chunks, mem_kind, nullptr, 0, &interval, ref, iters, gains_re_im)) return rc;
+    return solve_gains_batch(p, false, static_cast<const cf*>(rows), nullptr, n_chunks, mem_kind, nullptr, 0, interval, ref, iters,
+                             gains_re_im, step);
 }
 
 int fxc_pipe_destroy(fxc_pipe* q) {

@@ -636,12 +636,9 @@ class FxPlan(object):
         self._check(self._lib.fxc_estimate_delays(self._h, ptr, int(keep.shape[1]), kind, float(rate), int(ref), out.ctypes.data))
         return out
 
-    def fringe_fit(self, rows, bandwidth, frequency, ref=0, pad=2):
-        """Residual delay and delay rate of every antenna against antenna ``ref`` from SPECTRUM rows (fxcorr.h fxc_fringe_fit):
-        ``rows`` = [n_chunks, n_rows, nchan] complex64 as ``fx_rows(x)`` returns them (numpy, or a CUDA tensor on the plan's
-        device) -> (delays_s, rates_s_per_chunk, snr), float64 [n_ant] each, entry ``ref`` 0.  Added to what
-        ``set_delay_track`` was given they stop the fringes."""
-        self._sync_stream()
+    def _rows_in(self, rows, allow_2d):
+        """SPECTRUM rows as a call takes them -> (keep, ptr, mem_kind, shape): ``keep`` = the contiguous complex64 array ``ptr``
+        points into, ``shape`` = its (n_chunks, n_rows, nchan); with ``allow_2d`` a 2-D [n_rows, nchan] array is one chunk."""
         if _is_torch(rows):
             import torch
             if rows.dtype != torch.complex64 or not rows.is_cuda or rows.device.index != self.device:
@@ -652,8 +649,32 @@ class FxPlan(object):
             keep = np.ascontiguousarray(rows, dtype=np.complex64)
             ptr, kind = keep.ctypes.data, _lib.FXC_MEM_HOST
         shape = tuple(keep.shape)
-        if len(shape) != 3 or shape[1:] != (self.n_rows, self.nchan):
-            raise ValueError("rows must have shape (n_chunks, {}, {}), got {}".format(self.n_rows, self.nchan, shape))
+        if allow_2d and len(shape) == 2:
+            shape = (1,) + shape
+        if len(shape) != 3 or (allow_2d and shape[0] < 1) or shape[1:] != (self.n_rows, self.nchan):
+            raise ValueError("rows must have shape (n_chunks, {}, {}), got {}".format(self.n_rows, self.nchan, tuple(keep.shape)))
+        return keep, ptr, kind, shape
+
+    def _like_rows(self, x, name, device):
+        """float32 ``x`` (``weights``, ``prior``) in the memory of rows -> (keep, ptr)"""
+        if _is_torch(x) != device:
+            raise ValueError("{} must be in the memory of rows: a CUDA tensor for device rows, numpy for host rows".format(name))
+        if device:
+            import torch
+            if x.dtype != torch.float32 or not x.is_cuda or x.device.index != self.device:
+                raise ValueError("device {} must be a float32 CUDA tensor on device {}".format(name, self.device))
+            keep = x.contiguous()
+            return keep, keep.data_ptr()
+        keep = np.ascontiguousarray(x, dtype=np.float32)
+        return keep, keep.ctypes.data
+
+    def fringe_fit(self, rows, bandwidth, frequency, ref=0, pad=2):
+        """Residual delay and delay rate of every antenna against antenna ``ref`` from SPECTRUM rows (fxcorr.h fxc_fringe_fit):
+        ``rows`` = [n_chunks, n_rows, nchan] complex64 as ``fx_rows(x)`` returns them (numpy, or a CUDA tensor on the plan's
+        device) -> (delays_s, rates_s_per_chunk, snr), float64 [n_ant] each, entry ``ref`` 0.  Added to what
+        ``set_delay_track`` was given they stop the fringes."""
+        self._sync_stream()
+        keep, ptr, kind, shape = self._rows_in(rows, allow_2d=False)
         delays = np.zeros(self.n_ant, dtype=np.float64)
         rates = np.zeros(self.n_ant, dtype=np.float64)
         snr = np.zeros(self.n_ant, dtype=np.float64)
@@ -675,20 +696,7 @@ class FxPlan(object):
         visibilities, anything numpy casts to complex64, [n_baselines, nchan] or [n_int, n_baselines, nchan] (for instance
         ``offset_source_model``)."""
         self._sync_stream()
-        if _is_torch(rows):
-            import torch
-            if rows.dtype != torch.complex64 or not rows.is_cuda or rows.device.index != self.device:
-                raise ValueError("device input must be a complex64 CUDA tensor on device {}".format(self.device))
-            keep = rows.contiguous()
-            ptr, kind = keep.data_ptr(), _lib.FXC_MEM_DEVICE
-        else:
-            keep = np.ascontiguousarray(rows, dtype=np.complex64)
-            ptr, kind = keep.ctypes.data, _lib.FXC_MEM_HOST
-        shape = tuple(keep.shape)
-        if len(shape) == 2:
-            shape = (1,) + shape
-        if len(shape) != 3 or shape[0] < 1 or shape[1:] != (self.n_rows, self.nchan):
-            raise ValueError("rows must have shape (n_chunks, {}, {}), got {}".format(self.n_rows, self.nchan, tuple(keep.shape)))
+        keep, ptr, kind, shape = self._rows_in(rows, allow_2d=True)
         interval = int(interval)
         span = min(interval, shape[0]) if interval > 0 else shape[0]
         n_int = -(-shape[0] // span)
@@ -700,17 +708,7 @@ class FxPlan(object):
             return gains, step
         w_keep, w_ptr = None, None
         if weights is not None:
-            if _is_torch(weights) != (kind == _lib.FXC_MEM_DEVICE):
-                raise ValueError("weights must be in the memory of rows: a CUDA tensor for device rows, numpy for host rows")
-            if kind == _lib.FXC_MEM_DEVICE:
-                import torch
-                if weights.dtype != torch.float32 or not weights.is_cuda or weights.device.index != self.device:
-                    raise ValueError("device weights must be a float32 CUDA tensor on device {}".format(self.device))
-                w_keep = weights.contiguous()
-                w_ptr = w_keep.data_ptr()
-            else:
-                w_keep = np.ascontiguousarray(weights, dtype=np.float32)
-                w_ptr = w_keep.ctypes.data
+            w_keep, w_ptr = self._like_rows(weights, "weights", kind == _lib.FXC_MEM_DEVICE)
             w_shape = tuple(w_keep.shape)
             if len(w_shape) == 2 and len(tuple(keep.shape)) == 2:
                 w_shape = (1,) + w_shape
@@ -743,41 +741,20 @@ class FxPlan(object):
         keeps its prior.  With ``return_counts`` -> (weights, counts [n_win, n_baselines, 3] int64: not live at the start,
         flagged in time, flagged in frequency)."""
         self._sync_stream()
-        device = _is_torch(rows)
-        if device:
-            import torch
-            if rows.dtype != torch.complex64 or not rows.is_cuda or rows.device.index != self.device:
-                raise ValueError("device input must be a complex64 CUDA tensor on device {}".format(self.device))
-            keep = rows.contiguous()
-            ptr, kind = keep.data_ptr(), _lib.FXC_MEM_DEVICE
-        else:
-            keep = np.ascontiguousarray(rows, dtype=np.complex64)
-            ptr, kind = keep.ctypes.data, _lib.FXC_MEM_HOST
-        shape = tuple(keep.shape)
-        one = len(shape) == 2
-        if one:
-            shape = (1,) + shape
-        if len(shape) != 3 or shape[0] < 1 or shape[1:] != (self.n_rows, self.nchan):
-            raise ValueError("rows must have shape (n_chunks, {}, {}), got {}".format(self.n_rows, self.nchan, tuple(keep.shape)))
+        keep, ptr, kind, shape = self._rows_in(rows, allow_2d=True)
+        device = kind == _lib.FXC_MEM_DEVICE
+        one = keep.ndim == 2
         w_shape = (shape[0], self.n_baselines, self.nchan)
         p_keep, p_ptr = None, None
         if prior is not None:
-            if _is_torch(prior) != device:
-                raise ValueError("prior must be in the memory of rows: a CUDA tensor for device rows, numpy for host rows")
-            if device:
-                if prior.dtype != torch.float32 or not prior.is_cuda or prior.device.index != self.device:
-                    raise ValueError("device prior must be a float32 CUDA tensor on device {}".format(self.device))
-                p_keep = prior.contiguous()
-                p_ptr = p_keep.data_ptr()
-            else:
-                p_keep = np.ascontiguousarray(prior, dtype=np.float32)
-                p_ptr = p_keep.ctypes.data
+            p_keep, p_ptr = self._like_rows(prior, "prior", device)
             if tuple(p_keep.shape) != (w_shape[1:] if one else w_shape):
                 raise ValueError("prior must have shape {}, got {}".format(w_shape[1:] if one else w_shape, tuple(p_keep.shape)))
         window = int(window)
         span = min(window, shape[0]) if window > 0 else shape[0]
         counts = np.zeros((-(-shape[0] // span), self.n_baselines, 3), dtype=np.int64)
         if device:
+            import torch
             weights = torch.empty(w_shape, dtype=torch.float32, device=keep.device)      # the call writes every element
             w_ptr = weights.data_ptr()
             if not self._follow:      # a stream of the plan's own: torch's may still be using the block it handed out

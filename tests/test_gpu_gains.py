@@ -100,6 +100,45 @@ def test_solve_gains_matches_the_restatement(plan_mod, torch, n_ant, nchan):
         assert f["gain_rel"] <= bound_g and f["step_abs"] <= bound_s, (f, bound_g, bound_s)
 
 
+# antenna counts that are no power of two times a tile: tiles of 8, 4 and 4 bins, the workgroup's last wave partly idle
+ODD_ANTENNAS = [(17, 64), (33, 64), (55, 64)]
+# 31 chunks are every block of the average's walk: 16 + 8 + 4 + 2 + 1 with 16-byte loads (an even channel count; 1000 channels
+# leave the last tile partial), 3 x 8 + 4 + 2 + 1 with 8-byte loads (an odd one)
+LONG_CHUNKS = 31
+LONG = [(8, 1000), (5, 63)]
+
+
+def ceiling_case(plan_mod, torch, n_ant, nchan, n_chunks, refs, iters):
+    """intervals 0 and 5, host and device rows against gains_ref.solve_rows under CEIL_PARITY, and the two against each other
+    bit for bit"""
+    rng = np.random.default_rng(1000 * n_chunks + 100 * n_ant + nchan)
+    rows = gains_ref.model_rows(gains_ref.draw_gains(n_ant, nchan, rng), n_chunks, rng, sigma=SIGMA)
+    rows_dev = torch.from_numpy(rows).cuda()
+    with plan_mod.FxPlan(n_ant, nchan, 4, nchan * 8) as plan:
+        for interval in (0, 5):
+            for ref in refs:
+                want_g, want_s = gains_ref.solve_rows(rows, n_ant, interval=interval, ref=ref, iters=iters)
+                got = [plan.solve_gains(data, interval=interval, ref=ref, iters=iters) for data in (rows, rows_dev)]
+                for kind, (g, s) in zip(("host", "device"), got):
+                    assert g.shape == want_g.shape and s.shape == want_s.shape
+                    gain_rel = float(np.abs(g - want_g).max() / np.abs(want_g).max())
+                    step_abs = float(np.abs(s - want_s).max())
+                    print(json.dumps({"n_ant": n_ant, "nchan": nchan, "n_chunks": n_chunks, "interval": interval, "ref": ref,
+                                      "input": kind, "gain_rel": gain_rel, "step_abs": step_abs}))
+                    assert gain_rel <= CEIL_PARITY and step_abs <= CEIL_PARITY, (kind, interval, ref, gain_rel, step_abs)
+                assert same_bits(got[0][0], got[1][0]) and same_bits(got[0][1], got[1][1]), (interval, ref)
+
+
+@pytest.mark.parametrize("n_ant,nchan", ODD_ANTENNAS)
+def test_antenna_counts_that_leave_a_wave_partly_idle(plan_mod, torch, n_ant, nchan):
+    ceiling_case(plan_mod, torch, n_ant, nchan, N_CHUNKS, (0, n_ant // 2), 30)
+
+
+@pytest.mark.parametrize("n_ant,nchan", LONG)
+def test_every_block_of_the_average_walk(plan_mod, torch, n_ant, nchan):
+    ceiling_case(plan_mod, torch, n_ant, nchan, LONG_CHUNKS, (n_ant // 2,), 30)
+
+
 def test_odd_channel_counts_and_one_chunk(plan_mod, torch):
     """an odd channel count takes the 8-byte loads; a 2-D array is one chunk; a zero bin gives zero gains and step"""
     n_ant, nchan = 5, 63
