@@ -5,6 +5,7 @@
 //            held in VGPRs (every IQ sample is fetched from HBM exactly once; the frame loop is
 //            unrolled by four so the ring rotates by renaming, not by moves),
 //            radix-16 over r, twiddle w4096^(j*k1), exchange 1 through LDS        [s_barrier]
+//            (hardware thread t of an antenna owns branch set j = branch_of_thread(t), not t: see "exchanges" below)
 //   phase 2  (lane = antenna, k1, j0):  radix-16 over j1, twiddle w256^(j0*q1), exchange 2 —
 //            a 16x16 transpose that stays inside one wave (no s_barrier)
 //   phase 3  (lane = antenna, k1, q1):  radix-16 over j0 -> bins k = k1 + 16 q1 + 256 q2;
@@ -13,6 +14,15 @@
 // FFT decomposition (kernel exp(+2 pi i m k / 4096)):
 //   m = j + 256 r,  j = j0 + 16 j1,  k = k1 + 16 q1 + 256 q2
 //   w^(mk) = w16^(r k1) * w4096^(j k1) * w16^(j1 q1) * w256^(j0 q1) * w16^(j0 q2)
+//
+// Exchanges: both go through component planes of the region -- dwords [antenna][re, im][k1 row of kPlaneRow] -- and are
+// stored with ds_write_addtid_b32 (LDS address = M0 + immediate + 4 * lane: no address register, 2 cycles of the
+// register-to-LDS path per 4 bytes where ds_write_b64 takes 6 per 8 and ds_write2_b64 13 per 16).  A lane-addressed store
+// puts a wave's 64 values side by side, so the map of phase 1 is chosen such that side by side is where phase 2 wants them:
+// lane bit 0 carries bit 4 of j, and the two points j1 = 2u, 2u + 1 of a phase-2 lane are one ds_read_b64 of a plane.
+// Exchange 2 (a 16x16 transpose inside every 16-lane group) needs no such map: its two points j0 = 2u, 2u + 1 are
+// neighbouring lanes already.  The functions below keep taking the *logical* thread id (antenna << 8) | j for phase 1
+// and the hardware thread id for phases 2 and 3; under g++ a store writes the dword the hardware lane would.
 //
 // The same source is compiled by g++ in tests/emul (host emulation of the index logic; test
 // infrastructure only — the shipped library contains only the device build).
@@ -46,8 +56,10 @@ FX_HD cf lds_load(const cf* p) {
 constexpr int kN = 4096;
 constexpr int kT = 4;
 constexpr int kThreads = 512;
-constexpr int kRowPitch = 272;              // cf per k1 row; == 16 (mod 32) keeps ds_read_b64 conflict-free
-constexpr int kRegion = 16 * kRowPitch;     // cf per antenna
+constexpr int kPlaneRow = 288;              // dwords per k1 row of a plane: 256 columns + 32; == 32 (mod 64) keeps ds_read_b64 conflict-free
+constexpr int kPlane = 16 * kPlaneRow;      // dwords per component plane
+constexpr int kAntPlanes = 2 * kPlane;      // dwords per antenna: re plane, im plane
+constexpr int kRegionBytes = 2 * kAntPlanes * 4;
 constexpr int kAccPerThread = 8;
 #ifndef FXC_FIR_GROUP
 #define FXC_FIR_GROUP 4
@@ -55,10 +67,76 @@ constexpr int kAccPerThread = 8;
 constexpr int kFirGroup = FXC_FIR_GROUP;    // branches per software-pipeline group of the FIR's window reads
 
 // LDS carve (bytes); every offset is a multiple of 16
-constexpr int kLdsWin = 0;                                   // f4[4096]   window, [r*256 + j] = h[t*N + j + 256 r], t = x,y,z,w
-constexpr int kLdsRegion = kLdsWin + kN * 16;                // cf[2][kRegion]
-constexpr int kLdsTw2 = kLdsRegion + 2 * kRegion * 8;        // cf[256]    w256^(j0*q1) at [q1*16 + j0]
+// (the region comes first: the base of a lane-addressed store is the 16-bit M0 offset, so it has to lie below 64 KiB --
+// also behind the 20 KiB of static LDS of the DCK variant)
+constexpr int kLdsRegion = 0;                                // float[2][2][kPlane]
+constexpr int kLdsWin = kLdsRegion + kRegionBytes;           // f4[4096]   window, [r*256 + col] = h[t*N + j + 256 r], t = x,y,z,w;
+                                                             //            col = j for the header's own callers, the hardware thread in the kernel
+constexpr int kLdsTw2 = kLdsWin + kN * 16;                   // cf[256]    w256^(j0*q1) at [q1*16 + j0]
 constexpr int kLdsBytes = kLdsTw2 + 256 * 8;
+
+// phase 1: hardware thread t (0..255 within its antenna; lane l = t & 63, wave wv = t >> 6) <-> branch set j
+FX_HD int branch_of_thread(int t) {
+    const int l = t & 63, wv = (t >> 6) & 3;
+    return ((l >> 1) & 15) + 16 * ((l & 1) | ((l >> 5) << 1) | (wv << 2));
+}
+FX_HD int thread_of_branch(int j) { return ((j >> 4) & 1) | ((j & 15) << 1) | (j & 0xE0); }
+
+// Lane-addressed stores of one wave: dword `base_dw + DW + lane` of the region.  Device: base in M0 (written once; an SALU
+// write of M0 needs a wait state before such a store reads it, and the compiler does not look inside the asm), one
+// ds_write_addtid_b32 per call.  The compiler does not count these stores: lane_store_end() waits for them (uncounted LDS
+// operations in the queue only make the compiler's own lgkmcnt waits stricter: LDS operations return in order).
+struct LaneStore {
+#if defined(__HIP_DEVICE_COMPILE__)
+    unsigned m0;
+#else
+    float* at;
+#endif
+};
+
+FX_HD LaneStore lane_store_begin(cf* region, int base_dw, int lane) {
+    LaneStore ls;
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef __attribute__((address_space(3))) cf* lptr_t;
+    (void)lane;
+    ls.m0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lptr_t)region + 4u * (unsigned)base_dw);
+    asm volatile("s_nop 0" : : "{m0}"(ls.m0));
+#else
+    ls.at = reinterpret_cast<float*>(region) + base_dw + lane;
+#endif
+    return ls;
+}
+
+template <int DW>
+FX_HD void lane_store(const LaneStore& ls, float val) {
+    static_assert(DW >= 0 && 4 * DW < 65536, "16-bit immediate");
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("ds_write_addtid_b32 %0 offset:%1" : : "v"(val), "n"(4 * DW), "{m0}"(ls.m0));
+#else
+    ls.at[DW] = val;
+#endif
+}
+
+FX_HD void lane_store_end() {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("s_waitcnt lgkmcnt(0)" : : : "memory");
+#endif
+}
+
+// dft16_b_stream (fx_math.h) with the output index as a type, for the stores' immediates
+template <int K>
+struct KConst { static constexpr int value = K; };
+template <class Sink>
+FX_HD void dft16_b_stream_ct(cf (&v)[16], Sink&& sink) {
+    dft4(v[0], v[1], v[2], v[3]);
+    sink(KConst<0>{}, v[0]); sink(KConst<4>{}, v[1]); sink(KConst<8>{}, v[2]); sink(KConst<12>{}, v[3]);
+    dft4_scaled_c_bd(v[4], v[5], v[6], v[7]);
+    sink(KConst<1>{}, v[4]); sink(KConst<5>{}, v[5]); sink(KConst<9>{}, v[6]); sink(KConst<13>{}, v[7]);
+    dft4_bd_scaled(v[8], v[9], v[10], v[11]);
+    sink(KConst<2>{}, v[8]); sink(KConst<6>{}, v[9]); sink(KConst<10>{}, v[10]); sink(KConst<14>{}, v[11]);
+    dft4_scaled_c_bd(v[12], v[13], v[14], v[15]);
+    sink(KConst<3>{}, v[12]); sink(KConst<7>{}, v[13]); sink(KConst<11>{}, v[14]); sink(KConst<15>{}, v[15]);
+}
 
 struct State {
     // ring of four frames of this thread's 16 branch samples: slot PH holds the frame being
@@ -209,9 +287,10 @@ FX_HD int sample_offset(int j, int r) { return (kN - 1) - j - 256 * r; }
 // phase 1a for a frame in ring slot PH: 4-tap FIR (taps t = 0..3 on frames i, i-1, i-2, i-3, summed
 // in that order); result left in v[r]
 // G: branches per group (the kernel's AUTOS variant takes 2: 16 VGPRs fewer quads in flight, for its power sums)
+// col: this thread's column of the window table (see kLdsWin)
 template <int PH, int G = kFirGroup>
-FX_HD void phase1_fir(const State& s, const f4* win, int tid, cf (&v)[16]) {
-    const int j = tid & 255;
+FX_HD void phase1_fir_col(const State& s, const f4* win, int col, cf (&v)[16]) {
+    const int j = col;
     const cf (&x0)[16] = s.h[PH];
     const cf (&x1)[16] = s.h[(PH + 3) & 3];
     const cf (&x2)[16] = s.h[(PH + 2) & 3];
@@ -243,8 +322,13 @@ FX_HD void phase1_fir(const State& s, const f4* win, int tid, cf (&v)[16]) {
     }
 }
 
+template <int PH, int G = kFirGroup>
+FX_HD void phase1_fir(const State& s, const f4* win, int tid, cf (&v)[16]) {
+    phase1_fir_col<PH, G>(s, win, tid & 255, v);
+}
+
 // phase 1b: the second half of the radix-16 over r (dft16_b) with each output twiddled by w4096^(j*k1) and stored to
-// exchange 1 as soon as it exists -- the stores are bound by the LDS write path (64 KiB at ~85 B/clk per CU), and the
+// exchange 1 as soon as it exists -- the stores are bound by the register-to-LDS path (64 KiB at ~128 B/clk per CU), and the
 // 72 + 60 vector instructions of the butterflies and twiddles run in its shadow instead of in front of barrier B0.
 // Call after dft16_a(v).
 // LEAN_TW (the kernel's AUTOS variant): of the fifteen twiddles only w4096^(j k1) for k1 = 1, 2, 4, 8 live in registers across
@@ -264,9 +348,11 @@ FX_HD cf tw1_of(const cf (&pw2)[4], int k1) {
     return w;
 }
 
+// tid: the logical id (antenna << 8) | j.  Wave wv of antenna h stores at columns 64 wv .. 64 wv + 63 of every row of h's planes
 template <bool LEAN_TW = false>
 FX_HD void phase1_finish_store(const State& s, cf (&v)[16], cf* region, int tid) {
-    cf* mine = region + (tid >> 8) * kRegion + (tid & 255);
+    const int t = thread_of_branch(tid & 255);
+    const LaneStore ls = lane_store_begin(region, (tid >> 8) * kAntPlanes + (t & 0xC0), t & 63);
     cf pw2[4] = {s.tw1[1], s.tw1[2], s.tw1[4], s.tw1[8]};
 #if defined(__HIP_DEVICE_COMPILE__)
     if (LEAN_TW) {
@@ -274,10 +360,13 @@ FX_HD void phase1_finish_store(const State& s, cf (&v)[16], cf* region, int tid)
         for (int b = 0; b < 4; ++b) asm volatile("" : "+v"(pw2[b].x), "+v"(pw2[b].y));
     }
 #endif
-    dft16_b_stream(v, [&](int k1, cf val) {
+    dft16_b_stream_ct(v, [&](auto k, cf val) {
+        constexpr int k1 = decltype(k)::value;
         if (k1 > 0) val = cmul(val, LEAN_TW ? tw1_of(pw2, k1) : s.tw1[k1]);
-        mine[k1 * kRowPitch] = val;
+        lane_store<k1 * kPlaneRow>(ls, val.x);
+        lane_store<kPlane + k1 * kPlaneRow>(ls, val.y);
     });
+    lane_store_end();
 }
 
 // load this thread's twiddles from the [16][256] table w4096^(j*k1)
@@ -287,18 +376,19 @@ FX_HD void state_load_twiddles(State& s, const cf* tw1_table, int tid) {
     for (int k1 = 0; k1 < 16; ++k1) s.tw1[k1] = tw1_table[k1 * 256 + j];
 }
 
-// this lane's row for phases 2 and 3
-FX_HD cf* lane_row(cf* region, int tid) {
-    const int l = tid & 63, wave = tid >> 6;
-    const int ant = l >> 5, k1 = 2 * wave + ((l >> 4) & 1);
-    return region + ant * kRegion + k1 * kRowPitch;
-}
-
+// phase 2, lane = (antenna, k1, j0): the points j1 = 2u, 2u + 1 sit side by side in row k1 of the antenna's planes
+// (columns 32 u + 2 j0 + {0, 1}: the hardware threads whose branch sets are j0 + 16 j1)
 FX_HD void phase2_load(cf* region, int tid, cf (&v)[16]) {
-    const cf* row = lane_row(region, tid);
-    const int j0 = tid & 15;
+    const int l = tid & 63, wave = tid >> 6;
+    const int ant = l >> 5, k1 = 2 * wave + ((l >> 4) & 1), j0 = l & 15;
+    const float* row = reinterpret_cast<const float*>(region) + ant * kAntPlanes + k1 * kPlaneRow + 2 * j0;
 #pragma unroll
-    for (int j1 = 0; j1 < 16; ++j1) v[j1] = lds_load(row + j0 + 16 * j1);
+    for (int u = 0; u < 8; ++u) {
+        const cf re = lds_load(reinterpret_cast<const cf*>(row + 32 * u));
+        const cf im = lds_load(reinterpret_cast<const cf*>(row + kPlane + 32 * u));
+        v[2 * u] = mk(re.x, im.x);
+        v[2 * u + 1] = mk(re.y, im.y);
+    }
 }
 
 FX_HD void phase2_twiddle(cf (&v)[16], const cf* tw2, int tid) {
@@ -323,18 +413,38 @@ FX_HD void phase2_twiddle(cf (&v)[16], const cf* tw2, int tid) {
     }
 }
 
-FX_HD void phase2_store(const cf (&v)[16], cf* region, int tid) {
-    cf* row = lane_row(region, tid);
-    const int j0 = tid & 15;
-#pragma unroll
-    for (int q1 = 0; q1 < 16; ++q1) row[q1 * 17 + j0] = v[q1];
+// Exchange 2, wave-local: wave w reuses rows 2 w, 2 w + 1 of the four planes -- the rows its own phase 2 read, nobody
+// else's.  Component c of register q1 goes to stripe stripe_of(q1) + c * kAntPlanes of the wave's area, a stripe being the
+// wave's 64 lanes side by side: the real parts of q1 = 0..7 lie 66 dwords apart in what was antenna 0's re plane, those of
+// q1 = 8..15 in its im plane, 32 dwords further on (so that the 32 lanes of a half-wave read 64 distinct banks), the
+// imaginary parts the same in antenna 1's planes
+constexpr int kStripeHi = kPlane + 32;
+constexpr int stripe_of(int q1) { return (q1 >> 3) * kStripeHi + (q1 & 7) * 66; }
+
+template <int Q1>
+FX_HD void phase2_store_from(const LaneStore& ls, const cf (&v)[16]) {
+    lane_store<stripe_of(Q1)>(ls, v[Q1].x);
+    lane_store<stripe_of(Q1) + kAntPlanes>(ls, v[Q1].y);
+    if constexpr (Q1 < 15) phase2_store_from<Q1 + 1>(ls, v);
 }
 
+FX_HD void phase2_store(const cf (&v)[16], cf* region, int tid) {
+    const LaneStore ls = lane_store_begin(region, (tid >> 6) * 2 * kPlaneRow, tid & 63);
+    phase2_store_from<0>(ls, v);
+    lane_store_end();
+}
+
+// phase 3, lane = (antenna, k1, q1): the points j0 = 2u, 2u + 1 of its 16-lane group, side by side in stripe q1
 FX_HD void phase3_load(cf* region, int tid, cf (&v)[16]) {
-    const cf* row = lane_row(region, tid);
-    const int q1 = tid & 15;
+    const int l = tid & 63, wave = tid >> 6, q1 = l & 15;
+    const float* row = reinterpret_cast<const float*>(region) + wave * 2 * kPlaneRow + stripe_of(q1) + (l >> 4) * 16;
 #pragma unroll
-    for (int j0 = 0; j0 < 16; ++j0) v[j0] = lds_load(row + q1 * 17 + j0);
+    for (int u = 0; u < 8; ++u) {
+        const cf re = lds_load(reinterpret_cast<const cf*>(row + 2 * u));
+        const cf im = lds_load(reinterpret_cast<const cf*>(row + kAntPlanes + 2 * u));
+        v[2 * u] = mk(re.x, im.x);
+        v[2 * u + 1] = mk(re.y, im.y);
+    }
 }
 
 // X-stage on paired data: a = antenna 0, b = antenna 1 for this lane's bin q (lanes 0-31) or

@@ -257,7 +257,7 @@ __device__ __forceinline__ void fused_step(fxc::fused::State& s, float (&pw)[fxc
     const unsigned char* dck_base = reinterpret_cast<const unsigned char*>(x) + (int64_t)(c + (dck_next ? 1 + pos.seg_jump : 0)) * 4 * num_samp;
     if (U8) convert_frame_u8(s.h[PH], u8.off);   // the byte pairs fetched a step ago become the samples of slot PH
     cf v[16];
-    phase1_fir<PH, AUTOS ? 2 : kFirGroup>(s, win, tid, v);      // first use of this frame: waits for its loads (issued a step ago)
+    phase1_fir_col<PH, AUTOS ? 2 : kFirGroup>(s, win, tid & 255, v);      // (window in hardware-thread order) first use of this frame: waits for its loads (issued a step ago)
     FXC_STAMP(2);
     // The oldest ring slot is dead now: refill it with the next frame of this workgroup's range (next frame of
     // the chunk, or frame 0 of the next chunk; at the very end the current frame again, never used).  The 16
@@ -279,7 +279,8 @@ __device__ __forceinline__ void fused_step(fxc::fused::State& s, float (&pw)[fxc
     // second half of the radix-16 with the twiddle w4096^(j k1) and the exchange-1 store of every output as it forms:
     // the stores are bound by the LDS write path, the butterflies and twiddles run in its shadow (B0 in front of the
     // whole radix-16 instead: +7 %; exchange 2 streamed the same way: spills, +6 %)
-    phase1_finish_store<AUTOS>(s, v, region, tid);
+    // (lane-addressed stores: the store takes the logical id (antenna << 8) | j for the wave's base alone)
+    phase1_finish_store<AUTOS>(s, v, region, (tid & ~255) | branch_of_thread(tid & 255));
 #endif
     FXC_STAMP(5);
 #if !(FXC_ABL & 2)
@@ -416,11 +417,13 @@ __global__ __launch_bounds__(fxc::fused::kThreads, 2) void fx_fused4096_kernel(
     cf* tw2 = reinterpret_cast<cf*>(smem + kLdsTw2);
 
     const int tid = threadIdx.x;
-    const int ant = tid >> 8, j = tid & 255;
-    for (int idx = tid; idx < kN; idx += kThreads) win[idx] = win_g[idx];
+    // phase 1: this hardware thread owns branch set j (fx_fused4096.h "exchanges"); the window's columns are laid out in
+    // hardware-thread order, so that a wave's 16-byte window reads stay 1 KiB in a row
+    const int ant = tid >> 8, j = branch_of_thread(tid & 255);
+    for (int idx = tid; idx < kN; idx += kThreads) win[idx] = win_g[(idx & ~255) | branch_of_thread(idx & 255)];
     if (tid < 256) tw2[tid] = tw2_g[tid];
     State s;
-    state_load_twiddles(s, tw1_g, tid);
+    state_load_twiddles(s, tw1_g, (ant << 8) | j);
 #pragma unroll
     for (int q = 0; q < kAccPerThread; ++q) s.acc[q] = fxc::mk(0.f, 0.f);
     static_assert(!AUTOS || (!SPEC_OUT && !U8), "autos: the complex64 F+X variant only");
