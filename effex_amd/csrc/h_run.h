@@ -1,10 +1,13 @@
 // Part of libfxcorr's single translation unit: included by fxcorr.hip (not a stand-alone header).
 #pragma once
 
+// what a call runs: fx_rows_dev and fx_accumulate_dev go through one route ladder (fx_routes), which hands every pass's raw rows
+// to the call's consumer -- the rows kernels (launch_rows) or the fold into the accumulator (h_launch.h)
+
 namespace {
 
-// ---- plans with autos (fxcorr.h, FXC_PRODUCTS_CROSS_AUTO) ---------------------------------------------------------------
-// Every shape takes one route: the plan's F stage alone -- run_channelize, what fxc_channelize runs (the tiled, wave-local,
+// ---- plans with autos (fxcorr.h, FXC_PRODUCTS_CROSS_AUTO): the first route of fx_routes -----------------------------------
+// Every shape but the fused kernel's own (fused_autos) takes it: the plan's F stage alone -- run_channelize, what fxc_channelize runs (the tiled, wave-local,
 // per-channel-count, mixed-radix or generic F kernel of the shape) -- writes a pass of chunks' spectra to the workspace as
 // [chunk][antenna][frame][nchan] in natural bin order, then xengine_kernel<A, true> reads every spectrum once and writes raw rows
 // [n_prod][nchan]: the n_base cross rows, then the A auto rows.  A raw row is a float32 sum of at most kRowSpectra spectra: up
@@ -68,175 +71,9 @@ bool fused_autos(const fxc_plan* p, int64_t n_chunks) {
     return p->autos && p->path == FXC_PATH_FUSED && p->n_ant == 2 && !use_tiled(p, n_chunks);
 }
 
-int autos_accumulate_dev(fxc_plan* p, const cf* x, int64_t n_chunks) {
-    const AutoPass a = autos_pass(p, n_chunks, false);
-    int rc = ensure_ws(p, a.spec_bytes + a.raw_bytes + fold_part_bytes(p));
-    if (rc) return rc;
-    cf* spec = reinterpret_cast<cf*>(p->d_ws);
-    cf* raw = reinterpret_cast<cf*>(static_cast<char*>(p->d_ws) + a.spec_bytes);
-    cd* part = reinterpret_cast<cd*>(static_cast<char*>(p->d_ws) + a.spec_bytes + a.raw_bytes);
-    for (int64_t c0 = 0; c0 < n_chunks; c0 += a.cb) {
-        const int64_t nc = std::min(a.cb, n_chunks - c0);
-        const int64_t cg = autos_group(p, nc, a.unit);
-        const int xr = cg > 1 ? 1 : a.xr;
-        rc = autos_raw_sums(p, x + c0 * p->n_ant * p->num_samp, nc, spec, raw, cg, xr);
-        if (rc) return rc;
-        rc = fold_or_defer(p, raw, part, (nc + cg - 1) / cg * xr, 0, c0 + nc >= n_chunks);
-        if (rc) return rc;
-    }
-    p->spectra_count += (double)n_chunks * (double)p->n_pts;
-    return FXC_OK;
-}
-
-// (fx_rows_dev, below) the mode of a tracked fx_accumulate: its passes fold their rows into the accumulator
-constexpr int kModeTrackFold = -1;
-int fx_rows_dev(fxc_plan* p, const cf* x, void* out, int64_t n_chunks, int mode, double bandwidth, const cf* dc_u8 = nullptr,
-                bool dck = false);
-
-// device-resident implementation of fx_accumulate
-// dc_u8 != nullptr (fused 2-antenna plans only): x is the uint8 I,Q stream [n_chunks][2][num_samp][2] and dc_u8 its
-// per-stream conversion offsets; dck: the fused kernel sums its later chunks' bytes itself (never under a delay track)
-int fx_accumulate_dev(fxc_plan* p, const cf* x, int64_t n_chunks, const cf* dc_u8 = nullptr, bool dck = false) {
-    if (n_chunks == 0) return FXC_OK;
-    p->acc_track = p->track;
-    if (p->track) {
-        // rot changes from chunk to chunk, so it is applied before the sum over chunks: the rows routes' raw rows (one set per
-        // chunk), folded by track_fold_kernel
-        const int rc = fx_rows_dev(p, x, nullptr, n_chunks, kModeTrackFold, 1.0, dc_u8, dck);
-        if (rc) return rc;
-        p->spectra_count += (double)n_chunks * (double)p->n_pts;
-        return FXC_OK;
-    }
-    if (p->autos && !fused_autos(p, n_chunks)) return autos_accumulate_dev(p, x, n_chunks);
-    if (p->path == FXC_PATH_STREAM) {
-        const int64_t blocks = stream_blocks(p);
-        const int64_t cb = std::min<int64_t>(n_chunks, 65535);
-        int rc = ensure_ws(p, cb * blocks * (int64_t)sizeof(cf));
-        if (rc) return rc;
-        cf* raw = reinterpret_cast<cf*>(p->d_ws);
-        for (int64_t c0 = 0; c0 < n_chunks; c0 += cb) {
-            const int64_t nc = std::min(cb, n_chunks - c0);
-            rc = stream_raw_sums(p, x + c0 * 2 * p->num_samp, nc, raw);
-            if (rc) return rc;
-            hipLaunchKernelGGL(stream1_acc_kernel, dim3(1), dim3(256), 0, p->stream, raw, p->d_acc, nc * blocks);
-            FXC_HIP(p, hipGetLastError());
-        }
-    } else if ((p->path == FXC_PATH_FUSED && (dc_u8 || !use_tiled(p, n_chunks))) || (p->path == FXC_PATH_TILED && p->n_ant > 2)) {
-        using namespace fxc::fused;
-        const int64_t in_bytes = (int64_t)p->n_ant * p->num_samp * (dc_u8 ? 2 : (int64_t)sizeof(cf));   // per chunk
-        int64_t spec_bytes, raw_bytes;
-        const int64_t cb = fused_chunks_per_pass(p, n_chunks, &spec_bytes, &raw_bytes);
-        const int64_t part_bytes = fold_part_bytes(p);
-        int rc = ensure_ws(p, spec_bytes + raw_bytes + part_bytes);
-        if (rc) return rc;
-        cf* spec = reinterpret_cast<cf*>(p->d_ws);
-        cf* raw = reinterpret_cast<cf*>(static_cast<char*>(p->d_ws) + spec_bytes);
-        cd* part = reinterpret_cast<cd*>(static_cast<char*>(p->d_ws) + spec_bytes + raw_bytes);
-        for (int64_t c0 = 0; c0 < n_chunks; c0 += cb) {
-            const int64_t nc = std::min(cb, n_chunks - c0);
-            // chunks per raw row: 2 antennas, rows of up to kRowSpectra spectra; more, the X-engine's chunk groups
-            const int64_t unit = p->n_ant == 2 ? fused_unit(p) : xengine_group(p, nc, fused_unit(p));
-            rc = fused_raw_sums(p, reinterpret_cast<const cf*>(reinterpret_cast<const char*>(x) + c0 * in_bytes), nc, spec, raw,
-                                dc_u8 ? dc_u8 + c0 * 2 : nullptr, unit, false, dc_u8 && dck);
-            if (rc) return rc;
-            // 2 antennas: all the raw rows, leading parts included; more: one row [n_base][nchan] per chunk group
-            const int64_t n_rows = p->n_ant == 2 ? fused_rows(p, nc, unit, false) : (nc + unit - 1) / unit * x_ranges(p, unit);
-            rc = fold_or_defer(p, raw, part, n_rows, fused_layout(p), c0 + nc >= n_chunks);
-            if (rc) return rc;
-        }
-    } else if (p->split8192 && !dc_u8) {
-        const int N = p->nchan;
-        const int64_t cb = split_chunks_per_pass(p, n_chunks);
-        const int64_t row_bytes = (int64_t)fxc::fused::kN * (int64_t)sizeof(cf);
-        const int64_t raw_bytes = ((2 * cb + p->fused_grid_max) * row_bytes + 255) / 256 * 256;
-        const int64_t part_bytes = fold_part_bytes(p);
-        int rc = ensure_ws(p, raw_bytes + part_bytes);
-        if (rc) return rc;
-        cf* raw = reinterpret_cast<cf*>(p->d_ws);
-        cd* part = reinterpret_cast<cd*>(static_cast<char*>(p->d_ws) + raw_bytes);
-        for (int64_t c0 = 0; c0 < n_chunks; c0 += cb) {
-            const int64_t nc = std::min(cb, n_chunks - c0);
-            rc = split_raw_sums(p, x + c0 * 2 * p->num_samp, nc, raw);
-            if (rc) return rc;
-            // the nc pairs of 4096-rows are nc rows of 8192 in layout 3; the leading-part rows are added by parity
-            rc = fold_rows(p, raw, part, nc, 3, kNoFinish);
-            if (rc) return rc;
-            hipLaunchKernelGGL(split_lead_acc_kernel, dim3(N / 256), dim3(256), 0, p->stream, raw, p->d_acc, fused_lead(p, 2 * nc));
-            FXC_HIP(p, hipGetLastError());
-        }
-    } else if (use_tiled(p, n_chunks)) {
-        const int N = p->nchan;
-        const int64_t in_bytes = (int64_t)2 * p->num_samp * (dc_u8 ? 2 : (int64_t)sizeof(cf));   // per chunk
-        const int n_splits = tiled_splits(p, n_chunks);
-        const int64_t row_bytes = (int64_t)N * (int64_t)sizeof(cf);
-        const int64_t cb = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_chunks, tiled_streams_per_pass(p) / 2),
-                                                                  ws_target() / (row_bytes * n_splits)));
-        const int64_t raw_bytes = (cb * n_splits * row_bytes + 255) / 256 * 256;
-        const int64_t part_bytes = fold_part_bytes(p);
-        int rc = ensure_ws(p, raw_bytes + part_bytes);
-        if (rc) return rc;
-        cf* raw = reinterpret_cast<cf*>(p->d_ws);
-        cd* part = reinterpret_cast<cd*>(static_cast<char*>(p->d_ws) + raw_bytes);
-        for (int64_t c0 = 0; c0 < n_chunks; c0 += cb) {
-            const int64_t nc = std::min(cb, n_chunks - c0);
-            rc = tiled_raw_sums(p, reinterpret_cast<const cf*>(reinterpret_cast<const char*>(x) + c0 * in_bytes), nc, n_splits,
-                                raw, dc_u8 ? dc_u8 + c0 * 2 : nullptr);
-            if (rc) return rc;
-            rc = fold_or_defer(p, raw, part, nc * n_splits, 0, c0 + nc >= n_chunks);
-            if (rc) return rc;
-        }
-    } else {
-        const bool xf = mixed_one_pass(p, dc_u8 != nullptr);
-        const bool xm = !xf && two_pass_xm(p, dc_u8 != nullptr);
-        const XGeom g = x_geometry(p, n_chunks, xf, xm);
-        int64_t spec_bytes, raw_bytes;
-        const int64_t cb = generic_chunks_per_pass(p, n_chunks, g, &spec_bytes, &raw_bytes, xf, xm);
-        raw_bytes = (raw_bytes + 255) / 256 * 256;
-        int rc = ensure_ws(p, spec_bytes + raw_bytes + fold_part_bytes(p));
-        if (rc) return rc;
-        cf* spec = reinterpret_cast<cf*>(p->d_ws);
-        cf* raw = reinterpret_cast<cf*>(static_cast<char*>(p->d_ws) + spec_bytes);
-        cd* part = reinterpret_cast<cd*>(static_cast<char*>(p->d_ws) + spec_bytes + raw_bytes);
-        for (int64_t c0 = 0; c0 < n_chunks; c0 += cb) {
-            const int64_t nc = std::min(cb, n_chunks - c0);
-            KernelTimer kt(p);
-            if (xf) {
-                // (bytes in: two per sample, and the offsets of this pass's streams)
-                rc = dc_u8 ? mixed_fx_raw_sums(p, reinterpret_cast<const cf*>(reinterpret_cast<const char*>(x) + c0 * 2 * p->num_samp * 2),
-                                               nc, g.n_splits, raw, dc_u8 + c0 * 2)
-                           : mixed_fx_raw_sums(p, x + c0 * p->n_ant * p->num_samp, nc, g.n_splits, raw);
-                if (rc) return rc;
-            } else if (xm) {
-                rc = two_pass_raw_sums(p, x + c0 * p->n_ant * p->num_samp, nc, g.n_splits, spec, raw);
-                if (rc) return rc;
-            } else if (p->mixed_xeng) {
-                // 3 .. 64 antennas off the powers of two: spectra antenna-interleaved, then the X-engines of the tiled paths
-                rc = run_channelize(p, x + c0 * p->n_ant * p->num_samp, spec, nc * p->n_ant, p->n_ant);
-                if (rc) return rc;
-                rc = launch_xengine(p, spec, raw, nc, 1, g.n_splits);
-                if (rc) return rc;
-            } else {
-                rc = run_channelize(p, x + c0 * p->n_ant * p->num_samp, spec, nc * p->n_ant);
-                if (rc) return rc;
-                const int kblocks = (p->nchan + g.kx - 1) / g.kx;
-                const int64_t wgs = nc * p->n_base * kblocks * g.n_splits;
-                hipLaunchKernelGGL(xmul_kernel, dim3((int)std::min<int64_t>(wgs, (int64_t)p->cu_count * 8)), dim3(256), 0,
-                                   p->stream, spec, raw, p->n_ant, p->n_base, p->nchan, p->n_pts, g.kx, g.n_splits, nc);
-            }
-            kt.stop();
-            FXC_HIP(p, hipGetLastError());
-            // raw[split][chunk] = nc * n_splits rows of [n_base][nchan], natural bin order
-            rc = fold_or_defer(p, raw, part, nc * g.n_splits, 0, c0 + nc >= n_chunks);
-            if (rc) return rc;
-        }
-    }
-    p->spectra_count += (double)n_chunks * (double)p->n_pts;
-    return FXC_OK;
-}
-
 // Rows of a plan with per-antenna tables (fxc_set_rot_ant: 3 and more antennas) go to the rows kernels' ANT instantiations.
 // Every route of those plans lays its rows out as [chunk][n_prod] with the n_base cross rows first, so the kernels take
-// n_prod and n_cross from the plan then.  Every route of fx_rows_dev ends in launch_rows below.
+// n_prod and n_cross from the plan then (launch_rows below, where every route's rows end).
 //
 // Plans with a delay track (fxc_set_delay_track) go to the tracked instantiations: the pass's rows are [chunk][p->n_prod] on
 // every route (two antennas: 1 row, or cross + 2 autos), its chunks take the plan's counter onwards, and track_pass writes
@@ -277,13 +114,13 @@ void launch_rows_spectrum(fxc_plan* p, const cf* raw, cf* out, int nchan, int64_
     const dim3 grid(grid_for(rows * nchan, 256, p->cu_count));
     if (p->track && p->n_ant > 2)
         hipLaunchKernelGGL(rows_spectrum_track_kernel<true>, grid, dim3(256), 0, p->stream, raw, out, track_ant_rot_arg(p), nchan, rows,
-                           n_splits, split_stride, inv_pts, slots, lead, p->n_prod, p->n_base);
+                           n_splits, split_stride, inv_pts, slots, lead, n_prod, n_cross);
     else if (p->track)
         hipLaunchKernelGGL(rows_spectrum_track_kernel<false>, grid, dim3(256), 0, p->stream, raw, out, track_rot_arg(p), nchan, rows,
-                           n_splits, split_stride, inv_pts, slots, lead, p->n_prod, p->n_base);
+                           n_splits, split_stride, inv_pts, slots, lead, n_prod, n_cross);
     else if (p->rot_ant)
         hipLaunchKernelGGL(rows_spectrum_kernel<true>, grid, dim3(256), 0, p->stream, raw, out, ant_rot_arg(p), nchan, rows, n_splits,
-                           split_stride, inv_pts, slots, lead, p->n_prod, p->n_base);
+                           split_stride, inv_pts, slots, lead, n_prod, n_cross);
     else
         hipLaunchKernelGGL(rows_spectrum_kernel<false>, grid, dim3(256), 0, p->stream, raw, out, p->d_rot, nchan, rows, n_splits,
                            split_stride, inv_pts, slots, lead, n_prod, n_cross);
@@ -291,11 +128,7 @@ void launch_rows_spectrum(fxc_plan* p, const cf* raw, cf* out, int nchan, int64_
 
 // CONTINUUM rows: one workgroup per row when there are rows enough to fill the chip, else bin slices + a second small kernel
 int launch_rows_continuum(fxc_plan* p, const cf* raw, cd* out, int nchan, int64_t rows, int n_splits, int64_t split_stride,
-                          double scale, int slots, LeadRows lead, int n_prod = 1, int n_cross = 1) {
-    if (p->rot_ant || p->track) {
-        n_prod = p->n_prod;
-        n_cross = p->n_base;
-    }
+                          double scale, int slots, LeadRows lead, int n_prod, int n_cross) {
     const bool track_ant = p->track && p->n_ant > 2;
     const int slices = (int)std::min<int64_t>(32, nchan / 128);
     if (slices >= 2 && rows * 2 <= p->cu_count && rows <= 65535) {
@@ -334,8 +167,9 @@ int launch_rows_continuum(fxc_plan* p, const cf* raw, cd* out, int nchan, int64_
     return FXC_OK;
 }
 
-// What a pass of fx_rows_dev does with its raw rows: SPECTRUM or CONTINUUM rows into `out` from row `row0` on, or -- a tracked
-// fx_accumulate, which runs the rows routes -- the fold of the pass's chunks into the accumulator (track_fold_kernel)
+// What a pass does with its raw rows when they are one set per chunk: SPECTRUM or CONTINUUM rows into `out` from row `row0` on, or
+// -- kModeTrackFold, a tracked fx_accumulate -- the fold of the pass's chunks into the accumulator (track_fold_kernel)
+constexpr int kModeTrackFold = -1;
 struct RowsOut {
     int mode;
     void* out;
@@ -345,6 +179,10 @@ struct RowsOut {
 
 int launch_rows(fxc_plan* p, const RowsOut& o, int64_t row0, const cf* raw, int nchan, int64_t rows, int n_splits,
                 int64_t split_stride, int slots, LeadRows lead, int n_prod = 1, int n_cross = 1) {
+    if (p->rot_ant || p->track) {      // rows of [chunk][n_prod] on every route then: the plan's own counts
+        n_prod = p->n_prod;
+        n_cross = p->n_base;
+    }
     if (p->track) {
         const int rc = track_pass(p, rows / p->n_prod);
         if (rc) return rc;
@@ -369,140 +207,177 @@ int launch_rows(fxc_plan* p, const RowsOut& o, int64_t row0, const cf* raw, int 
     return FXC_OK;
 }
 
-// fx_rows of a plan with autos: one raw row per chunk and frame range, the ranges as the rows kernels' splits
-int autos_rows_dev(fxc_plan* p, const cf* x, const RowsOut& o, int64_t n_chunks) {
-    const AutoPass a = autos_pass(p, n_chunks, true);
-    int rc = ensure_ws(p, a.spec_bytes + a.raw_bytes);
+// The workspace of a call: a pass's spectra, its raw rows and -- `fold`, the plain fold -- the fold's partial sums, each from a
+// 256-byte boundary.  Once per call, before anything writes the workspace: ensure_ws flushes a pending fold that lives there.
+struct Workspace {
+    cf *spec, *raw;
+    cd* part;
+};
+
+int carve_ws(fxc_plan* p, bool fold, int64_t spec_bytes, int64_t raw_bytes, Workspace* w) {
+    spec_bytes = (spec_bytes + 255) / 256 * 256;
+    raw_bytes = (raw_bytes + 255) / 256 * 256;
+    const int rc = ensure_ws(p, spec_bytes + raw_bytes + (fold ? fold_part_bytes(p) : 0));
     if (rc) return rc;
-    cf* spec = reinterpret_cast<cf*>(p->d_ws);
-    cf* raw = reinterpret_cast<cf*>(static_cast<char*>(p->d_ws) + a.spec_bytes);
-    for (int64_t c0 = 0; c0 < n_chunks; c0 += a.cb) {
-        const int64_t nc = std::min(a.cb, n_chunks - c0);
-        rc = autos_raw_sums(p, x + c0 * p->n_ant * p->num_samp, nc, spec, raw, 1, a.xr);
-        if (rc) return rc;
-        const int64_t rows = nc * p->n_prod;
-        rc = launch_rows(p, o, c0 * p->n_prod, raw, p->nchan, rows, a.xr, rows * p->nchan, 0, kNoLead, p->n_prod, p->n_base);
-        if (rc) return rc;
-    }
+    char* base = static_cast<char*>(p->d_ws);
+    w->spec = reinterpret_cast<cf*>(base);
+    w->raw = reinterpret_cast<cf*>(base + spec_bytes);
+    w->part = fold ? reinterpret_cast<cd*>(base + spec_bytes + raw_bytes) : nullptr;
     return FXC_OK;
 }
 
-// the routes of fx_rows_dev: raw rows pass by pass, each pass finished by launch_rows
-int rows_routes(fxc_plan* p, const cf* x, const RowsOut& o, int64_t n_chunks, const cf* dc_u8, bool dck) {
-    if (p->autos && !fused_autos(p, n_chunks)) return autos_rows_dev(p, x, o, n_chunks);
-    if (p->path == FXC_PATH_STREAM) {
-        const int nb = (int)stream_blocks(p);
-        const int64_t cb = std::min<int64_t>(n_chunks, 65535);
-        int rc = ensure_ws(p, cb * nb * (int64_t)sizeof(cf));
+// chunk c0 of a call's samples: complex64, or -- bytes (2 antennas) -- the receivers' uint8 I,Q, two bytes per sample
+const cf* chunk_at(const fxc_plan* p, const cf* x, int64_t c0, bool bytes) {
+    return reinterpret_cast<const cf*>(reinterpret_cast<const char*>(x) + c0 * p->n_ant * p->num_samp * (bytes ? 2 : (int64_t)sizeof(cf)));
+}
+
+// The one route ladder: which kernels a call runs, for fx_rows and fx_accumulate alike.  A route sizes its passes, carves the
+// workspace, and pass by pass writes raw rows (float32 sums) and hands them on.  The consumer shows in two places of a route only:
+//   o != nullptr  rows (fx_rows, and kModeTrackFold): one chunk per raw row, each pass finished by launch_rows;
+//   o == nullptr  the plain fold of an untracked fx_accumulate: as many chunks per raw row as a float32 sum and the device's
+//                 width allow, each pass folded into the accumulator (the call's last one left pending: fold_or_defer).
+// dc_u8 != nullptr (2-antenna plans only): x is the uint8 I,Q stream [n_chunks][2][num_samp][2] and dc_u8 its per-stream
+// conversion offsets; dck: the fused kernel sums its later chunks' bytes itself (never under a delay track)
+int fx_routes(fxc_plan* p, const cf* x, const RowsOut* o, int64_t n_chunks, const cf* dc_u8, bool dck) {
+    const bool bytes = dc_u8 != nullptr;
+    Workspace w;
+    if (p->autos && !fused_autos(p, n_chunks)) {
+        // rows: one raw row per chunk and frame range, the ranges as the rows kernels' splits
+        const AutoPass a = autos_pass(p, n_chunks, o != nullptr);
+        int rc = carve_ws(p, !o, a.spec_bytes, a.raw_bytes, &w);
         if (rc) return rc;
-        cf* raw = reinterpret_cast<cf*>(p->d_ws);
-        for (int64_t c0 = 0; c0 < n_chunks; c0 += cb) {
-            const int64_t nc = std::min(cb, n_chunks - c0);
-            rc = stream_raw_sums(p, x + c0 * 2 * p->num_samp, nc, raw);
-            if (rc) return rc;
-            // raw[block][chunk]: the blocks play the role of the generic path's splits (nchan = n_base = 1)
-            rc = launch_rows(p, o, c0, raw, 1, nc, nb, nc, 0, kNoLead);
-            if (rc) return rc;
-        }
-        return FXC_OK;
-    }
-    if ((p->path == FXC_PATH_FUSED && (dc_u8 || !use_tiled(p, n_chunks))) || (p->path == FXC_PATH_TILED && p->n_ant > 2)) {
-        const int64_t in_bytes = (int64_t)p->n_ant * p->num_samp * (dc_u8 ? 2 : (int64_t)sizeof(cf));   // per chunk
-        int64_t spec_bytes, raw_bytes;
-        const int64_t cb = fused_chunks_per_pass(p, n_chunks, &spec_bytes, &raw_bytes);
-        int rc = ensure_ws(p, spec_bytes + raw_bytes);
-        if (rc) return rc;
-        cf* spec = reinterpret_cast<cf*>(p->d_ws);
-        cf* raw = reinterpret_cast<cf*>(static_cast<char*>(p->d_ws) + spec_bytes);
-        for (int64_t c0 = 0; c0 < n_chunks; c0 += cb) {
-            const int64_t nc = std::min(cb, n_chunks - c0);
-            rc = fused_raw_sums(p, reinterpret_cast<const cf*>(reinterpret_cast<const char*>(x) + c0 * in_bytes), nc, spec, raw,
-                                dc_u8 ? dc_u8 + c0 * 2 : nullptr, 1, true, dc_u8 && dck);
+        for (int64_t c0 = 0; c0 < n_chunks; c0 += a.cb) {
+            const int64_t nc = std::min(a.cb, n_chunks - c0);
+            const int64_t cg = autos_group(p, nc, a.unit);      // (rows: unit = 1, so one chunk)
+            const int xr = cg > 1 ? 1 : a.xr;
+            rc = autos_raw_sums(p, chunk_at(p, x, c0, false), nc, w.spec, w.raw, cg, xr);
             if (rc) return rc;
             const int64_t rows = nc * p->n_prod;
-            const LeadRows lead = p->n_ant == 2 ? fused_lead(p, nc) : kNoLead;
-            // 3 and more antennas: the frame ranges of a chunk are the rows kernels' splits (range-major raw rows)
-            const int xr = x_ranges(p, 1);
-            const int64_t xr_stride = rows * p->nchan;
-            rc = launch_rows(p, o, c0 * p->n_prod, raw, p->nchan, rows, xr, xr_stride, fused_layout(p), lead, p->n_prod, p->n_base);
+            rc = o ? launch_rows(p, *o, c0 * p->n_prod, w.raw, p->nchan, rows, xr, rows * p->nchan, 0, kNoLead, p->n_prod, p->n_base)
+                   : fold_or_defer(p, w.raw, w.part, (nc + cg - 1) / cg * xr, 0, c0 + nc >= n_chunks);
             if (rc) return rc;
         }
-        return FXC_OK;
-    }
-    if (p->split8192 && !dc_u8) {
-        const int N = p->nchan;
-        const int64_t cb = split_chunks_per_pass(p, n_chunks);
-        int rc = ensure_ws(p, (2 * cb + p->fused_grid_max) * (int64_t)fxc::fused::kN * (int64_t)sizeof(cf));
+    } else if (p->path == FXC_PATH_STREAM) {
+        const int nb = (int)stream_blocks(p);
+        const int64_t cb = std::min<int64_t>(n_chunks, 65535);
+        int rc = carve_ws(p, false, 0, cb * nb * (int64_t)sizeof(cf), &w);      // (stream1_acc_kernel needs no partials)
         if (rc) return rc;
-        cf* raw = reinterpret_cast<cf*>(p->d_ws);
         for (int64_t c0 = 0; c0 < n_chunks; c0 += cb) {
             const int64_t nc = std::min(cb, n_chunks - c0);
-            rc = split_raw_sums(p, x + c0 * 2 * p->num_samp, nc, raw);
+            rc = stream_raw_sums(p, chunk_at(p, x, c0, false), nc, w.raw);
             if (rc) return rc;
-            rc = launch_rows(p, o, c0, raw, N, nc, 1, (int64_t)0, 3, fused_lead(p, 2 * nc));
+            // raw[block][chunk]: the blocks play the role of the generic path's splits (nchan = n_base = 1)
+            if (o) {
+                rc = launch_rows(p, *o, c0, w.raw, 1, nc, nb, nc, 0, kNoLead);
+                if (rc) return rc;
+            } else {
+                hipLaunchKernelGGL(stream1_acc_kernel, dim3(1), dim3(256), 0, p->stream, w.raw, p->d_acc, nc * nb);
+                FXC_HIP(p, hipGetLastError());
+            }
+        }
+    } else if ((p->path == FXC_PATH_FUSED && (bytes || !use_tiled(p, n_chunks))) || (p->path == FXC_PATH_TILED && p->n_ant > 2)) {
+        int64_t spec_bytes, raw_bytes;
+        const int64_t cb = fused_chunks_per_pass(p, n_chunks, &spec_bytes, &raw_bytes);
+        int rc = carve_ws(p, !o, spec_bytes, raw_bytes, &w);
+        if (rc) return rc;
+        for (int64_t c0 = 0; c0 < n_chunks; c0 += cb) {
+            const int64_t nc = std::min(cb, n_chunks - c0);
+            // chunks per raw row.  Rows: one.  The plain fold: 2 antennas, rows of up to kRowSpectra spectra; more, the X-engine's
+            // chunk groups
+            const int64_t unit = o ? 1 : p->n_ant == 2 ? fused_unit(p) : xengine_group(p, nc, fused_unit(p));
+            rc = fused_raw_sums(p, chunk_at(p, x, c0, bytes), nc, w.spec, w.raw, bytes ? dc_u8 + c0 * 2 : nullptr, unit, o != nullptr,
+                                bytes && dck);
+            if (rc) return rc;
+            if (o) {
+                // 3 and more antennas: the frame ranges of a chunk are the rows kernels' splits (range-major raw rows)
+                const int64_t rows = nc * p->n_prod;
+                rc = launch_rows(p, *o, c0 * p->n_prod, w.raw, p->nchan, rows, x_ranges(p, 1), rows * p->nchan, fused_layout(p),
+                                 p->n_ant == 2 ? fused_lead(p, nc) : kNoLead, p->n_prod, p->n_base);
+            } else {
+                // 2 antennas: all the raw rows, leading parts included; more: one row [n_base][nchan] per chunk group and range
+                const int64_t n_rows = p->n_ant == 2 ? fused_rows(p, nc, unit, false) : (nc + unit - 1) / unit * x_ranges(p, unit);
+                rc = fold_or_defer(p, w.raw, w.part, n_rows, fused_layout(p), c0 + nc >= n_chunks);
+            }
             if (rc) return rc;
         }
-        return FXC_OK;
-    }
-    if (use_tiled(p, n_chunks)) {
+    } else if (p->split8192 && !dc_u8) {
         const int N = p->nchan;
-        const int64_t in_bytes = (int64_t)2 * p->num_samp * (dc_u8 ? 2 : (int64_t)sizeof(cf));   // per chunk
+        const int64_t cb = split_chunks_per_pass(p, n_chunks);
+        int rc = carve_ws(p, !o, 0, (2 * cb + p->fused_grid_max) * (int64_t)fxc::fused::kN * (int64_t)sizeof(cf), &w);
+        if (rc) return rc;
+        for (int64_t c0 = 0; c0 < n_chunks; c0 += cb) {
+            const int64_t nc = std::min(cb, n_chunks - c0);
+            rc = split_raw_sums(p, chunk_at(p, x, c0, false), nc, w.raw);
+            if (rc) return rc;
+            // the nc pairs of 4096-rows are nc rows of 8192 in layout 3; the leading-part rows are added by parity
+            const LeadRows lead = fused_lead(p, 2 * nc);
+            if (o) {
+                rc = launch_rows(p, *o, c0, w.raw, N, nc, 1, 0, 3, lead);
+                if (rc) return rc;
+            } else {      // (folded at once, never left pending: the leading parts follow it into the accumulator)
+                rc = fold_rows(p, w.raw, w.part, nc, 3, kNoFinish);
+                if (rc) return rc;
+                hipLaunchKernelGGL(split_lead_acc_kernel, dim3(N / 256), dim3(256), 0, p->stream, w.raw, p->d_acc, lead);
+                FXC_HIP(p, hipGetLastError());
+            }
+        }
+    } else if (use_tiled(p, n_chunks)) {
+        const int N = p->nchan;
         const int n_splits = tiled_splits(p, split_basis(p, n_chunks));
         const int64_t row_bytes = (int64_t)N * (int64_t)sizeof(cf);
         const int64_t cb = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_chunks, tiled_streams_per_pass(p) / 2),
                                                                   ws_target() / (row_bytes * n_splits)));
-        int rc = ensure_ws(p, cb * n_splits * row_bytes);
+        int rc = carve_ws(p, !o, 0, cb * n_splits * row_bytes, &w);
         if (rc) return rc;
-        cf* raw = reinterpret_cast<cf*>(p->d_ws);
         for (int64_t c0 = 0; c0 < n_chunks; c0 += cb) {
             const int64_t nc = std::min(cb, n_chunks - c0);
-            rc = tiled_raw_sums(p, reinterpret_cast<const cf*>(reinterpret_cast<const char*>(x) + c0 * in_bytes), nc, n_splits,
-                                raw, dc_u8 ? dc_u8 + c0 * 2 : nullptr);
+            rc = tiled_raw_sums(p, chunk_at(p, x, c0, bytes), nc, n_splits, w.raw, bytes ? dc_u8 + c0 * 2 : nullptr);
             if (rc) return rc;
-            rc = launch_rows(p, o, c0, raw, N, nc, n_splits, nc * N, 0, kNoLead);
+            rc = o ? launch_rows(p, *o, c0, w.raw, N, nc, n_splits, nc * N, 0, kNoLead)
+                   : fold_or_defer(p, w.raw, w.part, nc * n_splits, 0, c0 + nc >= n_chunks);
             if (rc) return rc;
         }
-        return FXC_OK;
-    }
-    const bool xf = mixed_one_pass(p, dc_u8 != nullptr);
-    const bool xm = !xf && two_pass_xm(p, dc_u8 != nullptr);
-    const XGeom g = x_geometry(p, split_basis(p, n_chunks), xf, xm);
-    int64_t spec_bytes, raw_bytes;
-    const int64_t cb = generic_chunks_per_pass(p, n_chunks, g, &spec_bytes, &raw_bytes, xf, xm);
-    int rc = ensure_ws(p, spec_bytes + raw_bytes);
-    if (rc) return rc;
-    cf* spec = reinterpret_cast<cf*>(p->d_ws);
-    cf* raw = reinterpret_cast<cf*>(static_cast<char*>(p->d_ws) + spec_bytes);
-    for (int64_t c0 = 0; c0 < n_chunks; c0 += cb) {
-        const int64_t nc = std::min(cb, n_chunks - c0);
-        KernelTimer kt(p);
-        if (xf) {
-            rc = dc_u8 ? mixed_fx_raw_sums(p, reinterpret_cast<const cf*>(reinterpret_cast<const char*>(x) + c0 * 2 * p->num_samp * 2),
-                                           nc, g.n_splits, raw, dc_u8 + c0 * 2)
-                       : mixed_fx_raw_sums(p, x + c0 * p->n_ant * p->num_samp, nc, g.n_splits, raw);
-            if (rc) return rc;
-        } else if (xm) {
-            rc = two_pass_raw_sums(p, x + c0 * p->n_ant * p->num_samp, nc, g.n_splits, spec, raw);
-            if (rc) return rc;
-        } else if (p->mixed_xeng) {
-            rc = run_channelize(p, x + c0 * p->n_ant * p->num_samp, spec, nc * p->n_ant, p->n_ant);
-            if (rc) return rc;
-            rc = launch_xengine(p, spec, raw, nc, 1, g.n_splits);
-            if (rc) return rc;
-        } else {
-            rc = run_channelize(p, x + c0 * p->n_ant * p->num_samp, spec, nc * p->n_ant);
-            if (rc) return rc;
-            const int kblocks = (p->nchan + g.kx - 1) / g.kx;
-            const int64_t wgs = nc * p->n_base * kblocks * g.n_splits;
-            hipLaunchKernelGGL(xmul_kernel, dim3((int)std::min<int64_t>(wgs, (int64_t)p->cu_count * 8)), dim3(256), 0,
-                               p->stream, spec, raw, p->n_ant, p->n_base, p->nchan, p->n_pts, g.kx, g.n_splits, nc);
-        }
-        kt.stop();
-        const int64_t rows = nc * p->n_base;
-        const int64_t split_stride = rows * p->nchan;
-        FXC_HIP(p, hipGetLastError());
-        rc = launch_rows(p, o, c0 * p->n_base, raw, p->nchan, rows, g.n_splits, split_stride, 0, kNoLead);
+    } else {
+        const bool xf = mixed_one_pass(p, bytes);
+        const bool xm = !xf && two_pass_xm(p, bytes);
+        const XGeom g = x_geometry(p, split_basis(p, n_chunks), xf, xm);
+        int64_t spec_bytes, raw_bytes;
+        const int64_t cb = generic_chunks_per_pass(p, n_chunks, g, &spec_bytes, &raw_bytes, xf, xm);
+        int rc = carve_ws(p, !o, spec_bytes, raw_bytes, &w);
         if (rc) return rc;
+        for (int64_t c0 = 0; c0 < n_chunks; c0 += cb) {
+            const int64_t nc = std::min(cb, n_chunks - c0);
+            const cf* xc = chunk_at(p, x, c0, bytes);
+            KernelTimer kt(p);
+            if (xf) {
+                // (bytes in: the offsets of this pass's streams)
+                rc = mixed_fx_raw_sums(p, xc, nc, g.n_splits, w.raw, bytes ? dc_u8 + c0 * 2 : nullptr);
+                if (rc) return rc;
+            } else if (xm) {
+                rc = two_pass_raw_sums(p, xc, nc, g.n_splits, w.spec, w.raw);
+                if (rc) return rc;
+            } else if (p->mixed_xeng) {
+                // 3 .. 64 antennas off the powers of two: spectra antenna-interleaved, then the X-engines of the tiled paths
+                rc = run_channelize(p, xc, w.spec, nc * p->n_ant, p->n_ant);
+                if (rc) return rc;
+                rc = launch_xengine(p, w.spec, w.raw, nc, 1, g.n_splits);
+                if (rc) return rc;
+            } else {
+                rc = run_channelize(p, xc, w.spec, nc * p->n_ant);
+                if (rc) return rc;
+                const int kblocks = (p->nchan + g.kx - 1) / g.kx;
+                const int64_t wgs = nc * p->n_base * kblocks * g.n_splits;
+                hipLaunchKernelGGL(xmul_kernel, dim3((int)std::min<int64_t>(wgs, (int64_t)p->cu_count * 8)), dim3(256), 0,
+                                   p->stream, w.spec, w.raw, p->n_ant, p->n_base, p->nchan, p->n_pts, g.kx, g.n_splits, nc);
+            }
+            kt.stop();
+            FXC_HIP(p, hipGetLastError());
+            // raw[split][chunk] = nc * n_splits rows of [n_base][nchan], natural bin order
+            const int64_t rows = nc * p->n_base;
+            rc = o ? launch_rows(p, *o, c0 * p->n_base, w.raw, p->nchan, rows, g.n_splits, rows * p->nchan, 0, kNoLead)
+                   : fold_or_defer(p, w.raw, w.part, nc * g.n_splits, 0, c0 + nc >= n_chunks);
+            if (rc) return rc;
+        }
     }
     return FXC_OK;
 }
@@ -513,9 +388,21 @@ int fx_rows_dev(fxc_plan* p, const cf* x, void* out, int64_t n_chunks, int mode,
     if (n_chunks == 0) return FXC_OK;
     const RowsOut o = {mode, out, (float)(1.0 / (double)p->n_pts), 1.0 / ((double)p->n_pts * (double)p->nchan * bandwidth)};
     const int64_t t0 = p->track_t;
-    const int rc = rows_routes(p, x, o, n_chunks, dc_u8, dck);
+    const int rc = fx_routes(p, x, &o, n_chunks, dc_u8, dck);
     if (rc) p->track_t = t0;
     return rc;
+}
+
+// device-resident implementation of fx_accumulate.  Under a delay track rot changes from chunk to chunk, so it is applied before
+// the sum over chunks: the call runs the ladder as rows (one raw row set per chunk), folded by track_fold_kernel
+int fx_accumulate_dev(fxc_plan* p, const cf* x, int64_t n_chunks, const cf* dc_u8, bool dck) {
+    if (n_chunks == 0) return FXC_OK;
+    p->acc_track = p->track;
+    const int rc = p->track ? fx_rows_dev(p, x, nullptr, n_chunks, kModeTrackFold, 1.0, dc_u8, dck)
+                            : fx_routes(p, x, nullptr, n_chunks, dc_u8, dck);
+    if (rc) return rc;
+    p->spectra_count += (double)n_chunks * (double)p->n_pts;
+    return FXC_OK;
 }
 
 // host-buffer helper: stage in, run, stage out (synchronous)
