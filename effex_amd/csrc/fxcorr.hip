@@ -3,7 +3,7 @@
 // One translation unit.  This file holds the ABI entry points; it includes
 //   fx_math.h, fx_fused4096.h, fx_tiled.h, fx_small.h, fx_mixed.h   index maps, butterflies and kernel phases (also compiled by
 //                                           g++ for the host emulation under tests/emul)
-//   k_generic.h k_finish.h (+ k_finish_rows.h) k_fused4096.h k_tiled.h k_small.h k_prepass.h k_stream.h k_conditioning.h k_track.h k_delay.h k_fringe.h k_gains.h k_synth.h
+//   k_generic.h k_finish.h k_fused4096.h k_tiled.h k_small.h k_prepass.h k_stream.h k_conditioning.h k_track.h k_delay.h k_fringe.h k_gains.h k_synth.h
 //                                           the __global__ kernels, one file per path / step
 //   h_plan.h h_rtc.h h_launch.h h_build.h h_run.h h_ingest.h h_rccl.h
 //                                           fxc_plan, the kernels compiled per channel count, the per-path launchers and
@@ -373,9 +373,6 @@ void release_gain_q(fxc_plan* p) {
         p->d_gain_q = nullptr;
     }
 }
-
-// the finalize kernels' rot: a tracked integration's sums are rotated already
-const cd* finalize_rot(const fxc_plan* p) { return p->track ? p->d_one : p->d_rot; }
 }  // namespace
 
 int fxc_set_delay_track(fxc_plan* p, const double* tau0_s, const double* rate_s_per_chunk, double bandwidth, double frequency,
@@ -805,7 +802,7 @@ int fxc_acc_reset(fxc_plan* p) {
 int fxc_acc_export(fxc_plan* p, void* sums_dev) {
     if (!p || !sums_dev) return fail(p, FXC_ERR_ARG, "NULL argument");
     FXC_DEVICE(p, p->device);
-    const FoldFinish fin = {static_cast<cd*>(sums_dev), nullptr, finalize_rot(p), p->spectra_count, 0};
+    const FoldFinish fin = {static_cast<cd*>(sums_dev), nullptr, nullptr, p->spectra_count, 0};
     return flush_pending(p, &fin);
 }
 
@@ -843,7 +840,7 @@ int finalize_enqueue(fxc_plan* p, const cd* sums_src, int mode, double bandwidth
     p->res_dst[slot] = user_out;
     if (!sums_src) {
         // SPECTRUM: one kernel.  CONTINUUM needs the mean over the bins of the finished accumulator: export, then reduce
-        FoldFinish fin = {nullptr, out, finalize_rot(p), p->spectra_count, reset ? 1 : 0};
+        FoldFinish fin = {nullptr, out, nullptr, p->spectra_count, reset ? 1 : 0};
         if (mode == FXC_MODE_CONTINUUM) {
             // into a buffer of its own: d_sums may hold reduced sums (fxc_reduce) that fxc_finalize_sums(plan, NULL) has yet
             // to read, and only fxc_reduce makes that copy valid
@@ -860,22 +857,16 @@ int finalize_enqueue(fxc_plan* p, const cd* sums_src, int mode, double bandwidth
     } else if (mode == FXC_MODE_SPECTRUM) {
         const int rc = flush_pending(p);
         if (rc) return rc;
-        if (p->rot_ant)
-            hipExtLaunchKernelGGL(finalize_spectrum_kernel<true>, dim3(grid_for(n, 256, p->cu_count)), dim3(256), 0, p->stream, nullptr,
-                                  big ? nullptr : p->ev_res[slot], 0, sums_src, out, ant_rot_arg(p), p->nchan, p->n_prod, p->n_base);
-        else
-            hipExtLaunchKernelGGL(finalize_spectrum_kernel<false>, dim3(grid_for(n, 256, p->cu_count)), dim3(256), 0, p->stream, nullptr,
-                                  big ? nullptr : p->ev_res[slot], 0, sums_src, out, finalize_rot(p), p->nchan, p->n_prod, p->n_base);
+        with_finish_rot(p, true, [&](auto ant, auto rot) {
+            hipExtLaunchKernelGGL(finalize_spectrum_kernel<decltype(ant)::value>, dim3(grid_for(n, 256, p->cu_count)), dim3(256), 0, p->stream,
+                                  nullptr, big ? nullptr : p->ev_res[slot], 0, sums_src, out, rot, p->nchan, p->n_prod, p->n_base);
+        });
     }
     if (mode == FXC_MODE_CONTINUUM) {
-        if (p->rot_ant)
-            hipExtLaunchKernelGGL(finalize_continuum_kernel<true>, dim3(p->n_prod), dim3(256), 0, p->stream, nullptr,
-                                  big ? nullptr : p->ev_res[slot], 0, sums_src, out, ant_rot_arg(p), p->nchan, p->n_prod,
-                                  1.0 / bandwidth, p->n_base);
-        else
-            hipExtLaunchKernelGGL(finalize_continuum_kernel<false>, dim3(p->n_prod), dim3(256), 0, p->stream, nullptr,
-                                  big ? nullptr : p->ev_res[slot], 0, sums_src, out, finalize_rot(p), p->nchan, p->n_prod, 1.0 / bandwidth,
-                                  p->n_base);
+        with_finish_rot(p, true, [&](auto ant, auto rot) {
+            hipExtLaunchKernelGGL(finalize_continuum_kernel<decltype(ant)::value>, dim3(p->n_prod), dim3(256), 0, p->stream, nullptr,
+                                  big ? nullptr : p->ev_res[slot], 0, sums_src, out, rot, p->nchan, p->n_prod, 1.0 / bandwidth, p->n_base);
+        });
     }
     FXC_HIP(p, hipGetLastError());
     if (big) {

@@ -334,7 +334,7 @@ int fold_splits(int64_t n_rows, int64_t row_len) {
 }
 int64_t fold_part_bytes(const fxc_plan* p) { return (int64_t)fold_max_splits((int64_t)p->n_prod * p->nchan) * p->n_prod * p->nchan * (int64_t)sizeof(cd); }
 
-const FoldFinish kNoFinish = {nullptr, nullptr, nullptr, 0.0, 0};
+const FoldFinish kNoFinish = {nullptr, nullptr, nullptr, 0.0, 0};      // (rot: with_finish_rot supplies it, here and in every FoldFinish)
 
 // `fin` with the plan's auto rows marked (they follow the n_base cross rows of the accumulator)
 FoldFinish with_autos(const fxc_plan* p, const FoldFinish& fin) {
@@ -343,39 +343,62 @@ FoldFinish with_autos(const fxc_plan* p, const FoldFinish& fin) {
     return f;
 }
 
-// the plan's per-antenna tables (fxc_set_rot_ant) as the finish kernels' ANT operand
+// ---- the rot operands (k_finish.h: RotArg, TrackRot): what a plan's rows and integrations are multiplied by -----------------
+// the plan's per-antenna tables (fxc_set_rot_ant) as the ANT operand; the shared table is p->d_rot itself
 AntRot ant_rot_arg(const fxc_plan* p) { return {p->d_rot_ant, p->d_pair}; }
+// the delay track's tables of a pass (h_run.h::track_pass writes them): one per chunk for two antennas, one per chunk and antenna for more
+int64_t track_stride(const fxc_plan* p) { return (int64_t)(p->n_ant == 2 ? 1 : p->n_ant) * p->nchan; }
+TrackRot<false> track_rot_arg(const fxc_plan* p) { return {static_cast<const cd*>(p->d_track), track_stride(p)}; }
+TrackRot<true> track_ant_rot_arg(const fxc_plan* p) { return {{static_cast<const cd*>(p->d_track), p->d_pair}, track_stride(p)}; }
+// the shared table of the finishing side: a tracked integration's sums are rotated already
+const cd* finalize_rot(const fxc_plan* p) { return p->track ? p->d_one : p->d_rot; }
 
-// `fin` for the ANT instantiations: it finalises (out != nullptr) on a plan with per-antenna tables
-bool ant_finish(const fxc_plan* p, const FoldFinish& fin) { return p->rot_ant && fin.out; }
-FinishT<true> with_ant_rot(const fxc_plan* p, const FoldFinish& f) { return {f.sums, f.out, ant_rot_arg(p), f.count, f.reset, f.auto_from}; }
+// The operand of the kernels that read a pass's rows, decided here alone: launch(ANT, TRACK, operand), the flags as
+// std::bool_constants for the kernel's template arguments
+template <class F>
+void with_rows_rot(const fxc_plan* p, F&& launch) {
+    if (p->track && p->n_ant > 2)
+        launch(std::true_type{}, std::true_type{}, track_ant_rot_arg(p));
+    else if (p->track)
+        launch(std::false_type{}, std::true_type{}, track_rot_arg(p));
+    else if (p->rot_ant)
+        launch(std::true_type{}, std::false_type{}, ant_rot_arg(p));
+    else
+        launch(std::false_type{}, std::false_type{}, static_cast<const cd*>(p->d_rot));
+}
+
+// The operand of the kernels that finish an integration: launch(ANT, operand).  The ANT instantiations where the launch
+// finalises on a plan with per-antenna tables; a fold that finalises nothing takes the plain one
+template <class F>
+void with_finish_rot(const fxc_plan* p, bool finalises, F&& launch) {
+    if (p->rot_ant && finalises)
+        launch(std::true_type{}, ant_rot_arg(p));
+    else
+        launch(std::false_type{}, finalize_rot(p));
+}
+template <bool ANT>
+FinishT<ANT> finish_with(const FoldFinish& f, RotArg<ANT> rot) { return {f.sums, f.out, rot, f.count, f.reset, f.auto_from}; }
 
 // acc[p][bin] += sum of the raw rows [n_prod][nchan], and `fin` for every element: two launches, one when the rows are few
 // `done`: an event to complete with the last kernel (it rides on that dispatch: no packet of its own in the stream)
 int fold_rows(fxc_plan* p, const cf* raw, cd* part, int64_t n_rows, int layout, const FoldFinish& fin_in, hipEvent_t done = nullptr) {
     const FoldFinish fin = with_autos(p, fin_in);
-    const bool ant = ant_finish(p, fin);
     const int64_t row_len = (int64_t)p->n_prod * p->nchan;
     const unsigned cols = (unsigned)((row_len + 255) / 256);
     const int splits = fold_splits(n_rows, row_len);
-    if (splits == 1) {
-        if (ant)
-            hipExtLaunchKernelGGL(fold_finish_kernel<cf, true>, dim3(cols), dim3(256 * kFoldPhases), 0, p->stream, nullptr, done, 0,
-                                  raw, n_rows, p->d_acc, p->nchan, p->n_prod, layout, with_ant_rot(p, fin));
-        else
-            hipExtLaunchKernelGGL(fold_finish_kernel<cf>, dim3(cols), dim3(256 * kFoldPhases), 0, p->stream, nullptr, done, 0, raw,
-                                  n_rows, p->d_acc, p->nchan, p->n_prod, layout, fin);
-    } else {
-        hipLaunchKernelGGL(fold_partial_kernel, dim3(cols, splits), dim3(256 * kFoldPhases), 0, p->stream, raw, part, row_len,
-                           n_rows, splits);
-        // the partials are in the rows' own layout
-        if (ant)
-            hipExtLaunchKernelGGL(fold_finish_kernel<cd, true>, dim3(cols), dim3(256 * kFoldPhases), 0, p->stream, nullptr, done, 0,
-                                  (const cd*)part, (int64_t)splits, p->d_acc, p->nchan, p->n_prod, layout, with_ant_rot(p, fin));
-        else
-            hipExtLaunchKernelGGL(fold_finish_kernel<cd>, dim3(cols), dim3(256 * kFoldPhases), 0, p->stream, nullptr, done, 0,
-                                  (const cd*)part, (int64_t)splits, p->d_acc, p->nchan, p->n_prod, layout, fin);
-    }
+    with_finish_rot(p, fin.out != nullptr, [&](auto ant, auto rot) {
+        constexpr bool ANT = decltype(ant)::value;
+        if (splits == 1) {
+            hipExtLaunchKernelGGL(fold_finish_kernel<cf, ANT>, dim3(cols), dim3(256 * kFoldPhases), 0, p->stream, nullptr, done, 0, raw,
+                                  n_rows, p->d_acc, p->nchan, p->n_prod, layout, finish_with<ANT>(fin, rot));
+        } else {
+            hipLaunchKernelGGL(fold_partial_kernel, dim3(cols, splits), dim3(256 * kFoldPhases), 0, p->stream, raw, part, row_len,
+                               n_rows, splits);
+            // the partials are in the rows' own layout
+            hipExtLaunchKernelGGL(fold_finish_kernel<cd, ANT>, dim3(cols), dim3(256 * kFoldPhases), 0, p->stream, nullptr, done, 0,
+                                  (const cd*)part, (int64_t)splits, p->d_acc, p->nchan, p->n_prod, layout, finish_with<ANT>(fin, rot));
+        }
+    });
     FXC_HIP(p, hipGetLastError());
     return FXC_OK;
 }
@@ -390,12 +413,11 @@ int flush_pending(fxc_plan* p, const FoldFinish* fin, hipEvent_t done) {
     if (fin) {
         const int64_t n = (int64_t)p->n_prod * p->nchan;
         const FoldFinish f = with_autos(p, *fin);
-        if (ant_finish(p, f))
-            hipExtLaunchKernelGGL(acc_finish_kernel<true>, dim3(grid_for(n, 256, p->cu_count)), dim3(256), 0, p->stream, nullptr, done,
-                                  0, p->d_acc, p->nchan, p->n_prod, with_ant_rot(p, f));
-        else
-            hipExtLaunchKernelGGL(acc_finish_kernel<false>, dim3(grid_for(n, 256, p->cu_count)), dim3(256), 0, p->stream, nullptr, done,
-                                  0, p->d_acc, p->nchan, p->n_prod, f);
+        with_finish_rot(p, f.out != nullptr, [&](auto ant, auto rot) {
+            constexpr bool ANT = decltype(ant)::value;
+            hipExtLaunchKernelGGL(acc_finish_kernel<ANT>, dim3(grid_for(n, 256, p->cu_count)), dim3(256), 0, p->stream, nullptr, done, 0,
+                                  p->d_acc, p->nchan, p->n_prod, finish_with<ANT>(f, rot));
+        });
         FXC_HIP(p, hipGetLastError());
     } else if (done) {
         FXC_HIP(p, hipEventRecord(done, p->stream));

@@ -95,10 +95,6 @@ int track_tables(fxc_plan* p, int64_t t0, int64_t n_t, cd* out, bool pair) {
     return FXC_OK;
 }
 
-int64_t track_stride(const fxc_plan* p) { return (int64_t)(p->n_ant == 2 ? 1 : p->n_ant) * p->nchan; }
-TrackRot<false> track_rot_arg(const fxc_plan* p) { return {static_cast<const cd*>(p->d_track), track_stride(p)}; }
-TrackRot<true> track_ant_rot_arg(const fxc_plan* p) { return {{static_cast<const cd*>(p->d_track), p->d_pair}, track_stride(p)}; }
-
 int track_pass(fxc_plan* p, int64_t n_chunks) {
     const int rg = grow(p, &p->d_track, &p->track_bytes, (size_t)(n_chunks * track_stride(p)) * sizeof(cd));
     if (rg) return rg;
@@ -112,57 +108,33 @@ int track_pass(fxc_plan* p, int64_t n_chunks) {
 void launch_rows_spectrum(fxc_plan* p, const cf* raw, cf* out, int nchan, int64_t rows, int n_splits, int64_t split_stride,
                           float inv_pts, int slots, LeadRows lead, int n_prod, int n_cross) {
     const dim3 grid(grid_for(rows * nchan, 256, p->cu_count));
-    if (p->track && p->n_ant > 2)
-        hipLaunchKernelGGL(rows_spectrum_track_kernel<true>, grid, dim3(256), 0, p->stream, raw, out, track_ant_rot_arg(p), nchan, rows,
-                           n_splits, split_stride, inv_pts, slots, lead, n_prod, n_cross);
-    else if (p->track)
-        hipLaunchKernelGGL(rows_spectrum_track_kernel<false>, grid, dim3(256), 0, p->stream, raw, out, track_rot_arg(p), nchan, rows,
-                           n_splits, split_stride, inv_pts, slots, lead, n_prod, n_cross);
-    else if (p->rot_ant)
-        hipLaunchKernelGGL(rows_spectrum_kernel<true>, grid, dim3(256), 0, p->stream, raw, out, ant_rot_arg(p), nchan, rows, n_splits,
-                           split_stride, inv_pts, slots, lead, n_prod, n_cross);
-    else
-        hipLaunchKernelGGL(rows_spectrum_kernel<false>, grid, dim3(256), 0, p->stream, raw, out, p->d_rot, nchan, rows, n_splits,
-                           split_stride, inv_pts, slots, lead, n_prod, n_cross);
+    with_rows_rot(p, [&](auto ant, auto trk, auto rot) {
+        hipLaunchKernelGGL((rows_spectrum_kernel<decltype(ant)::value, decltype(trk)::value>), grid, dim3(256), 0, p->stream, raw, out, rot,
+                           nchan, rows, n_splits, split_stride, inv_pts, slots, lead, n_prod, n_cross);
+    });
 }
 
 // CONTINUUM rows: one workgroup per row when there are rows enough to fill the chip, else bin slices + a second small kernel
 int launch_rows_continuum(fxc_plan* p, const cf* raw, cd* out, int nchan, int64_t rows, int n_splits, int64_t split_stride,
                           double scale, int slots, LeadRows lead, int n_prod, int n_cross) {
-    const bool track_ant = p->track && p->n_ant > 2;
     const int slices = (int)std::min<int64_t>(32, nchan / 128);
     if (slices >= 2 && rows * 2 <= p->cu_count && rows <= 65535) {
         const int rg = grow(p, &p->d_rowpart, &p->rowpart_bytes, (size_t)rows * slices * sizeof(cd));
         if (rg) return rg;
         cd* part = static_cast<cd*>(p->d_rowpart);
-        if (track_ant)
-            hipLaunchKernelGGL(rows_continuum_part_track_kernel<true>, dim3(slices, (unsigned)rows), dim3(256), 0, p->stream, raw, part,
-                               track_ant_rot_arg(p), nchan, rows, n_splits, split_stride, slots, lead, slices, n_prod, n_cross);
-        else if (p->track)
-            hipLaunchKernelGGL(rows_continuum_part_track_kernel<false>, dim3(slices, (unsigned)rows), dim3(256), 0, p->stream, raw, part,
-                               track_rot_arg(p), nchan, rows, n_splits, split_stride, slots, lead, slices, n_prod, n_cross);
-        else if (p->rot_ant)
-            hipLaunchKernelGGL(rows_continuum_part_kernel<true>, dim3(slices, (unsigned)rows), dim3(256), 0, p->stream, raw, part,
-                               ant_rot_arg(p), nchan, rows, n_splits, split_stride, slots, lead, slices, n_prod, n_cross);
-        else
-            hipLaunchKernelGGL(rows_continuum_part_kernel<false>, dim3(slices, (unsigned)rows), dim3(256), 0, p->stream, raw, part,
-                               p->d_rot, nchan, rows, n_splits, split_stride, slots, lead, slices, n_prod, n_cross);
+        with_rows_rot(p, [&](auto ant, auto trk, auto rot) {
+            hipLaunchKernelGGL((rows_continuum_part_kernel<decltype(ant)::value, decltype(trk)::value>), dim3(slices, (unsigned)rows),
+                               dim3(256), 0, p->stream, raw, part, rot, nchan, rows, n_splits, split_stride, slots, lead, slices, n_prod,
+                               n_cross);
+        });
         hipLaunchKernelGGL(rows_continuum_fin_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, p->stream, part, out, rows, slices,
                            scale);
     } else {
         const dim3 grid((int)std::min<int64_t>(rows, (int64_t)p->cu_count * 8));
-        if (track_ant)
-            hipLaunchKernelGGL(rows_continuum_track_kernel<true>, grid, dim3(continuum_threads(nchan)), 0, p->stream, raw, out,
-                               track_ant_rot_arg(p), nchan, rows, n_splits, split_stride, scale, slots, lead, n_prod, n_cross);
-        else if (p->track)
-            hipLaunchKernelGGL(rows_continuum_track_kernel<false>, grid, dim3(continuum_threads(nchan)), 0, p->stream, raw, out,
-                               track_rot_arg(p), nchan, rows, n_splits, split_stride, scale, slots, lead, n_prod, n_cross);
-        else if (p->rot_ant)
-            hipLaunchKernelGGL(rows_continuum_kernel<true>, grid, dim3(continuum_threads(nchan)), 0, p->stream, raw, out, ant_rot_arg(p),
-                               nchan, rows, n_splits, split_stride, scale, slots, lead, n_prod, n_cross);
-        else
-            hipLaunchKernelGGL(rows_continuum_kernel<false>, grid, dim3(continuum_threads(nchan)), 0, p->stream, raw, out, p->d_rot,
-                               nchan, rows, n_splits, split_stride, scale, slots, lead, n_prod, n_cross);
+        with_rows_rot(p, [&](auto ant, auto trk, auto rot) {
+            hipLaunchKernelGGL((rows_continuum_kernel<decltype(ant)::value, decltype(trk)::value>), grid, dim3(continuum_threads(nchan)), 0,
+                               p->stream, raw, out, rot, nchan, rows, n_splits, split_stride, scale, slots, lead, n_prod, n_cross);
+        });
     }
     return FXC_OK;
 }
@@ -196,12 +168,11 @@ int launch_rows(fxc_plan* p, const RowsOut& o, int64_t row0, const cf* raw, int 
         if (rc) return rc;
     } else {
         const dim3 grid(grid_for((int64_t)p->n_prod * nchan, 256, p->cu_count));
-        if (p->n_ant > 2)
-            hipLaunchKernelGGL(track_fold_kernel<true>, grid, dim3(256), 0, p->stream, raw, p->d_acc, track_ant_rot_arg(p), nchan,
-                               rows / p->n_prod, n_splits, split_stride, slots, lead, p->n_prod, p->n_base);
-        else
-            hipLaunchKernelGGL(track_fold_kernel<false>, grid, dim3(256), 0, p->stream, raw, p->d_acc, track_rot_arg(p), nchan,
-                               rows / p->n_prod, n_splits, split_stride, slots, lead, p->n_prod, p->n_base);
+        with_rows_rot(p, [&](auto ant, auto trk, auto rot) {
+            if constexpr (decltype(trk)::value)      // (kModeTrackFold: plans with a track only)
+                hipLaunchKernelGGL(track_fold_kernel<decltype(ant)::value>, grid, dim3(256), 0, p->stream, raw, p->d_acc, rot, nchan,
+                                   rows / p->n_prod, n_splits, split_stride, slots, lead, p->n_prod, p->n_base);
+        });
     }
     FXC_HIP(p, hipGetLastError());
     return FXC_OK;

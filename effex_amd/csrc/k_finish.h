@@ -97,6 +97,14 @@ __device__ __forceinline__ RotArg<ANT> chunk_rot(const TrackRot<ANT>& r, int64_t
         return r.rot + (row / n_prod) * r.stride;
 }
 
+// What the rows kernels take: the plan's table(s) as they are, or -- TRACK -- the delay track's, of which every row picks its
+// chunk's.  Untracked, the pick is the operand itself (by reference: nothing is formed).
+template <bool ANT, bool TRACK> using RowsRot = std::conditional_t<TRACK, TrackRot<ANT>, RotArg<ANT>>;
+template <bool ANT>
+__device__ __forceinline__ const RotArg<ANT>& chunk_rot(const RotArg<ANT>& r, int64_t, int) {
+    return r;
+}
+
 __device__ __forceinline__ double block_sum(double v, double* red) {
     red[threadIdx.x] = v;
     __syncthreads();
@@ -132,20 +140,153 @@ __device__ __forceinline__ void sum_splits(const cf* src, int n_splits, int64_t 
 constexpr int kContinuumThreads = 1024;
 inline int continuum_threads(int nchan) { return nchan >= kContinuumThreads ? kContinuumThreads : 256; }
 
-#define FXC_ROWS_NAME(stem) stem##_kernel
-#define FXC_ROWS_ROT RotArg<ANT> rot
-#define FXC_ROWS_CHUNK_ROT(row)
-#include "k_finish_rows.h"
-#undef FXC_ROWS_NAME
-#undef FXC_ROWS_ROT
-#undef FXC_ROWS_CHUNK_ROT
-#define FXC_ROWS_NAME(stem) stem##_track_kernel
-#define FXC_ROWS_ROT TrackRot<ANT> rot_arg
-#define FXC_ROWS_CHUNK_ROT(row) const RotArg<ANT> rot = chunk_rot<ANT>(rot_arg, row, n_prod);
-#include "k_finish_rows.h"
-#undef FXC_ROWS_NAME
-#undef FXC_ROWS_ROT
-#undef FXC_ROWS_CHUNK_ROT
+// The rows kernels, one text for the four rot operands (RowsRot above): ANT = per-antenna tables instead of one table per
+// baseline row, TRACK = the tables of the row's chunk (row / n_prod) instead of the plan's.  `rot` is the operand a row is
+// multiplied by; without TRACK it is a reference to the kernel's own argument, so the untracked instantiations carry nothing
+// of the track (a copy instead of the reference cost rows_spectrum_kernel<true> a different register assignment).
+
+// SPECTRUM rows: out[c][p][(k + N/2) % N] = (sum_split raw) * conj(rot[k]) / n_pts   (effex.py:520-521)
+// ANT: the rows are [chunk][n_prod] (baseline p = row % n_prod)
+template <bool ANT = false, bool TRACK = false>
+__global__ void rows_spectrum_kernel(const cf* __restrict__ raw, cf* __restrict__ out, RowsRot<ANT, TRACK> rot_arg,
+                                     int nchan, int64_t rows, int n_splits, int64_t split_stride, float inv_pts,
+                                     int slots, LeadRows lead, int n_prod, int n_cross) {
+    const int64_t total = rows * nchan;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += stride) {
+        const int k = (int)(idx % nchan);
+        const int64_t row = idx / nchan;
+        float ar = 0.f, ai = 0.f;
+        // sixteen loads in flight, added in the order of the splits (one at a time a bin of a single chunk with 256 rows -- few
+        // channels, many slots -- waited out 256 trips to L2: 0.1 ms)
+        const cf* src = raw + row * nchan + raw_index(k, slots);
+        int s = 0;
+        for (; s + 16 <= n_splits; s += 16) {
+            cf r[16];
+#pragma unroll
+            for (int q = 0; q < 16; ++q) r[q] = src[(s + q) * split_stride];
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                ar += r[q].x;
+                ai += r[q].y;
+            }
+        }
+        for (; s < n_splits; ++s) {
+            const cf r = src[s * split_stride];
+            ar += r.x;
+            ai += r.y;
+        }
+        add_lead_rows(raw, lead, row, nchan, k, slots, ar, ai);
+        int ks = k + nchan / 2;
+        if (ks >= nchan) ks -= nchan;
+        if (auto_row(row, n_prod, n_cross)) {
+            out[row * nchan + ks] = fxc::mk(ar * inv_pts, 0.f);
+            continue;
+        }
+        float cr, ci;
+        const RotArg<ANT>& rot = chunk_rot<ANT>(rot_arg, row, n_prod);
+        if constexpr (ANT) {
+            const cd w = ant_rot(rot, row % n_prod, k, nchan);
+            cr = (float)w.x;
+            ci = (float)w.y;
+        } else {
+            cr = (float)rot[k].x;
+            ci = (float)rot[k].y;
+        }
+        // (ar + i ai) * (cr - i ci)
+        const float orr = (ar * cr + ai * ci) * inv_pts;
+        const float oi = (ai * cr - ar * ci) * inv_pts;
+        out[row * nchan + ks] = fxc::mk(orr, oi);
+    }
+}
+
+// CONTINUUM rows: out[row] = mean_k( raw * conj(rot) / n_pts ) / bandwidth   (effex.py:523-524); one WG per row, of
+// kContinuumThreads threads: a reference-sized call is a single row whose frames the F+X kernel spread over the whole grid,
+// so each bin gathers up to grid - 1 leading-part rows -- 72 us with 256 threads, the largest item of that call
+template <bool ANT = false, bool TRACK = false>
+__global__ __launch_bounds__(kContinuumThreads) void rows_continuum_kernel(const cf* __restrict__ raw, cd* __restrict__ out,
+                                                                           RowsRot<ANT, TRACK> rot_arg, int nchan, int64_t rows, int n_splits,
+                                                                           int64_t split_stride, double scale, int slots, LeadRows lead,
+                                                                           int n_prod, int n_cross) {
+    __shared__ double red[kContinuumThreads];
+    for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
+        const bool au = auto_row(row, n_prod, n_cross);
+        const RotArg<ANT>& rot = chunk_rot<ANT>(rot_arg, row, n_prod);
+        double ar = 0.0, ai = 0.0;
+        for (int k = threadIdx.x; k < nchan; k += blockDim.x) {
+            double xr = 0.0, xi = 0.0;
+            sum_splits(raw + row * nchan + raw_index(k, slots), n_splits, split_stride, xr, xi);
+            float lr_re = 0.f, lr_im = 0.f;
+            add_lead_rows(raw, lead, row, nchan, k, slots, lr_re, lr_im);
+            xr += lr_re;
+            xi += lr_im;
+            if (au) {
+                ar += xr;
+                continue;
+            }
+            cd w;
+            if constexpr (ANT)
+                w = ant_rot(rot, row % n_prod, k, nchan);
+            else
+                w = rot[k];
+            ar += xr * w.x + xi * w.y;
+            ai += xi * w.x - xr * w.y;
+        }
+        ar = block_sum(ar, red);
+        ai = block_sum(ai, red);
+        if (threadIdx.x == 0) {
+            cd o;
+            o.x = ar * scale;
+            o.y = ai * scale;          // (auto rows: ai stayed an exact 0)
+            out[row] = o;
+        }
+    }
+}
+
+// The same for a call of few rows (the reference's own call is ONE: effex.py:490-494): a row's bins are cut into `slices`
+// workgroups (grid = slices x rows) that leave float64 partial sums, and rows_continuum_fin_kernel adds them in slice
+// order -- one workgroup per row gathered a chunk pair's up to 255 leading-part rows for all 4096 bins in 33 us, the largest
+// item of that call.
+template <bool ANT = false, bool TRACK = false>
+__global__ __launch_bounds__(256) void rows_continuum_part_kernel(const cf* __restrict__ raw, cd* __restrict__ part,
+                                                                 RowsRot<ANT, TRACK> rot_arg, int nchan, int64_t rows, int n_splits,
+                                                                 int64_t split_stride, int slots, LeadRows lead, int slices,
+                                                                 int n_prod, int n_cross) {
+    __shared__ double red[256];
+    const int64_t row = blockIdx.y;
+    const RotArg<ANT>& rot = chunk_rot<ANT>(rot_arg, row, n_prod);
+    const bool au = auto_row(row, n_prod, n_cross);
+    const int per = (nchan + slices - 1) / slices;
+    const int k_lo = blockIdx.x * per, k_hi = k_lo + per < nchan ? k_lo + per : nchan;
+    double ar = 0.0, ai = 0.0;
+    for (int k = k_lo + threadIdx.x; k < k_hi; k += blockDim.x) {
+        double xr = 0.0, xi = 0.0;
+        sum_splits(raw + row * nchan + raw_index(k, slots), n_splits, split_stride, xr, xi);
+        float lr_re = 0.f, lr_im = 0.f;
+        add_lead_rows(raw, lead, row, nchan, k, slots, lr_re, lr_im);
+        xr += lr_re;
+        xi += lr_im;
+        if (au) {
+            ar += xr;
+            continue;
+        }
+        cd w;
+        if constexpr (ANT)
+            w = ant_rot(rot, row % n_prod, k, nchan);
+        else
+            w = rot[k];
+        ar += xr * w.x + xi * w.y;
+        ai += xi * w.x - xr * w.y;
+    }
+    ar = block_sum(ar, red);
+    ai = block_sum(ai, red);
+    if (threadIdx.x == 0) {
+        cd o;
+        o.x = ar;
+        o.y = ai;
+        part[row * slices + blockIdx.x] = o;
+    }
+}
 
 __global__ void rows_continuum_fin_kernel(const cd* __restrict__ part, cd* __restrict__ out, int64_t rows, int slices, double scale) {
     const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -72,7 +72,8 @@ def test_per_antenna_finish_kernels_compile_without_scratch(asm_listing):  # noq
     for kernel in ("rows_spectrum_kernel", "rows_continuum_kernel", "rows_continuum_part_kernel", "acc_finish_kernel",
                    "finalize_spectrum_kernel", "finalize_continuum_kernel"):
         for flag in ("1", "0"):
-            hits = _by_pattern(res, r"{}{}ILb{}E".format(len(kernel), kernel, flag))
+            # (the rows kernels: <ANT, TRACK>, the untracked forms here -- test_tracking_host.py has the tracked ones)
+            hits = _by_pattern(res, r"{}{}ILb{}E{}".format(len(kernel), kernel, flag, "Lb0E" if kernel.startswith("rows_") else ""))
             assert len(hits) == 1, (kernel, flag, sorted(hits))
             vgprs, _, _, scratch, _ = next(iter(hits.values()))
             assert scratch == 0 and vgprs <= 128, (kernel, flag, vgprs, scratch)

@@ -97,6 +97,7 @@ def test_per_antenna_rot_matches_the_oracle(plan_mod, torch, n_ant, nchan, num_s
         plan.fx_accumulate(x)
         integ = plan.finalize("SPECTRUM", reset=False)
         assert rel_err(integ, cross_i) < TOL_VIS
+        assert rel_err(plan.finalize("SPECTRUM", reset=False), cross_i) < TOL_VIS      # nothing pending: acc_finish_kernel<true>
         integ_c = plan.finalize("CONTINUUM", BW)
         assert rel_err(integ_c, cross_i.mean(axis=-1) / BW) < TOL_VIS
         plan.fx_accumulate(x)

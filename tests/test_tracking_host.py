@@ -59,7 +59,7 @@ def test_tracked_kernels_compile_without_scratch(asm_listing):  # noqa: F811
     for kernel in ("rows_spectrum_kernel", "rows_continuum_kernel", "rows_continuum_part_kernel"):
         for ant in ("0", "1"):
             for trk in ("0", "1"):
-                hits = {n: r for n, r in res.items() if re.search(r"{}{}ILb{}E".format(len(kernel), kernel, ant), n)}
+                hits = {n: r for n, r in res.items() if re.search(r"{}{}ILb{}ELb{}E".format(len(kernel), kernel, ant, trk), n)}
                 assert len(hits) == 1, (kernel, ant, trk, sorted(hits))
                 vgprs, _, _, scratch, _ = next(iter(hits.values()))
                 assert scratch == 0 and vgprs <= 128, (kernel, ant, trk, vgprs, scratch)
@@ -69,3 +69,13 @@ def test_tracked_kernels_compile_without_scratch(asm_listing):  # noqa: F811
             assert len(hits) == 1, (kernel, flag, sorted(hits))
             vgprs, _, _, scratch, _ = next(iter(hits.values()))
             assert scratch == 0 and vgprs <= 128, (kernel, flag, vgprs, scratch)
+
+
+@needs_hipcc
+def test_rows_kernels_are_one_template(asm_listing):  # noqa: F811
+    """The rows kernels are one text over <ANT, TRACK>: three stems x four instantiations, and no kernel named *_track_kernel
+    (the tracked forms' names before they were template arguments)."""
+    assert "_track_kernel" not in asm_listing
+    names = list(kernel_resources(asm_listing))
+    rows = [n for n in names if re.search(r"\d+rows_(spectrum|continuum|continuum_part)_kernelI", n)]
+    assert len(rows) == 12 and len(set(rows)) == 12, sorted(rows)
