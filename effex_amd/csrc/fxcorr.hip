@@ -141,6 +141,7 @@ int64_t ws_target() {
 #include "k_fringe.h"
 #include "k_gains.h"
 #include "k_flag.h"
+#include "k_average.h"
 #include "k_synth.h"
 #include "h_plan.h"
 #include "h_rtc.h"
@@ -1498,6 +1499,81 @@ int flag_rows_batch(fxc_plan* p, const cf* rows, const float* prior, int64_t n_c
     return FXC_OK;
 }
 
+// The averager (fxcorr.h fxc_average_rows; kernel in k_average.h).  Device rows need no workspace: the launches are bounded by the
+// grid limits alone.  Host rows go through the workspace in slabs: the rows, the weights and the outputs of some whole baselines
+// of one interval (one strided copy in, the slab's outputs copied back), sized by the workspace target (FXC_WS_MB), one baseline
+// at least.  An output cell belongs to one launch, so no bit depends on the sizes.  One synchronisation ends the call.
+int average_rows_batch(fxc_plan* p, const cf* rows, const float* weights, int64_t n_chunks, int mem_kind, int64_t interval, int freq_bin,
+                       cf* out_rows, float* out_weights) {
+    FXC_DEVICE(p, p->device);
+    const int nchan = p->nchan, n_base = p->n_base;
+    const int64_t n_rows = p->n_prod;
+    const int64_t n_int = (n_chunks + interval - 1) / interval;
+    const int n_out = (nchan + freq_bin - 1) / freq_bin;
+    const int tile = kAverageTile / freq_bin * freq_bin;      // the largest multiple of freq_bin within two bins a thread
+    const int64_t out_elems = (int64_t)n_base * n_out;        // per interval
+    const dim3 block(kAverageThreads);
+    const unsigned gx = (unsigned)((nchan + tile - 1) / tile);
+    constexpr int64_t kGridMax = 65535;
+    if (mem_kind == FXC_MEM_DEVICE) {
+        const int64_t c_stride = n_rows * nchan, w_stride = (int64_t)n_base * nchan;
+        const int vec = nchan % 2 == 0 && tile % 2 == 0 && reinterpret_cast<uintptr_t>(rows) % 16 == 0 &&
+                        reinterpret_cast<uintptr_t>(weights) % 8 == 0;
+        for (int64_t s0 = 0; s0 < n_int; s0 += kGridMax) {
+            const int64_t n_s = std::min(kGridMax, n_int - s0), c0 = s0 * interval;
+            for (int64_t b0 = 0; b0 < n_base; b0 += kGridMax) {
+                const int64_t nb = std::min<int64_t>(kGridMax, n_base - b0), at = s0 * out_elems + b0 * n_out;
+                hipLaunchKernelGGL(rows_average_kernel, dim3(gx, (unsigned)nb, (unsigned)n_s), block, 0, p->stream,
+                                   rows + (c0 * n_rows + b0) * nchan, c_stride, weights ? weights + (c0 * n_base + b0) * nchan : nullptr,
+                                   w_stride, interval, n_chunks - c0, out_rows + at, out_weights ? out_weights + at : nullptr, out_elems,
+                                   nchan, freq_bin, tile, n_out, vec);
+                FXC_HIP(p, hipGetLastError());
+            }
+        }
+        FXC_HIP(p, hipStreamSynchronize(p->stream));
+        return FXC_OK;
+    }
+    // per baseline of a slab: the interval's rows (and weights) and the outputs; the four blocks start on 256-byte boundaries
+    const int64_t in_one = interval * nchan * (int64_t)(sizeof(cf) + (weights ? sizeof(float) : 0));
+    const int64_t out_one = n_out * (int64_t)(sizeof(cf) + sizeof(float));
+    const int64_t nb_slab = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_base, kGridMax), (ws_target() - 4 * 256) / (in_one + out_one)));
+    auto up = [](int64_t bytes) { return (bytes + 255) / 256 * 256; };
+    const int64_t rows_bytes = up(nb_slab * interval * nchan * (int64_t)sizeof(cf));
+    const int64_t w_bytes = weights ? up(nb_slab * interval * nchan * (int64_t)sizeof(float)) : 0;
+    const int64_t vis_bytes = up(nb_slab * n_out * (int64_t)sizeof(cf));
+    int rc = ensure_ws(p, rows_bytes + w_bytes + vis_bytes + up(nb_slab * n_out * (int64_t)sizeof(float)));
+    if (rc) return rc;
+    char* ws = static_cast<char*>(p->d_ws);
+    cf* stage = reinterpret_cast<cf*>(ws);
+    float* stage_w = reinterpret_cast<float*>(ws + rows_bytes);
+    cf* stage_vis = reinterpret_cast<cf*>(ws + rows_bytes + w_bytes);
+    float* stage_sum = reinterpret_cast<float*>(ws + rows_bytes + w_bytes + vis_bytes);
+    for (int64_t s = 0; s < n_int; ++s) {
+        const int64_t c0 = s * interval, n = std::min(interval, n_chunks - c0);
+        for (int64_t b0 = 0; b0 < n_base; b0 += nb_slab) {
+            const int64_t nb = std::min<int64_t>(nb_slab, n_base - b0), at = s * out_elems + b0 * n_out;
+            const size_t width = (size_t)(nb * nchan);
+            FXC_HIP(p, hipMemcpy2DAsync(stage, width * sizeof(cf), rows + (c0 * n_rows + b0) * nchan, (size_t)(n_rows * nchan) * sizeof(cf),
+                                        width * sizeof(cf), (size_t)n, hipMemcpyHostToDevice, p->stream));
+            if (weights)
+                FXC_HIP(p, hipMemcpy2DAsync(stage_w, width * sizeof(float), weights + (c0 * n_base + b0) * nchan,
+                                            (size_t)n_base * nchan * sizeof(float), width * sizeof(float), (size_t)n, hipMemcpyHostToDevice,
+                                            p->stream));
+            // the staging blocks are 256-byte aligned: an even width keeps every chunk of the slab 16-byte aligned
+            const int vec = nchan % 2 == 0 && tile % 2 == 0;
+            hipLaunchKernelGGL(rows_average_kernel, dim3(gx, (unsigned)nb, 1), block, 0, p->stream, stage, (int64_t)width,
+                               weights ? stage_w : nullptr, (int64_t)width, interval, n, stage_vis, stage_sum, (int64_t)0, nchan, freq_bin,
+                               tile, n_out, vec);
+            FXC_HIP(p, hipGetLastError());
+            FXC_HIP(p, hipMemcpyAsync(out_rows + at, stage_vis, (size_t)(nb * n_out) * sizeof(cf), hipMemcpyDeviceToHost, p->stream));
+            if (out_weights)
+                FXC_HIP(p, hipMemcpyAsync(out_weights + at, stage_sum, (size_t)(nb * n_out) * sizeof(float), hipMemcpyDeviceToHost, p->stream));
+        }
+    }
+    FXC_HIP(p, hipStreamSynchronize(p->stream));
+    return FXC_OK;
+}
+
 }  // namespace
 
 int fxc_flag_rows(fxc_plan* p, const void* rows, const void* prior, int64_t n_chunks, int mem_kind, int64_t window, float time_threshold,
@@ -1516,6 +1592,21 @@ int fxc_flag_rows(fxc_plan* p, const void* rows, const void* prior, int64_t n_ch
         return fail(p, FXC_ERR_UNSUPPORTED, "%lld chunks in a window: a column lives in LDS, 1024 chunks at most", (long long)window);
     return flag_rows_batch(p, static_cast<const cf*>(rows), static_cast<const float*>(prior), n_chunks, mem_kind, window, time_threshold,
                            freq_threshold, std::min(half_width, p->nchan), iters, static_cast<float*>(weights), counts);
+}
+
+int fxc_average_rows(fxc_plan* p, const void* rows, const void* weights, int64_t n_chunks, int mem_kind, int64_t time_bin, int freq_bin,
+                     void* out_rows, void* out_weights) {
+    if (!p || !rows || !out_rows) return fail(p, FXC_ERR_ARG, "NULL argument");
+    if (n_chunks < 1) return fail(p, FXC_ERR_ARG, "n_chunks=%lld: the averager needs 1 or more chunks", (long long)n_chunks);
+    if (time_bin < 0) return fail(p, FXC_ERR_ARG, "time_bin=%lld is negative", (long long)time_bin);
+    if (freq_bin < 1) return fail(p, FXC_ERR_ARG, "freq_bin=%d is not 1 or more", freq_bin);
+    if (mem_kind != FXC_MEM_HOST && mem_kind != FXC_MEM_DEVICE) return fail(p, FXC_ERR_ARG, "bad mem_kind %d", mem_kind);
+    if (p->n_base < 1) return fail(p, FXC_ERR_ARG, "the averager needs 2 or more antennas, the plan has %d", p->n_ant);
+    if (freq_bin > kAverageMaxBin)
+        return fail(p, FXC_ERR_UNSUPPORTED, "freq_bin=%d: a workgroup's tile holds a whole output bin, 256 input bins at most", freq_bin);
+    if (time_bin == 0 || time_bin > n_chunks) time_bin = n_chunks;
+    return average_rows_batch(p, static_cast<const cf*>(rows), static_cast<const float*>(weights), n_chunks, mem_kind, time_bin, freq_bin,
+                              static_cast<cf*>(out_rows), static_cast<float*>(out_weights));
 }
 
 // The argument checks of both gain solves, in the order that gives each call its code and message; the plain call has no model.

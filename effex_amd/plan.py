@@ -101,6 +101,17 @@ def offset_source_model(n_ant, nchan, bandwidth, frequency, delays_s, flux=1.0):
     return np.stack(out).astype(np.complex64)
 
 
+def averaged_freqs(nchan, bandwidth, frequency, freq_bin=1):
+    """The mean frequency of each output bin of ``FxPlan.average_rows(.., freq_bin=)``, float64 [ceil(nchan / freq_bin)]: the
+    rows' bins in their fftshifted order have the frequencies ``frequency + fftshift(fftfreq(nchan, 1 / bandwidth))``; output bin
+    m is the mean over the input bins [m freq_bin, min((m + 1) freq_bin, nchan)) -- the last one may hold fewer."""
+    nchan, freq_bin = int(nchan), int(freq_bin)
+    if nchan < 1 or freq_bin < 1:
+        raise ValueError("nchan and freq_bin must be 1 or more")
+    freqs = np.fft.fftshift(np.fft.fftfreq(nchan, d=1.0 / bandwidth)) + frequency
+    return np.array([freqs[k:k + freq_bin].mean() for k in range(0, nchan, freq_bin)])
+
+
 def gain_track_solution(chunk, n_solutions, interval, first_chunk):
     """The solution chunk ``chunk`` takes under a gain track (fxcorr.h fxc_set_track_gains):
     ``clamp(floor((chunk - first_chunk) / interval), 0, n_solutions - 1)``; interval 0 (one solution) is solution 0."""
@@ -767,6 +778,43 @@ class FxPlan(object):
         if one:
             weights = weights[0]
         return (weights, counts) if return_counts else weights
+
+    def average_rows(self, rows, weights=None, time_bin=0, freq_bin=1):
+        """The weighted mean of SPECTRUM rows over intervals of chunks and bins of channels (fxcorr.h fxc_average_rows): ``rows``
+        = [n_chunks, n_rows, nchan] complex64 as ``fx_rows(x)`` returns them (numpy, or a CUDA tensor on the plan's device; a 2-D
+        [n_rows, nchan] array is one chunk), ``weights`` = float32 [n_chunks, n_baselines, nchan] in the memory of rows, for
+        instance from ``flag_rows`` (None: every weight 1); a sample counts iff its weight is > 0, and what a sample that does
+        not count holds is never used.  -> (vis [n_int, n_baselines, n_out] complex64, wsum [n_int, n_baselines, n_out] float32)
+        in the memory of rows: one interval per ``time_bin`` chunks (0: one over all), one output bin per ``freq_bin`` input bins
+        (256 at most; the last may be partial, ``averaged_freqs`` gives the bins' frequencies); a cell without a counted sample
+        is 0 with weight 0.  At ``freq_bin`` 1 the pair goes straight into ``solve_gains(vis, weights=wsum)``, ``flag_rows(vis,
+        prior=wsum)`` or ``fringe_fit(vis, ..)``."""
+        self._sync_stream()
+        keep, ptr, kind, shape = self._rows_in(rows, allow_2d=True)
+        device = kind == _lib.FXC_MEM_DEVICE
+        w_keep, w_ptr = None, None
+        if weights is not None:
+            w_keep, w_ptr = self._like_rows(weights, "weights", device)
+            w_shape = (shape[0], self.n_baselines, self.nchan)
+            if tuple(w_keep.shape) != (w_shape[1:] if keep.ndim == 2 else w_shape):
+                raise ValueError("weights must have shape {}, got {}".format(w_shape[1:] if keep.ndim == 2 else w_shape,
+                                                                             tuple(w_keep.shape)))
+        time_bin, freq_bin = int(time_bin), int(freq_bin)
+        span = min(time_bin, shape[0]) if time_bin > 0 else shape[0]
+        out_shape = (-(-shape[0] // span), self.n_baselines, -(-self.nchan // max(freq_bin, 1)))
+        if device:
+            import torch
+            vis = torch.empty(out_shape, dtype=torch.complex64, device=keep.device)      # the call writes every element
+            wsum = torch.empty(out_shape, dtype=torch.float32, device=keep.device)
+            v_ptr, s_ptr = vis.data_ptr(), wsum.data_ptr()
+            if not self._follow:      # a stream of the plan's own: torch's may still be using the blocks it handed out
+                torch.cuda.current_stream(keep.device).synchronize()
+        else:
+            vis = np.zeros(out_shape, dtype=np.complex64)
+            wsum = np.zeros(out_shape, dtype=np.float32)
+            v_ptr, s_ptr = vis.ctypes.data, wsum.ctypes.data
+        self._check(self._lib.fxc_average_rows(self._h, ptr, w_ptr, int(shape[0]), kind, time_bin, freq_bin, v_ptr, s_ptr))
+        return vis, wsum
 
     def set_gains(self, gains, delays_s=None, bandwidth=None, frequency=None):
         """Correct the rows for the per-antenna gains ``gains`` [n_ant, nchan] (one solution of ``solve_gains``, bins in the

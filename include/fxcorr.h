@@ -531,6 +531,46 @@ int fxc_flag_rows(fxc_plan* plan, const void* rows, const void* prior, int64_t n
                   void* weights   /* [n_chunks][n_baselines][nchan] float32, in the memory kind of rows */,
                   int64_t* counts /* [n_win][n_baselines][3], host, may be NULL */);
 
+/* Averager: the weighted mean of the SPECTRUM rows over intervals of chunks and bins of channels, and the summed weights
+ *  -- the integrated visibility spectrum with the flagged samples left out, the product fxc_flag_rows was added
+ * for and the data-reduction step between flagging and whatever comes next.
+ * rows = [n_chunks][n_rows][nchan] complex64 as for fxc_solve_gains, exactly what fxc_fx_rows(.., FXC_MODE_SPECTRUM) writes; only
+ * the first n_baselines rows of a chunk are read: auto rows are skipped.  weights = [n_chunks][n_baselines][nchan] float32 in the
+ * memory kind of rows (fxc_solve_gains_weighted's and fxc_flag_rows' layout), or NULL: no weight buffer is read and every weight
+ * is 1.  A sample counts iff w > 0: a zero, negative or NaN weight leaves it out.  The VALUE of a sample that does not count is
+ * never used: NaN, Inf or 1e30 there changes no output bit.  A counted sample's value is used as it is: a non-finite value with
+ * a positive weight, or with NULL weights, propagates (stated, not checked).
+ * Intervals: with L = time_bin (0: L = n_chunks), interval s covers the chunks [s L, min((s + 1) L, n_chunks)) and n_int =
+ * ceil(n_chunks / L).  Output bins: with F = freq_bin, output bin m covers the input bins [m F, min((m + 1) F, nchan)) of the
+ * rows' fftshifted order, which is monotonic in frequency; n_out = ceil(nchan / F), the last bin may be partial.
+ * Per (interval, baseline, input bin j):
+ *   Sx, Sy, W  start at 0; for the interval's chunks c ascending, if w_c > 0: Sx += (double)w_c (double)x_c, Sy likewise with y_c,
+ *              W += (double)w_c.  The product of two float32 values is exact in float64, so the sums have one value whether or
+ *              not the compiler contracts (the argument of fxc_solve_gains_weighted).
+ * Per output bin m:
+ *   Tx, Ty, Wm start at 0 and add the Sx, Sy, W of its input bins with plain float64 adds, j ascending;
+ *   out_rows[s][b][m]    = Wm > 0 ? ((float)(Tx / Wm), (float)(Ty / Wm)) : (+0, +0): an IEEE float64 division, one rounding to
+ *                          float32;
+ *   out_weights[s][b][m] = (float)Wm.
+ * out_rows = [n_int][n_baselines][n_out] complex64 and out_weights = [n_int][n_baselines][n_out] float32, both in the memory
+ * kind of rows; out_weights may be NULL.  At freq_bin 1 the two have exactly the layout fxc_solve_gains_weighted, fxc_flag_rows
+ * (prior) and fxc_fringe_fit take on a plan without autos.
+ * Multiplying all weights by a power of two changes no bit of out_rows and scales out_weights by that power (barring overflow
+ * and underflow).  No output depends on batching, the workspace target or host against device input.  At freq_bin 1 with NULL
+ * weights out_rows is the complex64 rounding of the V that fxc_solve_gains averages.
+ * Device rows go through in launches bounded by the grid limits; host rows and weights are staged through the workspace in
+ * slabs of whole baselines of one interval and a slab's outputs copied back, so every output cell belongs to one launch.  Uses
+ * the plan's device, stream and workspace; synchronises like fxc_flag_rows (one synchronisation ends the call); neither reads
+ * nor changes the rot tables, the tracks or their counters.  Works from one baseline (2 antennas) up and at nchan 1.
+ * FXC_ERR_ARG, before any device work: a NULL plan / rows / out_rows, n_chunks < 1, time_bin < 0, freq_bin < 1, an unknown
+ * mem_kind, a plan with fewer than 2 antennas.
+ * FXC_ERR_UNSUPPORTED: freq_bin > 256 (one workgroup's tile holds a whole output bin; wider bins are out of scope).
+ * The outputs are written on FXC_OK only. */
+int fxc_average_rows(fxc_plan* plan, const void* rows, const void* weights, int64_t n_chunks, int mem_kind, int64_t time_bin,
+                     int freq_bin,
+                     void* out_rows    /* [n_int][n_baselines][n_out] complex64, in the memory kind of rows */,
+                     void* out_weights /* [n_int][n_baselines][n_out] float32, in the memory kind of rows, may be NULL */);
+
 /* Host-fed front end: replaces the reference's blocking per-chunk copies
  * (effex.py:391-392, 508-509, 693).  A pipe owns `depth` slots of pinned host staging + device buffers.
  * fxc_pipe_acquire hands the producer the pinned input buffer of the next free slot
