@@ -36,6 +36,8 @@ FXC_MEM_DEVICE = 1
 FXC_MEM_DEVICE_TO_PINNED = 2
 FXC_MODE_SPECTRUM = 0
 FXC_MODE_CONTINUUM = 1
+FXC_BEAM_POWER = 0
+FXC_BEAM_VOLTAGE = 1
 FXC_IQ_C64 = 0
 FXC_IQ_U8 = 1
 FXC_IQ_C128 = 2
@@ -124,6 +126,7 @@ SIGNATURES = {
     "fxc_flag_rows": (_c.c_int, [_vp, _vp, _vp, _c.c_int64, _c.c_int, _c.c_int64, _c.c_float, _c.c_float, _c.c_int, _c.c_int, _vp,
                                  _vp]),
     "fxc_average_rows": (_c.c_int, [_vp, _vp, _vp, _c.c_int64, _c.c_int, _c.c_int64, _c.c_int, _vp, _vp]),
+    "fxc_beamform": (_c.c_int, [_vp, _vp, _vp, _c.c_int, _vp, _c.c_int64, _c.c_int, _c.c_int, _c.c_int64]),
     "fxc_pipe_create": (_c.c_int, [_c.POINTER(_vp), _vp, _c.c_int64, _c.c_int, _c.c_int, _c.c_double]),
     "fxc_pipe_create_u8": (_c.c_int, [_c.POINTER(_vp), _vp, _c.c_int64, _c.c_int, _c.c_int, _c.c_double, _c.c_int]),
     "fxc_pipe_create_iq": (_c.c_int, [_c.POINTER(_vp), _vp, _c.c_int64, _c.c_int, _c.c_int, _c.c_double, _c.c_int,

@@ -142,6 +142,7 @@ int64_t ws_target() {
 #include "k_gains.h"
 #include "k_flag.h"
 #include "k_average.h"
+#include "k_beam.h"
 #include "k_synth.h"
 #include "h_plan.h"
 #include "h_rtc.h"
@@ -1574,6 +1575,82 @@ int average_rows_batch(fxc_plan* p, const cf* rows, const float* weights, int64_
     return FXC_OK;
 }
 
+// The beamformer (fxcorr.h fxc_beamform; kernels in k_beam.h), everything on the device.  The workspace holds, each from a
+// 256-byte boundary: the device copy of host weights, a pass's spectra [chunk][antenna][frame][nchan] and -- plans with a track --
+// the pass's effective weights [chunk][beam][antenna][nchan].  A pass takes as many chunks as the workspace target (FXC_WS_MB)
+// allows, one at least; an output element belongs to one thread of one launch and no sum crosses a chunk, so no bit depends on
+// the passes.  Under a track the pass's chunks take the plan's counter onwards; the caller puts it back when the call fails.
+int beamform_dev(fxc_plan* p, const cf* x, const cf* weights, bool weights_on_host, int n_beam, void* out, int64_t n_chunks, int mode,
+                 int64_t tint) {
+    const int nchan = p->nchan, n_ant = p->n_ant;
+    const bool power = mode == FXC_BEAM_POWER;
+    if (tint == 0) tint = p->n_pts;
+    const int64_t n_tbin = (p->n_pts + tint - 1) / tint;
+    auto up = [](int64_t bytes) { return (bytes + 255) / 256 * 256; };
+    const int64_t w_elems = (int64_t)n_beam * n_ant * nchan;
+    const int64_t wcopy_bytes = weights_on_host ? up(w_elems * (int64_t)sizeof(cf)) : 0;
+    const int64_t spec_per_chunk = (int64_t)n_ant * p->n_pts * nchan * (int64_t)sizeof(cf);
+    const int64_t weff_per_chunk = p->track ? w_elems * (int64_t)sizeof(cf) : 0;
+    constexpr int64_t kGridMax = 65535;
+    const int64_t cb = std::max<int64_t>(1, std::min<int64_t>(std::min(n_chunks, kGridMax), (ws_target() - wcopy_bytes) / (spec_per_chunk + weff_per_chunk)));
+    const int64_t spec_bytes = up(cb * spec_per_chunk);
+    int rc = ensure_ws(p, wcopy_bytes + spec_bytes + up(cb * weff_per_chunk));      // (flushes a pending fold: it lives in the workspace)
+    if (rc) return rc;
+    char* base = static_cast<char*>(p->d_ws);
+    cf* spec = reinterpret_cast<cf*>(base + wcopy_bytes);
+    cf* weff = reinterpret_cast<cf*>(base + wcopy_bytes + spec_bytes);
+    if (weights_on_host) {
+        FXC_HIP(p, hipMemcpyAsync(base, weights, (size_t)w_elems * sizeof(cf), hipMemcpyHostToDevice, p->stream));
+        weights = reinterpret_cast<const cf*>(base);
+    }
+    // frames per range (grid.y): whole time bins, 32 frames or more where a bin is shorter; a function of (n_pts, tint) alone
+    const int64_t unit = power ? tint : kBeamFrames;
+    int64_t fpr = unit * std::max<int64_t>(1, 32 / unit);
+    fpr = std::max(fpr, ((p->n_pts + kGridMax - 1) / kGridMax + unit - 1) / unit * unit);
+    const int64_t out_per_chunk = power ? (int64_t)n_beam * n_tbin * nchan * (int64_t)sizeof(float)
+                                        : (int64_t)n_beam * p->n_pts * nchan * (int64_t)sizeof(cf);
+    for (int64_t c0 = 0; c0 < n_chunks; c0 += cb) {
+        const int64_t nc = std::min(cb, n_chunks - c0);
+        rc = run_channelize(p, chunk_at(p, x, c0, false), spec, nc * n_ant);
+        if (rc) return rc;
+        const cf* wk = weights;
+        if (p->track) {
+            const int rg = grow(p, &p->d_track, &p->track_bytes, (size_t)(nc * n_ant * nchan) * sizeof(cd));
+            if (rg) return rg;
+            rc = track_tables(p, p->track_t, nc, static_cast<cd*>(p->d_track), false);
+            if (rc) return rc;
+            p->track_t += nc;
+            hipLaunchKernelGGL(beam_weights_kernel, dim3(grid_for(nc * w_elems, 256, p->cu_count)), dim3(256), 0, p->stream, weights,
+                               static_cast<const cd*>(p->d_track), weff, n_beam, n_ant, nchan, nc);
+            FXC_HIP(p, hipGetLastError());
+            wk = weff;
+        }
+        void* o = static_cast<char*>(out) + c0 * out_per_chunk;
+        const dim3 grid((unsigned)((nchan + kBeamThreads - 1) / kBeamThreads), (unsigned)((p->n_pts + fpr - 1) / fpr), (unsigned)nc);
+        KernelTimer kt(p);
+#define FXC_BEAM_LAUNCH(BT, B0)                                                                                                  \
+    do {                                                                                                                         \
+        if (power)                                                                                                               \
+            hipLaunchKernelGGL((beam_kernel<BT, true>), grid, dim3(kBeamThreads), 0, p->stream, spec, wk, p->track ? w_elems : 0, o, \
+                               n_ant, p->n_pts, nchan, n_beam, B0, tint, fpr, n_tbin);                                           \
+        else                                                                                                                     \
+            hipLaunchKernelGGL((beam_kernel<BT, false>), grid, dim3(kBeamThreads), 0, p->stream, spec, wk, p->track ? w_elems : 0, o, \
+                               n_ant, p->n_pts, nchan, n_beam, B0, tint, fpr, n_tbin);                                           \
+    } while (0)
+        for (int b0 = 0; b0 < n_beam; b0 += kBeamTile) {      // the tile of a call's beams is a function of n_beam alone
+            const int left = n_beam - b0;
+            if (left > 4) FXC_BEAM_LAUNCH(8, b0);
+            else if (left > 2) FXC_BEAM_LAUNCH(4, b0);
+            else if (left > 1) FXC_BEAM_LAUNCH(2, b0);
+            else FXC_BEAM_LAUNCH(1, b0);
+        }
+#undef FXC_BEAM_LAUNCH
+        kt.stop();
+        FXC_HIP(p, hipGetLastError());
+    }
+    return FXC_OK;
+}
+
 }  // namespace
 
 int fxc_flag_rows(fxc_plan* p, const void* rows, const void* prior, int64_t n_chunks, int mem_kind, int64_t window, float time_threshold,
@@ -1607,6 +1684,35 @@ int fxc_average_rows(fxc_plan* p, const void* rows, const void* weights, int64_t
     if (time_bin == 0 || time_bin > n_chunks) time_bin = n_chunks;
     return average_rows_batch(p, static_cast<const cf*>(rows), static_cast<const float*>(weights), n_chunks, mem_kind, time_bin, freq_bin,
                               static_cast<cf*>(out_rows), static_cast<float*>(out_weights));
+}
+
+int fxc_beamform(fxc_plan* p, const void* x, const void* weights, int n_beam, void* out, int64_t n_chunks, int mem_kind, int mode,
+                 int64_t tint) {
+    if (!p) return fail(p, FXC_ERR_ARG, "NULL plan");
+    if (n_chunks < 0) return fail(p, FXC_ERR_ARG, "n_chunks < 0");
+    if (n_beam < 1) return fail(p, FXC_ERR_ARG, "n_beam=%d is not 1 or more", n_beam);
+    if (mode != FXC_BEAM_POWER && mode != FXC_BEAM_VOLTAGE) return fail(p, FXC_ERR_ARG, "bad beam mode %d", mode);
+    if (mem_kind != FXC_MEM_HOST && mem_kind != FXC_MEM_DEVICE) return fail(p, FXC_ERR_ARG, "bad mem_kind %d", mem_kind);
+    if (tint < 0 || tint > p->n_pts) return fail(p, FXC_ERR_ARG, "tint=%lld is not within 0 .. %lld frames", (long long)tint, (long long)p->n_pts);
+    if (n_beam > kBeamMax) return fail(p, FXC_ERR_UNSUPPORTED, "n_beam=%d: a call forms %d beams at most", n_beam, kBeamMax);
+    if (n_chunks == 0 || p->n_pts == 0) return FXC_OK;
+    if (!x || !weights || !out) return fail(p, FXC_ERR_ARG, "NULL buffer");
+    if (p->track && p->live_pipes) return fail(p, FXC_ERR_STATE, "an fxc_pipe uses the plan");
+    FXC_DEVICE(p, p->device);
+    const int64_t t0 = p->track_t;
+    int rc;
+    if (mem_kind == FXC_MEM_DEVICE) {
+        rc = beamform_dev(p, static_cast<const cf*>(x), static_cast<const cf*>(weights), false, n_beam, out, n_chunks, mode, tint);
+    } else {
+        const int64_t n_tbin = tint ? (p->n_pts + tint - 1) / tint : 1;
+        const size_t ob = mode == FXC_BEAM_POWER ? (size_t)n_chunks * n_beam * n_tbin * p->nchan * sizeof(float)
+                                                 : (size_t)n_chunks * n_beam * p->n_pts * p->nchan * sizeof(cf);
+        rc = with_host_staging(p, x, (size_t)n_chunks * p->n_ant * p->num_samp * sizeof(cf), out, ob, [&](const cf* dx, void* dout) {
+            return beamform_dev(p, dx, static_cast<const cf*>(weights), true, n_beam, dout, n_chunks, mode, tint);
+        });
+    }
+    if (rc) p->track_t = t0;
+    return rc;
 }
 
 // The argument checks of both gain solves, in the order that gives each call its code and message; the plain call has no model.

@@ -1,0 +1,135 @@
+// Part of libfxcorr's single translation unit: included by fxcorr.hip (not a stand-alone header).
+#pragma once
+
+namespace {
+
+// ------------------------------------------------------------------------------------------
+// tied-array beamformer (fxcorr.h fxc_beamform): y_b[c,i,k] = sum_a weff[c,b,a,k] f_a[c,i,k] over the spectra the
+// plan's F stage wrote to the workspace as [chunk][antenna][frame][nchan], natural bin order.  The shape of xengine_kernel
+// (k_finish.h): one 64-lane wave per column of 64 channels, 8-byte loads coalesced across channels, every spectrum read once
+// with the nontemporal hint.  A thread keeps BT beams x kBeamFrames frames of complex sums in registers and walks the antennas
+// in index order, two a trip: 2 x 8 samples from HBM and 2 x BT effective weights from L2 in flight, then 2 x BT x 8 complex
+// multiply-adds (four fused multiply-adds each).  BT <= kBeamFrames, so a trip never loads more weights than samples; BT = 8
+// reads the spectra once for up to 8 beams (128 accumulator registers), BT = 4 / 2 / 1 spend no arithmetic on beams that are not
+// there.  More than 8 beams: one launch per tile of 8 (the spectra are read once per tile).  Every register array is indexed
+// by unrolled loops only.
+// ------------------------------------------------------------------------------------------
+constexpr int kBeamThreads = 64;
+constexpr int kBeamFrames = 8;      // F_T
+constexpr int kBeamTile = 8;        // the largest B_T
+constexpr int kBeamMax = 16;        // beams of one call (fxc_beamform)
+
+// weff[c][b][a][k] = w[b][a][k] * (complex64) rho[c][a][k]: the chunk's track table rounded once to float32, then a float32
+// complex product with every operation rounded on its own.  Plans without a track skip this: weff = w, the same for every chunk.
+__global__ __launch_bounds__(256) void beam_weights_kernel(const cf* __restrict__ w, const cd* __restrict__ rho, cf* __restrict__ weff,
+                                                           int n_beam, int n_ant, int nchan, int64_t n_chunks) {
+#pragma clang fp contract(off)
+    const int64_t per_beam = (int64_t)n_ant * nchan;
+    const int64_t total = n_chunks * n_beam * per_beam;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += stride) {
+        const int64_t ak = idx % per_beam;
+        const int64_t cb = idx / per_beam;
+        const int64_t b = cb % n_beam, c = cb / n_beam;
+        const cd r = rho[c * per_beam + ak];
+        const float rx = (float)r.x, ry = (float)r.y;
+        const cf v = w[b * per_beam + ak];
+        weff[idx] = fxc::mk(v.x * rx - v.y * ry, v.x * ry + v.y * rx);
+    }
+}
+
+// NA antennas from `s` (antenna stride s_ant) and their BT weights from `w` (antenna stride nchan, beam b at wb[b]) into y, the
+// antennas in index order
+template <int BT, int NA>
+__device__ __forceinline__ void beam_trip(cf (&y)[BT][kBeamFrames], const cf* __restrict__ s, int64_t s_ant,
+                                          const int64_t (&off)[kBeamFrames], const cf* __restrict__ w, int nchan,
+                                          const int64_t (&wb)[BT]) {
+    cf z[NA][kBeamFrames], g[NA][BT];
+#pragma unroll
+    for (int u = 0; u < NA; ++u) {
+#pragma unroll
+        for (int f = 0; f < kBeamFrames; ++f) z[u][f] = FXC_X_LOAD(s + u * s_ant + off[f]);
+#pragma unroll
+        for (int b = 0; b < BT; ++b) g[u][b] = w[wb[b] + (int64_t)u * nchan];
+    }
+#pragma unroll
+    for (int u = 0; u < NA; ++u)
+#pragma unroll
+        for (int b = 0; b < BT; ++b)
+#pragma unroll
+            for (int f = 0; f < kBeamFrames; ++f) {
+                y[b][f].x = __builtin_fmaf(-g[u][b].y, z[u][f].y, __builtin_fmaf(g[u][b].x, z[u][f].x, y[b][f].x));
+                y[b][f].y = __builtin_fmaf(g[u][b].y, z[u][f].x, __builtin_fmaf(g[u][b].x, z[u][f].y, y[b][f].y));
+            }
+}
+
+// Workgroup (x = column of 64 channels, y = frame range, z = chunk of the pass) forms the beams b0 .. b0 + BT - 1 (those below
+// n_beam are stored; a partial tile reads the last beam's weights again) over the frames [y fpr, min((y + 1) fpr, n_pts)) in
+// tiles of kBeamFrames; the frames past the range's end of a last, partial tile are read as the range's last frame and dropped.
+// weff = [chunk][n_beam][n_ant][nchan] with w_chunk elements between chunks (0: one set for every chunk).
+// POWER: fpr is a multiple of tint, so a range holds whole time bins: the thread adds |y|^2 of a bin's frames in frame order
+// from 0 and stores sum / count at the bin's last frame (count = tint, less in a partial last bin of the chunk), to bin
+// (k + nchan / 2) % nchan -- numpy's fftshift, odd counts included: out[c][b][j][k'] float32.  What a bin's sum is made of does
+// not depend on fpr, the pass or the launch.  Otherwise out[c][b][i][k] = y, complex64, natural order.
+template <int BT, bool POWER>
+__global__ __launch_bounds__(kBeamThreads) void beam_kernel(const cf* __restrict__ spec, const cf* __restrict__ weff, int64_t w_chunk,
+                                                            void* __restrict__ out, int n_ant, int64_t n_pts, int nchan, int n_beam,
+                                                            int b0, int64_t tint, int64_t fpr, int64_t n_tbin) {
+    const int pos = blockIdx.x * kBeamThreads + threadIdx.x;
+    if (pos >= nchan) return;      // part of a wave
+    const int64_t c = blockIdx.z;
+    const int64_t i0 = (int64_t)blockIdx.y * fpr;
+    const int64_t i1 = i0 + fpr < n_pts ? i0 + fpr : n_pts;
+    const int64_t s_ant = n_pts * nchan;
+    const cf* __restrict__ s = spec + c * n_ant * s_ant + pos;
+    const cf* __restrict__ w = weff + c * w_chunk + pos;
+    int64_t wb[BT];
+#pragma unroll
+    for (int b = 0; b < BT; ++b) wb[b] = (int64_t)(b0 + b < n_beam ? b0 + b : n_beam - 1) * n_ant * nchan;
+    float pacc[BT];
+#pragma unroll
+    for (int b = 0; b < BT; ++b) pacc[b] = 0.f;
+    int64_t cnt = 0;
+    int kout = pos + nchan / 2;
+    if (kout >= nchan) kout -= nchan;
+    for (int64_t i = i0; i < i1; i += kBeamFrames) {
+        int64_t off[kBeamFrames];
+#pragma unroll
+        for (int f = 0; f < kBeamFrames; ++f) off[f] = (i + f < i1 ? i + f : i1 - 1) * nchan;
+        cf y[BT][kBeamFrames];
+#pragma unroll
+        for (int b = 0; b < BT; ++b)
+#pragma unroll
+            for (int f = 0; f < kBeamFrames; ++f) y[b][f] = fxc::mk(0.f, 0.f);
+        int a = 0;
+        for (; a + 2 <= n_ant; a += 2) beam_trip<BT, 2>(y, s + a * s_ant, s_ant, off, w + (int64_t)a * nchan, nchan, wb);
+        if (a < n_ant) beam_trip<BT, 1>(y, s + a * s_ant, s_ant, off, w + (int64_t)a * nchan, nchan, wb);
+#pragma unroll
+        for (int f = 0; f < kBeamFrames; ++f) {
+            const int64_t frame = i + f;
+            if (frame >= i1) break;
+            if constexpr (POWER) {
+#pragma unroll
+                for (int b = 0; b < BT; ++b) pacc[b] += __builtin_fmaf(y[b][f].y, y[b][f].y, y[b][f].x * y[b][f].x);
+                ++cnt;
+                if (cnt == tint || frame == n_pts - 1) {
+                    const int64_t j = frame / tint;
+                    const float n = (float)cnt;
+#pragma unroll
+                    for (int b = 0; b < BT; ++b) {
+                        if (b0 + b < n_beam)
+                            static_cast<float*>(out)[((c * n_beam + b0 + b) * n_tbin + j) * nchan + kout] = pacc[b] / n;
+                        pacc[b] = 0.f;
+                    }
+                    cnt = 0;
+                }
+            } else {
+#pragma unroll
+                for (int b = 0; b < BT; ++b)
+                    if (b0 + b < n_beam) static_cast<cf*>(out)[((c * n_beam + b0 + b) * n_pts + frame) * nchan + pos] = y[b][f];
+            }
+        }
+    }
+}
+
+}  // namespace

@@ -33,6 +33,7 @@ def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
 
+BEAM_MODES = {"POWER": _lib.FXC_BEAM_POWER, "VOLTAGE": _lib.FXC_BEAM_VOLTAGE}
 IQ_FORMATS = {"c64": _lib.FXC_IQ_C64, "u8": _lib.FXC_IQ_U8, "c128": _lib.FXC_IQ_C128}
 _IQ_DTYPES = {"c64": np.complex64, "u8": np.uint8, "c128": np.complex128}
 
@@ -98,6 +99,35 @@ def offset_source_model(n_ant, nchan, bandwidth, frequency, delays_s, flux=1.0):
         raise ValueError("delays_s must have {} entries".format(n_ant))
     rot = np.fft.fftshift(rot_tables(nchan, bandwidth, frequency, delays), axes=1)
     out = [float(flux) * np.conj(rot[a]) * rot[b] for a in range(n_ant) for b in range(a + 1, n_ant)]
+    return np.stack(out).astype(np.complex64)
+
+
+def beam_weights(n_ant, nchan, bandwidth, frequency, delays_s=None, beam_delays_s=None, gains=None, taper=None):
+    """Weights [n_beam, n_ant, nchan] complex64 for ``FxPlan.beamform``, natural bin order: beam b's row of antenna a is the
+    table that phases the antenna for ``delays_s[a] + beam_delays_s[b, a]`` -- ``rot_tables(..)``, or with ``gains`` [n_ant, nchan]
+    (one solution of ``solve_gains``, bins in the rows' order) ``gain_tables(gains, .., delays)``, which also undoes the gains --
+    times ``taper[a]`` (default 1 / n_ant: the beam is the mean of the phased antennas).  ``beam_delays_s`` is [n_beam, n_ant]
+    seconds; None is one beam at the phase centre.  ``delays_s`` None is 0: under a delay track the track carries the delays
+    (and ``set_track_gains`` the gains).  Formed in float64 and rounded once."""
+    n_ant, nchan = int(n_ant), int(nchan)
+    base = np.zeros(n_ant) if delays_s is None else np.asarray(delays_s, dtype=np.float64).reshape(-1)
+    if base.shape != (n_ant,):
+        raise ValueError("delays_s must have {} entries".format(n_ant))
+    offsets = np.zeros((1, n_ant)) if beam_delays_s is None else np.asarray(beam_delays_s, dtype=np.float64)
+    if offsets.ndim == 1:
+        offsets = offsets[None]
+    if offsets.ndim != 2 or offsets.shape[0] < 1 or offsets.shape[1] != n_ant:
+        raise ValueError("beam_delays_s must have shape (n_beam, {})".format(n_ant))
+    taper = np.full(n_ant, 1.0 / n_ant) if taper is None else np.asarray(taper, dtype=np.float64).reshape(-1)
+    if taper.shape != (n_ant,):
+        raise ValueError("taper must have {} entries".format(n_ant))
+    out = []
+    for off in offsets:
+        if gains is not None:
+            tables = gain_tables(gains, n_ant, nchan, base + off, bandwidth, frequency)
+        else:
+            tables = rot_tables(nchan, bandwidth, frequency, base + off)
+        out.append(tables * taper[:, None])
     return np.stack(out).astype(np.complex64)
 
 
@@ -401,6 +431,63 @@ class FxPlan(object):
         ptr, kind, n, keep = self._in(x, (self.num_samp,))
         out, optr = self._out(x, (n, self.n_pts, self.nchan), np.complex64)
         self._check(self._lib.fxc_channelize(self._h, ptr, optr, n, kind))
+        return out
+
+    def beamform(self, x, weights, tint=0, mode="POWER", out=None):
+        """Tied-array beams: phased sums of the antennas' spectra (fxcorr.h fxc_beamform).  ``x`` = [n_chunks, n_ant, num_samp]
+        complex64 (numpy, or a CUDA tensor on the plan's device), ``weights`` = [n_beam, n_ant, nchan] complex64 in natural bin
+        order (``beam_weights``; [n_ant, nchan] is one beam; numpy weights with a CUDA ``x`` are moved to the device).  Under a
+        delay track every chunk's tables (gains included) multiply the weights and the track's counter advances; the tables of
+        ``set_rot`` / ``set_rot_ant`` are not applied.  mode "POWER" -> [n_chunks, n_beam, n_tbin, nchan] float32, the mean of
+        |y|^2 over time bins of ``tint`` frames (0: the whole chunk; the last may be partial), bins in the rows' fftshifted
+        order; "VOLTAGE" -> [n_chunks, n_beam, n_pts, nchan] complex64, natural bin order.  numpy in, numpy out; CUDA tensor in,
+        CUDA tensor out.  ``out``: an array / tensor of the result's shape and dtype to receive it.  At most 16 beams."""
+        m = BEAM_MODES[mode.upper()]
+        ptr, kind, n, keep = self._in(x, (self.n_ant, self.num_samp))
+        device = kind == _lib.FXC_MEM_DEVICE
+        if device:
+            import torch
+            if not _is_torch(weights):
+                weights = torch.from_numpy(np.ascontiguousarray(weights, dtype=np.complex64)).to(keep.device)
+            if weights.dtype != torch.complex64 or not weights.is_cuda or weights.device.index != self.device:
+                raise ValueError("device weights must be a complex64 CUDA tensor on device {}".format(self.device))
+            w_keep = weights.contiguous()
+            w_ptr = w_keep.data_ptr()
+        else:
+            if _is_torch(weights):
+                raise ValueError("weights must be in the memory of x: numpy weights for host samples")
+            w_keep = np.ascontiguousarray(weights, dtype=np.complex64)
+            w_ptr = w_keep.ctypes.data
+        w_shape = tuple(w_keep.shape)
+        if len(w_shape) == 2:
+            w_shape = (1,) + w_shape
+        if len(w_shape) != 3 or w_shape[0] < 1 or w_shape[1:] != (self.n_ant, self.nchan):
+            raise ValueError("weights must have shape (n_beam, {}, {}), got {}".format(self.n_ant, self.nchan, tuple(w_keep.shape)))
+        n_beam, tint = int(w_shape[0]), int(tint)
+        if m == _lib.FXC_BEAM_POWER:
+            n_tbin = -(-self.n_pts // tint) if 0 < tint <= self.n_pts else 1      # (a tint out of range: the call answers)
+            shape, dtype = (n, n_beam, n_tbin, self.nchan), np.float32
+        else:
+            shape, dtype = (n, n_beam, self.n_pts, self.nchan), np.complex64
+        if out is not None:
+            if _is_torch(out) != device:
+                raise ValueError("out must be of the same kind (host array / CUDA tensor) as x")
+            if device:
+                tdt = torch.float32 if dtype == np.float32 else torch.complex64
+                if out.dtype != tdt or tuple(out.shape) != shape or not out.is_contiguous() or not out.is_cuda or \
+                        out.device.index != self.device:
+                    raise ValueError("out must be a contiguous {} CUDA tensor of shape {}".format(np.dtype(dtype).name, shape))
+            elif out.dtype != dtype or out.shape != shape or not out.flags.c_contiguous or not out.flags.writeable:
+                raise ValueError("out must be a writable C-contiguous {} array of shape {}".format(np.dtype(dtype).name, shape))
+        elif device:
+            out = torch.empty(shape, dtype=torch.float32 if dtype == np.float32 else torch.complex64, device=keep.device)
+        else:
+            out = np.empty(shape, dtype=dtype)
+        o_ptr = out.data_ptr() if device else out.ctypes.data
+        if device and not self._follow:      # a stream of the plan's own: torch's may still be filling the moved weights
+            torch.cuda.current_stream(keep.device).synchronize()
+        self._beam_keep = (keep, w_keep)     # until the next call: the queued kernels read them
+        self._check(self._lib.fxc_beamform(self._h, ptr, w_ptr, n_beam, o_ptr, n, kind, m, tint))
         return out
 
     # -- F + X ------------------------------------------------------------------------------

@@ -571,6 +571,38 @@ int fxc_average_rows(fxc_plan* plan, const void* rows, const void* weights, int6
                      void* out_rows    /* [n_int][n_baselines][n_out] complex64, in the memory kind of rows */,
                      void* out_weights /* [n_int][n_baselines][n_out] float32, in the memory kind of rows, may be NULL */);
 
+/* Tied-array beamformer: phased sums of the antennas' spectra -- the other product an array with calibrated
+ * per-antenna delays and gains delivers beside visibilities: the sensitivity of the whole array at full time resolution.
+ * With f_a[c,i,k] antenna a's spectrum of frame i of chunk c exactly as fxc_channelize writes it (natural bin order, n_pts =
+ * num_samp / nchan frames a chunk) and weights = w[b][a][k], complex64 [n_beam][n_ant][nchan] in NATURAL bin order like every
+ * rot table, the beam voltage is
+ *     y_b[c,i,k] = sum_{a = 0 .. n_ant-1}  w[b,a,k] * rho_a[k](t_c) * f_a[c,i,k]
+ * rho comes from the plan's state.  A delay track (fxc_set_delay_track, with or without fxc_set_track_gains): rho_a[k](t) is the
+ * chunk's per-antenna table exactly as fxc_delay_track_tables returns it, rounded once to complex64; the call's chunks take
+ * t = the plan's counter, counter + 1, ..; the counter advances by n_chunks as in fxc_fx_rows, and a call that fails puts it
+ * back.  No track: rho = 1.  The tables of fxc_set_rot and fxc_set_rot_ant are NOT applied: they are host tables, and the caller
+ * folds them into w (Python: beam_weights).  The effective weight w * rho is a float32 complex product; the antennas are added
+ * in index order from 0, four fused multiply-adds each.
+ * mode = FXC_BEAM_POWER:   out[c][b][j][k'] float32 [n_chunks][n_beam][n_tbin][nchan] = fftshift_k(mean_{i in bin j} |y_b[c,i,k]|^2):
+ *   the bins in the rows' order (k' = (k + nchan / 2) % nchan, odd counts included).  tint = frames per time bin, 0 = the whole
+ *   chunk; n_tbin = ceil(n_pts / tint); the last bin may be partial and is divided by its own count.  One thread adds a bin's
+ *   |y|^2 in frame order in float32 and divides once: bins of many thousands of frames carry that sum's rounding.
+ * mode = FXC_BEAM_VOLTAGE: out[c][b][i][k] = y_b, complex64 [n_chunks][n_beam][n_pts][nchan], natural bin order, the layout of
+ *   fxc_channelize; tint is ignored (but checked).
+ * x = [n_chunks][n_ant][num_samp] complex64.  x, weights and out are all host memory (FXC_MEM_HOST: staged like the other calls,
+ * synchronous) or all device memory (FXC_MEM_DEVICE: queued on the plan's stream).  The F stage of the plan runs a pass of
+ * chunks into the workspace and one kernel reads every spectrum once (9 .. 16 beams: twice); the passes are sized by the
+ * workspace target (FXC_WS_MB), and no output bit depends on the batch size, the workspace target or host against device
+ * input.  The call does not touch the accumulator (a pending fold is launched first).
+ * FXC_OK: n_chunks == 0 (nothing is read).  FXC_ERR_ARG: a NULL argument, n_beam < 1, n_chunks < 0, an unknown mode or mem_kind
+ * (FXC_MEM_DEVICE_TO_PINNED included), tint < 0 or tint > n_pts.  FXC_ERR_UNSUPPORTED: n_beam > 16.  FXC_ERR_STATE: the plan has
+ * a track and an fxc_pipe uses the plan.
+ * Out of scope: uint8 and complex128 input, pipes, more than 16 beams, incoherent beams (sums of the antennas' powers),
+ * Correlator integration, bench.py. */
+enum fxc_beam_mode { FXC_BEAM_POWER = 0, FXC_BEAM_VOLTAGE = 1 };
+int fxc_beamform(fxc_plan* plan, const void* x, const void* weights, int n_beam, void* out, int64_t n_chunks, int mem_kind, int mode,
+                 int64_t tint);
+
 /* Host-fed front end: replaces the reference's blocking per-chunk copies
  * (effex.py:391-392, 508-509, 693).  A pipe owns `depth` slots of pinned host staging + device buffers.
  * fxc_pipe_acquire hands the producer the pinned input buffer of the next free slot
