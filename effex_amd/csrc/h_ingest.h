@@ -233,7 +233,7 @@ int fx_call(fxc_plan* p, const FxCall& c, const void* x, void* out, int64_t n_ch
     if (done) return FXC_OK;
     FXC_DEVICE(p, p->device);
     if (mem_kind == FXC_MEM_DEVICE) return fx_call_dev(p, c, x, out, n_chunks, false);
-    if (mem_kind != FXC_MEM_HOST) return fail(p, FXC_ERR_ARG, "bad mem_kind %d", mem_kind);
+    if (const int rc = bad_mem_kind(p, mem_kind)) return rc;
     return with_host_staging(p, x, input_bytes(p, c.fmt, n_chunks), out, c.rows ? (size_t)n_chunks * row_bytes(p, c.mode) : 0,
                              [&](const cf* dx, void* dout) { return fx_call_dev(p, c, dx, dout, n_chunks, true); });
 }

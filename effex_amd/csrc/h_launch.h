@@ -321,7 +321,7 @@ int64_t generic_chunks_per_pass(const fxc_plan* p, int64_t n_chunks, const XGeom
     if (cb < 1) cb = 1;
     if (cb > n_chunks) cb = n_chunks;
     if (p->mixed_xeng && cb > 65535 / g.n_splits) cb = std::max<int64_t>(1, 65535 / g.n_splits);   // the X-engines carry chunk and range in grid.y
-    *spec_bytes = (cb * spec_per_chunk + 255) / 256 * 256;
+    *spec_bytes = up256(cb * spec_per_chunk);
     *raw_bytes = cb * raw_per_chunk;
     return cb;
 }
@@ -559,9 +559,9 @@ int64_t fused_chunks_per_pass(const fxc_plan* p, int64_t n_chunks, int64_t* spec
     if (cb < 1) cb = 1;
     if (cb > n_chunks) cb = n_chunks;
     if (p->n_ant > 2 && cb > 65535 / xr) cb = std::max<int64_t>(1, 65535 / xr);   // the X-engines carry group and range in grid.y
-    *spec_bytes = (cb * spec_per_chunk + 255) / 256 * 256;
+    *spec_bytes = up256(cb * spec_per_chunk);
     // 2 antennas: one leading-part row per workgroup after the chunk rows (fx_fused4096_kernel)
-    *raw_bytes = ((cb + (p->n_ant == 2 ? p->fused_grid_max : 0)) * raw_per_chunk + 255) / 256 * 256;
+    *raw_bytes = up256((cb + (p->n_ant == 2 ? p->fused_grid_max : 0)) * raw_per_chunk);
     return cb;
 }
 

@@ -252,6 +252,13 @@ struct DeviceGuard {
                         hipGetErrorString(e__));                                                               \
     } while (0)
 
+int bad_mem_kind(const fxc_plan* p, int mem_kind) {      // FXC_OK for host and for device memory
+    return mem_kind == FXC_MEM_HOST || mem_kind == FXC_MEM_DEVICE ? FXC_OK : fail(p, FXC_ERR_ARG, "bad mem_kind %d", mem_kind);
+}
+
+constexpr int64_t kGridMax = 65535;      // gridDim.y, gridDim.z
+int64_t up256(int64_t bytes) { return (bytes + 255) / 256 * 256; }      // up to the 256-byte boundary a workspace block starts on
+
 int grid_for(int64_t work_items, int block, int cu_count) {
     int64_t g = (work_items + block - 1) / block;
     const int64_t cap = (int64_t)cu_count * 8;

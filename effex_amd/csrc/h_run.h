@@ -30,8 +30,8 @@ AutoPass autos_pass(const fxc_plan* p, int64_t n_chunks, bool rows) {
     cb = std::max<int64_t>(1, std::min<int64_t>(cb, n_chunks));
     cb = std::min<int64_t>(cb, std::max<int64_t>(1, 65535 / a.xr));     // groups x ranges ride in grid.y
     a.cb = cb;
-    a.spec_bytes = (cb * spec_per_chunk + 255) / 256 * 256;
-    a.raw_bytes = (cb * raw_per_chunk + 255) / 256 * 256;
+    a.spec_bytes = up256(cb * spec_per_chunk);
+    a.raw_bytes = up256(cb * raw_per_chunk);
     return a;
 }
 
@@ -186,8 +186,8 @@ struct Workspace {
 };
 
 int carve_ws(fxc_plan* p, bool fold, int64_t spec_bytes, int64_t raw_bytes, Workspace* w) {
-    spec_bytes = (spec_bytes + 255) / 256 * 256;
-    raw_bytes = (raw_bytes + 255) / 256 * 256;
+    spec_bytes = up256(spec_bytes);
+    raw_bytes = up256(raw_bytes);
     const int rc = ensure_ws(p, spec_bytes + raw_bytes + (fold ? fold_part_bytes(p) : 0));
     if (rc) return rc;
     char* base = static_cast<char*>(p->d_ws);

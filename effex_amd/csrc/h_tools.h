@@ -1,0 +1,601 @@
+// Part of libfxcorr's single translation unit: included by fxcorr.hip (not a stand-alone header).
+// The rows tools' drivers -- delays, fringe fit, gain solve, detector, averager, beamformer -- and the host helpers they share.
+// The entry points that check a call's arguments and hand it to a driver are in fxcorr.hip.
+#pragma once
+
+namespace {
+
+// The blocks of a call's workspace, listed once in their order: take() gives the offset of the next block and moves on by
+// exactly `bytes` (a caller that wants a block on a 256-byte boundary rounds with up256 itself), total() is what ensure_ws
+// is asked for, ws_at() the block's address once the workspace stands.
+struct WsCarver {
+    int64_t off = 0;
+    int64_t take(int64_t bytes) { return (off += bytes) - bytes; }
+    int64_t total() const { return off; }
+};
+template <typename T>
+T* ws_at(const fxc_plan* p, int64_t off) { return reinterpret_cast<T*>(static_cast<char*>(p->d_ws) + off); }
+
+// Forward (sign -1, kernel exp(-2 pi i ...) like cp.fft.fft) or inverse (+1, un-normalised) transform of n_lines adjacent lines
+// of len = 2^lg points in buf[0], ping-pong with buf[1]: radix-16 passes, then one radix-8 / 4 / 2 pass for the remaining bits
+// of lg; at most kGridMax lines (gridDim.y) a launch.  -> the index of the buffer that holds the result
+int stockham_lines(fxc_plan* p, cf* const buf[2], int64_t n_lines, int64_t len, int lg, double sign) {
+    int cur = 0;
+    int64_t pp = 1;
+    for (int bits = lg; bits > 0;) {
+        const int r = bits >= 4 ? 4 : bits;
+        for (int64_t l0 = 0; l0 < n_lines; l0 += kGridMax) {
+            const dim3 grid(grid_for(len >> r, 256, p->cu_count), (unsigned)std::min<int64_t>(kGridMax, n_lines - l0));
+            const cf* in = buf[cur] + l0 * len;
+            cf* out = buf[cur ^ 1] + l0 * len;
+            if (r == 4) hipLaunchKernelGGL(stockham_stage_kernel<16>, grid, dim3(256), 0, p->stream, in, out, len, pp, sign);
+            else if (r == 3) hipLaunchKernelGGL(stockham_stage_kernel<8>, grid, dim3(256), 0, p->stream, in, out, len, pp, sign);
+            else if (r == 2) hipLaunchKernelGGL(stockham_stage_kernel<4>, grid, dim3(256), 0, p->stream, in, out, len, pp, sign);
+            else hipLaunchKernelGGL(stockham_stage_kernel<2>, grid, dim3(256), 0, p->stream, in, out, len, pp, sign);
+        }
+        pp <<= r;
+        bits -= r;
+        cur ^= 1;
+    }
+    return cur;
+}
+
+// n rows of `width` elements, dst_stride / src_stride elements from one row to the next, between host and device: a slab of
+// some whole baselines of some chunks of rows, weights or prior
+template <typename T>
+hipError_t copy_rows(fxc_plan* p, T* dst, int64_t dst_stride, const T* src, int64_t src_stride, int64_t width, int64_t n, hipMemcpyKind kind) {
+    return hipMemcpy2DAsync(dst, (size_t)dst_stride * sizeof(T), src, (size_t)src_stride * sizeof(T), (size_t)width * sizeof(T), (size_t)n,
+                            kind, p->stream);
+}
+
+// a call's result words to the host: the one copy and the one synchronisation that end it
+int read_back(fxc_plan* p, const void* dev, int64_t bytes, std::vector<char>& host) {
+    host.resize((size_t)bytes);
+    FXC_HIP(p, hipMemcpyAsync(host.data(), dev, (size_t)bytes, hipMemcpyDeviceToHost, p->stream));
+    FXC_HIP(p, hipStreamSynchronize(p->stream));
+    return FXC_OK;
+}
+
+// the peak's offset from the middle of three magnitudes, in cells: a parabola through their logarithms (effex.py:619-625)
+double peak_offset(double a, double b, double c) {
+    const double la = std::log(a), lb = std::log(b), lc = std::log(c);
+    return 0.5 * (la - lc) / (la - 2.0 * lb + lc);
+}
+
+// 0 .. n - 1 without ref: the order of the results of a call that measures against antenna (stream) ref
+std::vector<int> all_but(int ref, int n) {
+    std::vector<int> v;
+    for (int i = 0; i < n; ++i) if (i != ref) v.push_back(i);
+    return v;
+}
+
+// Delays of n_streams equal-length streams against streams[ref] (effex.py:583-627 for each pair (ref, s)): delays_s[s] is
+// (n - (imax + delta)) / rate of the correlation f_ref * conj(f_s), delays_s[ref] = 0.  The reference's spectrum is formed once;
+// the other streams go through in batches (k_delay.h) of as many as fit the workspace target (FXC_WS_MB), every batch's
+// arg-max words into one result block: one copy to the host and one synchronisation for the whole call.
+int estimate_delays_batch(fxc_plan* p, const cf* const* streams, int n_streams, int ref, int64_t n, int mem_kind, double rate,
+                          double* delays_s) {
+    if (n < 2 || n > (1ll << 28)) return fail(p, FXC_ERR_ARG, "n=%lld out of range", (long long)n);
+    if (!(rate > 0.0)) return fail(p, FXC_ERR_ARG, "rate must be > 0");
+    if (const int rc = bad_mem_kind(p, mem_kind)) return rc;
+    if (n_streams < 2 || ref < 0 || ref >= n_streams) return fail(p, FXC_ERR_ARG, "ref=%d outside [0, %d)", ref, n_streams);
+    FXC_DEVICE(p, p->device);
+    int lg = 1;
+    while ((1ll << lg) < 2 * n) ++lg;
+    const int64_t len = 1ll << lg;
+    // workspace: the reference's two transform buffers, two per stream of a batch, staging for host inputs (the reference
+    // and a batch), the result words of every stream (best[n_streams], then out3[n_streams][3])
+    const int64_t buf_bytes = len * (int64_t)sizeof(cf);
+    const int64_t stage_one = mem_kind == FXC_MEM_HOST ? up256(n * (int64_t)sizeof(cf)) : 0;
+    const int64_t res_bytes = up256((int64_t)n_streams * (8 + 3 * (int64_t)sizeof(cf)));
+    const int64_t fixed = 2 * buf_bytes + stage_one + res_bytes, per_stream = 2 * buf_bytes + stage_one;
+    const int n_other = n_streams - 1;
+    const int64_t fit = (ws_target() - fixed) / per_stream;
+    const int batch = (int)std::max<int64_t>(1, std::min<int64_t>(fit, std::min(n_other, kDelayBatch)));
+    WsCarver ws;
+    const int64_t o_rbuf[2] = {ws.take(buf_bytes), ws.take(buf_bytes)};
+    const int64_t o_sbuf[2] = {ws.take(batch * buf_bytes), ws.take(batch * buf_bytes)};
+    const int64_t o_stage = ws.take((1 + batch) * stage_one), o_res = ws.take(res_bytes);      // stage: [1 + batch][stage_one]
+    if (const int rc = ensure_ws(p, ws.total())) return rc;
+    cf* rbuf[2] = {ws_at<cf>(p, o_rbuf[0]), ws_at<cf>(p, o_rbuf[1])};
+    cf* sbuf[2] = {ws_at<cf>(p, o_sbuf[0]), ws_at<cf>(p, o_sbuf[1])};
+    cf* stage = ws_at<cf>(p, o_stage);
+    unsigned long long* best = ws_at<unsigned long long>(p, o_res);
+    cf* out3 = ws_at<cf>(p, o_res + 8 * (int64_t)n_streams);
+    const int64_t stage_elems = stage_one / (int64_t)sizeof(cf);
+    // stream s as the device sees it: staged into row `row` of the staging block when it is host memory
+    auto device_stream = [&](int s, int row) -> const cf* {
+        if (mem_kind == FXC_MEM_DEVICE) return streams[s];
+        cf* st = stage + row * stage_elems;
+        const hipError_t e = hipMemcpyAsync(st, streams[s], (size_t)n * sizeof(cf), hipMemcpyHostToDevice, p->stream);
+        return e == hipSuccess ? st : nullptr;
+    };
+    const int g_len = grid_for(len, 256, p->cu_count);
+    FXC_HIP(p, hipMemsetAsync(best, 0, 8 * (size_t)n_streams, p->stream));
+    DelayStreams xs{};
+    xs.x[0] = device_stream(ref, 0);
+    if (!xs.x[0]) return fail(p, FXC_ERR_HIP, "host staging copy failed");
+    hipLaunchKernelGGL(delay_pad_kernel, dim3(g_len, 1), dim3(256), 0, p->stream, xs, rbuf[0], n, len);
+    const cf* f_ref = rbuf[stockham_lines(p, rbuf, 1, len, lg, -1.0)];
+    const std::vector<int> others = all_but(ref, n_streams);
+    for (int b0 = 0; b0 < n_other; b0 += batch) {
+        const int nb = std::min(batch, n_other - b0);
+        for (int q = 0; q < nb; ++q) {
+            xs.x[q] = device_stream(others[b0 + q], 1 + q);
+            if (!xs.x[q]) return fail(p, FXC_ERR_HIP, "host staging copy failed");
+        }
+        hipLaunchKernelGGL(delay_pad_kernel, dim3(g_len, nb), dim3(256), 0, p->stream, xs, sbuf[0], n, len);
+        const int cur = stockham_lines(p, sbuf, nb, len, lg, -1.0);
+        hipLaunchKernelGGL(mul_conj_kernel, dim3(g_len, nb), dim3(256), 0, p->stream, f_ref, sbuf[cur], len);   // f_ref * conj(f_s)
+        cf* inv[2] = {sbuf[cur], sbuf[cur ^ 1]};      // back to lags, un-normalised: the peak fit is scale free
+        cf* const r = inv[stockham_lines(p, inv, nb, len, lg, 1.0)];
+        // the batch's streams are consecutive in `others`, so their result words are too
+        hipLaunchKernelGGL(delay_argmax_kernel, dim3(grid_for(2 * n, 256, p->cu_count), nb), dim3(256), 0, p->stream, r, best + b0, n,
+                           len);
+        hipLaunchKernelGGL(delay_fetch_kernel, dim3(nb), dim3(64), 0, p->stream, r, best + b0, out3 + 3 * (int64_t)b0, n, len);
+        FXC_HIP(p, hipGetLastError());
+    }
+    std::vector<char> h_res;
+    if (const int rc = read_back(p, best, res_bytes, h_res)) return rc;
+    const unsigned long long* h_best = reinterpret_cast<const unsigned long long*>(h_res.data());
+    const cf* h3_all = reinterpret_cast<const cf*>(h_res.data() + 8 * (int64_t)n_streams);
+    for (int q = 0; q < n_other; ++q) {
+        const cf* h3 = h3_all + 3 * q;
+        const int64_t imax = (int64_t)(0xFFFFFFFFull - (h_best[q] & 0xFFFFFFFFull));
+        if (imax + 1 >= 2 * n)
+            return fail(p, FXC_ERR_STATE, "correlation peak at the last lag (the reference raises IndexError here)");
+        const double xprev = std::hypot((double)h3[0].x, (double)h3[0].y);
+        const double xbest = std::hypot((double)h3[1].x, (double)h3[1].y);
+        const double xnext = std::hypot((double)h3[2].x, (double)h3[2].y);
+        delays_s[others[q]] = ((double)n - ((double)imax + peak_offset(xprev, xbest, xnext))) / rate;
+    }
+    delays_s[ref] = 0.0;
+    return FXC_OK;
+}
+
+// The fringe fit of the baselines (ref, b), b != ref (fxcorr.h fxc_fringe_fit; kernels in k_fringe.h).  The baselines go
+// through in batches of as many as fit the workspace target (FXC_WS_MB): gather, frequency transform, time transform + peak,
+// stencil; every batch's result words go into one block: one copy to the host and one synchronisation for the whole call.
+int fringe_fit_batch(fxc_plan* p, const cf* rows, int64_t n_chunks, int mem_kind, double bandwidth, double frequency, int ref,
+                     int lk_log, int lt_log, double* delay_s, double* rate_s_per_chunk, double* snr) {
+    FXC_DEVICE(p, p->device);
+    const int n_ant = p->n_ant, nchan = p->nchan, n_other = n_ant - 1;
+    const int64_t lk = 1ll << lk_log, lt = 1ll << lt_log;
+    const int64_t n_rows = p->n_prod;
+    // the time-axis tile: as many adjacent columns (a power of two, 64 at most) as fit the LDS budget beside the twiddles
+    int tm_log = 0, pad = 1;
+    for (int cand = 6; cand >= 0; --cand) {
+        const int64_t tm = 1ll << cand, pd = tm < 32 ? tm : 0;
+        if (tm <= lk && (lt * tm + (lt >> 4) * pd + lt) * (int64_t)sizeof(cf) <= kFringeLdsBytes) {
+            tm_log = cand;
+            pad = (int)pd;
+            break;
+        }
+    }
+    const int64_t lds = (lt * (1ll << tm_log) + (lt >> 4) * pad + lt) * (int64_t)sizeof(cf);
+    const int first_log = lt_log % 4 ? lt_log % 4 : 4;
+    // workspace: two transform buffers [n_chunks][Lk] per baseline of a batch, its rows staged when they are host memory,
+    // and the result words of every baseline (best[n_other], stencil[n_other][5] complex128, part[n_other][kFringeParts])
+    const int64_t buf_one = n_chunks * lk * (int64_t)sizeof(cf);
+    const int64_t stage_one = mem_kind == FXC_MEM_HOST ? up256(n_chunks * nchan * (int64_t)sizeof(cf)) : 0;
+    const int64_t res_bytes = up256((int64_t)n_other * (8 + 80 + 8 * kFringeParts));
+    const int64_t per_base = 2 * buf_one + stage_one;
+    const int64_t fit = (ws_target() - res_bytes) / per_base;
+    const int batch = (int)std::max<int64_t>(1, std::min<int64_t>(fit, std::min(n_other, kFringeBatch)));
+    WsCarver ws;
+    const int64_t o_gbuf[2] = {ws.take(batch * buf_one), ws.take(batch * buf_one)};
+    const int64_t o_stage = ws.take(batch * stage_one), o_res = ws.take(res_bytes);
+    if (const int rc = ensure_ws(p, ws.total())) return rc;
+    FXC_HIP(p, hipFuncSetAttribute(reinterpret_cast<const void*>(&fringe_time_peak_kernel),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, kFringeLdsBytes));
+    cf* gbuf[2] = {ws_at<cf>(p, o_gbuf[0]), ws_at<cf>(p, o_gbuf[1])};
+    cf* stage = ws_at<cf>(p, o_stage);
+    unsigned long long* best = ws_at<unsigned long long>(p, o_res);
+    double* stencil = ws_at<double>(p, o_res + 8 * (int64_t)n_other);
+    double* part = stencil + 10 * (int64_t)n_other;
+    const std::vector<int> others = all_but(ref, n_ant);
+    FXC_HIP(p, hipMemsetAsync(best, 0, 8 * (size_t)n_other, p->stream));
+    for (int b0 = 0; b0 < n_other; b0 += batch) {
+        const int nb = std::min(batch, n_other - b0);
+        FringeRows br{};
+        for (int q = 0; q < nb; ++q) {
+            const int b = others[(size_t)(b0 + q)], lo = std::min(ref, b), hi = std::max(ref, b);
+            const int64_t row = (int64_t)lo * (2 * n_ant - lo - 1) / 2 + (hi - lo - 1);     // the baseline order of the results
+            br.conj[q] = b < ref;
+            if (mem_kind == FXC_MEM_HOST) {
+                cf* st = stage + q * (stage_one / (int64_t)sizeof(cf));
+                FXC_HIP(p, copy_rows(p, st, nchan, rows + row * nchan, n_rows * nchan, nchan, n_chunks, hipMemcpyHostToDevice));
+                br.off[q] = st - stage;
+            } else {
+                br.off[q] = row * nchan;
+            }
+        }
+        const cf* src = mem_kind == FXC_MEM_HOST ? stage : rows;
+        const int64_t t_stride = mem_kind == FXC_MEM_HOST ? nchan : n_rows * nchan;
+        hipLaunchKernelGGL(fringe_gather_kernel, dim3(kFringeParts, nb), dim3(kFringeThreads), 0, p->stream, src, br, t_stride, gbuf[0],
+                           part + (int64_t)b0 * kFringeParts, (int)n_chunks, nchan, lk_log);
+        // frequency axis: forward Stockham stages over the nb n_chunks rows
+        const cf* g = gbuf[stockham_lines(p, gbuf, (int64_t)nb * n_chunks, lk, lk_log, -1.0)];
+        hipLaunchKernelGGL(fringe_time_peak_kernel, dim3((unsigned)(lk >> tm_log), nb), dim3(kFringeThreads), (size_t)lds, p->stream, g,
+                           best + b0, (int)n_chunks, lk_log, lt_log, tm_log, pad, first_log);
+        hipLaunchKernelGGL(fringe_stencil_kernel, dim3(nb), dim3(kFringeThreads), 0, p->stream, g, best + b0,
+                           stencil + 10 * (int64_t)b0, (int)n_chunks, lk_log, lt_log);
+        FXC_HIP(p, hipGetLastError());
+    }
+    std::vector<char> h_res;
+    if (const int rc = read_back(p, best, res_bytes, h_res)) return rc;
+    const unsigned long long* h_best = reinterpret_cast<const unsigned long long*>(h_res.data());
+    const double* h_st = reinterpret_cast<const double*>(h_res.data() + 8 * (int64_t)n_other);
+    const double* h_part = h_st + 10 * (int64_t)n_other;
+    for (int i = 0; i < n_other; ++i) {
+        const unsigned lin = (unsigned)(0xFFFFFFFFull - (h_best[i] & 0xFFFFFFFFull));
+        int64_t q = (int64_t)(lin >> lk_log) & (lt - 1), m = (int64_t)lin & (lk - 1);
+        double a[5];
+        for (int k = 0; k < 5; ++k) a[k] = std::hypot(h_st[(i * 5 + k) * 2], h_st[(i * 5 + k) * 2 + 1]);
+        const double dm = peak_offset(a[1], a[0], a[2]), dq = peak_offset(a[3], a[0], a[4]);
+        if (m >= lk / 2) m -= lk;
+        if (q >= lt / 2) q -= lt;
+        double power = 0.0;
+        for (int k = 0; k < kFringeParts; ++k) power += h_part[(int64_t)i * kFringeParts + k];
+        const int b = others[(size_t)i];
+        delay_s[b] = ((double)m + dm) * (double)nchan / ((double)lk * bandwidth);
+        rate_s_per_chunk[b] = ((double)q + dq) / ((double)lt * frequency);
+        if (snr) snr[b] = a[0] / std::sqrt(power);
+    }
+    delay_s[ref] = 0.0;
+    rate_s_per_chunk[ref] = 0.0;
+    if (snr) snr[ref] = 0.0;
+    return FXC_OK;
+}
+
+// The argument checks of both gain solves, in the order that gives each call its code and message; the plain call has no model.
+// Sets an interval of 0 or beyond the chunks to all of them.
+int check_solve_gains(fxc_plan* p, const void* rows, int64_t n_chunks, int mem_kind, const void* model, int64_t n_model,
+                      int64_t* interval, int ref, int iters, const double* gains_re_im) {
+    if (!p || !rows || !gains_re_im) return fail(p, FXC_ERR_ARG, "NULL argument");
+    if (n_chunks < 1) return fail(p, FXC_ERR_ARG, "n_chunks=%lld: a gain solve needs 1 or more chunks", (long long)n_chunks);
+    if (*interval < 0) return fail(p, FXC_ERR_ARG, "interval=%lld is negative", (long long)*interval);
+    if (ref < 0 || ref >= p->n_ant) return fail(p, FXC_ERR_ARG, "ref=%d outside [0, %d)", ref, p->n_ant);
+    if (iters < 1 || iters > 1000) return fail(p, FXC_ERR_ARG, "iters=%d outside 1 .. 1000", iters);
+    if (const int rc = bad_mem_kind(p, mem_kind)) return rc;
+    if (*interval == 0 || *interval > n_chunks) *interval = n_chunks;
+    const int64_t n_int = (n_chunks + *interval - 1) / *interval;
+    if ((model == nullptr) != (n_model == 0)) return fail(p, FXC_ERR_ARG, "model and n_model=%lld disagree", (long long)n_model);
+    if (model && n_model != 1 && n_model != n_int)
+        return fail(p, FXC_ERR_ARG, "n_model=%lld is neither 1 nor the number of intervals %lld", (long long)n_model, (long long)n_int);
+    if (p->n_ant < 3)
+        return fail(p, FXC_ERR_UNSUPPORTED, "a gain solve needs 3 or more antennas, the plan has %d: one baseline closes nothing", p->n_ant);
+    if (model) {
+        const float* m = static_cast<const float*>(model);
+        const int64_t n = 2 * n_model * (int64_t)p->n_base * p->nchan;
+        for (int64_t i = 0; i < n; ++i)
+            if (!std::isfinite(m[i])) return fail(p, FXC_ERR_ARG, "model value %lld is not finite", (long long)(i / 2));
+    }
+    return FXC_OK;
+}
+
+// The gain solve (fxcorr.h fxc_solve_gains and, `weighted`, fxc_solve_gains_weighted; kernels in k_gains.h).  The workspace holds
+// the results of every interval (gains, step), the averaged matrices of a group of intervals (V; weighted: U and D, 24 bytes per
+// baseline and bin) and, for host rows, a staging block of cross rows (weighted: with a weight block beside it where there are
+// weights); the model of a group of intervals is uploaded once per group (of all intervals once when there is one model).  The
+// intervals go through in groups and a group's host chunks in batches, both sized by the workspace target (FXC_WS_MB).  A batch
+// continues the sums of the batch before it in V (U, D), so no bit depends on the sizes.  One copy to the host and one
+// synchronisation.
+int solve_gains_batch(fxc_plan* p, bool weighted, const cf* rows, const float* weights, int64_t n_chunks, int mem_kind, const cf* model,
+                      int64_t n_model, int64_t interval, int ref, int iters, double* gains_re_im, double* step) {
+    FXC_DEVICE(p, p->device);
+    const int n_ant = p->n_ant, nchan = p->nchan, n_base = p->n_base;
+    const int64_t n_rows = p->n_prod;
+    const int64_t n_int = (n_chunks + interval - 1) / interval;
+    // the solve's tile: as many adjacent bins (a power of two) as give every (antenna, bin) a thread and fit the LDS budget
+    const int tile_bytes = weighted ? kGainsWeightedTileBytes : kGainsTileBytes;
+    const int64_t lds_bin = (int64_t)n_base * tile_bytes + (int64_t)n_ant * kGainsImageBytes;
+    int tm_log = 0;
+    for (int cand = 6; cand >= 0; --cand) {
+        const int64_t tm = 1ll << cand;
+        if (tm <= kGainsMaxTile && n_ant * tm <= kGainsThreads && lds_bin * tm <= kGainsLdsBytes) {
+            tm_log = cand;
+            break;
+        }
+    }
+    const int64_t lds = lds_bin << tm_log;
+    const int64_t elems = (int64_t)n_base * nchan;
+    const int64_t gains_bytes = n_int * n_ant * nchan * (int64_t)sizeof(cd);
+    const int64_t res_bytes = up256(gains_bytes + n_int * nchan * (int64_t)sizeof(double));
+    const int64_t model_one = elems * (int64_t)sizeof(cf);
+    // per interval: V (U + D), and the interval's own model where there is one per interval; a single model is a fixed part
+    const int64_t v_one = elems * tile_bytes + (n_model > 1 ? model_one : 0);
+    const int64_t fixed = n_model == 1 ? model_one : 0;
+    const int64_t stage_one = elems * (int64_t)(sizeof(cf) + (weights ? sizeof(float) : 0));
+    const bool host = mem_kind == FXC_MEM_HOST;
+    const int64_t avail = std::max<int64_t>(0, ws_target() - res_bytes - fixed);
+    const int64_t group = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_int, kGridMax), (host ? avail / 2 : avail) / v_one));
+    const int64_t group_chunks = std::min(n_chunks, group * interval);
+    const int64_t batch = host ? std::max<int64_t>(1, std::min(group_chunks, (avail - group * v_one) / stage_one)) : 0;
+    const int64_t model_slots = n_model > 1 ? group : n_model;
+    WsCarver ws;
+    const int64_t o_res = ws.take(res_bytes), o_v = ws.take(group * elems * tile_bytes);      // gains, then step; V (U, then D)
+    const int64_t o_model = ws.take(model_slots * model_one), o_stage = ws.take(batch * stage_one);      // stage: rows, then weights
+    if (const int rc = ensure_ws(p, ws.total())) return rc;
+    FXC_HIP(p, hipFuncSetAttribute(weighted ? reinterpret_cast<const void*>(&gains_weighted_solve_kernel)
+                                            : reinterpret_cast<const void*>(&gains_solve_kernel),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, kGainsLdsBytes));
+    cd* d_gains = ws_at<cd>(p, o_res);
+    double* d_step = ws_at<double>(p, o_res + gains_bytes);
+    cd* d_v = ws_at<cd>(p, o_v);
+    double* d_d = ws_at<double>(p, o_v + group * elems * (int64_t)sizeof(cd));      // weighted only
+    cf* d_model = ws_at<cf>(p, o_model);
+    cf* stage = ws_at<cf>(p, o_stage);
+    float* stage_w = reinterpret_cast<float*>(stage + batch * elems);
+    const dim3 block(kGainsThreads);
+    const dim3 solve_grid((unsigned)((nchan + (1 << tm_log) - 1) >> tm_log));
+    const dim3 solve_block((unsigned)(((n_ant << tm_log) + 63) / 64 * 64));      // weighted
+    const unsigned gx = (unsigned)(((nchan + 1) / 2 + kGainsThreads - 1) / kGainsThreads);
+    const int64_t model_stride = n_model > 1 ? elems : 0;
+    // rows [c_lo, c_hi) at src, c_stride elements a chunk (weights: elems a chunk), into the intervals sa .. sa + n_s - 1
+    auto average = [&](const cf* src, int64_t c_stride, const float* w, int64_t c_lo, int64_t c_hi, int64_t sa, int64_t n_s, int64_t s0,
+                       const cf* d_m, int vec) {
+        const dim3 grid(gx, n_base, (unsigned)n_s);
+        if (weighted)
+            hipLaunchKernelGGL(gains_weighted_average_kernel, grid, block, 0, p->stream, src, c_stride, w, elems, d_m, model_stride, c_lo, c_hi,
+                               interval, n_chunks, sa, s0, d_v, d_d, n_base, nchan, vec);
+        else
+            hipLaunchKernelGGL(gains_average_kernel, grid, block, 0, p->stream, src, c_stride, c_lo, c_hi, interval, n_chunks, sa, s0, d_v,
+                               n_base, nchan, vec);
+    };
+    if (n_model == 1) FXC_HIP(p, hipMemcpyAsync(d_model, model, (size_t)model_one, hipMemcpyHostToDevice, p->stream));
+    for (int64_t s0 = 0; s0 < n_int; s0 += group) {
+        const int64_t s1 = std::min(n_int, s0 + group), c0 = s0 * interval, c1 = std::min(n_chunks, s1 * interval);
+        if (n_model > 1)
+            FXC_HIP(p, hipMemcpyAsync(d_model, model + s0 * elems, (size_t)((s1 - s0) * model_one), hipMemcpyHostToDevice, p->stream));
+        const cf* d_m = n_model ? d_model : nullptr;
+        if (host) {
+            for (int64_t b0 = c0; b0 < c1; b0 += batch) {
+                const int64_t b1 = std::min(c1, b0 + batch), sa = b0 / interval, sb = (b1 - 1) / interval;
+                FXC_HIP(p, copy_rows(p, stage, elems, rows + b0 * n_rows * nchan, n_rows * nchan, elems, b1 - b0, hipMemcpyHostToDevice));
+                if (weights)
+                    FXC_HIP(p, hipMemcpyAsync(stage_w, weights + b0 * elems, (size_t)((b1 - b0) * elems) * sizeof(float),
+                                              hipMemcpyHostToDevice, p->stream));
+                average(stage, elems, weights ? stage_w : nullptr, b0, b1, sa, sb - sa + 1, s0, d_m, (int)(nchan % 2 == 0));
+            }
+        } else {
+            const int vec = nchan % 2 == 0 && reinterpret_cast<uintptr_t>(rows) % 16 == 0 && reinterpret_cast<uintptr_t>(weights) % 8 == 0;
+            average(rows + c0 * n_rows * nchan, n_rows * nchan, weights ? weights + c0 * elems : nullptr, c0, c1, s0, s1 - s0, s0, d_m, vec);
+        }
+        const dim3 grid(solve_grid.x, (unsigned)(s1 - s0));
+        if (weighted)
+            hipLaunchKernelGGL(gains_weighted_solve_kernel, grid, solve_block, (size_t)lds, p->stream, d_v, d_d, d_gains + s0 * n_ant * nchan,
+                               d_step + s0 * nchan, n_ant, nchan, tm_log, ref, iters);
+        else
+            hipLaunchKernelGGL(gains_solve_kernel, grid, block, (size_t)lds, p->stream, d_v, d_gains + s0 * n_ant * nchan, d_step + s0 * nchan,
+                               n_ant, nchan, tm_log, ref, iters);
+        FXC_HIP(p, hipGetLastError());
+    }
+    std::vector<char> h_res;
+    if (const int rc = read_back(p, d_gains, res_bytes, h_res)) return rc;
+    std::memcpy(gains_re_im, h_res.data(), (size_t)gains_bytes);
+    if (step) std::memcpy(step, h_res.data() + gains_bytes, (size_t)(n_int * nchan) * sizeof(double));
+    return FXC_OK;
+}
+
+// The detector (fxcorr.h fxc_flag_rows; kernels in k_flag.h).  The workspace holds the counts of every window, the level and
+// scatter planes of the windows and baselines of one launch and, for host rows, a slab: the rows, the prior and the weights of
+// some whole baselines of one window (one strided copy each way).  Slabs and window groups are sized by the workspace target
+// (FXC_WS_MB); a column belongs to one launch and a baseline's bins to one slab, so no bit depends on the sizes.
+int flag_rows_batch(fxc_plan* p, const cf* rows, const float* prior, int64_t n_chunks, int mem_kind, int64_t window, float time_threshold,
+                    float freq_threshold, int half_width, int iters, float* weights, int64_t* counts) {
+    FXC_DEVICE(p, p->device);
+    const int nchan = p->nchan, n_base = p->n_base;
+    const int64_t n_rows = p->n_prod;
+    const int64_t n_win = (n_chunks + window - 1) / window;
+    // a wave's columns: as many (a power of two, 16 at most) as leave a lane 8 samples of the longest window -- short loops and
+    // little LDS a wave, so that many waves share a CU --, 2 where the window is longer than that allows (32 samples at 1024 chunks)
+    int q_log = 1;
+    for (int cand = kFlagMaxQLog; cand >= 1; --cand) {
+        if (((window << cand) + 63) / 64 <= kFlagTargetLaneSamples) {
+            q_log = cand;
+            break;
+        }
+    }
+    const int plane_stride = (int)(((window << q_log) + 63) / 64 * 64);
+    const size_t lds = (size_t)(kFlagThreads / 64) * 3 * plane_stride * sizeof(uint32_t);
+    const bool host = mem_kind == FXC_MEM_HOST;
+    const int64_t counts_bytes = up256(n_win * n_base * 3 * (int64_t)sizeof(unsigned long long));
+    const int64_t stats_base = (int64_t)nchan * 2 * (int64_t)sizeof(uint32_t);      // per window and baseline
+    const int64_t slab_base = host ? window * nchan * (int64_t)(sizeof(cf) + sizeof(float) + (prior ? sizeof(float) : 0)) : 0;
+    const int64_t avail = std::max<int64_t>(0, ws_target() - counts_bytes);
+    const int64_t nb_slab = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_base, kGridMax), avail / (stats_base + slab_base)));
+    const int64_t group = host || nb_slab < n_base ? 1
+                                                   : std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_win, kGridMax),
+                                                                                            avail / (stats_base * n_base)));
+    const int64_t slab_elems = nb_slab * window * nchan;      // samples of a host slab
+    WsCarver ws;
+    const int64_t o_counts = ws.take(counts_bytes), o_stats = ws.take(group * nb_slab * stats_base);
+    const int64_t o_stage = ws.take(nb_slab * slab_base);      // host rows: the slab's rows, weights and prior
+    if (const int rc = ensure_ws(p, ws.total())) return rc;
+    FXC_HIP(p, hipFuncSetAttribute(reinterpret_cast<const void*>(&flag_time_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)lds));
+    unsigned long long* d_counts = ws_at<unsigned long long>(p, o_counts);
+    uint32_t* d_stats = ws_at<uint32_t>(p, o_stats);
+    cf* stage = ws_at<cf>(p, o_stage);
+    float* stage_w = reinterpret_cast<float*>(stage + (host ? slab_elems : 0));
+    float* stage_p = stage_w + (host ? slab_elems : 0);
+    FXC_HIP(p, hipMemsetAsync(d_counts, 0, (size_t)counts_bytes, p->stream));
+    const dim3 block(kFlagThreads);
+    const unsigned gx_time = (unsigned)((nchan + (4 << q_log) - 1) / (4 << q_log)), gx_freq = (unsigned)((nchan + kFlagThreads - 1) / kFlagThreads);
+    for (int64_t s0 = 0; s0 < n_win; s0 += group) {
+        const int64_t s1 = std::min(n_win, s0 + group), c0 = s0 * window;
+        for (int64_t b0 = 0; b0 < n_base; b0 += nb_slab) {
+            const int64_t nb = std::min<int64_t>(nb_slab, n_base - b0);
+            unsigned long long* d_c = d_counts + (s0 * n_base + b0) * 3;
+            const dim3 grid_time(gx_time, (unsigned)nb, (unsigned)(s1 - s0)), grid_freq(gx_freq, (unsigned)nb, (unsigned)(s1 - s0));
+            const int64_t w_stride = (int64_t)n_base * nchan, at = (c0 * n_base + b0) * nchan;
+            if (host) {
+                const int64_t n = std::min(window, n_chunks - c0), width = nb * nchan;
+                FXC_HIP(p, copy_rows(p, stage, width, rows + (c0 * n_rows + b0) * nchan, n_rows * nchan, width, n, hipMemcpyHostToDevice));
+                if (prior) FXC_HIP(p, copy_rows(p, stage_p, width, prior + at, w_stride, width, n, hipMemcpyHostToDevice));
+                hipLaunchKernelGGL(flag_time_kernel, grid_time, block, lds, p->stream, stage, width, prior ? stage_p : nullptr, stage_w, width,
+                                   window, n, time_threshold, iters, d_stats, d_c, n_base, nchan, q_log, plane_stride);
+                hipLaunchKernelGGL(flag_freq_kernel, grid_freq, block, 0, p->stream, d_stats, stage_w, width, window, n, freq_threshold,
+                                   half_width, d_c, n_base, nchan);
+                FXC_HIP(p, copy_rows(p, weights + at, w_stride, stage_w, width, width, n, hipMemcpyDeviceToHost));
+            } else {
+                hipLaunchKernelGGL(flag_time_kernel, grid_time, block, lds, p->stream, rows + (c0 * n_rows + b0) * nchan, n_rows * nchan,
+                                   prior ? prior + at : nullptr, weights + at, w_stride, window, n_chunks - c0, time_threshold, iters, d_stats,
+                                   d_c, n_base, nchan, q_log, plane_stride);
+                hipLaunchKernelGGL(flag_freq_kernel, grid_freq, block, 0, p->stream, d_stats, weights + at, w_stride, window, n_chunks - c0,
+                                   freq_threshold, half_width, d_c, n_base, nchan);
+            }
+            FXC_HIP(p, hipGetLastError());
+        }
+    }
+    std::vector<char> h_counts;
+    if (const int rc = read_back(p, d_counts, n_win * n_base * 3 * (int64_t)sizeof(int64_t), h_counts)) return rc;
+    if (counts) std::memcpy(counts, h_counts.data(), h_counts.size());
+    return FXC_OK;
+}
+
+// The averager (fxcorr.h fxc_average_rows; kernel in k_average.h).  Device rows need no workspace: the launches are bounded by the
+// grid limits alone.  Host rows go through the workspace in slabs: the rows, the weights and the outputs of some whole baselines
+// of one interval (one strided copy in, the slab's outputs copied back), sized by the workspace target (FXC_WS_MB), one baseline
+// at least.  An output cell belongs to one launch, so no bit depends on the sizes.  One synchronisation ends the call.
+int average_rows_batch(fxc_plan* p, const cf* rows, const float* weights, int64_t n_chunks, int mem_kind, int64_t interval, int freq_bin,
+                       cf* out_rows, float* out_weights) {
+    FXC_DEVICE(p, p->device);
+    const int nchan = p->nchan, n_base = p->n_base;
+    const int64_t n_rows = p->n_prod;
+    const int64_t n_int = (n_chunks + interval - 1) / interval;
+    const int n_out = (nchan + freq_bin - 1) / freq_bin;
+    const int tile = kAverageTile / freq_bin * freq_bin;      // the largest multiple of freq_bin within two bins a thread
+    const int64_t out_elems = (int64_t)n_base * n_out;        // per interval
+    const dim3 block(kAverageThreads);
+    const unsigned gx = (unsigned)((nchan + tile - 1) / tile);
+    if (mem_kind == FXC_MEM_DEVICE) {
+        const int64_t c_stride = n_rows * nchan, w_stride = (int64_t)n_base * nchan;
+        const int vec = nchan % 2 == 0 && tile % 2 == 0 && reinterpret_cast<uintptr_t>(rows) % 16 == 0 &&
+                        reinterpret_cast<uintptr_t>(weights) % 8 == 0;
+        for (int64_t s0 = 0; s0 < n_int; s0 += kGridMax) {
+            const int64_t n_s = std::min(kGridMax, n_int - s0), c0 = s0 * interval;
+            for (int64_t b0 = 0; b0 < n_base; b0 += kGridMax) {
+                const int64_t nb = std::min<int64_t>(kGridMax, n_base - b0), at = s0 * out_elems + b0 * n_out;
+                hipLaunchKernelGGL(rows_average_kernel, dim3(gx, (unsigned)nb, (unsigned)n_s), block, 0, p->stream,
+                                   rows + (c0 * n_rows + b0) * nchan, c_stride, weights ? weights + (c0 * n_base + b0) * nchan : nullptr,
+                                   w_stride, interval, n_chunks - c0, out_rows + at, out_weights ? out_weights + at : nullptr, out_elems,
+                                   nchan, freq_bin, tile, n_out, vec);
+                FXC_HIP(p, hipGetLastError());
+            }
+        }
+        FXC_HIP(p, hipStreamSynchronize(p->stream));
+        return FXC_OK;
+    }
+    // per baseline of a slab: the interval's rows (and weights) and the outputs; the four blocks start on 256-byte boundaries
+    const int64_t in_one = interval * nchan * (int64_t)(sizeof(cf) + (weights ? sizeof(float) : 0));
+    const int64_t out_one = n_out * (int64_t)(sizeof(cf) + sizeof(float));
+    const int64_t nb_slab = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_base, kGridMax), (ws_target() - 4 * 256) / (in_one + out_one)));
+    WsCarver ws;
+    const int64_t o_stage = ws.take(up256(nb_slab * interval * nchan * (int64_t)sizeof(cf)));
+    const int64_t o_stage_w = ws.take(weights ? up256(nb_slab * interval * nchan * (int64_t)sizeof(float)) : 0);
+    const int64_t o_vis = ws.take(up256(nb_slab * n_out * (int64_t)sizeof(cf))), o_sum = ws.take(up256(nb_slab * n_out * (int64_t)sizeof(float)));
+    if (const int rc = ensure_ws(p, ws.total())) return rc;
+    cf* stage = ws_at<cf>(p, o_stage);
+    float* stage_w = ws_at<float>(p, o_stage_w);
+    cf* stage_vis = ws_at<cf>(p, o_vis);
+    float* stage_sum = ws_at<float>(p, o_sum);
+    for (int64_t s = 0; s < n_int; ++s) {
+        const int64_t c0 = s * interval, n = std::min(interval, n_chunks - c0);
+        for (int64_t b0 = 0; b0 < n_base; b0 += nb_slab) {
+            const int64_t nb = std::min<int64_t>(nb_slab, n_base - b0), at = s * out_elems + b0 * n_out, width = nb * nchan;
+            FXC_HIP(p, copy_rows(p, stage, width, rows + (c0 * n_rows + b0) * nchan, n_rows * nchan, width, n, hipMemcpyHostToDevice));
+            if (weights)
+                FXC_HIP(p, copy_rows(p, stage_w, width, weights + (c0 * n_base + b0) * nchan, (int64_t)n_base * nchan, width, n,
+                                     hipMemcpyHostToDevice));
+            // the staging blocks are 256-byte aligned: an even width keeps every chunk of the slab 16-byte aligned
+            const int vec = nchan % 2 == 0 && tile % 2 == 0;
+            hipLaunchKernelGGL(rows_average_kernel, dim3(gx, (unsigned)nb, 1), block, 0, p->stream, stage, width,
+                               weights ? stage_w : nullptr, width, interval, n, stage_vis, stage_sum, (int64_t)0, nchan, freq_bin,
+                               tile, n_out, vec);
+            FXC_HIP(p, hipGetLastError());
+            FXC_HIP(p, hipMemcpyAsync(out_rows + at, stage_vis, (size_t)(nb * n_out) * sizeof(cf), hipMemcpyDeviceToHost, p->stream));
+            if (out_weights)
+                FXC_HIP(p, hipMemcpyAsync(out_weights + at, stage_sum, (size_t)(nb * n_out) * sizeof(float), hipMemcpyDeviceToHost, p->stream));
+        }
+    }
+    FXC_HIP(p, hipStreamSynchronize(p->stream));
+    return FXC_OK;
+}
+
+// The beamformer (fxcorr.h fxc_beamform; kernels in k_beam.h), everything on the device.  The workspace holds, each from a
+// 256-byte boundary: the device copy of host weights, a pass's spectra [chunk][antenna][frame][nchan] and -- plans with a track --
+// the pass's effective weights [chunk][beam][antenna][nchan].  A pass takes as many chunks as the workspace target (FXC_WS_MB)
+// allows, one at least; an output element belongs to one thread of one launch and no sum crosses a chunk, so no bit depends on
+// the passes.  Under a track the pass's chunks take the plan's counter onwards; the caller puts it back when the call fails.
+int beamform_dev(fxc_plan* p, const cf* x, const cf* weights, bool weights_on_host, int n_beam, void* out, int64_t n_chunks, int mode,
+                 int64_t tint) {
+    const int nchan = p->nchan, n_ant = p->n_ant;
+    const bool power = mode == FXC_BEAM_POWER;
+    if (tint == 0) tint = p->n_pts;
+    const int64_t n_tbin = (p->n_pts + tint - 1) / tint;
+    const int64_t w_elems = (int64_t)n_beam * n_ant * nchan;
+    const int64_t wcopy_bytes = weights_on_host ? up256(w_elems * (int64_t)sizeof(cf)) : 0;
+    const int64_t spec_per_chunk = (int64_t)n_ant * p->n_pts * nchan * (int64_t)sizeof(cf);
+    const int64_t weff_per_chunk = p->track ? w_elems * (int64_t)sizeof(cf) : 0;
+    const int64_t cb = std::max<int64_t>(1, std::min<int64_t>(std::min(n_chunks, kGridMax), (ws_target() - wcopy_bytes) / (spec_per_chunk + weff_per_chunk)));
+    WsCarver ws;
+    const int64_t o_wcopy = ws.take(wcopy_bytes), o_spec = ws.take(up256(cb * spec_per_chunk)), o_weff = ws.take(up256(cb * weff_per_chunk));
+    int rc = ensure_ws(p, ws.total());      // (flushes a pending fold: it lives in the workspace)
+    if (rc) return rc;
+    cf* spec = ws_at<cf>(p, o_spec);
+    cf* weff = ws_at<cf>(p, o_weff);
+    if (weights_on_host) {
+        FXC_HIP(p, hipMemcpyAsync(ws_at<cf>(p, o_wcopy), weights, (size_t)w_elems * sizeof(cf), hipMemcpyHostToDevice, p->stream));
+        weights = ws_at<cf>(p, o_wcopy);
+    }
+    // frames per range (grid.y): whole time bins, 32 frames or more where a bin is shorter; a function of (n_pts, tint) alone
+    const int64_t unit = power ? tint : kBeamFrames;
+    int64_t fpr = unit * std::max<int64_t>(1, 32 / unit);
+    fpr = std::max(fpr, ((p->n_pts + kGridMax - 1) / kGridMax + unit - 1) / unit * unit);
+    const int64_t out_per_chunk = power ? (int64_t)n_beam * n_tbin * nchan * (int64_t)sizeof(float)
+                                        : (int64_t)n_beam * p->n_pts * nchan * (int64_t)sizeof(cf);
+    for (int64_t c0 = 0; c0 < n_chunks; c0 += cb) {
+        const int64_t nc = std::min(cb, n_chunks - c0);
+        rc = run_channelize(p, chunk_at(p, x, c0, false), spec, nc * n_ant);
+        if (rc) return rc;
+        const cf* wk = weights;
+        if (p->track) {
+            const int rg = grow(p, &p->d_track, &p->track_bytes, (size_t)(nc * n_ant * nchan) * sizeof(cd));
+            if (rg) return rg;
+            rc = track_tables(p, p->track_t, nc, static_cast<cd*>(p->d_track), false);
+            if (rc) return rc;
+            p->track_t += nc;
+            hipLaunchKernelGGL(beam_weights_kernel, dim3(grid_for(nc * w_elems, 256, p->cu_count)), dim3(256), 0, p->stream, weights,
+                               static_cast<const cd*>(p->d_track), weff, n_beam, n_ant, nchan, nc);
+            FXC_HIP(p, hipGetLastError());
+            wk = weff;
+        }
+        void* o = static_cast<char*>(out) + c0 * out_per_chunk;
+        const dim3 grid((unsigned)((nchan + kBeamThreads - 1) / kBeamThreads), (unsigned)((p->n_pts + fpr - 1) / fpr), (unsigned)nc);
+        KernelTimer kt(p);
+#define FXC_BEAM_LAUNCH(BT, B0)                                                                                                  \
+    do {                                                                                                                         \
+        if (power)                                                                                                               \
+            hipLaunchKernelGGL((beam_kernel<BT, true>), grid, dim3(kBeamThreads), 0, p->stream, spec, wk, p->track ? w_elems : 0, o, \
+                               n_ant, p->n_pts, nchan, n_beam, B0, tint, fpr, n_tbin);                                           \
+        else                                                                                                                     \
+            hipLaunchKernelGGL((beam_kernel<BT, false>), grid, dim3(kBeamThreads), 0, p->stream, spec, wk, p->track ? w_elems : 0, o, \
+                               n_ant, p->n_pts, nchan, n_beam, B0, tint, fpr, n_tbin);                                           \
+    } while (0)
+        for (int b0 = 0; b0 < n_beam; b0 += kBeamTile) {      // the tile of a call's beams is a function of n_beam alone
+            const int left = n_beam - b0;
+            if (left > 4) FXC_BEAM_LAUNCH(8, b0);
+            else if (left > 2) FXC_BEAM_LAUNCH(4, b0);
+            else if (left > 1) FXC_BEAM_LAUNCH(2, b0);
+            else FXC_BEAM_LAUNCH(1, b0);
+        }
+#undef FXC_BEAM_LAUNCH
+        kt.stop();
+        FXC_HIP(p, hipGetLastError());
+    }
+    return FXC_OK;
+}
+
+}  // namespace

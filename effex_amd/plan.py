@@ -766,6 +766,32 @@ class FxPlan(object):
         keep = np.ascontiguousarray(x, dtype=np.float32)
         return keep, keep.ctypes.data
 
+    def _weights_in(self, x, name, keep_rows, n_chunks, either=False):
+        """``_like_rows`` of ``x`` shaped [n_chunks, n_baselines, nchan], 2-D for 2-D rows (``either``: or 3-D, the shape the message names)"""
+        keep, ptr = self._like_rows(x, name, _is_torch(keep_rows))
+        full = (n_chunks, self.n_baselines, self.nchan)
+        want = full[1:] if keep_rows.ndim == 2 else full
+        got = tuple(keep.shape)
+        if got != want and not (either and got == full):
+            raise ValueError("{} must have shape {}, got {}".format(name, full if either else want, got))
+        return keep, ptr
+
+    @staticmethod
+    def _n_spans(n_chunks, span):
+        """intervals (windows) of ``span`` chunks in ``n_chunks``; 0 or beyond the chunks means all of them in one"""
+        return -(-n_chunks // (min(span, n_chunks) if span > 0 else n_chunks))
+
+    def _out_like_rows(self, shape, dtype, keep, device):
+        """an output of a call in the memory of the rows ``keep`` -> (array, ptr); ``dtype`` = the numpy type"""
+        if device:
+            import torch
+            out = torch.empty(shape, dtype=getattr(torch, np.dtype(dtype).name), device=keep.device)      # the call writes every element
+            if not self._follow:      # a stream of the plan's own: torch's may still be using the block it handed out
+                torch.cuda.current_stream(keep.device).synchronize()
+            return out, out.data_ptr()
+        out = np.zeros(shape, dtype=dtype)
+        return out, out.ctypes.data
+
     def fringe_fit(self, rows, bandwidth, frequency, ref=0, pad=2):
         """Residual delay and delay rate of every antenna against antenna ``ref`` from SPECTRUM rows (fxcorr.h fxc_fringe_fit):
         ``rows`` = [n_chunks, n_rows, nchan] complex64 as ``fx_rows(x)`` returns them (numpy, or a CUDA tensor on the plan's
@@ -796,8 +822,7 @@ class FxPlan(object):
         self._sync_stream()
         keep, ptr, kind, shape = self._rows_in(rows, allow_2d=True)
         interval = int(interval)
-        span = min(interval, shape[0]) if interval > 0 else shape[0]
-        n_int = -(-shape[0] // span)
+        n_int = self._n_spans(shape[0], interval)
         gains = np.zeros((n_int, self.n_ant, self.nchan), dtype=np.complex128)
         step = np.zeros((n_int, self.nchan), dtype=np.float64)
         if weights is None and model is None:
@@ -806,13 +831,7 @@ class FxPlan(object):
             return gains, step
         w_keep, w_ptr = None, None
         if weights is not None:
-            w_keep, w_ptr = self._like_rows(weights, "weights", kind == _lib.FXC_MEM_DEVICE)
-            w_shape = tuple(w_keep.shape)
-            if len(w_shape) == 2 and len(tuple(keep.shape)) == 2:
-                w_shape = (1,) + w_shape
-            if w_shape != (shape[0], self.n_baselines, self.nchan):
-                raise ValueError("weights must have shape ({}, {}, {}), got {}".format(shape[0], self.n_baselines, self.nchan,
-                                                                                      tuple(w_keep.shape)))
+            w_keep, w_ptr = self._weights_in(weights, "weights", keep, shape[0], either=True)
         m_keep, m_ptr, n_model = None, None, 0
         if model is not None:
             m_keep = np.ascontiguousarray(np.asarray(model).astype(np.complex64))
@@ -841,28 +860,15 @@ class FxPlan(object):
         self._sync_stream()
         keep, ptr, kind, shape = self._rows_in(rows, allow_2d=True)
         device = kind == _lib.FXC_MEM_DEVICE
-        one = keep.ndim == 2
-        w_shape = (shape[0], self.n_baselines, self.nchan)
         p_keep, p_ptr = None, None
         if prior is not None:
-            p_keep, p_ptr = self._like_rows(prior, "prior", device)
-            if tuple(p_keep.shape) != (w_shape[1:] if one else w_shape):
-                raise ValueError("prior must have shape {}, got {}".format(w_shape[1:] if one else w_shape, tuple(p_keep.shape)))
+            p_keep, p_ptr = self._weights_in(prior, "prior", keep, shape[0])
         window = int(window)
-        span = min(window, shape[0]) if window > 0 else shape[0]
-        counts = np.zeros((-(-shape[0] // span), self.n_baselines, 3), dtype=np.int64)
-        if device:
-            import torch
-            weights = torch.empty(w_shape, dtype=torch.float32, device=keep.device)      # the call writes every element
-            w_ptr = weights.data_ptr()
-            if not self._follow:      # a stream of the plan's own: torch's may still be using the block it handed out
-                torch.cuda.current_stream(keep.device).synchronize()
-        else:
-            weights = np.zeros(w_shape, dtype=np.float32)
-            w_ptr = weights.ctypes.data
+        counts = np.zeros((self._n_spans(shape[0], window), self.n_baselines, 3), dtype=np.int64)
+        weights, w_ptr = self._out_like_rows((shape[0], self.n_baselines, self.nchan), np.float32, keep, device)
         self._check(self._lib.fxc_flag_rows(self._h, ptr, p_ptr, int(shape[0]), kind, window, float(time_threshold),
                                             float(freq_threshold), int(half_width), int(iters), w_ptr, counts.ctypes.data))
-        if one:
+        if keep.ndim == 2:
             weights = weights[0]
         return (weights, counts) if return_counts else weights
 
@@ -881,25 +887,11 @@ class FxPlan(object):
         device = kind == _lib.FXC_MEM_DEVICE
         w_keep, w_ptr = None, None
         if weights is not None:
-            w_keep, w_ptr = self._like_rows(weights, "weights", device)
-            w_shape = (shape[0], self.n_baselines, self.nchan)
-            if tuple(w_keep.shape) != (w_shape[1:] if keep.ndim == 2 else w_shape):
-                raise ValueError("weights must have shape {}, got {}".format(w_shape[1:] if keep.ndim == 2 else w_shape,
-                                                                             tuple(w_keep.shape)))
+            w_keep, w_ptr = self._weights_in(weights, "weights", keep, shape[0])
         time_bin, freq_bin = int(time_bin), int(freq_bin)
-        span = min(time_bin, shape[0]) if time_bin > 0 else shape[0]
-        out_shape = (-(-shape[0] // span), self.n_baselines, -(-self.nchan // max(freq_bin, 1)))
-        if device:
-            import torch
-            vis = torch.empty(out_shape, dtype=torch.complex64, device=keep.device)      # the call writes every element
-            wsum = torch.empty(out_shape, dtype=torch.float32, device=keep.device)
-            v_ptr, s_ptr = vis.data_ptr(), wsum.data_ptr()
-            if not self._follow:      # a stream of the plan's own: torch's may still be using the blocks it handed out
-                torch.cuda.current_stream(keep.device).synchronize()
-        else:
-            vis = np.zeros(out_shape, dtype=np.complex64)
-            wsum = np.zeros(out_shape, dtype=np.float32)
-            v_ptr, s_ptr = vis.ctypes.data, wsum.ctypes.data
+        out_shape = (self._n_spans(shape[0], time_bin), self.n_baselines, -(-self.nchan // max(freq_bin, 1)))
+        vis, v_ptr = self._out_like_rows(out_shape, np.complex64, keep, device)
+        wsum, s_ptr = self._out_like_rows(out_shape, np.float32, keep, device)
         self._check(self._lib.fxc_average_rows(self._h, ptr, w_ptr, int(shape[0]), kind, time_bin, freq_bin, v_ptr, s_ptr))
         return vis, wsum
 

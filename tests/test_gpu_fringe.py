@@ -264,6 +264,30 @@ def test_outputs_do_not_depend_on_the_batches(plan_mod, torch):
         assert np.array_equal(got["single"][key].view(np.uint64), want.view(np.uint64)), key
 
 
+def test_outputs_do_not_depend_on_the_split_of_the_lines(plan_mod, torch):
+    """More lines in a batch than one launch of a frequency pass takes: 16 baselines of 4096 chunks are 65536 lines, passes of
+    65535 and 1 (gridDim.y).  This process, with the default workspace target, against a child whose target of 1 MiB holds one
+    baseline a batch (4096 lines, no split): the same bits."""
+    n_ant, nchan, n_chunks, ref = 17, 16, 4096, 5
+    rng = np.random.default_rng(17)
+    delays, rates = fringe_ref.draw_antennas(n_ant, nchan, rng)
+    rows = fringe_ref.model_rows(n_chunks, n_ant, nchan, delays, rates, SNR_IN, rng)
+    code = ("import numpy as np, torch, sys; sys.path.insert(0, %r); from effex_amd import plan\n"
+            "dev = torch.from_numpy(np.load(sys.argv[1])).cuda()\n"
+            "with plan.FxPlan(%d, %d, 4, %d) as p:\n"
+            "    np.save(sys.argv[2], np.stack(p.fringe_fit(dev, %r, %r, ref=%d, pad=1)))\n" % (ROOT, n_ant, nchan, nchan * 8, BW, FC, ref))
+    with plan_mod.FxPlan(n_ant, nchan, 4, nchan * 8) as plan:
+        split = np.stack(plan.fringe_fit(torch.from_numpy(rows).cuda(), BW, FC, ref=ref, pad=1))
+    with tempfile.TemporaryDirectory() as tmp:
+        np.save(os.path.join(tmp, "rows.npy"), rows)
+        env = dict(os.environ, FXC_WS_MB="1")
+        res = os.path.join(tmp, "single.npy")
+        subprocess.run([sys.executable, "-c", code, os.path.join(tmp, "rows.npy"), res], check=True, env=env, timeout=600)
+        single = np.load(res)
+    assert split.shape == (3, n_ant) and np.all(split[2, np.arange(n_ant) != ref] > 0.0)
+    assert np.array_equal(single.view(np.uint64), split.view(np.uint64))
+
+
 # -- nothing else moved -------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n_ant,nchan,n_spec", [(3, 64, 20), (2, 4096, 5)])
 def test_fringe_fit_leaves_the_rows_alone(plan_mod, torch, n_ant, nchan, n_spec):
