@@ -53,6 +53,21 @@ FX_HD cf lds_load(const cf* p) {
 #endif
 }
 
+// One 16-byte LDS read that stays where the source puts it: the compiler moves plain reads of the window table up past
+// FXC_SCHED_FENCE() (all sixteen quads of a step in flight, 64 VGPRs); a volatile read keeps its place among the fences.
+FX_HD f4 lds_load4(const f4* p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef float lds_v4f __attribute__((ext_vector_type(4)));
+    typedef const volatile __attribute__((address_space(3))) lds_v4f* lds_v4f_ptr;
+    const lds_v4f u = *(lds_v4f_ptr)(p);
+    f4 r;
+    r.x = u[0]; r.y = u[1]; r.z = u[2]; r.w = u[3];
+    return r;
+#else
+    return *p;
+#endif
+}
+
 constexpr int kN = 4096;
 constexpr int kT = 4;
 constexpr int kThreads = 512;
@@ -145,6 +160,8 @@ struct State {
     cf tw1[16];                  // w4096^(j*k1), k1 = 1..15 ([0] unused): 15 twiddles in 30 VGPRs beat 6 stored
                                  // powers + 9 extra complex multiplies (the kernel is limited by energy per spectrum)
     cf acc[kAccPerThread];       // sum_i spec0*conj(spec1) for this lane's 8 bins
+    cf tw2[16];                  // w256^(j0*q1) of this lane's j0, q1 = 1..kTw2Resident (the rest unused): only the kernel's default
+                                 // instantiation loads them (state_load_twiddles2) -- every other user reads the LDS table each step
 };
 
 // zero PFB history at the start of every chunk; the chunk's frame 0 sits in slot PH
@@ -288,7 +305,9 @@ FX_HD int sample_offset(int j, int r) { return (kN - 1) - j - 256 * r; }
 // in that order); result left in v[r]
 // G: branches per group (the kernel's AUTOS variant takes 2: 16 VGPRs fewer quads in flight, for its power sums)
 // col: this thread's column of the window table (see kLdsWin)
-template <int PH, int G = kFirGroup>
+// PIN: the window reads keep their place between the fences (lds_load4): two groups of quads in flight, no more -- the kernel's
+// default instantiation, whose resident w256 twiddles take registers the other quads would
+template <int PH, int G = kFirGroup, bool PIN = false>
 FX_HD void phase1_fir_col(const State& s, const f4* win, int col, cf (&v)[16]) {
     const int j = col;
     const cf (&x0)[16] = s.h[PH];
@@ -301,12 +320,15 @@ FX_HD void phase1_fir_col(const State& s, const f4* win, int col, cf (&v)[16]) {
     constexpr int NG = 16 / G;
     f4 w[2][G];
 #pragma unroll
-    for (int q = 0; q < G; ++q) w[0][q] = win[q * 256 + j];
+    for (int q = 0; q < G; ++q) w[0][q] = PIN ? lds_load4(win + q * 256 + j) : win[q * 256 + j];
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
         if (g < NG - 1) {
 #pragma unroll
-            for (int q = 0; q < G; ++q) w[(g + 1) & 1][q] = win[(G * (g + 1) + q) * 256 + j];
+            for (int q = 0; q < G; ++q) {
+                const f4* at = win + (G * (g + 1) + q) * 256 + j;
+                w[(g + 1) & 1][q] = PIN ? lds_load4(at) : *at;
+            }
         }
         FXC_SCHED_FENCE();
 #pragma unroll
@@ -318,6 +340,12 @@ FX_HD void phase1_fir_col(const State& s, const f4* win, int col, cf (&v)[16]) {
             a = cfma(t.z, x2[r], a);
             v[r] = cfma(t.w, x3[r], a);
         }
+#if defined(__HIP_DEVICE_COMPILE__)
+        if (PIN) {      // the group's results exist before the next reads go out: an empty statement the reads cannot pass
+#pragma unroll
+            for (int q = 0; q < G; ++q) asm volatile("" : "+v"(v[G * g + q].x), "+v"(v[G * g + q].y));
+        }
+#endif
         FXC_SCHED_FENCE();
     }
 }
@@ -411,6 +439,42 @@ FX_HD void phase2_twiddle(cf (&v)[16], const cf* tw2, int tid) {
         }
         FXC_SCHED_FENCE();
     }
+}
+
+// The same twiddles held in registers across frames (State::tw2): loaded once per launch, the same cmul with the same operands
+// in the same order as phase2_twiddle -- bit-identical, without their ds_read_b64 every step
+// How many of them: q1 = 1 .. kTw2Resident come from State::tw2, the others from the LDS table as before.  Ten is what the kernel's
+// budget of 248 VGPRs (tests/test_autos_host.py) holds without scratch: every further twiddle is two registers more, all fifteen 256
+#ifndef FXC_TW2_RESIDENT
+#define FXC_TW2_RESIDENT 10
+#endif
+constexpr int kTw2Resident = FXC_TW2_RESIDENT;
+static_assert(kTw2Resident >= 0 && kTw2Resident <= 15, "q1 = 1 .. 15");
+FX_HD void state_load_twiddles2(State& s, const cf* tw2_table, int tid) {
+    const int j0 = tid & 15;
+#pragma unroll
+    for (int q1 = 1; q1 <= kTw2Resident; ++q1) s.tw2[q1] = tw2_table[q1 * 16 + j0];
+}
+
+// fetch: the twiddles that are not resident, requested from the LDS table ahead of the radix-16 they follow, so that the reads'
+// latency passes behind its butterflies (read right before their use, as phase2_twiddle does, the wave waits for them)
+FX_HD void phase2_twiddle_fetch(cf (&t)[16], const cf* tw2, int tid) {
+    const int j0 = tid & 15;
+#pragma unroll
+    for (int q1 = kTw2Resident + 1; q1 < 16; ++q1) t[q1] = lds_load(tw2 + q1 * 16 + j0);
+}
+
+// cmul with its two fused multiply-adds spelled out, as the compiler contracts phase2_twiddle's cmul: left to itself it picks the
+// other product of the imaginary part for some of the fetched twiddles, and the last bit of 3 in 16 bins changes
+FX_HD cf cmul_tw(cf a, cf b) {
+    return mk(__builtin_fmaf(a.x, b.x, -(a.y * b.y)), __builtin_fmaf(a.y, b.x, a.x * b.y));
+}
+
+FX_HD void phase2_twiddle_reg(cf (&v)[16], const State& s, const cf (&t)[16]) {
+#pragma unroll
+    for (int q1 = 1; q1 <= kTw2Resident; ++q1) v[q1] = cmul_tw(v[q1], s.tw2[q1]);
+#pragma unroll
+    for (int q1 = kTw2Resident + 1; q1 < 16; ++q1) v[q1] = cmul_tw(v[q1], t[q1]);
 }
 
 // Exchange 2, wave-local: wave w reuses rows 2 w, 2 w + 1 of the four planes -- the rows its own phase 2 read, nobody

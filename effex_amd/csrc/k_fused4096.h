@@ -31,17 +31,44 @@ typedef unsigned v4u32 __attribute__((ext_vector_type(4)));
 #define FXC_LOAD_AUX 2   // cache policy of the IQ stream loads: bit 0 sc0, bit 1 nt, bit 4 sc1.  nt (the samples are read once): the
                          // headline kernel 8.57 - 8.66 -> 8.47 - 8.49 ms, the F-only variant of 8 antennas - 1.6 % (profiles/r05/experiments.md 10)
 #endif
+#ifndef FXC_PAIR_SOFF
+#define FXC_PAIR_SOFF 1  // two branch rows per scalar offset: row 2k + 1 rides on the offset of row 2k through a second descriptor, whose
+                         // base lies one row (2 048 bytes) further on.  (The load's 12-bit immediate would do as well, but the constant has
+                         // to be added to the VGPR offset for that, and the compiler hoists that sum into a VGPR of its own -- which the
+                         // default instantiation does not have.  The second descriptor costs scalar registers only.)
+#endif
+// What the complex64 loads of a frame work from: the base of the frame's chunk and the two descriptors made of it, of the base
+// itself and of the base one branch row further on (the range check is on the VGPR offset alone).  The kernel's step carries one
+// of these in scalar registers from step to step (FXC_CARRY_BASE).
+struct FetchBase {
+    const cf* base;
+    __amdgpu_buffer_rsrc_t rs, rs_odd;
+};
+__device__ __forceinline__ void fetch_base_set(FetchBase& fb, const cf* chunk_base, unsigned chunk_bytes) {
+    fb.base = chunk_base;
+    fb.rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<cf*>(chunk_base), 0, (int)chunk_bytes, 0x00020000);
+    fb.rs_odd = __builtin_amdgcn_make_buffer_rsrc(const_cast<cf*>(chunk_base + 256), 0, (int)chunk_bytes, 0x00020000);
+}
+
+template <int R0, int CNT>
+__device__ __forceinline__ void load_frame_part(cf (&xr)[16], const FetchBase& fb, unsigned voff, int64_t i) {
+    const __amdgpu_buffer_rsrc_t rs = fb.rs, rs_odd = fb.rs_odd;
+    const unsigned soff = (unsigned)(i * fxc::fused::kN * (int64_t)sizeof(cf));
+    constexpr unsigned kRowBytes = 256 * sizeof(cf);
+    static_assert(R0 % 2 == 0 && CNT % 2 == 0, "whole row pairs");
+#pragma unroll
+    for (int r = R0; r < R0 + CNT; ++r) {
+        const int row = 15 - r, srow = FXC_PAIR_SOFF ? (row & ~1) : row;
+        const v2u32 d = __builtin_amdgcn_raw_buffer_load_b64(row != srow ? rs_odd : rs, voff, soff + (unsigned)srow * kRowBytes, FXC_LOAD_AUX);
+        xr[r] = fxc::mk(__uint_as_float(d[0]), __uint_as_float(d[1]));
+    }
+}
 template <int R0, int CNT>
 __device__ __forceinline__ void load_frame_part(cf (&xr)[16], const cf* chunk_base, unsigned chunk_bytes, unsigned voff,
                                                 int64_t i) {
-    __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<cf*>(chunk_base), 0, (int)chunk_bytes,
-                                                                   0x00020000);
-    const unsigned soff = (unsigned)(i * fxc::fused::kN * (int64_t)sizeof(cf));
-#pragma unroll
-    for (int r = R0; r < R0 + CNT; ++r) {
-        const v2u32 d = __builtin_amdgcn_raw_buffer_load_b64(rs, voff, soff + (unsigned)(256 * (15 - r) * sizeof(cf)), FXC_LOAD_AUX);
-        xr[r] = fxc::mk(__uint_as_float(d[0]), __uint_as_float(d[1]));
-    }
+    FetchBase fb;
+    fetch_base_set(fb, chunk_base, chunk_bytes);
+    load_frame_part<R0, CNT>(xr, fb, voff, i);
 }
 
 // uint8 ingest (RTL-SDR interleaved I,Q bytes): the same 16 branches as raw byte pairs, one
@@ -105,8 +132,10 @@ constexpr int kAutoLdsBytes = fxc::fused::kAccPerThread * fxc::fused::kThreads *
         if (U8)                                                                                                 \
             load_frame_part_u8<R0, 4>(nx, reinterpret_cast<const unsigned short*>(x) + (int64_t)pc * 2 * num_samp, \
                                       chunk_bytes, voff, nframe);                                               \
+        else if (FXC_CARRY_BASE)                                                                                \
+            load_frame_part<R0, 4>(nx, fb, voff, nframe);                                                       \
         else                                                                                                    \
-            load_frame_part<R0, 4>(nx, nbase, chunk_bytes, voff, nframe);                                       \
+            load_frame_part<R0, 4>(nx, x + (int64_t)pc * 2 * num_samp, chunk_bytes, voff, nframe);              \
         FXC_SCHED_FENCE();                                                                                      \
     } while (0)
 #endif
@@ -231,13 +260,24 @@ __device__ __forceinline__ cf dck_offset(unsigned* acc, unsigned* red, int tid, 
     return fxc::mk((float)(-mr / 127.5), (float)(-mi / 127.5));
 }
 
+#ifndef FXC_REG_TW2
+#define FXC_REG_TW2 1    // the default instantiation holds ten of its fifteen w256 twiddles in VGPRs (State::tw2, kTw2Resident) and bounds the
+                         // FIR's window quads in flight; it stays at its 248 VGPRs
+#endif
+#ifndef FXC_CARRY_BASE
+#define FXC_CARRY_BASE 1 // complex64 ingest: the chunk base of the frame being prefetched and its buffer descriptors are carried from step to
+                         // step (FetchBase) and moved by an addition where the prefetch changes chunk, instead of the 64-bit product
+                         // chunk * 2 * num_samp and two fresh descriptors every step
+#endif
+// (A fast path round the walk's general code for steps that end neither a chunk nor the part -- 32 scalar instructions a step instead
+// of 54 -- measured no gain on top of this and was taken out again: profiles/r08/experiments.md 2.)
 #ifndef FXC_SPEC_STORE_AUX
 #define FXC_SPEC_STORE_AUX 2      // cache policy of the F-only spectra stores: nt (written once, read by the X pass: 8 antennas 2.35 -> 2.19 ms)
 #endif
 template <int PH, bool SPEC_OUT, bool U8, bool DCK, bool AUTOS>
 __device__ __forceinline__ void fused_step(fxc::fused::State& s, float (&pw)[fxc::fused::kAccPerThread], float* pw_lds, U8State& u8, const cf* dc, const f4* win, cf* region,
                                            const cf* tw2, int tid, const cf* x, int64_t num_samp, unsigned chunk_bytes,
-                                           unsigned voff, fxc::fused::RangeWalk& pos, cf* rows_raw, int hp, v4u32_t* dck_stage,
+                                           unsigned voff, fxc::fused::RangeWalk& pos, FetchBase& fb, cf* rows_raw, int hp, v4u32_t* dck_stage,
                                            unsigned* dck_acc, unsigned* dck_red,
                                            unsigned long long (&seg)[kStampSegs], unsigned long long& t_prev) {
     using namespace fxc::fused;
@@ -257,7 +297,8 @@ __device__ __forceinline__ void fused_step(fxc::fused::State& s, float (&pw)[fxc
     const unsigned char* dck_base = reinterpret_cast<const unsigned char*>(x) + (int64_t)(c + (dck_next ? 1 + pos.seg_jump : 0)) * 4 * num_samp;
     if (U8) convert_frame_u8(s.h[PH], u8.off);   // the byte pairs fetched a step ago become the samples of slot PH
     cf v[16];
-    phase1_fir_col<PH, AUTOS ? 2 : kFirGroup>(s, win, tid & 255, v);      // (window in hardware-thread order) first use of this frame: waits for its loads (issued a step ago)
+    constexpr bool REG_TW2 = FXC_REG_TW2 && !SPEC_OUT && !U8 && !DCK && !AUTOS;
+    phase1_fir_col<PH, AUTOS ? 2 : kFirGroup, REG_TW2>(s, win, tid & 255, v);      // (window in hardware-thread order) first use of this frame: waits for its loads (issued a step ago)
     FXC_STAMP(2);
     // The oldest ring slot is dead now: refill it with the next frame of this workgroup's range (next frame of
     // the chunk, or frame 0 of the next chunk; at the very end the current frame again, never used).  The 16
@@ -265,7 +306,13 @@ __device__ __forceinline__ void fused_step(fxc::fused::State& s, float (&pw)[fxc
     // stall in the in-order vector-memory issue (measured -7 %).
     int pc, nframe;
     range_walk_prefetch(pos, pc, nframe);
-    const cf* nbase = x + (int64_t)pc * 2 * num_samp;
+    // complex64 ingest: fb holds the base of the current frame's chunk (what the previous step fetched from); it moves on, by an
+    // addition, where the prefetch starts another chunk (segment jump included: pc - c chunks) -- a uniform, rarely taken branch: no
+    // 64-bit product and no fresh descriptors in the steady step
+    if (FXC_CARRY_BASE && !U8 && pc != pos.c) {
+        asm volatile("" ::: "memory");
+        fetch_base_set(fb, fb.base + (int64_t)(pc - pos.c) * 2 * num_samp, chunk_bytes);
+    }
     cf (&nx)[16] = s.h[(PH + 1) & 3];
     FXC_PREFETCH(0);
     fxc::dft16_a(v);
@@ -292,13 +339,16 @@ __device__ __forceinline__ void fused_step(fxc::fused::State& s, float (&pw)[fxc
         dck_fetch(dck_base, num_samp, i, tid, dck_stage);
     }
     FXC_STAMP(6);
+    cf tw2_late[16];      // (in front of phase 2's own reads: LDS reads return in order, so the waits for those cover these)
+    if (REG_TW2) phase2_twiddle_fetch(tw2_late, tw2, tid);
 #if !(FXC_ABL & 4)
     phase2_load(region, tid, v);
 #endif
     FXC_PREFETCH(8);
     fxc::dft16(v);
     FXC_STAMP(7);
-    phase2_twiddle(v, tw2, tid);
+    if (REG_TW2) phase2_twiddle_reg(v, s, tw2_late);
+    else phase2_twiddle(v, tw2, tid);
     FXC_STAMP(8);
 #if !(FXC_ABL & 8)
     wave_sync();       // exchange 2 is a 16x16 transpose inside each 16-lane group: no s_barrier
@@ -424,6 +474,7 @@ __global__ __launch_bounds__(fxc::fused::kThreads, 2) void fx_fused4096_kernel(
     if (tid < 256) tw2[tid] = tw2_g[tid];
     State s;
     state_load_twiddles(s, tw1_g, (ant << 8) | j);
+    if (FXC_REG_TW2 && !SPEC_OUT && !U8 && !DCK && !AUTOS) state_load_twiddles2(s, tw2_g, tid);
 #pragma unroll
     for (int q = 0; q < kAccPerThread; ++q) s.acc[q] = fxc::mk(0.f, 0.f);
     static_assert(!AUTOS || (!SPEC_OUT && !U8), "autos: the complex64 F+X variant only");
@@ -501,16 +552,18 @@ __global__ __launch_bounds__(fxc::fused::kThreads, 2) void fx_fused4096_kernel(
             load_frame_part_u8<0, 16>(s.h[0], reinterpret_cast<const unsigned short*>(cbase), chunk_bytes, voff, pos.i);
         else
             load_frame_part<0, 16>(s.h[0], cbase, chunk_bytes, voff, pos.i);
+        FetchBase fb;                 // (complex64 ingest: what the step's prefetches work from, fused_step)
+        fetch_base_set(fb, cbase, chunk_bytes);
         // frame g of the part sits in ring slot g & 3: unrolled by four so the ring rotates by register renaming
 #pragma unroll 1
         for (int g = 0; g < total; g += 4) {
-            fused_step<0, SPEC_OUT, U8, DCK, AUTOS>(s, pw, pw_lds, u8, dc, win, region, tw2, tid, x, num_samp, chunk_bytes, voff, pos, rows_raw, SPEC_OUT ? unit : 0, dck_stage, dck_acc, dck_red, seg_t, t_prev);
+            fused_step<0, SPEC_OUT, U8, DCK, AUTOS>(s, pw, pw_lds, u8, dc, win, region, tw2, tid, x, num_samp, chunk_bytes, voff, pos, fb, rows_raw, SPEC_OUT ? unit : 0, dck_stage, dck_acc, dck_red, seg_t, t_prev);
             if (g + 1 < total)
-                fused_step<1, SPEC_OUT, U8, DCK, AUTOS>(s, pw, pw_lds, u8, dc, win, region, tw2, tid, x, num_samp, chunk_bytes, voff, pos, rows_raw, SPEC_OUT ? unit : 0, dck_stage, dck_acc, dck_red, seg_t, t_prev);
+                fused_step<1, SPEC_OUT, U8, DCK, AUTOS>(s, pw, pw_lds, u8, dc, win, region, tw2, tid, x, num_samp, chunk_bytes, voff, pos, fb, rows_raw, SPEC_OUT ? unit : 0, dck_stage, dck_acc, dck_red, seg_t, t_prev);
             if (g + 2 < total)
-                fused_step<2, SPEC_OUT, U8, DCK, AUTOS>(s, pw, pw_lds, u8, dc, win, region, tw2, tid, x, num_samp, chunk_bytes, voff, pos, rows_raw, SPEC_OUT ? unit : 0, dck_stage, dck_acc, dck_red, seg_t, t_prev);
+                fused_step<2, SPEC_OUT, U8, DCK, AUTOS>(s, pw, pw_lds, u8, dc, win, region, tw2, tid, x, num_samp, chunk_bytes, voff, pos, fb, rows_raw, SPEC_OUT ? unit : 0, dck_stage, dck_acc, dck_red, seg_t, t_prev);
             if (g + 3 < total)
-                fused_step<3, SPEC_OUT, U8, DCK, AUTOS>(s, pw, pw_lds, u8, dc, win, region, tw2, tid, x, num_samp, chunk_bytes, voff, pos, rows_raw, SPEC_OUT ? unit : 0, dck_stage, dck_acc, dck_red, seg_t, t_prev);
+                fused_step<3, SPEC_OUT, U8, DCK, AUTOS>(s, pw, pw_lds, u8, dc, win, region, tw2, tid, x, num_samp, chunk_bytes, voff, pos, fb, rows_raw, SPEC_OUT ? unit : 0, dck_stage, dck_acc, dck_red, seg_t, t_prev);
         }
         frames_done += total;
     }

@@ -10,7 +10,8 @@ mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
 pass() {
   local name=$1; shift
-  rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d "$out/$name" -o t -- python3 "$root/tools/kbench.py" --frames 10000 --reps 4 --path fused > "$out/$name.log" 2>&1
+  # (a pass that fails or outlasts its time limit ends the collection: nothing more is started on the GPU after it)
+  timeout -k 10 300 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d "$out/$name" -o t -- python3 "$root/tools/kbench.py" --frames 10000 --reps 4 --path fused > "$out/$name.log" 2>&1 || { rc=$?; echo "pass $name: exit $rc"; tail -5 "$out/$name.log"; exit $rc; }
 }
 pass cycles SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAVES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY
 pass insts SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM
