@@ -1,16 +1,12 @@
 // Part of libfxcorr's single translation unit: included by fxcorr.hip (not a stand-alone header).
 #pragma once
 
-// per-path launchers: which kernels a pass over a batch of chunks takes, and how the workspace is cut into passes
+// per-path launchers: which kernels a pass over a batch of chunks takes, and how the workspace is cut into passes -- the sizing
+// rules (each once), then the launchers (FusedLaunch, SpecLaunch, TiledLaunch: their launch descriptions), then the routes' *_raw_sums
 
 namespace {
 
-int launch_fused(fxc_plan* p, const cf* x, int64_t n_pairs, cf* out, bool spec_out, const cf* dc_u8 = nullptr,
-                 int64_t unit = 1, bool rows_are_chunks = true, int64_t num_samp = 0, bool dck = false, int whole_grid = 0);
-
-// F-stage of `n_streams` streams: x -> spec (both device, natural bin order)
-int tiled_channelize(fxc_plan* p, const cf* x, cf* spec, int64_t n_streams, int spec_a = 0);
-int64_t spec_wg_splits(const fxc_plan* p, const SpecKernel* k, int64_t n_groups, bool sums);
+// ---- sizing: which kernels a plan takes, and every launch's geometry --------------------------------------------------------
 
 // Every route cuts a chunk's frames into runs (float32 partial sums) by the size of the call: more runs for few chunks, to fill the
 // device.  Under a delay track the rows of a chunk must not depend on the call that brought it (fxcorr.h), so the routes then ask
@@ -21,9 +17,19 @@ int64_t split_basis(const fxc_plan* p, int64_t n_chunks) { return p->track ? (in
 // Slots of one wave (tpr <= 64) go without the workgroup barrier between their steps: measured on one box, two antennas
 // 7 - 16 % faster at 8 ... 250 channels, F only 5 - 7 % faster at 96 ... 250 but 17 % slower at 12 (slots of 4 threads) -- so F
 // only from 16 threads per slot.  Developer knob: FXC_MIXED_WAVELOCAL=0 keeps the barrier everywhere.
+constexpr bool kFusedX = true, kFOnly = false;
 int mixed_wave_local(const fxc_plan* p, bool fused_x) {
     static const int v = FXC_DEV_ENV_INT("FXC_MIXED_WAVELOCAL", 1);
     return v && (fused_x || p->mixed_tpr >= 16);
+}
+
+// Workgroups of pfb_fft_mixed_kernel's F-only forms over n_groups frame groups: runs of up to `run_cap` groups per workgroup (the
+// FIR's re-reads of a frame stay in one L2), many more workgroups than fit at once when there are rows for it (no second,
+// part-filled round of resident workgroups)
+constexpr int kMixedRun = 16;
+int mixed_grid(const fxc_plan* p, int64_t n_groups, int64_t run_cap) {
+    const int64_t run = std::max<int64_t>(1, std::min<int64_t>(run_cap, n_groups / ((int64_t)p->cu_count * 8)));
+    return (int)std::max<int64_t>(1, std::min<int64_t>((n_groups + run - 1) / run, 1 << 30));
 }
 
 // may this plan take the kernels built for its channel count (fx_spec.h through hiprtc, h_rtc.h)?  Mixed-radix plans of up to four taps
@@ -52,182 +58,19 @@ const SpecKernel* spec_f_kernel(fxc_plan* p) {
     return spec_once(p, &p->spec_f, &p->spec_f_tried, kSpecFOnly);
 }
 
-int run_channelize(fxc_plan* p, const cf* x, cf* spec, int64_t n_streams, int ant = 1) {
-    if (n_streams == 0 || p->n_pts == 0) return FXC_OK;
-    // the F-only tiled kernel writes natural-order spectra straight to `spec` (no workspace): any caller may use it
-    if (p->tiled_f) return tiled_channelize(p, x, spec, n_streams);
-    if (p->mixed && p->mixed_blu) {
-        // a large prime factor: chirp-z rows of nfft = 2^j >= 2 nchan - 1, one row per workgroup pass
-        const int threads = std::max(256, p->mixed_tpr);
-        const int rpw = threads / p->mixed_tpr;
-        const bool twl = p->blu_nfft <= 4096;
-        const size_t lds = ((size_t)rpw * 2 + (twl ? 1 : 0)) * p->blu_nfft * sizeof(cf);
-        const int64_t n_groups = n_streams * ((p->n_pts + rpw - 1) / rpw);
-        const int64_t run = std::max<int64_t>(1, std::min<int64_t>(16, n_groups / ((int64_t)p->cu_count * 8)));
-        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n_groups + run - 1) / run, 1 << 30));
-        const MixedExtras blu = {mixed_wave_local(p, false), ant, p->blu_nfft, p->d_chirp, p->d_blud, nullptr};
-        if (twl)
-            hipLaunchKernelGGL((pfb_fft_mixed_kernel<true, 1, false, true>), dim3(grid), dim3(threads), lds, p->stream, x, p->d_win,
-                               spec, p->d_tw, p->mixed_plan, p->num_samp, p->nchan, p->ntaps, p->n_pts, n_streams, p->mixed_tpr, 1, blu);
-        else
-            hipLaunchKernelGGL((pfb_fft_mixed_kernel<false, 1, false, true>), dim3(grid), dim3(threads), lds, p->stream, x, p->d_win,
-                               spec, p->d_tw, p->mixed_plan, p->num_samp, p->nchan, p->ntaps, p->n_pts, n_streams, p->mixed_tpr, 1, blu);
-        FXC_HIP(p, hipGetLastError());
-        return FXC_OK;
-    }
-    // the F stage built for exactly this channel count (fx_spec.h, FXM_FONLY: a workgroup carries two streams through the
-    // stages, the last butterfly stores the spectra); compiled on first use
-    if (const SpecKernel* k = spec_f_kernel(p)) {
-        const int64_t pairs = (n_streams + k->shape.rows - 1) / k->shape.rows;      // (groups of streams: a workgroup's rows)
-        const int64_t ws = spec_wg_splits(p, k, pairs, false);
-        if (pairs * ws > (1ll << 30)) return fail(p, FXC_ERR_ARG, "too many streams for one launch");
-        SpecArgs a = {x, p->d_win, spec, p->d_tw, nullptr, (long long)p->num_samp, (long long)p->n_pts, (long long)n_streams, (int)ws, ant,
-                      reinterpret_cast<const float*>(p->d_win4), k->d_tw1, 0, nullptr};
-        void* params[] = {&a};
-        FXC_HIP(p, hipModuleLaunchKernel(k->fn, (unsigned)(pairs * ws), 1, 1, (unsigned)k->shape.threads(), 1, 1, 0, p->stream, params, nullptr));
-        return FXC_OK;
-    }
-    if (p->mixed && p->nchan > kMixedMaxN) {
-        // one LDS row, the other in the output (pfb_fft_mixed_kernel, BIG): one frame per workgroup pass, 1024 threads
-        const int64_t n_groups = n_streams * p->n_pts;
-        const int64_t run = std::max<int64_t>(1, std::min<int64_t>(16, n_groups / ((int64_t)p->cu_count * 8)));
-        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n_groups + run - 1) / run, 1 << 30));
-        hipLaunchKernelGGL((pfb_fft_mixed_kernel<false, 1, false, false, true>), dim3(grid), dim3(1024), (size_t)p->nchan * sizeof(cf),
-                           p->stream, x, p->d_win, spec, p->d_tw, p->mixed_plan, p->num_samp, p->nchan, p->ntaps, p->n_pts, n_streams,
-                           1024, 1, MixedExtras{0, ant, p->nchan, nullptr, nullptr, nullptr});
-        FXC_HIP(p, hipGetLastError());
-        return FXC_OK;
-    }
-    if (p->mixed) {
-        const int threads = std::max(256, p->mixed_tpr);
-        const int rpw = threads / p->mixed_tpr;
-        const MixedExtras no_blu = {mixed_wave_local(p, false), ant, p->nchan, nullptr, nullptr, nullptr};
-        static const int tw_knob = FXC_DEV_ENV_INT("FXC_MIXED_TWLDS", 1), u_knob = FXC_DEV_ENV_INT("FXC_MIXED_U", 0);
-        // U = 2 frames per slot where the measurements favour it (tools/bench_channelize.py, r04 experiments.md §7): up to 1280
-        // channels (three or more 256-thread workgroups still fit a CU's LDS) and, with 512 or 1024 threads per row, from 1321 to
-        // 4096 (1440 ... 2000 channels: 10 - 25 % faster than one frame per slot on 256 threads)
-        const size_t row_bytes = (size_t)p->nchan * sizeof(cf);
-        int u = (p->nchan <= 1280 || (p->mixed_tpr >= 512 && p->nchan <= 4096)) ? 2 : 1;
-        u = std::min(u, fxc::mixed_rows_per_slot_cap(p->mixed_plan));     // 11 / 13: register butterflies one frame at a time here
-        if (u_knob == 1 || u_knob == 2) u = u_knob;
-        const bool twl = tw_knob && (1 + (size_t)rpw * 2 * u) * row_bytes <= (size_t)(160 * 1024);
-        if (!twl) u = 1;
-        const size_t lds = ((size_t)rpw * 2 * u + (twl ? 1 : 0)) * row_bytes;
-        const int fpg = rpw * u;
-        const int64_t n_groups = n_streams * ((p->n_pts + fpg - 1) / fpg);
-        // runs of up to 16 frame groups per workgroup (the FIR's re-reads of a frame stay in one L2), many more workgroups than
-        // fit at once when there are rows for it (no second, part-filled round of resident workgroups)
-        static const int run_knob = FXC_DEV_ENV_INT("FXC_MIXED_RUN", 16);
-        const int64_t run = std::max<int64_t>(1, std::min<int64_t>(run_knob, n_groups / ((int64_t)p->cu_count * 8)));
-        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n_groups + run - 1) / run, 1 << 30));
-#define FXC_MIXED_LAUNCH(TWL, UU)                                                                                                     \
-    hipLaunchKernelGGL((pfb_fft_mixed_kernel<TWL, UU, false>), dim3(grid), dim3(threads), lds, p->stream, x, p->d_win, spec, p->d_tw, \
-                       p->mixed_plan, p->num_samp, p->nchan, p->ntaps, p->n_pts, n_streams, p->mixed_tpr, 1, no_blu)
-        if (!twl)
-            FXC_MIXED_LAUNCH(false, 1);
-        else if (u == 2)
-            FXC_MIXED_LAUNCH(true, 2);
-        else
-            FXC_MIXED_LAUNCH(true, 1);
-#undef FXC_MIXED_LAUNCH
-        FXC_HIP(p, hipGetLastError());
-        return FXC_OK;
-    }
-    const int64_t total = n_streams * p->n_pts * p->nchan;
-    hipLaunchKernelGGL(pfb_fir_kernel, dim3(grid_for(total, 256, p->cu_count)), dim3(256), 0, p->stream, x, p->d_win,
-                       spec, p->num_samp, p->nchan, p->ntaps, p->n_pts, total);
-    const int64_t rows = n_streams * p->n_pts;
-    if (p->nchan > 1) {
-        const int grid = (int)std::min<int64_t>(rows, (int64_t)p->cu_count * 4);
-        const size_t lds = (size_t)std::max(p->nchan, p->pow2 ? 512 : 0) * sizeof(cf);   // small N: 512 / N rows per workgroup
-        if (p->pow2)
-            hipLaunchKernelGGL(fft_pow2_kernel, dim3(grid), dim3(256), lds, p->stream, spec, p->d_tw, p->nchan,
-                               p->lg2n, rows);
-        else
-#if FXC_DEV_KERNELS
-            hipLaunchKernelGGL(dft_any_kernel, dim3(grid), dim3(256), lds, p->stream, spec, p->d_tw, p->nchan, rows);
-#else
-            return fail(p, FXC_ERR_UNSUPPORTED, "no FFT kernel for %d channels in this build", p->nchan);      // (every such count takes the mixed-radix kernel)
-#endif
-    }
-    FXC_HIP(p, hipGetLastError());
-    return FXC_OK;
-}
-
-// Two antennas above 4096 channels off the powers of two (complex64 samples): two passes of the kernels built for the channel count --
-// antenna 0 of every chunk pair through the F stage into `spec` [chunk][frame][nchan], then antenna 1 through the same stages with the
-// last butterfly multiplying by antenna 0's values and adding to the thread's sums (fx_spec.h, FXM_XM): 2 x the algorithmic bytes, where
-// the spectra of both antennas + xmul_kernel move 3 x.  raw[split][chunk][nchan] out, as mixed_fx_raw_sums.
+// Two antennas above 4096 channels off the powers of two (complex64 samples): two passes of the kernels built for the channel count
+// (two_pass_raw_sums)?
 bool two_pass_xm(fxc_plan* p, bool bytes_in) {
     if (bytes_in || p->n_ant != 2 || !p->mixed || p->mixed_blu || p->nchan <= 4096 || p->mixed_xeng) return false;
     if (!spec_f_kernel(p) || p->spec_f->shape.rows != 1) return false;
     if (!FXC_DEV_ENV_INT("FXC_XM", 1)) return false;
     return spec_once(p, &p->spec_xm, &p->spec_xm_tried, kSpecXM) != nullptr;      // (none: both antennas' spectra + xmul_kernel)
 }
-int two_pass_raw_sums(fxc_plan* p, const cf* x, int64_t n_chunks, int n_splits, cf* spec, cf* raw) {
-    const SpecKernel* kf = p->spec_f;
-    const SpecKernel* kx = p->spec_xm;
-    if (n_splits % kx->shape.slots) return fail(p, FXC_ERR_STATE, "row splits and the second-pass kernel's slots disagree");
-    const int64_t wsf = spec_wg_splits(p, kf, n_chunks, false);
-    const int wsx = n_splits / kx->shape.slots;
-    if (n_chunks * std::max<int64_t>(wsf, wsx) > (1ll << 30)) return fail(p, FXC_ERR_ARG, "too many chunks for one launch");
-    SpecArgs a0 = {x, p->d_win, spec, p->d_tw, nullptr, (long long)p->num_samp, (long long)p->n_pts, (long long)n_chunks, (int)wsf, 1,
-                   reinterpret_cast<const float*>(p->d_win4), kf->d_tw1, 2 * (long long)p->num_samp, nullptr};
-    void* params0[] = {&a0};
-    FXC_HIP(p, hipModuleLaunchKernel(kf->fn, (unsigned)(n_chunks * wsf), 1, 1, (unsigned)kf->shape.threads(), 1, 1, 0, p->stream, params0, nullptr));
-    SpecArgs a1 = {x + p->num_samp, p->d_win, raw, p->d_tw, nullptr, (long long)p->num_samp, (long long)p->n_pts, (long long)n_chunks, wsx, 1,
-                   reinterpret_cast<const float*>(p->d_win4), kx->d_tw1, 2 * (long long)p->num_samp, spec};
-    void* params1[] = {&a1};
-    FXC_HIP(p, hipModuleLaunchKernel(kx->fn, (unsigned)(n_chunks * wsx), 1, 1, (unsigned)kx->shape.threads(), 1, 1, 0, p->stream, params1, nullptr));
-    return FXC_OK;
-}
 
-// two antennas on the mixed-radix kernel: F and X in one pass, raw[split][chunk][nchan] out (xmul_kernel's layout)
-// (dc_u8 != nullptr: x is the uint8 I,Q stream of these chunks and dc_u8 its conversion offsets per stream)
-int mixed_fx_raw_sums(fxc_plan* p, const cf* x, int64_t n_chunks, int n_splits, cf* raw, const cf* dc_u8 = nullptr) {
-    if (p->spec) {
-        // the build of fx_spec.h made for this channel count (h_rtc.h); its byte-ingest twin is compiled on first use
-        const SpecKernel* k = p->spec;
-        if (dc_u8) k = spec_once(p, &p->spec_u8, &p->spec_u8_tried, kSpecU8);
-        if (k && n_splits % k->shape.slots == 0 && n_splits / k->shape.slots >= 1) {
-            const int wg_splits = n_splits / k->shape.slots;
-            const int64_t grid = n_chunks * wg_splits;
-            if (grid > (1ll << 30)) return fail(p, FXC_ERR_ARG, "too many chunks for one launch");
-            SpecArgs a = {x, p->d_win, raw, p->d_tw, dc_u8, (long long)p->num_samp, (long long)p->n_pts, (long long)n_chunks, wg_splits, 1,
-                          reinterpret_cast<const float*>(p->d_win4), k->d_tw1, 0, nullptr};
-            void* params[] = {&a};
-            FXC_HIP(p, hipModuleLaunchKernel(k->fn, (unsigned)grid, 1, 1, (unsigned)k->shape.threads(), 1, 1, 0, p->stream, params, nullptr));
-            return FXC_OK;
-        }
-        if (env_int("FXC_RTC_VERBOSE", 0))      // (results stay correct: the any-shape kernel below takes the call)
-            std::fprintf(stderr, "libfxcorr: %d channels: the %s build of the kernel per channel count does not take this call (%s), the any-shape kernel does\n",
-                         p->nchan, dc_u8 ? "byte-ingest" : "complex64", !k ? "no such build" : "its slots per workgroup do not divide the call's row splits");
-    }
-    const int threads = std::max(256, p->mixed_tpr);
-    const int rpw = threads / p->mixed_tpr;
-    const size_t lds = ((size_t)rpw * 4 + (p->mixed_xf_twl ? 1 : 0)) * p->nchan * sizeof(cf);
-    const int64_t grid = n_chunks * n_splits;
-    if (grid > (1ll << 30)) return fail(p, FXC_ERR_ARG, "too many chunks for one launch");
-    const MixedExtras ex = {mixed_wave_local(p, true), 1, p->nchan, nullptr, nullptr, dc_u8};
-#define FXC_MIXED_XF_LAUNCH(TWL, BYTES)                                                                                            \
-    hipLaunchKernelGGL((pfb_fft_mixed_kernel<TWL, 2, true, false, false, BYTES>), dim3((unsigned)grid), dim3(threads), lds, p->stream, \
-                       x, p->d_win, raw, p->d_tw, p->mixed_plan, p->num_samp, p->nchan, p->ntaps, p->n_pts, n_chunks, p->mixed_tpr,    \
-                       n_splits, ex)
-    if (p->mixed_xf_twl) {
-        if (dc_u8)
-            FXC_MIXED_XF_LAUNCH(true, true);
-        else
-            FXC_MIXED_XF_LAUNCH(true, false);
-    } else {
-        if (dc_u8)
-            FXC_MIXED_XF_LAUNCH(false, true);
-        else
-            FXC_MIXED_XF_LAUNCH(false, false);
-    }
-#undef FXC_MIXED_XF_LAUNCH
-    FXC_HIP(p, hipGetLastError());
-    return FXC_OK;
-}
+// F and X in one pass for this call?  mixed_xf plans above 4096 channels that have the F stage built for their channel count
+// (fx_spec.h, one stream per workgroup) take it for complex64 input -- F pass + xmul_kernel: 4500 channels 4.39 -> 3.43 ms -- and keep
+// the one-pass kernel for the receivers' bytes, which it converts itself (3.5 ms against 5.0 through the conversion pass)
+bool mixed_one_pass(const fxc_plan* p, bool bytes_in) { return p->mixed_xf && (bytes_in || !p->xf_bytes_only); }
 
 // float32 sums of up to kRowSpectra spectra per raw row (the rows themselves are summed in float64).  Measured on 10 000
 // frames against the float64 mean of the per-frame rows (profiles/r02/round2_experiments.md): 256 spectra per row 5.6e-9 of
@@ -235,14 +78,14 @@ int mixed_fx_raw_sums(fxc_plan* p, const cf* x, int64_t n_chunks, int n_splits, 
 // instead of 92 MB per 10 000 frames)
 constexpr int64_t kRowSpectra = 1024;
 
-struct XGeom {
-    int kx, n_splits;
-};
+// frame ranges of a chunk that is a raw row group of its own on the X-engines (k_finish.h::x_range): one per kRowSpectra frames
+int frame_ranges(const fxc_plan* p) { return (int)std::min<int64_t>((p->n_pts + kRowSpectra - 1) / kRowSpectra, 4096); }
 
 // Workgroup splits of a chunk's (or stream pair's) frames for a specialised kernel: workgroups = groups x splits, every slot of a
 // workgroup with a run of its own.  A run re-reads ntaps - 1 frames of history and should be 16 frames at least; with the X stage
-// in the kernel a run is a float32 sum of at most kRowSpectra spectra; among the splits that allow, the one that fills the device's
-// resident workgroups in whole rounds best
+// in the kernel (kRowSums) a run is a float32 sum of at most kRowSpectra spectra; among the splits that allow, the one that fills the
+// device's resident workgroups in whole rounds best
+constexpr bool kRowSums = true, kSpectraOut = false;
 int64_t spec_wg_splits(const fxc_plan* p, const SpecKernel* k, int64_t n_groups, bool sums) {
     const SpecShape& sh = k->shape;
     const int64_t cap = (int64_t)p->cu_count * k->wgs_per_cu;
@@ -271,17 +114,16 @@ int64_t spec_wg_splits(const fxc_plan* p, const SpecKernel* k, int64_t n_groups,
     return best;
 }
 
-// xf: this call takes the mixed-radix kernel that does F and X in one pass (mixed_xf plans; h_run.h::mixed_one_pass)
-XGeom x_geometry(const fxc_plan* p, int64_t n_chunks, bool xf, bool xm = false) {
-    XGeom g;
-    if (xm) {      // two passes of the kernels built for the channel count (two_pass_raw_sums): the second one's rows
-        g.kx = 1;
-        g.n_splits = (int)(spec_wg_splits(p, p->spec_xm, n_chunks, true) * p->spec_xm->shape.slots);
-        return g;
-    }
-    if (xf && p->spec) {
-        g.kx = 1;
-        g.n_splits = (int)(spec_wg_splits(p, p->spec, n_chunks, true) * p->spec->shape.slots);
+struct XGeom {
+    int kx, n_splits;
+};
+
+// xf: this call takes the mixed-radix kernel that does F and X in one pass (mixed_xf plans; mixed_one_pass)
+XGeom x_geometry(const fxc_plan* p, int64_t n_chunks, bool xf, bool xm) {
+    XGeom g = {1, 1};
+    if (xm || (xf && p->spec)) {      // the kernels built for the channel count; xm: two passes (two_pass_raw_sums), the second one's rows
+        const SpecKernel* k = xm ? p->spec_xm : p->spec;
+        g.n_splits = (int)(spec_wg_splits(p, k, n_chunks, kRowSums) * k->shape.slots);
         return g;
     }
     if (xf) {
@@ -289,7 +131,6 @@ XGeom x_geometry(const fxc_plan* p, int64_t n_chunks, bool xf, bool xm = false) 
         const int rpw = std::max(256, p->mixed_tpr) / p->mixed_tpr;
         const int64_t gps = (p->n_pts + rpw - 1) / rpw;
         const int64_t want = ((int64_t)p->cu_count * 8 + n_chunks - 1) / std::max<int64_t>(n_chunks, 1);
-        g.kx = 1;
         g.n_splits = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(want, 256), gps / 4));
         // a slot sums its run of frame groups -- one spectrum per group -- in float32 registers: no run longer than the
         // kRowSpectra spectra every other path limits a float32 row to (few channels with long chunks: nchan 12,
@@ -297,7 +138,6 @@ XGeom x_geometry(const fxc_plan* p, int64_t n_chunks, bool xf, bool xm = false) 
         g.n_splits = (int)std::min<int64_t>(std::max<int64_t>(g.n_splits, (gps + kRowSpectra - 1) / kRowSpectra), 1 << 16);
         return g;
     }
-    g.kx = 1;
     while (g.kx < 256 && g.kx < p->nchan) g.kx <<= 1;
     const int iy = 256 / g.kx;
     int64_t splits = (p->n_pts + (int64_t)iy * 64 - 1) / ((int64_t)iy * 64);
@@ -307,14 +147,9 @@ XGeom x_geometry(const fxc_plan* p, int64_t n_chunks, bool xf, bool xm = false) 
     return g;
 }
 
-// F and X in one pass for this call?  mixed_xf plans above 4096 channels that have the F stage built for their channel count
-// (fx_spec.h, one stream per workgroup) take it for complex64 input -- F pass + xmul_kernel: 4500 channels 4.39 -> 3.43 ms -- and keep
-// the one-pass kernel for the receivers' bytes, which it converts itself (3.5 ms against 5.0 through the conversion pass)
-bool mixed_one_pass(const fxc_plan* p, bool bytes_in) { return p->mixed_xf && (bytes_in || !p->xf_bytes_only); }
-
 // chunks per pass on the generic path so that spectra + raw sums fit the workspace target
 int64_t generic_chunks_per_pass(const fxc_plan* p, int64_t n_chunks, const XGeom& g, int64_t* spec_bytes,
-                                int64_t* raw_bytes, bool xf, bool xm = false) {
+                                int64_t* raw_bytes, bool xf, bool xm) {
     const int64_t spec_per_chunk = xf ? 0 : (int64_t)(xm ? 1 : p->n_ant) * p->n_pts * p->nchan * (int64_t)sizeof(cf);      // (xm: antenna 0's spectra only)
     const int64_t raw_per_chunk = (int64_t)g.n_splits * p->n_base * p->nchan * (int64_t)sizeof(cf);
     int64_t cb = ws_target() / std::max<int64_t>(1, spec_per_chunk + raw_per_chunk);
@@ -334,13 +169,166 @@ int fold_splits(int64_t n_rows, int64_t row_len) {
 }
 int64_t fold_part_bytes(const fxc_plan* p) { return (int64_t)fold_max_splits((int64_t)p->n_prod * p->nchan) * p->n_prod * p->nchan * (int64_t)sizeof(cd); }
 
-const FoldFinish kNoFinish = {nullptr, nullptr, nullptr, 0.0, 0};      // (rot: with_finish_rot supplies it, here and in every FoldFinish)
+// workgroups of a fused launch over n_pairs chunk pairs: one per CU; a launch with fewer chunks than that is all
+// tail (frame ranges), on fewer workgroups when a range would be under four frames (each reloads up to three
+// frames of history)
+int fused_grid(const fxc_plan* p, int64_t n_pairs) {
+    if (n_pairs >= p->fused_grid_max) return p->fused_grid_max;
+    const int64_t frames = n_pairs * p->n_pts;
+    return (int)std::max<int64_t>(1, std::min<int64_t>(frames / 4, p->fused_grid_max));
+}
 
-// `fin` with the plan's auto rows marked (they follow the n_base cross rows of the accumulator)
-FoldFinish with_autos(const fxc_plan* p, const FoldFinish& fin) {
-    FoldFinish f = fin;
-    f.auto_from = p->n_prod > p->n_base ? (int64_t)p->n_base * p->nchan : 0;
-    return f;
+// chunks per raw row when only the integration is wanted: float32 sums of up to kRowSpectra spectra
+int64_t fused_unit(const fxc_plan* p) { return std::max<int64_t>(1, std::min<int64_t>(kRowSpectra / std::max<int64_t>(1, p->n_pts), 64)); }
+
+// products in a raw row of the 2-antenna fused kernel: plans with autos take its AUTOS variant, rows of [3][kN] (h_run.h::fused_autos)
+int fused_row_prods(const fxc_plan* p) { return p->autos && p->nchan == fxc::fused::kN ? p->n_prod : 1; }
+
+// raw rows a 2-antenna fused launch over nc chunks writes (leading-part rows included)
+int64_t fused_rows(const fxc_plan* p, int64_t nc, int64_t unit, bool rows_are_chunks) {
+    return fxc::fused::range_split(fused_grid(p, nc), (int)nc, (int)p->fused_seg, (int)unit, rows_are_chunks).n_rows;
+}
+
+const LeadRows kNoLead = {0, 0, 0, 0, 0};
+LeadRows fused_lead(const fxc_plan* p, int64_t nc) {
+    if (p->track) return kNoLead;      // (whole chunks only: fused_raw_sums)
+    const bool rows_are_chunks = true;      // (the rows of fx_rows: one chunk each)
+    const fxc::fused::RangeSplit sp = fxc::fused::range_split(fused_grid(p, nc), (int)nc, (int)p->fused_seg, 1, rows_are_chunks);
+    LeadRows lr;
+    lr.first_chunk = sp.n_full;
+    lr.n_frames = sp.n_tail * p->n_pts;
+    lr.n_pts = p->n_pts;
+    lr.n_prod = fused_row_prods(p);
+    lr.offset = nc * (int64_t)fxc::fused::kN * lr.n_prod;
+    lr.grid = fused_grid(p, nc);
+    return lr;
+}
+
+// antenna tiles of 16 of the matrix-core X-engine: XT = 1 .. 4
+#define FXC_XMFMA_DISPATCH(p, ...)                       \
+    do {                                                 \
+        switch (((p)->n_ant + 15) / 16) {                \
+            case 1: { constexpr int XT = 1; __VA_ARGS__; } break; \
+            case 2: { constexpr int XT = 2; __VA_ARGS__; } break; \
+            case 3: { constexpr int XT = 3; __VA_ARGS__; } break; \
+            default: { constexpr int XT = 4; __VA_ARGS__; } break; \
+        }                                                \
+    } while (0)
+
+// bins of a matrix-core X-engine workgroup's column
+int xmfma_column(const fxc_plan* p) {
+    int x_ch = 16;
+    if (p->x_mfma) FXC_XMFMA_DISPATCH(p, x_ch = XMfmaGeo<XT>::kCH);
+    return x_ch;
+}
+
+// chunks per X-engine workgroup (= per raw row) for an integration over nc chunks.  The kernel's one-wave workgroups
+// all do the same work, so the launch is cut into exactly as many as are resident at once (p->x_resident, from the
+// occupancy API: one round, no tail) unless a float32 row (fused_unit) allows fewer chunks than that: then many rounds
+int64_t xengine_group(const fxc_plan* p, int64_t nc, int64_t unit) {
+    // more than 8 antennas: a column of 16 bins with all antennas per workgroup (xengine_mfma_kernel), or -- the vector
+    // kernel it replaced -- a column of 64 shared by the G (G + 1) / 2 pairs of antenna blocks (xengine_block_kernel)
+    const int64_t gb = (p->n_ant + kXB - 1) / kXB;
+    const int64_t cols = p->x_mfma ? std::max<int64_t>(1, p->nchan / xmfma_column(p))
+                                   : std::max<int64_t>(1, p->nchan / kXThreads) * (p->n_ant > kXB ? gb * (gb + 1) / 2 : 1);
+    const int64_t groups = std::max<int64_t>(1, p->x_resident / cols);
+    return std::max<int64_t>(1, std::min<int64_t>(unit, (nc + groups - 1) / groups));
+}
+
+// frame ranges per chunk group of the X-engines: groups of one chunk with more than kRowSpectra frames
+int x_ranges(const fxc_plan* p, int64_t unit) { return p->n_ant <= 2 || unit > 1 ? 1 : frame_ranges(p); }
+
+// layout of the raw per-chunk sums the fused paths produce (see raw_index)
+int fused_layout(const fxc_plan* p) { return p->n_ant == 2 ? 1 : (p->path == FXC_PATH_FUSED ? 2 : 0); }
+
+// chunks per pass on the fused paths: 2 antennas only need the raw rows; more antennas also the spectra
+int64_t fused_chunks_per_pass(const fxc_plan* p, int64_t n_chunks, int64_t* spec_bytes, int64_t* raw_bytes) {
+    // (3 and more antennas: one raw row per chunk and frame range at most, x_ranges)
+    const int64_t xr = x_ranges(p, 1);
+    const int64_t raw_per_chunk = (int64_t)p->n_prod * p->nchan * (int64_t)sizeof(cf) * xr;
+    const int64_t spec_per_chunk = p->n_ant == 2 ? 0 : (int64_t)p->n_ant * p->n_pts * p->nchan * (int64_t)sizeof(cf);
+    int64_t cb = ws_target() / (raw_per_chunk + spec_per_chunk);
+    if (cb < 1) cb = 1;
+    if (cb > n_chunks) cb = n_chunks;
+    if (p->n_ant > 2 && cb > 65535 / xr) cb = std::max<int64_t>(1, 65535 / xr);   // the X-engines carry group and range in grid.y
+    *spec_bytes = up256(cb * spec_per_chunk);
+    // 2 antennas: one leading-part row per workgroup after the chunk rows (fx_fused4096_kernel)
+    *raw_bytes = up256((cb + (p->n_ant == 2 ? p->fused_grid_max : 0)) * raw_per_chunk);
+    return cb;
+}
+
+bool tiled_nchan(int n) { return n == 512 || n == 1024 || n == 2048 || n == 4096 || n == 8192; }
+bool small_nchan(int n) { return n == 16 || n == 32 || n == 64 || n == 128 || n == 256; }
+
+// workgroups of the wave-local kernels (k_small.h) over `items` work items
+int small_grid(const fxc_plan* p, int64_t items) {
+    const int64_t items_per_wg = 4 * (32 / (p->nchan / 16));
+    return (int)std::min<int64_t>((items + items_per_wg - 1) / items_per_wg, p->small_wgs);
+}
+
+// The 8192-channel ring (f8192_ring_kernel: one stream per workgroup, 8 us a frame) over n streams: runs of eight frames at least (a
+// run re-reads three frames of history) -- unless those would leave CUs idle: a handful of chunks, or one stream (_spectrometer_poly
+// itself), is about latency (see spec_wg_splits) and takes runs of one
+bool ring8192_few(const fxc_plan* p, int64_t n) { return n * std::max<int64_t>(1, p->n_pts / 8) < p->cu_count; }
+// ... its frame splits: enough workgroups for two rounds of the CUs when the streams are few
+int ring8192_splits(const fxc_plan* p, int64_t n) {
+    const int64_t want = (2 * (int64_t)p->cu_count + n - 1) / n;
+    return (int)std::max<int64_t>(1, std::min<int64_t>(want, p->n_pts / (ring8192_few(p, n) ? 1 : 8)));
+}
+dim3 ring8192_grid(const fxc_plan* p, int64_t n, int n_splits) {
+    return dim3((unsigned)std::min<int64_t>(n, std::max<int64_t>(1, (int64_t)p->cu_count * 8 / n_splits)), (unsigned)n_splits);
+}
+
+// frame ranges per chunk so that a launch has at least ~2 work items per resident workgroup (`cap` of them)
+int64_t tiled_fill(const fxc_plan* p, int64_t n_chunks, int64_t cap) {
+    const int64_t want = (2 * cap + n_chunks - 1) / n_chunks;
+    // runs of eight frames at least -- the two-pass 8192-channel route with a handful of chunks: of one (ring8192_few)
+    const bool few = p->x8192 && ring8192_few(p, n_chunks);
+    const int64_t most = std::max<int64_t>(1, p->n_pts / (few ? 1 : 8));
+    return std::max<int64_t>(1, std::min<int64_t>(std::min(want, most), 256));
+}
+// F only: n_chunks pairs of streams
+int tiled_f_splits(const fxc_plan* p, int64_t n_chunks) { return (int)tiled_fill(p, n_chunks, p->tiled_grid_max_f); }
+// F+X: a work item sums its frames in float32, like the headline kernel's rows at most kRowSpectra of them (small
+// channel counts and long chunks have thousands of frames per chunk)
+int tiled_splits(const fxc_plan* p, int64_t n_chunks) {
+    const int64_t exact = std::min<int64_t>((p->n_pts + kRowSpectra - 1) / kRowSpectra, 65536);
+    return (int)std::max(tiled_fill(p, n_chunks, p->tiled_grid_max), exact);
+}
+
+// streams of the tiled path per pass: what a pass keeps beside the raw rows -- the pre-filter's output, or antenna 0's spectra of the
+// two-pass 8192-channel route -- stays within the workspace target
+int64_t tiled_streams_per_pass(const fxc_plan* p) {
+    if (p->x8192) {       // 8192 channels in two passes: antenna 0's spectra of a pass stay within the workspace target
+        const int64_t chunks = std::max<int64_t>(1, ws_target() / (p->n_pts * (int64_t)p->nchan * (int64_t)sizeof(cf)));
+        return 2 * std::min<int64_t>(chunks, 1 << 20);
+    }
+    if (!p->prefilter) return INT64_MAX;
+    int64_t n = ws_target() / (p->num_samp * (int64_t)sizeof(cf));
+    n = std::min<int64_t>(n, 65534) & ~(int64_t)1;      // grid.y carries the stream (or a row of them); whole pairs
+    return std::max<int64_t>(2, n);
+}
+
+// Frames per frame split (grid.z) of the pre-filter passes, `blocks` workgroups a split: frame splits so that a few-stream call still
+// fills the chip; each split reloads one block of history, and takes whole blocks of 2 tp frames
+int64_t prefilter_frames(const fxc_plan* p, int64_t blocks) {
+    const int tp = p->pre_tp;
+    int64_t fs = std::max<int64_t>(1, (2 * (int64_t)p->cu_count + blocks - 1) / blocks);
+    fs = std::min<int64_t>(fs, std::max<int64_t>(1, p->n_pts / (4 * tp)));
+    return ((p->n_pts + fs - 1) / fs + 2 * tp - 1) / (2 * tp) * (2 * tp);
+}
+
+// nchan 8192 as two 4096-channel problems (pfb_split8192_kernel): chunks per pass
+int64_t split_chunks_per_pass(const fxc_plan* p, int64_t n_chunks) {
+    const int64_t per_chunk = 4 * p->n_pts * 4096 * (int64_t)sizeof(cf) + 2 * 4096 * (int64_t)sizeof(cf);   // y + two raw rows
+    return std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_chunks, 32767), ws_target() / per_chunk));
+}
+
+// nchan == 1 streaming path: raw[block][chunk] partial sums
+bool stream_is_t4(const fxc_plan* p) { return p->ntaps <= 4 && (p->num_samp % 2) == 0; }
+
+int64_t stream_blocks(const fxc_plan* p) {
+    return stream_is_t4(p) ? kStream4Blocks : (p->num_samp + kStreamBlock - 1) / kStreamBlock;
 }
 
 // ---- the rot operands (k_finish.h: RotArg, TrackRot): what a plan's rows and integrations are multiplied by -----------------
@@ -378,6 +366,16 @@ void with_finish_rot(const fxc_plan* p, bool finalises, F&& launch) {
 }
 template <bool ANT>
 FinishT<ANT> finish_with(const FoldFinish& f, RotArg<ANT> rot) { return {f.sums, f.out, rot, f.count, f.reset, f.auto_from}; }
+
+// ---- the fold of a pass's raw rows into the accumulator ----------------------------------------------------------------------
+const FoldFinish kNoFinish = {nullptr, nullptr, nullptr, 0.0, 0};      // (rot: with_finish_rot supplies it, here and in every FoldFinish)
+
+// `fin` with the plan's auto rows marked (they follow the n_base cross rows of the accumulator)
+FoldFinish with_autos(const fxc_plan* p, const FoldFinish& fin) {
+    FoldFinish f = fin;
+    f.auto_from = p->n_prod > p->n_base ? (int64_t)p->n_base * p->nchan : 0;
+    return f;
+}
 
 // acc[p][bin] += sum of the raw rows [n_prod][nchan], and `fin` for every element: two launches, one when the rows are few
 // `done`: an event to complete with the last kernel (it rides on that dispatch: no packet of its own in the stream)
@@ -436,49 +434,30 @@ int fold_or_defer(fxc_plan* p, const cf* raw, cd* part, int64_t n_rows, int layo
     return FXC_OK;
 }
 
-// workgroups of a fused launch over n_pairs chunk pairs: one per CU; a launch with fewer chunks than that is all
-// tail (frame ranges), on fewer workgroups when a range would be under four frames (each reloads up to three
-// frames of history)
-int fused_grid(const fxc_plan* p, int64_t n_pairs) {
-    if (n_pairs >= p->fused_grid_max) return p->fused_grid_max;
-    const int64_t frames = n_pairs * p->n_pts;
-    return (int)std::max<int64_t>(1, std::min<int64_t>(frames / 4, p->fused_grid_max));
-}
+// ---- launchers: one kernel, or one F stage, each ----------------------------------------------------------------------------
 
-// chunks per raw row when only the integration is wanted: float32 sums of up to kRowSpectra spectra
-int64_t fused_unit(const fxc_plan* p) { return std::max<int64_t>(1, std::min<int64_t>(kRowSpectra / std::max<int64_t>(1, p->n_pts), 64)); }
+// A launch of the fused kernel (fx_fused4096_kernel): x, n_pairs and out, then what the call site means beside them
+enum FusedOut { kFusedRawRows, kFusedSpectra };
+struct FusedLaunch {
+    const cf* x;                     // n_pairs pairs of consecutive antenna streams to channelise
+    int64_t n_pairs;
+    cf* out;
+    FusedOut what = kFusedRawRows;   // raw rows (X sums), or spectra: the F pass of 3 and more antennas (p->n_ant / 2 stream pairs per chunk)
+    const cf* dc_u8 = nullptr;       // x is the uint8 I,Q stream and dc_u8 its per-stream conversion offsets (2 antennas, X fused in)
+    bool dck = false;                // ... and the kernel sums its later chunks' bytes itself
+    int64_t unit = 1;                // chunks per raw row, and whether a raw row holds whole chunks: the raw-row layout
+    bool rows_are_chunks = true;     //   (fx_fused4096.h::RangeWalk)
+    int64_t num_samp = 0;            // samples per stream where not the plan's (the 8192-channel split runs on half-size streams)
+    int whole_grid = 0;              // > 0: that many workgroups, one chunk pair at a time each (n_pairs a multiple of it: no frame ranges)
+};
 
-// raw rows a 2-antenna fused launch over nc chunks writes (leading-part rows included)
-int64_t fused_rows(const fxc_plan* p, int64_t nc, int64_t unit, bool rows_are_chunks) {
-    return fxc::fused::range_split(fused_grid(p, nc), (int)nc, (int)p->fused_seg, (int)unit, rows_are_chunks).n_rows;
-}
-
-LeadRows fused_lead(const fxc_plan* p, int64_t nc) {
-    if (p->track) return LeadRows{0, 0, 0, 0, 0};      // (whole chunks only: fused_raw_sums)
-    const fxc::fused::RangeSplit sp = fxc::fused::range_split(fused_grid(p, nc), (int)nc, (int)p->fused_seg, 1, true);
-    LeadRows lr;
-    lr.first_chunk = sp.n_full;
-    lr.n_frames = sp.n_tail * p->n_pts;
-    lr.n_pts = p->n_pts;
-    lr.n_prod = p->autos && p->nchan == fxc::fused::kN ? p->n_prod : 1;    // (fused_autos: rows of [3][kN])
-    lr.offset = nc * (int64_t)fxc::fused::kN * lr.n_prod;
-    lr.grid = fused_grid(p, nc);
-    return lr;
-}
-const LeadRows kNoLead = {0, 0, 0, 0, 0};
-
-// n_pairs = pairs of consecutive antenna streams to channelise; spec_out: write spectra instead of X sums
-// dc_u8 != nullptr: x is the uint8 I,Q stream and dc_u8 its per-stream conversion offsets (2 antennas, X fused in)
-// unit / rows_are_chunks: the raw-row layout (fx_fused4096.h::RangeWalk)
-// whole_grid > 0: that many workgroups, one chunk pair at a time each (n_pairs a multiple of it: no frame ranges)
-int launch_fused(fxc_plan* p, const cf* x, int64_t n_pairs, cf* out, bool spec_out, const cf* dc_u8, int64_t unit,
-                 bool rows_are_chunks, int64_t num_samp, bool dck, int whole_grid) {
+int launch_fused(fxc_plan* p, const FusedLaunch& f) {
     using namespace fxc::fused;
-    if (num_samp == 0) num_samp = p->num_samp;      // (the 8192-channel split runs on half-size streams)
+    const int64_t num_samp = f.num_samp ? f.num_samp : p->num_samp;
     const f4* win4 = p->split8192 ? p->d_unit4 : p->d_win4;      // (the split's own pass has applied the FIR: one unit tap)
-    const int grid = whole_grid > 0 ? whole_grid : fused_grid(p, n_pairs);
-    const int seg = whole_grid > 0 ? 1 : (int)p->fused_seg;
-    if (n_pairs * p->n_pts >= (1ll << 31)) return fail(p, FXC_ERR_ARG, "more than 2^31 frames in one launch");
+    const int grid = f.whole_grid > 0 ? f.whole_grid : fused_grid(p, f.n_pairs);
+    const int seg = f.whole_grid > 0 ? 1 : (int)p->fused_seg;
+    if (f.n_pairs * p->n_pts >= (1ll << 31)) return fail(p, FXC_ERR_ARG, "more than 2^31 frames in one launch");
     unsigned long long* stamps = nullptr;
 #if FXC_STAMPS
     if (!p->d_stamps) FXC_HIP(p, hipMalloc(&p->d_stamps, (size_t)p->fused_grid_max * 8 * kStampSegs * 8));
@@ -491,147 +470,47 @@ int launch_fused(fxc_plan* p, const cf* x, int64_t n_pairs, cf* out, bool spec_o
     // of stream time per launch, profiles/r03/experiments.md)
     hipEvent_t ev_a = nullptr, ev_b = nullptr;
     if (p->profiling && (hipEventCreate(&ev_a) != hipSuccess || hipEventCreate(&ev_b) != hipSuccess)) ev_a = ev_b = nullptr;
-#define FXC_FUSED_LAUNCH(KERNEL, LDS, ...) \
-    hipExtLaunchKernelGGL(KERNEL, dim3(grid), dim3(kThreads), LDS, p->stream, ev_a, ev_b, 0, __VA_ARGS__)
-    if (dc_u8 && dck)
-        FXC_FUSED_LAUNCH((fx_fused4096_kernel<false, true, true>), kLdsBytes + kDckLdsBytes, x, num_samp, p->n_pts, n_pairs,
-                         win4, p->d_tw1, p->d_tw2, out, stamps, dc_u8, seg, (int)unit, rows_are_chunks ? 1 : 0);
-    else if (dc_u8)
-        FXC_FUSED_LAUNCH((fx_fused4096_kernel<false, true>), kLdsBytes, x, num_samp, p->n_pts, n_pairs, win4, p->d_tw1,
-                         p->d_tw2, out, stamps, dc_u8, seg, (int)unit, rows_are_chunks ? 1 : 0);
-    else if (spec_out)      // (`unit` carries the stream pairs per chunk here)
-        FXC_FUSED_LAUNCH((fx_fused4096_kernel<true, false>), kLdsBytes, x, num_samp, p->n_pts, n_pairs, win4, p->d_tw1,
-                         p->d_tw2, out, stamps, (const cf*)nullptr, seg, p->n_ant / 2, 1);
-    else if (p->autos && p->nchan == kN)      // (plans with autos: rows of [3][kN], fx_fused4096_kernel AUTOS)
-        FXC_FUSED_LAUNCH((fx_fused4096_kernel<false, false, false, true>), kLdsBytes + kAutoLdsBytes, x, num_samp, p->n_pts, n_pairs, win4,
-                         p->d_tw1, p->d_tw2, out, stamps, (const cf*)nullptr, seg, (int)unit, rows_are_chunks ? 1 : 0);
+    // the kernel's last two operands: the raw-row layout, or -- spectra out -- the stream pairs per chunk
+    const bool spec_out = f.what == kFusedSpectra;
+    const int unit = spec_out ? p->n_ant / 2 : (int)f.unit, by_chunk = spec_out || f.rows_are_chunks ? 1 : 0;
+#define FXC_FUSED_LAUNCH(KERNEL, LDS)                                                                                               \
+    hipExtLaunchKernelGGL(KERNEL, dim3(grid), dim3(kThreads), LDS, p->stream, ev_a, ev_b, 0, f.x, num_samp, p->n_pts, f.n_pairs, win4, \
+                          p->d_tw1, p->d_tw2, f.out, stamps, f.dc_u8, seg, unit, by_chunk)
+    if (f.dc_u8 && f.dck)
+        FXC_FUSED_LAUNCH((fx_fused4096_kernel<false, true, true>), kLdsBytes + kDckLdsBytes);
+    else if (f.dc_u8)
+        FXC_FUSED_LAUNCH((fx_fused4096_kernel<false, true>), kLdsBytes);
+    else if (spec_out)
+        FXC_FUSED_LAUNCH((fx_fused4096_kernel<true, false>), kLdsBytes);
+    else if (fused_row_prods(p) > 1)      // (plans with autos: rows of [3][kN], fx_fused4096_kernel AUTOS)
+        FXC_FUSED_LAUNCH((fx_fused4096_kernel<false, false, false, true>), kLdsBytes + kAutoLdsBytes);
     else
-        FXC_FUSED_LAUNCH((fx_fused4096_kernel<false, false>), kLdsBytes, x, num_samp, p->n_pts, n_pairs, win4, p->d_tw1,
-                         p->d_tw2, out, stamps, (const cf*)nullptr, seg, (int)unit, rows_are_chunks ? 1 : 0);
+        FXC_FUSED_LAUNCH((fx_fused4096_kernel<false, false>), kLdsBytes);
 #undef FXC_FUSED_LAUNCH
     if (ev_a) p->kev.emplace_back(ev_a, ev_b);
     FXC_HIP(p, hipGetLastError());
     return FXC_OK;
 }
 
-// chunks per X-engine workgroup (= per raw row) for an integration over nc chunks.  The kernel's one-wave workgroups
-// all do the same work, so the launch is cut into exactly as many as are resident at once (p->x_resident, from the
-// occupancy API: one round, no tail) unless a float32 row (fused_unit) allows fewer chunks than that: then many rounds
-// antenna tiles of 16 of the matrix-core X-engine: XT = 1 .. 4
-#define FXC_XMFMA_DISPATCH(p, ...)                       \
-    do {                                                 \
-        switch (((p)->n_ant + 15) / 16) {                \
-            case 1: { constexpr int XT = 1; __VA_ARGS__; } break; \
-            case 2: { constexpr int XT = 2; __VA_ARGS__; } break; \
-            case 3: { constexpr int XT = 3; __VA_ARGS__; } break; \
-            default: { constexpr int XT = 4; __VA_ARGS__; } break; \
-        }                                                \
-    } while (0)
+// A launch of a kernel built for the plan's channel count (fx_spec.h through h_rtc.h), `groups` x `ws` workgroups: what differs
+// between its forms; the plan's tables and sizes fill the rest of SpecArgs
+struct SpecLaunch {
+    const cf* x;
+    cf* out;                         // spectra (the F-only build) or raw rows
+    int64_t n_streams;               // streams, or -- the builds with the X stage -- chunks
+    int64_t groups, ws;              // a workgroup's share of the streams, and the workgroup splits of a group's frames
+    int ant = 1;                     // antennas interleaved by frame in the spectra written
+    const cf* dc_u8 = nullptr;       // the byte-ingest build: the streams' conversion offsets
+    int64_t stride = 0;              // samples from a group's stream to the next group's, where they are not consecutive
+    const cf* spec0 = nullptr;       // the second pass (FXM_XM): antenna 0's spectra
+};
 
-int64_t xengine_group(const fxc_plan* p, int64_t nc, int64_t unit) {
-    // more than 8 antennas: a column of 16 bins with all antennas per workgroup (xengine_mfma_kernel), or -- the vector
-    // kernel it replaced -- a column of 64 shared by the G (G + 1) / 2 pairs of antenna blocks (xengine_block_kernel)
-    const int64_t gb = (p->n_ant + kXB - 1) / kXB;
-    int x_ch = 16;
-    if (p->x_mfma) FXC_XMFMA_DISPATCH(p, x_ch = XMfmaGeo<XT>::kCH);
-    const int64_t cols = p->x_mfma ? std::max<int64_t>(1, p->nchan / x_ch)
-                                   : std::max<int64_t>(1, p->nchan / kXThreads) * (p->n_ant > kXB ? gb * (gb + 1) / 2 : 1);
-    const int64_t groups = std::max<int64_t>(1, p->x_resident / cols);
-    return std::max<int64_t>(1, std::min<int64_t>(unit, (nc + groups - 1) / groups));
-}
-
-// frame ranges per chunk group of the X-engines (k_finish.h::x_range): groups of one chunk with more than kRowSpectra frames
-int x_ranges(const fxc_plan* p, int64_t unit) {
-    if (p->n_ant <= 2 || unit > 1) return 1;
-    return (int)std::min<int64_t>((p->n_pts + kRowSpectra - 1) / kRowSpectra, 4096);
-}
-
-// layout of the raw per-chunk sums the fused paths produce (see raw_index)
-int fused_layout(const fxc_plan* p) { return p->n_ant == 2 ? 1 : (p->path == FXC_PATH_FUSED ? 2 : 0); }
-
-// chunks per pass on the fused paths: 2 antennas only need the raw rows; more antennas also the spectra
-int64_t fused_chunks_per_pass(const fxc_plan* p, int64_t n_chunks, int64_t* spec_bytes, int64_t* raw_bytes) {
-    // (3 and more antennas: one raw row per chunk and frame range at most, x_ranges)
-    const int64_t xr = x_ranges(p, 1);
-    const int64_t raw_per_chunk = (int64_t)p->n_prod * p->nchan * (int64_t)sizeof(cf) * xr;
-    const int64_t spec_per_chunk = p->n_ant == 2 ? 0 : (int64_t)p->n_ant * p->n_pts * p->nchan * (int64_t)sizeof(cf);
-    int64_t cb = ws_target() / (raw_per_chunk + spec_per_chunk);
-    if (cb < 1) cb = 1;
-    if (cb > n_chunks) cb = n_chunks;
-    if (p->n_ant > 2 && cb > 65535 / xr) cb = std::max<int64_t>(1, 65535 / xr);   // the X-engines carry group and range in grid.y
-    *spec_bytes = up256(cb * spec_per_chunk);
-    // 2 antennas: one leading-part row per workgroup after the chunk rows (fx_fused4096_kernel)
-    *raw_bytes = up256((cb + (p->n_ant == 2 ? p->fused_grid_max : 0)) * raw_per_chunk);
-    return cb;
-}
-
-int launch_xengine(fxc_plan* p, const cf* spec, cf* raw, int64_t nc, int cg, int xr);
-
-// Two antennas under a delay track: every chunk pair is summed whole, frame after frame by one workgroup, so its row is the same
-// bits in any call (the kernel's frame ranges would cut the last chunks of a launch by the launch's size).  Two launches of the
-// unchanged kernel: full rounds over fused_grid_max workgroups, then the rest with one workgroup per chunk pair.  Row c = chunk c;
-// the second launch's rows start where the first one's (empty) leading-part rows lie, and its own end within the nc +
-// fused_grid_max rows of the pass.
-int fused_whole_chunks(fxc_plan* p, const cf* x, int64_t nc, cf* raw, const cf* dc_u8, int64_t num_samp) {
-    const int64_t samp = num_samp ? num_samp : p->num_samp;
-    const int64_t in_bytes = 2 * samp * (dc_u8 ? 2 : (int64_t)sizeof(cf));      // per chunk pair
-    const int64_t row = (int64_t)fxc::fused::kN * (p->autos && p->nchan == fxc::fused::kN ? p->n_prod : 1);
-    const int64_t g = p->fused_grid_max;
-    const int64_t n1 = nc / g * g;
-    if (n1 > 0) {
-        const int rc = launch_fused(p, x, n1, raw, false, dc_u8, 1, true, num_samp, false, (int)g);
-        if (rc) return rc;
-    }
-    if (nc > n1)
-        return launch_fused(p, reinterpret_cast<const cf*>(reinterpret_cast<const char*>(x) + n1 * in_bytes), nc - n1, raw + n1 * row, false,
-                            dc_u8 ? dc_u8 + n1 * 2 : nullptr, 1, true, num_samp, false, (int)(nc - n1));
-    return FXC_OK;
-}
-
-// raw[c][p][layout] for nc chunks starting at x; spec = scratch for the multi-antenna path.  2 antennas: rows of
-// `unit` chunks + leading-part rows (fused_rows() of them in all)
-int fused_raw_sums(fxc_plan* p, const cf* x, int64_t nc, cf* spec, cf* raw, const cf* dc_u8 = nullptr, int64_t unit = 1,
-                   bool rows_are_chunks = true, bool dck = false) {
-    using namespace fxc::fused;
-    if (p->n_ant == 2 && p->track) return fused_whole_chunks(p, x, nc, raw, dc_u8, 0);
-    if (p->n_ant == 2) return launch_fused(p, x, nc, raw, false, dc_u8, unit, rows_are_chunks, 0, dck);
-    // 3 .. 64 antennas: spectra to HBM as [chunk][frame][antenna] rows (the F-only fused kernel in its own position order
-    // at nchan 4096 / ntaps 4, the F-only tiled kernel in natural order otherwise), then the register-resident X-engine
-    // (over blocks of 8 antennas beyond 8).
-    // unit = chunks per raw row here too: ceil(nc / unit) rows come out
-    int rc = p->path == FXC_PATH_FUSED ? launch_fused(p, x, nc * (p->n_ant / 2), spec, true)
-                                       : tiled_channelize(p, x, spec, nc * p->n_ant, p->n_ant);
-    if (rc) return rc;
-    return launch_xengine(p, spec, raw, nc, (int)unit, x_ranges(p, unit));
-}
-
-// spec[chunk][frame][antenna][nchan] -> raw[range][group][baseline][nchan] (natural bin order): 3 .. 8 antennas in registers,
-// more on the matrix cores (plans whose nchan the tiles divide) or over blocks of 8
-int launch_xengine(fxc_plan* p, const cf* spec, cf* raw, int64_t nc, int cg, int xr) {
-    int x_ch = 16;
-    if (p->x_mfma) FXC_XMFMA_DISPATCH(p, x_ch = XMfmaGeo<XT>::kCH);
-    const dim3 grid((p->nchan + kXThreads - 1) / kXThreads, (unsigned)(((nc + cg - 1) / cg) * xr));
-#define FXC_X_LAUNCH(A) \
-    hipLaunchKernelGGL(xengine_kernel<A>, grid, dim3(kXThreads), 0, p->stream, spec, raw, p->n_pts, p->nchan, nc, cg, xr)
-    switch (p->n_ant) {
-        case 3: FXC_X_LAUNCH(3); break;
-        case 4: FXC_X_LAUNCH(4); break;
-        case 5: FXC_X_LAUNCH(5); break;
-        case 6: FXC_X_LAUNCH(6); break;
-        case 7: FXC_X_LAUNCH(7); break;
-        case 8: FXC_X_LAUNCH(8); break;
-        default: if (p->x_mfma && p->nchan % x_ch == 0) {       // (the matrix-core tiles take whole columns of x_ch bins)
-            FXC_XMFMA_DISPATCH(p, hipLaunchKernelGGL(xengine_mfma_kernel<XT>, dim3((unsigned)(p->nchan / XMfmaGeo<XT>::kCH), grid.y),
-                                                     dim3(XMfmaGeo<XT>::kThreads), XMfmaGeo<XT>::kLdsBytes, p->stream, spec, raw,
-                                                     p->n_pts, p->nchan, nc, cg, p->n_ant, xr, FXC_DEV_ENV_INT("FXC_XMFMA_ABL", 0)));
-        } else {
-            const unsigned gb = (unsigned)((p->n_ant + kXB - 1) / kXB);
-            hipLaunchKernelGGL(xengine_block_kernel, dim3(grid.x, grid.y, gb * (gb + 1) / 2), dim3(kXThreads), 0, p->stream, spec,
-                               raw, p->n_pts, p->nchan, nc, cg, p->n_ant, xr);
-        } break;
-    }
-#undef FXC_X_LAUNCH
-    FXC_HIP(p, hipGetLastError());
+int launch_spec(fxc_plan* p, const SpecKernel* k, const SpecLaunch& s) {
+    if (s.groups * s.ws > (1ll << 30)) return fail(p, FXC_ERR_ARG, "too many streams or chunks for one launch");
+    SpecArgs a = {s.x, p->d_win, s.out, p->d_tw, s.dc_u8, (long long)p->num_samp, (long long)p->n_pts, (long long)s.n_streams, (int)s.ws,
+                  s.ant, reinterpret_cast<const float*>(p->d_win4), k->d_tw1, (long long)s.stride, s.spec0};
+    void* params[] = {&a};
+    FXC_HIP(p, hipModuleLaunchKernel(k->fn, (unsigned)(s.groups * s.ws), 1, 1, (unsigned)k->shape.threads(), 1, 1, 0, p->stream, params, nullptr));
     return FXC_OK;
 }
 
@@ -667,30 +546,41 @@ int tiled_setup(fxc_plan* p) {
     return FXC_OK;
 }
 
-// SPEC: x = n_streams consecutive streams, nc = pairs of them, raw = spectra [stream][i][k]
+// A launch of the tiled or the wave-local kernels over nc work items, each cut into n_splits frame ranges: chunks, raw sums out, or
+// -- the F-only forms (SPEC) -- pairs of the n_streams consecutive streams at x, spectra [stream][i][k] out
+struct TiledLaunch {
+    const cf* x;
+    int64_t nc;
+    int n_splits;
+    cf* out;
+    int64_t n_streams;
+    const cf* dc_u8 = nullptr;       // F+X: x is the byte stream, dc_u8 the streams' conversion offsets
+    int spec_a = 0;                  // F only: spectra by frame, spec_a antennas interleaved (0: by stream) ...
+    int64_t s_base = 0;              // ... with the rows placed from the global stream index: that of the launch's first stream
+};
+
 template <class G, bool SPEC>
-void tiled_launch(fxc_plan* p, const cf* x, int64_t nc, int n_splits, cf* raw, int64_t n_streams, const cf* dc_u8 = nullptr,
-                  int spec_a = 0, int64_t s_base = 0) {
-    const int grid = (int)std::min<int64_t>(nc * n_splits, SPEC ? p->tiled_grid_max_f : p->tiled_grid_max);
+void tiled_launch(fxc_plan* p, const TiledLaunch& t) {
+    const int grid = (int)std::min<int64_t>(t.nc * t.n_splits, SPEC ? p->tiled_grid_max_f : p->tiled_grid_max);
     if constexpr (G::N <= 4096) {
         if (p->tiled_ring) {
+#define FXC_RING_LAUNCH(U8)                                                                                                          \
+    hipLaunchKernelGGL((fx_tiled_ring_kernel<G, SPEC, U8>), dim3(grid), dim3(G::kThreads), G::kLdsBytesRing, p->stream, t.x, p->num_samp, \
+                       p->n_pts, t.nc, t.n_splits, p->d_win4, p->d_tw0, p->d_tw1, p->d_tw2, t.out, t.n_streams, t.dc_u8, t.spec_a, t.s_base)
             if constexpr (!SPEC) {
-                if (dc_u8) {   // uint8 ingest: x is the byte stream
-                    hipLaunchKernelGGL((fx_tiled_ring_kernel<G, false, true>), dim3(grid), dim3(G::kThreads), G::kLdsBytesRing,
-                                       p->stream, x, p->num_samp, p->n_pts, nc, n_splits, p->d_win4, p->d_tw0, p->d_tw1,
-                                       p->d_tw2, raw, n_streams, dc_u8, 0, (int64_t)0);
+                if (t.dc_u8) {   // uint8 ingest: x is the byte stream
+                    FXC_RING_LAUNCH(true);
                     return;
                 }
             }
-            hipLaunchKernelGGL((fx_tiled_ring_kernel<G, SPEC, false>), dim3(grid), dim3(G::kThreads), G::kLdsBytesRing,
-                               p->stream, x, p->num_samp, p->n_pts, nc, n_splits, p->d_win4, p->d_tw0, p->d_tw1, p->d_tw2, raw,
-                               n_streams, (const cf*)nullptr, spec_a, s_base);
+            FXC_RING_LAUNCH(false);
+#undef FXC_RING_LAUNCH
             return;
         }
     }
-    hipLaunchKernelGGL((fx_tiled_kernel<G, SPEC>), dim3(grid), dim3(G::kThreads), G::kLdsBytes, p->stream, x, p->num_samp,
-                       p->n_pts, nc, n_splits, p->prefilter ? 1 : p->ntaps, p->prefilter ? p->d_ones : p->d_win, p->d_tw0,
-                       p->d_tw1, p->d_tw2, raw, n_streams, spec_a, s_base);
+    hipLaunchKernelGGL((fx_tiled_kernel<G, SPEC>), dim3(grid), dim3(G::kThreads), G::kLdsBytes, p->stream, t.x, p->num_samp,
+                       p->n_pts, t.nc, t.n_splits, p->prefilter ? 1 : p->ntaps, p->prefilter ? p->d_ones : p->d_win, p->d_tw0,
+                       p->d_tw1, p->d_tw2, t.out, t.n_streams, t.spec_a, t.s_base);
 }
 
 #define FXC_TILED_DISPATCH(p, CALL)                                                   \
@@ -703,13 +593,11 @@ void tiled_launch(fxc_plan* p, const cf* x, int64_t nc, int n_splits, cf* raw, i
         default: return fail(p, FXC_ERR_UNSUPPORTED, "no tiled kernel for nchan=%d", (p)->nchan); \
     }
 
-// this call goes through the tiled kernels.  (Round 1 also sent few-chunk calls on the headline shape here to split a
-// chunk's frames over workgroups; the fused kernel's frame ranges do that themselves now, faster: one reference-sized
-// call 25 us against 56.)
-bool use_tiled(const fxc_plan* p, int64_t) { return p->path == FXC_PATH_TILED; }
-
-bool tiled_nchan(int n) { return n == 512 || n == 1024 || n == 2048 || n == 4096 || n == 8192; }
-bool small_nchan(int n) { return n == 16 || n == 32 || n == 64 || n == 128 || n == 256; }
+template <bool SPEC>
+int tiled_dispatch(fxc_plan* p, const TiledLaunch& t) {
+    FXC_TILED_DISPATCH(p, (tiled_launch<G, SPEC>(p, t)));
+    return FXC_OK;
+}
 
 // ---- tiled path, 16 .. 256 channels (k_small.h) -----------------------------------------------------
 #define FXC_SMALL_DISPATCH(p, CALL)                                                   \
@@ -728,89 +616,27 @@ int small_setup(fxc_plan* p) {
                               &per_cu, reinterpret_cast<const void*>(&fx_small_ring_kernel<P, false, false>), 256, 0)));
     if (per_cu < 1) return fail(p, FXC_ERR_HIP, "small-transform kernel for nchan=%d does not fit a CU", p->nchan);
     p->small_wgs = per_cu * p->cu_count;
-    // work items resident at once (tiled_splits); the F-only variant has the same launch geometry
+    // work items resident at once (tiled_fill); the F-only variant has the same launch geometry
     p->tiled_grid_max = p->tiled_grid_max_f = p->small_wgs * 4 * (32 / (p->nchan / 16));
     return FXC_OK;
 }
 
-int small_grid(const fxc_plan* p, int64_t items) {
-    const int64_t items_per_wg = 4 * (32 / (p->nchan / 16));
-    return (int)std::min<int64_t>((items + items_per_wg - 1) / items_per_wg, p->small_wgs);
-}
-
-// dc_u8 != nullptr: x is the byte stream, dc_u8 the streams' conversion offsets
-int small_launch(fxc_plan* p, const cf* x, int64_t nc, int n_splits, cf* raw, const cf* dc_u8) {
-    const int grid = small_grid(p, nc * n_splits);
-    if (dc_u8) {
-        FXC_SMALL_DISPATCH(p, hipLaunchKernelGGL((fx_small_ring_kernel<P, true, false>), dim3(grid), dim3(256), 0, p->stream, x,
-                                                 p->num_samp, p->n_pts, nc, n_splits, p->d_win4, p->d_tw_small, raw, dc_u8,
-                                                 2 * nc, 0, (int64_t)0));
-    } else {
-        FXC_SMALL_DISPATCH(p, hipLaunchKernelGGL((fx_small_ring_kernel<P, false, false>), dim3(grid), dim3(256), 0, p->stream, x,
-                                                 p->num_samp, p->n_pts, nc, n_splits, p->d_win4, p->d_tw_small, raw,
-                                                 (const cf*)nullptr, 2 * nc, 0, (int64_t)0));
-    }
-    return FXC_OK;
-}
-
-int tiled_splits(const fxc_plan* p, int64_t n_chunks, bool f_only = false);
-
-// F-stage only (see tiled_channelize): n_streams consecutive streams -> natural-order spectra, pairs of streams per item
-int tiled_splits(const fxc_plan* p, int64_t n_chunks, bool f_only);
-int64_t tiled_streams_per_pass(const fxc_plan* p);
-int tiled_prefilter(fxc_plan* p, const cf* x, int64_t n_streams, const cf** y_out);
-
-int small_channelize(fxc_plan* p, const cf* x, cf* spec, int64_t n_streams, int spec_a) {
-    KernelTimer kt(p);
-    const int64_t per_pass = tiled_streams_per_pass(p);      // everything at once unless the pre-filter bounds a pass
-    for (int64_t s0 = 0; s0 < n_streams; s0 += per_pass) {
-        const int64_t ns = std::min(per_pass, n_streams - s0);
-        const cf* xs = x + s0 * p->num_samp;
-        if (p->prefilter) {
-            const int rc = tiled_prefilter(p, xs, ns, &xs);
-            if (rc) return rc;
+template <bool SPEC>
+int small_launch(fxc_plan* p, const TiledLaunch& t) {
+    const int grid = small_grid(p, t.nc * t.n_splits);
+#define FXC_SMALL_LAUNCH(U8)                                                                                                          \
+    FXC_SMALL_DISPATCH(p, hipLaunchKernelGGL((fx_small_ring_kernel<P, U8, SPEC>), dim3(grid), dim3(256), 0, p->stream, t.x, p->num_samp, \
+                                             p->n_pts, t.nc, t.n_splits, p->d_win4, p->d_tw_small, t.out, t.dc_u8, t.n_streams,          \
+                                             t.spec_a, t.s_base))
+    if constexpr (!SPEC) {
+        if (t.dc_u8) {
+            FXC_SMALL_LAUNCH(true);
+            return FXC_OK;
         }
-        const int64_t pairs = (ns + 1) / 2;
-        const int n_splits = tiled_splits(p, pairs, true);
-        const int grid = small_grid(p, pairs * n_splits);
-        // spec_a == 0: this pass's streams start at row s0 * n_pts; by frame: rows are placed from the global stream index
-        FXC_SMALL_DISPATCH(p, hipLaunchKernelGGL((fx_small_ring_kernel<P, false, true>), dim3(grid), dim3(256), 0, p->stream, xs,
-                                                 p->num_samp, p->n_pts, pairs, n_splits, p->d_win4, p->d_tw_small,
-                                                 spec_a ? spec : spec + s0 * p->n_pts * p->nchan, (const cf*)nullptr, ns, spec_a,
-                                                 spec_a ? s0 : (int64_t)0));
     }
-    kt.stop();
-    FXC_HIP(p, hipGetLastError());
+    FXC_SMALL_LAUNCH(false);
+#undef FXC_SMALL_LAUNCH
     return FXC_OK;
-}
-
-// frame ranges per chunk so that a launch has at least ~2 work items per resident workgroup
-int tiled_splits(const fxc_plan* p, int64_t n_chunks, bool f_only) {
-    const int64_t cap = f_only ? p->tiled_grid_max_f : p->tiled_grid_max;
-    const int64_t want = (2 * cap + n_chunks - 1) / n_chunks;
-    // runs of eight frames at least -- the two-pass 8192-channel route (one workgroup per CU, 8 us a frame) with a handful of chunks:
-    // of one (latency: see spec_wg_splits)
-    const bool few = p->x8192 && n_chunks * std::max<int64_t>(1, p->n_pts / 8) < p->cu_count;
-    const int64_t most = std::max<int64_t>(1, p->n_pts / (few ? 1 : 8));
-    const int64_t fill = std::max<int64_t>(1, std::min<int64_t>(std::min(want, most), 256));
-    if (f_only) return (int)fill;
-    // F+X: a work item sums its frames in float32, like the headline kernel's rows at most kRowSpectra of them (small
-    // channel counts and long chunks have thousands of frames per chunk)
-    const int64_t exact = std::min<int64_t>((p->n_pts + kRowSpectra - 1) / kRowSpectra, 65536);
-    return (int)std::max(fill, exact);
-}
-
-// streams of the tiled path per pass: what a pass keeps beside the raw rows -- the pre-filter's output, or antenna 0's spectra of the
-// two-pass 8192-channel route -- stays within the workspace target
-int64_t tiled_streams_per_pass(const fxc_plan* p) {
-    if (p->x8192) {       // 8192 channels in two passes: antenna 0's spectra of a pass stay within the workspace target
-        const int64_t chunks = std::max<int64_t>(1, ws_target() / (p->n_pts * (int64_t)p->nchan * (int64_t)sizeof(cf)));
-        return 2 * std::min<int64_t>(chunks, 1 << 20);
-    }
-    if (!p->prefilter) return INT64_MAX;
-    int64_t n = ws_target() / (p->num_samp * (int64_t)sizeof(cf));
-    n = std::min<int64_t>(n, 65534) & ~(int64_t)1;      // grid.y carries the stream (or a row of them); whole pairs
-    return std::max<int64_t>(2, n);
 }
 
 // y = pre-filtered copy of n_streams streams (plan buffer, grown on demand)
@@ -829,11 +655,7 @@ int tiled_prefilter(fxc_plan* p, const cf* x, int64_t n_streams, const cf** y_ou
     const int spb = (int)std::max<int64_t>(1, std::min<int64_t>(256 * w / p->nchan, (1ll << 31) / stream_bytes));
     const bool pack = p->nchan < 256 * w;
     const int64_t rows = (n_streams + spb - 1) / spb;
-    // frame splits so that a few-stream call still fills the chip; each split reloads one block of history
-    const int64_t blocks = std::max<int64_t>(1, p->nchan / (256 * w)) * rows;
-    int64_t fs = std::max<int64_t>(1, (2 * (int64_t)p->cu_count + blocks - 1) / blocks);
-    fs = std::min<int64_t>(fs, std::max<int64_t>(1, p->n_pts / (4 * tp)));
-    const int64_t per = ((p->n_pts + fs - 1) / fs + 2 * tp - 1) / (2 * tp) * (2 * tp);
+    const int64_t per = prefilter_frames(p, std::max<int64_t>(1, p->nchan / (256 * w)) * rows);
     const dim3 grid((unsigned)std::max(1, p->nchan / (256 * w)), (unsigned)rows, (unsigned)((p->n_pts + per - 1) / per));
 #define FXC_PRE_LAUNCH(TP, W)                                                                                                    \
     do {                                                                                                                         \
@@ -858,20 +680,267 @@ int tiled_prefilter(fxc_plan* p, const cf* x, int64_t n_streams, const cf** y_ou
     return FXC_OK;
 }
 
-// raw[split][c][k] (natural bin order) for nc chunks starting at x (nc * 2 <= tiled_streams_per_pass())
-int tiled_raw_sums(fxc_plan* p, const cf* x, int64_t nc, int n_splits, cf* raw, const cf* dc_u8 = nullptr) {
+// F-stage only: n_streams consecutive streams -> natural-order spectra spec[stream][i][k] (spec_a antennas interleaved by frame:
+// [chunk][i][antenna][k]), pairs of streams per work item
+int tiled_channelize(fxc_plan* p, const cf* x, cf* spec, int64_t n_streams, int spec_a = 0) {
     KernelTimer kt(p);
-    if (p->small) {
-        if (p->prefilter && !dc_u8) {       // more than four taps: the FIR as its own pass, the wave-local kernel with one unit tap
-            const int rp = tiled_prefilter(p, x, 2 * nc, &x);
-            if (rp) return rp;
+    if (p->f8192 && p->num_samp < (1ll << 28)) {
+        const int n_splits = ring8192_splits(p, n_streams);
+        hipLaunchKernelGGL((f8192_ring_kernel<false, false>), ring8192_grid(p, n_streams, n_splits), dim3(kF8192Threads), 0, p->stream, x,
+                           p->num_samp, p->n_pts, n_streams, n_splits, p->d_win4, p->d_tw0, p->d_tw1, p->d_tw2, spec, spec_a, (int64_t)0,
+                           p->num_samp, (const cf*)nullptr, (const cf*)nullptr, 0);
+    } else {
+        const int64_t per_pass = tiled_streams_per_pass(p);      // everything at once unless the pre-filter bounds a pass
+        for (int64_t s0 = 0; s0 < n_streams; s0 += per_pass) {
+            const int64_t ns = std::min(per_pass, n_streams - s0);
+            const cf* xs = x + s0 * p->num_samp;
+            if (p->prefilter) {
+                const int rc = tiled_prefilter(p, xs, ns, &xs);
+                if (rc) return rc;
+            }
+            // spec_a == 0: this pass's streams start at row s0 * n_pts; by frame: the kernel places rows from the global stream index
+            const int64_t pairs = (ns + 1) / 2;
+            TiledLaunch t = {xs, pairs, tiled_f_splits(p, pairs), spec_a ? spec : spec + s0 * p->n_pts * p->nchan, ns};
+            t.spec_a = spec_a;
+            t.s_base = spec_a ? s0 : 0;
+            const int rc = p->small_f ? small_launch<true>(p, t) : tiled_dispatch<true>(p, t);
+            if (rc) return rc;
         }
-        const int rc = small_launch(p, x, nc, n_splits, raw, dc_u8);
-        if (rc) return rc;
-        kt.stop();
-        FXC_HIP(p, hipGetLastError());
-        return FXC_OK;
     }
+    kt.stop();
+    FXC_HIP(p, hipGetLastError());
+    return FXC_OK;
+}
+
+// the plan's F stage alone over n_streams consecutive streams: x -> spec (both device, natural bin order), `ant` antennas
+// interleaved by frame
+int run_channelize(fxc_plan* p, const cf* x, cf* spec, int64_t n_streams, int ant = 1) {
+    if (n_streams == 0 || p->n_pts == 0) return FXC_OK;
+    // the F-only tiled kernel writes natural-order spectra straight to `spec` (no workspace): any caller may use it
+    if (p->tiled_f) return tiled_channelize(p, x, spec, n_streams);
+    if (p->mixed && p->mixed_blu) {
+        // a large prime factor: chirp-z rows of nfft = 2^j >= 2 nchan - 1, one row per workgroup pass
+        const int threads = std::max(256, p->mixed_tpr);
+        const int rpw = threads / p->mixed_tpr;
+        const bool twl = p->blu_nfft <= 4096;
+        const size_t lds = ((size_t)rpw * 2 + (twl ? 1 : 0)) * p->blu_nfft * sizeof(cf);
+        const int grid = mixed_grid(p, n_streams * ((p->n_pts + rpw - 1) / rpw), kMixedRun);
+        const MixedExtras blu = {mixed_wave_local(p, kFOnly), ant, p->blu_nfft, p->d_chirp, p->d_blud, nullptr};
+        if (twl)
+            hipLaunchKernelGGL((pfb_fft_mixed_kernel<true, 1, false, true>), dim3(grid), dim3(threads), lds, p->stream, x, p->d_win,
+                               spec, p->d_tw, p->mixed_plan, p->num_samp, p->nchan, p->ntaps, p->n_pts, n_streams, p->mixed_tpr, 1, blu);
+        else
+            hipLaunchKernelGGL((pfb_fft_mixed_kernel<false, 1, false, true>), dim3(grid), dim3(threads), lds, p->stream, x, p->d_win,
+                               spec, p->d_tw, p->mixed_plan, p->num_samp, p->nchan, p->ntaps, p->n_pts, n_streams, p->mixed_tpr, 1, blu);
+    } else if (const SpecKernel* k = spec_f_kernel(p)) {
+        // the F stage built for exactly this channel count (fx_spec.h, FXM_FONLY: a workgroup carries two streams through the
+        // stages, the last butterfly stores the spectra); compiled on first use
+        const int64_t pairs = (n_streams + k->shape.rows - 1) / k->shape.rows;      // (groups of streams: a workgroup's rows)
+        SpecLaunch s = {x, spec, n_streams, pairs, spec_wg_splits(p, k, pairs, kSpectraOut)};
+        s.ant = ant;
+        return launch_spec(p, k, s);
+    } else if (p->mixed && p->nchan > kMixedMaxN) {
+        // one LDS row, the other in the output (pfb_fft_mixed_kernel, BIG): one frame per workgroup pass, 1024 threads
+        const int grid = mixed_grid(p, n_streams * p->n_pts, kMixedRun);
+        hipLaunchKernelGGL((pfb_fft_mixed_kernel<false, 1, false, false, true>), dim3(grid), dim3(1024), (size_t)p->nchan * sizeof(cf),
+                           p->stream, x, p->d_win, spec, p->d_tw, p->mixed_plan, p->num_samp, p->nchan, p->ntaps, p->n_pts, n_streams,
+                           1024, 1, MixedExtras{0, ant, p->nchan, nullptr, nullptr, nullptr});
+    } else if (p->mixed) {
+        const int threads = std::max(256, p->mixed_tpr);
+        const int rpw = threads / p->mixed_tpr;
+        const MixedExtras no_blu = {mixed_wave_local(p, kFOnly), ant, p->nchan, nullptr, nullptr, nullptr};
+        static const int tw_knob = FXC_DEV_ENV_INT("FXC_MIXED_TWLDS", 1), u_knob = FXC_DEV_ENV_INT("FXC_MIXED_U", 0);
+        // U = 2 frames per slot where the measurements favour it (tools/bench_channelize.py, r04 experiments.md §7): up to 1280
+        // channels (three or more 256-thread workgroups still fit a CU's LDS) and, with 512 or 1024 threads per row, from 1321 to
+        // 4096 (1440 ... 2000 channels: 10 - 25 % faster than one frame per slot on 256 threads)
+        const size_t row_bytes = (size_t)p->nchan * sizeof(cf);
+        int u = (p->nchan <= 1280 || (p->mixed_tpr >= 512 && p->nchan <= 4096)) ? 2 : 1;
+        u = std::min(u, fxc::mixed_rows_per_slot_cap(p->mixed_plan));     // 11 / 13: register butterflies one frame at a time here
+        if (u_knob == 1 || u_knob == 2) u = u_knob;
+        const bool twl = tw_knob && (1 + (size_t)rpw * 2 * u) * row_bytes <= (size_t)(160 * 1024);
+        if (!twl) u = 1;
+        const size_t lds = ((size_t)rpw * 2 * u + (twl ? 1 : 0)) * row_bytes;
+        const int fpg = rpw * u;
+        static const int run_knob = FXC_DEV_ENV_INT("FXC_MIXED_RUN", kMixedRun);
+        const int grid = mixed_grid(p, n_streams * ((p->n_pts + fpg - 1) / fpg), run_knob);
+#define FXC_MIXED_LAUNCH(TWL, UU)                                                                                                     \
+    hipLaunchKernelGGL((pfb_fft_mixed_kernel<TWL, UU, false>), dim3(grid), dim3(threads), lds, p->stream, x, p->d_win, spec, p->d_tw, \
+                       p->mixed_plan, p->num_samp, p->nchan, p->ntaps, p->n_pts, n_streams, p->mixed_tpr, 1, no_blu)
+        if (!twl)
+            FXC_MIXED_LAUNCH(false, 1);
+        else if (u == 2)
+            FXC_MIXED_LAUNCH(true, 2);
+        else
+            FXC_MIXED_LAUNCH(true, 1);
+#undef FXC_MIXED_LAUNCH
+    } else {
+        const int64_t total = n_streams * p->n_pts * p->nchan;
+        hipLaunchKernelGGL(pfb_fir_kernel, dim3(grid_for(total, 256, p->cu_count)), dim3(256), 0, p->stream, x, p->d_win,
+                           spec, p->num_samp, p->nchan, p->ntaps, p->n_pts, total);
+        const int64_t rows = n_streams * p->n_pts;
+        if (p->nchan > 1) {
+            const int grid = (int)std::min<int64_t>(rows, (int64_t)p->cu_count * 4);
+            const size_t lds = (size_t)std::max(p->nchan, p->pow2 ? 512 : 0) * sizeof(cf);   // small N: 512 / N rows per workgroup
+            if (p->pow2)
+                hipLaunchKernelGGL(fft_pow2_kernel, dim3(grid), dim3(256), lds, p->stream, spec, p->d_tw, p->nchan,
+                                   p->lg2n, rows);
+            else
+#if FXC_DEV_KERNELS
+                hipLaunchKernelGGL(dft_any_kernel, dim3(grid), dim3(256), lds, p->stream, spec, p->d_tw, p->nchan, rows);
+#else
+                return fail(p, FXC_ERR_UNSUPPORTED, "no FFT kernel for %d channels in this build", p->nchan);      // (every such count takes the mixed-radix kernel)
+#endif
+        }
+    }
+    FXC_HIP(p, hipGetLastError());
+    return FXC_OK;
+}
+
+// spec -> raw[range][group][product][nchan] (natural bin order), groups of cg chunks and xr frame ranges: 3 .. 8 antennas in
+// registers, more on the matrix cores (plans whose nchan the tiles divide) or over blocks of 8, from spec[chunk][frame][antenna][nchan].
+// AUTOS (2 .. 8 antennas): the antennas' power sums after the baselines, from the spectra the F stage alone writes -- [chunk][antenna]
+// [frame][nchan]: frames one row apart, antennas n_pts
+template <bool AUTOS = false>
+int launch_xengine(fxc_plan* p, const cf* spec, cf* raw, int64_t nc, int cg, int xr) {
+    const dim3 grid((p->nchan + kXThreads - 1) / kXThreads, (unsigned)(((nc + cg - 1) / cg) * xr));
+#define FXC_X_LAUNCH(A)                                                                                                                 \
+    hipLaunchKernelGGL((xengine_kernel<A, AUTOS>), grid, dim3(kXThreads), 0, p->stream, spec, raw, p->n_pts, p->nchan, nc, cg, xr,       \
+                       (int64_t)(AUTOS ? 1 : A), AUTOS ? p->n_pts : (int64_t)1)
+    switch (p->n_ant) {
+        case 3: FXC_X_LAUNCH(3); break;
+        case 4: FXC_X_LAUNCH(4); break;
+        case 5: FXC_X_LAUNCH(5); break;
+        case 6: FXC_X_LAUNCH(6); break;
+        case 7: FXC_X_LAUNCH(7); break;
+        case 8: FXC_X_LAUNCH(8); break;
+        default:
+            if constexpr (AUTOS) {      // (two antennas: the X-engine with autos only; without, F and X share a kernel)
+                if (p->n_ant != 2) return fail(p, FXC_ERR_UNSUPPORTED, "autos for %d antennas", p->n_ant);
+                FXC_X_LAUNCH(2);
+            } else if (p->x_mfma && p->nchan % xmfma_column(p) == 0) {       // (the matrix-core tiles take whole columns of bins)
+                FXC_XMFMA_DISPATCH(p, hipLaunchKernelGGL(xengine_mfma_kernel<XT>, dim3((unsigned)(p->nchan / XMfmaGeo<XT>::kCH), grid.y),
+                                                         dim3(XMfmaGeo<XT>::kThreads), XMfmaGeo<XT>::kLdsBytes, p->stream, spec, raw,
+                                                         p->n_pts, p->nchan, nc, cg, p->n_ant, xr, FXC_DEV_ENV_INT("FXC_XMFMA_ABL", 0)));
+            } else {
+                const unsigned gb = (unsigned)((p->n_ant + kXB - 1) / kXB);
+                hipLaunchKernelGGL(xengine_block_kernel, dim3(grid.x, grid.y, gb * (gb + 1) / 2), dim3(kXThreads), 0, p->stream, spec,
+                                   raw, p->n_pts, p->nchan, nc, cg, p->n_ant, xr);
+            }
+            break;
+    }
+#undef FXC_X_LAUNCH
+    FXC_HIP(p, hipGetLastError());
+    return FXC_OK;
+}
+
+// ---- the routes: raw rows of a pass of nc chunks starting at x ----------------------------------------------------------------
+
+// Two antennas above 4096 channels off the powers of two (complex64 samples, two_pass_xm): two passes of the kernels built for the
+// channel count -- antenna 0 of every chunk pair through the F stage into `spec` [chunk][frame][nchan], then antenna 1 through the
+// same stages with the last butterfly multiplying by antenna 0's values and adding to the thread's sums (fx_spec.h, FXM_XM): 2 x the
+// algorithmic bytes, where the spectra of both antennas + xmul_kernel move 3 x.  raw[split][chunk][nchan] out, as mixed_fx_raw_sums.
+int two_pass_raw_sums(fxc_plan* p, const cf* x, int64_t n_chunks, int n_splits, cf* spec, cf* raw) {
+    const SpecKernel* kx = p->spec_xm;
+    if (n_splits % kx->shape.slots) return fail(p, FXC_ERR_STATE, "row splits and the second-pass kernel's slots disagree");
+    // (the streams of an antenna lie two chunks apart)
+    SpecLaunch f = {x, spec, n_chunks, n_chunks, spec_wg_splits(p, p->spec_f, n_chunks, kSpectraOut)};
+    f.stride = 2 * p->num_samp;
+    SpecLaunch xm = {x + p->num_samp, raw, n_chunks, n_chunks, n_splits / kx->shape.slots};
+    xm.stride = f.stride;
+    xm.spec0 = spec;
+    const int rc = launch_spec(p, p->spec_f, f);
+    return rc ? rc : launch_spec(p, kx, xm);
+}
+
+// two antennas on the mixed-radix kernel: F and X in one pass, raw[split][chunk][nchan] out (xmul_kernel's layout)
+// (dc_u8 != nullptr: x is the uint8 I,Q stream of these chunks and dc_u8 its conversion offsets per stream)
+int mixed_fx_raw_sums(fxc_plan* p, const cf* x, int64_t n_chunks, int n_splits, cf* raw, const cf* dc_u8) {
+    if (p->spec) {
+        // the build of fx_spec.h made for this channel count (h_rtc.h); its byte-ingest twin is compiled on first use
+        const SpecKernel* k = p->spec;
+        if (dc_u8) k = spec_once(p, &p->spec_u8, &p->spec_u8_tried, kSpecU8);
+        if (k && n_splits % k->shape.slots == 0 && n_splits / k->shape.slots >= 1) {
+            SpecLaunch s = {x, raw, n_chunks, n_chunks, n_splits / k->shape.slots};
+            s.dc_u8 = dc_u8;
+            return launch_spec(p, k, s);
+        }
+        if (env_int("FXC_RTC_VERBOSE", 0))      // (results stay correct: the any-shape kernel below takes the call)
+            std::fprintf(stderr, "libfxcorr: %d channels: the %s build of the kernel per channel count does not take this call (%s), the any-shape kernel does\n",
+                         p->nchan, dc_u8 ? "byte-ingest" : "complex64", !k ? "no such build" : "its slots per workgroup do not divide the call's row splits");
+    }
+    const int threads = std::max(256, p->mixed_tpr);
+    const int rpw = threads / p->mixed_tpr;
+    const size_t lds = ((size_t)rpw * 4 + (p->mixed_xf_twl ? 1 : 0)) * p->nchan * sizeof(cf);
+    const int64_t grid = n_chunks * n_splits;
+    if (grid > (1ll << 30)) return fail(p, FXC_ERR_ARG, "too many chunks for one launch");
+    const MixedExtras ex = {mixed_wave_local(p, kFusedX), 1, p->nchan, nullptr, nullptr, dc_u8};
+#define FXC_MIXED_XF_LAUNCH(TWL, BYTES)                                                                                            \
+    hipLaunchKernelGGL((pfb_fft_mixed_kernel<TWL, 2, true, false, false, BYTES>), dim3((unsigned)grid), dim3(threads), lds, p->stream, \
+                       x, p->d_win, raw, p->d_tw, p->mixed_plan, p->num_samp, p->nchan, p->ntaps, p->n_pts, n_chunks, p->mixed_tpr,    \
+                       n_splits, ex)
+    if (p->mixed_xf_twl) {
+        if (dc_u8)
+            FXC_MIXED_XF_LAUNCH(true, true);
+        else
+            FXC_MIXED_XF_LAUNCH(true, false);
+    } else {
+        if (dc_u8)
+            FXC_MIXED_XF_LAUNCH(false, true);
+        else
+            FXC_MIXED_XF_LAUNCH(false, false);
+    }
+#undef FXC_MIXED_XF_LAUNCH
+    FXC_HIP(p, hipGetLastError());
+    return FXC_OK;
+}
+
+// Two antennas under a delay track: every chunk pair is summed whole, frame after frame by one workgroup, so its row is the same
+// bits in any call (the kernel's frame ranges would cut the last chunks of a launch by the launch's size).  Two launches of the
+// unchanged kernel: full rounds over fused_grid_max workgroups, then the rest with one workgroup per chunk pair.  Row c = chunk c;
+// the second launch's rows start where the first one's (empty) leading-part rows lie, and its own end within the nc +
+// fused_grid_max rows of the pass.  `f`: the pass -- its input, chunk pairs, rows, byte offsets and stream length
+int fused_whole_chunks(fxc_plan* p, FusedLaunch f) {
+    const int64_t in_bytes = 2 * (f.num_samp ? f.num_samp : p->num_samp) * (f.dc_u8 ? 2 : (int64_t)sizeof(cf));      // per chunk pair
+    const int64_t nc = f.n_pairs, n1 = nc / p->fused_grid_max * p->fused_grid_max;
+    if (n1 > 0) {
+        f.n_pairs = n1;
+        f.whole_grid = p->fused_grid_max;
+        const int rc = launch_fused(p, f);
+        if (rc) return rc;
+    }
+    if (nc == n1) return FXC_OK;
+    f.x = reinterpret_cast<const cf*>(reinterpret_cast<const char*>(f.x) + n1 * in_bytes);
+    f.out += n1 * fxc::fused::kN * fused_row_prods(p);
+    if (f.dc_u8) f.dc_u8 += n1 * 2;
+    f.n_pairs = f.whole_grid = (int)(nc - n1);
+    return launch_fused(p, f);
+}
+
+// raw[c][p][layout] for nc chunks starting at x; spec = scratch for the multi-antenna path.  2 antennas: rows of
+// `unit` chunks + leading-part rows (fused_rows() of them in all); dc_u8, dck: FusedLaunch
+int fused_raw_sums(fxc_plan* p, const cf* x, int64_t nc, cf* spec, cf* raw, const cf* dc_u8, int64_t unit, bool rows_are_chunks, bool dck) {
+    if (p->n_ant == 2) {
+        FusedLaunch f = {x, nc, raw};
+        f.dc_u8 = dc_u8;
+        if (p->track) return fused_whole_chunks(p, f);
+        f.dck = dck;
+        f.unit = unit;
+        f.rows_are_chunks = rows_are_chunks;
+        return launch_fused(p, f);
+    }
+    // 3 .. 64 antennas: spectra to HBM as [chunk][frame][antenna] rows (the F-only fused kernel in its own position order
+    // at nchan 4096 / ntaps 4, the F-only tiled kernel in natural order otherwise), then the register-resident X-engine
+    // (over blocks of 8 antennas beyond 8).
+    // unit = chunks per raw row here too: ceil(nc / unit) rows come out
+    const int rc = p->path == FXC_PATH_FUSED ? launch_fused(p, {x, nc * (p->n_ant / 2), spec, kFusedSpectra})
+                                             : tiled_channelize(p, x, spec, nc * p->n_ant, p->n_ant);
+    if (rc) return rc;
+    return launch_xengine(p, spec, raw, nc, (int)unit, x_ranges(p, unit));
+}
+
+// raw[split][c][k] (natural bin order) for nc chunks starting at x (nc * 2 <= tiled_streams_per_pass())
+int tiled_raw_sums(fxc_plan* p, const cf* x, int64_t nc, int n_splits, cf* raw, const cf* dc_u8) {
+    KernelTimer kt(p);
     if (p->x8192 && p->num_samp < (1ll << 28)) {
         // 8192 channels, two antennas, up to four taps, in TWO passes (2 x the algorithmic bytes; the split into two 4096-channel
         // problems and the pair kernel move 3 x): f8192_ring_kernel writes antenna 0's spectra (in register order: a layout private
@@ -881,11 +950,8 @@ int tiled_raw_sums(fxc_plan* p, const cf* x, int64_t nc, int n_splits, cf* raw, 
         int rc = grow(p, &p->d_pre, &p->pre_bytes, (size_t)nc * p->n_pts * p->nchan * sizeof(cf));
         if (rc) return rc;
         cf* s0 = static_cast<cf*>(p->d_pre);
-        const int64_t want = (2 * (int64_t)p->cu_count + nc - 1) / nc;
-        const bool few = nc * std::max<int64_t>(1, p->n_pts / 8) < p->cu_count;
-        const int f_splits = (int)std::max<int64_t>(1, std::min<int64_t>(want, p->n_pts / (few ? 1 : 8)));
-        const dim3 grid_f((unsigned)std::min<int64_t>(nc, std::max<int64_t>(1, (int64_t)p->cu_count * 8 / f_splits)), (unsigned)f_splits);
-        const dim3 grid_x((unsigned)std::min<int64_t>(nc, std::max<int64_t>(1, (int64_t)p->cu_count * 8 / n_splits)), (unsigned)n_splits);
+        const int f_splits = ring8192_splits(p, nc);
+        const dim3 grid_f = ring8192_grid(p, nc, f_splits), grid_x = ring8192_grid(p, nc, n_splits);
         // antenna 1's stream of the first chunk: num_samp samples (of 8 bytes, or of 2) behind antenna 0's
         const cf* x1 = reinterpret_cast<const cf*>(reinterpret_cast<const char*>(x) + p->num_samp * (dc_u8 ? 2 : (int64_t)sizeof(cf)));
 #define FXC_X8192_LAUNCH(U8)                                                                                                                  \
@@ -898,65 +964,23 @@ int tiled_raw_sums(fxc_plan* p, const cf* x, int64_t nc, int n_splits, cf* raw, 
         if (dc_u8) FXC_X8192_LAUNCH(true);
         else FXC_X8192_LAUNCH(false);
 #undef FXC_X8192_LAUNCH
-        kt.stop();
-        FXC_HIP(p, hipGetLastError());
-        return FXC_OK;
-    }
-    if (p->prefilter && !dc_u8) {
-        const int rc = tiled_prefilter(p, x, 2 * nc, &x);
-        if (rc) return rc;
-    }
-    FXC_TILED_DISPATCH(p, (tiled_launch<G, false>(p, x, nc, n_splits, raw, 2 * nc, dc_u8)));
-    kt.stop();
-    FXC_HIP(p, hipGetLastError());
-    return FXC_OK;
-}
-
-// F-stage only: n_streams consecutive streams -> spec[stream][i][k], pairs of streams per work item
-int tiled_channelize(fxc_plan* p, const cf* x, cf* spec, int64_t n_streams, int spec_a) {
-    if (p->small_f) return small_channelize(p, x, spec, n_streams, spec_a);
-    if (p->f8192 && p->num_samp < (1ll << 28)) {
-        // one stream per workgroup; runs of at least eight frames (a run re-reads three frames of history), enough workgroups
-        // for two rounds of the CUs when the streams are few
-        KernelTimer kt8(p);
-        const int64_t want = (2 * (int64_t)p->cu_count + n_streams - 1) / n_streams;
-        const bool few = n_streams * std::max<int64_t>(1, p->n_pts / 8) < p->cu_count;      // (one stream: _spectrometer_poly itself -- latency)
-        const int n_splits = (int)std::max<int64_t>(1, std::min<int64_t>(want, p->n_pts / (few ? 1 : 8)));
-        const int grid_x = (int)std::min<int64_t>(n_streams, std::max<int64_t>(1, (int64_t)p->cu_count * 8 / n_splits));
-        const dim3 grid((unsigned)grid_x, (unsigned)n_splits);
-        hipLaunchKernelGGL((f8192_ring_kernel<false, false>), grid, dim3(kF8192Threads), 0, p->stream, x, p->num_samp, p->n_pts, n_streams, n_splits,
-                           p->d_win4, p->d_tw0, p->d_tw1, p->d_tw2, spec, spec_a, (int64_t)0, p->num_samp, (const cf*)nullptr, (const cf*)nullptr, 0);
-        kt8.stop();
-        FXC_HIP(p, hipGetLastError());
-        return FXC_OK;
-    }
-    KernelTimer kt(p);
-    const int64_t per_pass = tiled_streams_per_pass(p);
-    for (int64_t s0 = 0; s0 < n_streams; s0 += per_pass) {
-        const int64_t ns = std::min(per_pass, n_streams - s0);
-        const cf* xs = x + s0 * p->num_samp;
-        if (p->prefilter) {
-            const int rc = tiled_prefilter(p, xs, ns, &xs);
+    } else {
+        if (p->prefilter && !dc_u8) {       // more than four taps: the FIR as its own pass, the kernels with one unit tap
+            const int rc = tiled_prefilter(p, x, 2 * nc, &x);
             if (rc) return rc;
         }
-        const int64_t pairs = (ns + 1) / 2;
-        const int n_splits = tiled_splits(p, pairs, true);
-        // spec_a == 0: this pass's streams start at row s0 * n_pts; by frame: the kernel places rows from the global stream index
-        FXC_TILED_DISPATCH(p, (tiled_launch<G, true>(p, xs, pairs, n_splits, spec_a ? spec : spec + s0 * p->n_pts * p->nchan, ns,
-                                                     nullptr, spec_a, spec_a ? s0 : 0)));
+        TiledLaunch t = {x, nc, n_splits, raw, 2 * nc};
+        t.dc_u8 = dc_u8;
+        const int rc = p->small ? small_launch<false>(p, t) : tiled_dispatch<false>(p, t);
+        if (rc) return rc;
     }
     kt.stop();
     FXC_HIP(p, hipGetLastError());
     return FXC_OK;
 }
 
-// ---- nchan 8192 as two 4096-channel problems (pfb_split8192_kernel) ---------------------------------
-int64_t split_chunks_per_pass(const fxc_plan* p, int64_t n_chunks) {
-    const int64_t per_chunk = 4 * p->n_pts * 4096 * (int64_t)sizeof(cf) + 2 * 4096 * (int64_t)sizeof(cf);   // y + two raw rows
-    return std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_chunks, 32767), ws_target() / per_chunk));
-}
-
-// raw = the fused kernel's rows over 2 nc chunk pairs (+ leading-part rows) for nc chunks of 8192-channel input
+// nchan 8192 as two 4096-channel problems (pfb_split8192_kernel): raw = the fused kernel's rows over 2 nc chunk pairs (+ leading-part
+// rows) for nc chunks of 8192-channel input
 int split_raw_sums(fxc_plan* p, const cf* x, int64_t nc, cf* raw) {
     const int64_t half_samp = p->n_pts * 4096;
     int rc = grow(p, &p->d_pre, &p->pre_bytes, (size_t)nc * 4 * half_samp * sizeof(cf));
@@ -966,10 +990,7 @@ int split_raw_sums(fxc_plan* p, const cf* x, int64_t nc, cf* raw) {
     // two adjacent positions per thread (16-byte accesses) for the 4- and 8-frame blocks (the 16-frame one has no registers left)
     static const bool narrow = FXC_DEV_ENV_INT("FXC_PRE_W", 0) == 1;
     const int w = (!narrow && tp <= 8 && (p->num_samp % 2) == 0 && (reinterpret_cast<uintptr_t>(x) % 16) == 0) ? 2 : 1;
-    const int64_t blocks = (16 / w) * 2 * nc;
-    int64_t fs = std::max<int64_t>(1, (2 * (int64_t)p->cu_count + blocks - 1) / blocks);
-    fs = std::min<int64_t>(fs, std::max<int64_t>(1, p->n_pts / (4 * tp)));
-    const int64_t per = ((p->n_pts + fs - 1) / fs + 2 * tp - 1) / (2 * tp) * (2 * tp);
+    const int64_t per = prefilter_frames(p, (16 / w) * 2 * nc);
     const dim3 grid((unsigned)(16 / w), (unsigned)(2 * nc), (unsigned)((p->n_pts + per - 1) / per));
     KernelTimer kt(p);
 #define FXC_SPLIT_LAUNCH(TP, W)                                                                                             \
@@ -987,17 +1008,12 @@ int split_raw_sums(fxc_plan* p, const cf* x, int64_t nc, cf* raw) {
 #undef FXC_SPLIT_LAUNCH
     FXC_HIP(p, hipGetLastError());
     kt.stop();
-    if (p->track) return fused_whole_chunks(p, y, 2 * nc, raw, nullptr, half_samp);
-    return launch_fused(p, y, 2 * nc, raw, false, nullptr, 1, true, half_samp);
+    FusedLaunch f = {y, 2 * nc, raw};
+    f.num_samp = half_samp;
+    return p->track ? fused_whole_chunks(p, f) : launch_fused(p, f);
 }
 
 // nchan == 1 streaming path: raw[block][chunk] partial sums for nc chunks
-bool stream_is_t4(const fxc_plan* p) { return p->ntaps <= 4 && (p->num_samp % 2) == 0; }
-
-int64_t stream_blocks(const fxc_plan* p) {
-    return stream_is_t4(p) ? kStream4Blocks : (p->num_samp + kStreamBlock - 1) / kStreamBlock;
-}
-
 int stream_raw_sums(fxc_plan* p, const cf* x, int64_t nc, cf* raw) {
     const int blocks = (int)stream_blocks(p);
     KernelTimer kt(p);

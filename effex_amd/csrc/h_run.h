@@ -23,7 +23,7 @@ struct AutoPass {
 AutoPass autos_pass(const fxc_plan* p, int64_t n_chunks, bool rows) {
     AutoPass a;
     a.unit = rows ? 1 : fused_unit(p);
-    a.xr = a.unit > 1 ? 1 : (int)std::min<int64_t>((p->n_pts + kRowSpectra - 1) / kRowSpectra, 4096);
+    a.xr = a.unit > 1 ? 1 : frame_ranges(p);
     const int64_t spec_per_chunk = (int64_t)p->n_ant * p->n_pts * p->nchan * (int64_t)sizeof(cf);
     const int64_t raw_per_chunk = (int64_t)p->n_prod * p->nchan * (int64_t)sizeof(cf) * a.xr;
     int64_t cb = ws_target() / (spec_per_chunk + raw_per_chunk);
@@ -42,34 +42,9 @@ int64_t autos_group(const fxc_plan* p, int64_t nc, int64_t unit) {
     return std::max<int64_t>(1, std::min<int64_t>(unit, (nc + groups - 1) / groups));
 }
 
-// raw[range][group][n_prod][nchan] for nc chunks starting at x
-int autos_raw_sums(fxc_plan* p, const cf* x, int64_t nc, cf* spec, cf* raw, int64_t cg, int xr) {
-    int rc = run_channelize(p, x, spec, nc * p->n_ant);
-    if (rc) return rc;
-    const dim3 grid((p->nchan + kXThreads - 1) / kXThreads, (unsigned)(((nc + cg - 1) / cg) * xr));
-#define FXC_XA_LAUNCH(A)                                                                                                        \
-    hipLaunchKernelGGL((xengine_kernel<A, true>), grid, dim3(kXThreads), 0, p->stream, spec, raw, p->n_pts, p->nchan, nc, (int)cg, \
-                       xr, (int64_t)1, p->n_pts)
-    switch (p->n_ant) {
-        case 2: FXC_XA_LAUNCH(2); break;
-        case 3: FXC_XA_LAUNCH(3); break;
-        case 4: FXC_XA_LAUNCH(4); break;
-        case 5: FXC_XA_LAUNCH(5); break;
-        case 6: FXC_XA_LAUNCH(6); break;
-        case 7: FXC_XA_LAUNCH(7); break;
-        case 8: FXC_XA_LAUNCH(8); break;
-        default: return fail(p, FXC_ERR_UNSUPPORTED, "autos for %d antennas", p->n_ant);
-    }
-#undef FXC_XA_LAUNCH
-    FXC_HIP(p, hipGetLastError());
-    return FXC_OK;
-}
-
 // 2 antennas at 4096 channels / 4 taps (complex64; byte input is converted first): the fused kernel's AUTOS variant, one pass
 // (k_fused4096.h) -- the route of the cross-only plan, whole chunks and frame ranges alike, with raw rows of [3][kN]
-bool fused_autos(const fxc_plan* p, int64_t n_chunks) {
-    return p->autos && p->path == FXC_PATH_FUSED && p->n_ant == 2 && !use_tiled(p, n_chunks);
-}
+bool fused_autos(const fxc_plan* p) { return p->autos && p->path == FXC_PATH_FUSED && p->n_ant == 2; }
 
 // Rows of a plan with per-antenna tables (fxc_set_rot_ant: 3 and more antennas) go to the rows kernels' ANT instantiations.
 // Every route of those plans lays its rows out as [chunk][n_prod] with the n_base cross rows first, so the kernels take
@@ -198,7 +173,7 @@ int carve_ws(fxc_plan* p, bool fold, int64_t spec_bytes, int64_t raw_bytes, Work
 }
 
 // chunk c0 of a call's samples: complex64, or -- bytes (2 antennas) -- the receivers' uint8 I,Q, two bytes per sample
-const cf* chunk_at(const fxc_plan* p, const cf* x, int64_t c0, bool bytes) {
+const cf* chunk_at(const fxc_plan* p, const cf* x, int64_t c0, bool bytes = false) {
     return reinterpret_cast<const cf*>(reinterpret_cast<const char*>(x) + c0 * p->n_ant * p->num_samp * (bytes ? 2 : (int64_t)sizeof(cf)));
 }
 
@@ -212,7 +187,7 @@ const cf* chunk_at(const fxc_plan* p, const cf* x, int64_t c0, bool bytes) {
 int fx_routes(fxc_plan* p, const cf* x, const RowsOut* o, int64_t n_chunks, const cf* dc_u8, bool dck) {
     const bool bytes = dc_u8 != nullptr;
     Workspace w;
-    if (p->autos && !fused_autos(p, n_chunks)) {
+    if (p->autos && !fused_autos(p)) {
         // rows: one raw row per chunk and frame range, the ranges as the rows kernels' splits
         const AutoPass a = autos_pass(p, n_chunks, o != nullptr);
         int rc = carve_ws(p, !o, a.spec_bytes, a.raw_bytes, &w);
@@ -221,7 +196,10 @@ int fx_routes(fxc_plan* p, const cf* x, const RowsOut* o, int64_t n_chunks, cons
             const int64_t nc = std::min(a.cb, n_chunks - c0);
             const int64_t cg = autos_group(p, nc, a.unit);      // (rows: unit = 1, so one chunk)
             const int xr = cg > 1 ? 1 : a.xr;
-            rc = autos_raw_sums(p, chunk_at(p, x, c0, false), nc, w.spec, w.raw, cg, xr);
+            // raw[range][group][n_prod][nchan]
+            rc = run_channelize(p, chunk_at(p, x, c0), w.spec, nc * p->n_ant);
+            if (rc) return rc;
+            rc = launch_xengine<true>(p, w.spec, w.raw, nc, (int)cg, xr);
             if (rc) return rc;
             const int64_t rows = nc * p->n_prod;
             rc = o ? launch_rows(p, *o, c0 * p->n_prod, w.raw, p->nchan, rows, xr, rows * p->nchan, 0, kNoLead, p->n_prod, p->n_base)
@@ -231,11 +209,12 @@ int fx_routes(fxc_plan* p, const cf* x, const RowsOut* o, int64_t n_chunks, cons
     } else if (p->path == FXC_PATH_STREAM) {
         const int nb = (int)stream_blocks(p);
         const int64_t cb = std::min<int64_t>(n_chunks, 65535);
-        int rc = carve_ws(p, false, 0, cb * nb * (int64_t)sizeof(cf), &w);      // (stream1_acc_kernel needs no partials)
+        const bool fold_parts = false;      // (stream1_acc_kernel needs none)
+        int rc = carve_ws(p, fold_parts, 0, cb * nb * (int64_t)sizeof(cf), &w);
         if (rc) return rc;
         for (int64_t c0 = 0; c0 < n_chunks; c0 += cb) {
             const int64_t nc = std::min(cb, n_chunks - c0);
-            rc = stream_raw_sums(p, chunk_at(p, x, c0, false), nc, w.raw);
+            rc = stream_raw_sums(p, chunk_at(p, x, c0), nc, w.raw);
             if (rc) return rc;
             // raw[block][chunk]: the blocks play the role of the generic path's splits (nchan = n_base = 1)
             if (o) {
@@ -246,7 +225,7 @@ int fx_routes(fxc_plan* p, const cf* x, const RowsOut* o, int64_t n_chunks, cons
                 FXC_HIP(p, hipGetLastError());
             }
         }
-    } else if ((p->path == FXC_PATH_FUSED && (bytes || !use_tiled(p, n_chunks))) || (p->path == FXC_PATH_TILED && p->n_ant > 2)) {
+    } else if (p->path == FXC_PATH_FUSED || (p->path == FXC_PATH_TILED && p->n_ant > 2)) {
         int64_t spec_bytes, raw_bytes;
         const int64_t cb = fused_chunks_per_pass(p, n_chunks, &spec_bytes, &raw_bytes);
         int rc = carve_ws(p, !o, spec_bytes, raw_bytes, &w);
@@ -278,7 +257,7 @@ int fx_routes(fxc_plan* p, const cf* x, const RowsOut* o, int64_t n_chunks, cons
         if (rc) return rc;
         for (int64_t c0 = 0; c0 < n_chunks; c0 += cb) {
             const int64_t nc = std::min(cb, n_chunks - c0);
-            rc = split_raw_sums(p, chunk_at(p, x, c0, false), nc, w.raw);
+            rc = split_raw_sums(p, chunk_at(p, x, c0), nc, w.raw);
             if (rc) return rc;
             // the nc pairs of 4096-rows are nc rows of 8192 in layout 3; the leading-part rows are added by parity
             const LeadRows lead = fused_lead(p, 2 * nc);
@@ -292,7 +271,7 @@ int fx_routes(fxc_plan* p, const cf* x, const RowsOut* o, int64_t n_chunks, cons
                 FXC_HIP(p, hipGetLastError());
             }
         }
-    } else if (use_tiled(p, n_chunks)) {
+    } else if (p->path == FXC_PATH_TILED) {
         const int N = p->nchan;
         const int n_splits = tiled_splits(p, split_basis(p, n_chunks));
         const int64_t row_bytes = (int64_t)N * (int64_t)sizeof(cf);

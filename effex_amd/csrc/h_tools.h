@@ -558,7 +558,7 @@ int beamform_dev(fxc_plan* p, const cf* x, const cf* weights, bool weights_on_ho
                                         : (int64_t)n_beam * p->n_pts * nchan * (int64_t)sizeof(cf);
     for (int64_t c0 = 0; c0 < n_chunks; c0 += cb) {
         const int64_t nc = std::min(cb, n_chunks - c0);
-        rc = run_channelize(p, chunk_at(p, x, c0, false), spec, nc * n_ant);
+        rc = run_channelize(p, chunk_at(p, x, c0), spec, nc * n_ant);
         if (rc) return rc;
         const cf* wk = weights;
         if (p->track) {
