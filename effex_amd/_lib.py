@@ -38,6 +38,8 @@ FXC_MODE_SPECTRUM = 0
 FXC_MODE_CONTINUUM = 1
 FXC_BEAM_POWER = 0
 FXC_BEAM_VOLTAGE = 1
+FXC_FRINGE_REF = 0
+FXC_FRINGE_ALL = 1
 FXC_IQ_C64 = 0
 FXC_IQ_U8 = 1
 FXC_IQ_C128 = 2
@@ -120,6 +122,8 @@ SIGNATURES = {
     "fxc_estimate_delay": (_c.c_int, [_vp, _vp, _vp, _c.c_int64, _c.c_int, _c.c_double, _c.POINTER(_c.c_double)]),
     "fxc_estimate_delays": (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int, _c.c_double, _c.c_int, _vp]),
     "fxc_fringe_fit": (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int, _c.c_double, _c.c_double, _c.c_int, _c.c_int, _vp, _vp, _vp]),
+    "fxc_fringe_fit_weighted": (_c.c_int, [_vp, _vp, _vp, _c.c_int64, _c.c_int, _c.c_double, _c.c_double, _c.c_int, _c.c_int, _c.c_int,
+                                           _c.c_double, _vp, _vp, _vp, _vp]),
     "fxc_solve_gains": (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int, _c.c_int64, _c.c_int, _c.c_int, _vp, _vp]),
     "fxc_solve_gains_weighted": (_c.c_int, [_vp, _vp, _vp, _c.c_int64, _c.c_int, _vp, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int, _vp,
                                             _vp]),

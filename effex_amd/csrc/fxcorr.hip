@@ -1054,26 +1054,23 @@ int fxc_estimate_delays(fxc_plan* p, const void* x, int64_t n, int mem_kind, dou
 
 int fxc_fringe_fit(fxc_plan* p, const void* rows, int64_t n_chunks, int mem_kind, double bandwidth, double frequency, int ref,
                    int pad, double* delay_s, double* rate_s_per_chunk, double* snr) {
-    if (!p || !rows || !delay_s || !rate_s_per_chunk) return fail(p, FXC_ERR_ARG, "NULL argument");
-    if (p->n_ant < 2) return fail(p, FXC_ERR_ARG, "a fringe fit needs 2 or more antennas, the plan has %d", p->n_ant);
-    if (ref < 0 || ref >= p->n_ant) return fail(p, FXC_ERR_ARG, "ref=%d outside [0, %d)", ref, p->n_ant);
-    if (n_chunks < 2) return fail(p, FXC_ERR_ARG, "n_chunks=%lld: a fringe fit needs 2 or more chunks", (long long)n_chunks);
-    if (pad != 1 && pad != 2 && pad != 4 && pad != 8) return fail(p, FXC_ERR_ARG, "pad=%d is not 1, 2, 4 or 8", pad);
-    if (!std::isfinite(bandwidth) || !(bandwidth > 0.0)) return fail(p, FXC_ERR_ARG, "bandwidth must be finite and > 0");
-    if (!std::isfinite(frequency) || !(frequency > 0.0)) return fail(p, FXC_ERR_ARG, "frequency must be finite and > 0");
-    if (const int rc = bad_mem_kind(p, mem_kind)) return rc;
-    if (p->nchan == 1) return fail(p, FXC_ERR_UNSUPPORTED, "a fringe fit needs a frequency axis: nchan is 1");
-    int lk_log = 0, lt_log = 0;
-    while ((1ll << lk_log) < (int64_t)pad * p->nchan) ++lk_log;
-    while (lt_log < 13 && (1ll << lt_log) < (int64_t)pad * n_chunks) ++lt_log;
-    if (lt_log > 12)
-        return fail(p, FXC_ERR_UNSUPPORTED, "Lt = pad * n_chunks rounded up to a power of two exceeds 4096 (pad %d, %lld chunks)", pad,
-                    (long long)n_chunks);
-    if (lk_log > 16)
-        return fail(p, FXC_ERR_UNSUPPORTED, "Lk = pad * nchan rounded up to a power of two exceeds 65536 (pad %d, %d channels)", pad,
-                    p->nchan);
-    return fringe_fit_batch(p, static_cast<const cf*>(rows), n_chunks, mem_kind, bandwidth, frequency, ref, lk_log, lt_log, delay_s,
-                            rate_s_per_chunk, snr);
+    int lk_log, lt_log;
+    if (const int rc = check_fringe_fit(p, rows, n_chunks, mem_kind, bandwidth, frequency, ref, pad, FXC_FRINGE_REF, 0.0, delay_s,
+                                        rate_s_per_chunk, &lk_log, &lt_log))
+        return rc;
+    return fringe_fit_run(p, static_cast<const cf*>(rows), nullptr, n_chunks, mem_kind, bandwidth, frequency, ref, lk_log, lt_log, false,
+                          FXC_FRINGE_REF, 0.0, delay_s, rate_s_per_chunk, snr, nullptr);
+}
+
+int fxc_fringe_fit_weighted(fxc_plan* p, const void* rows, const void* weights, int64_t n_chunks, int mem_kind, double bandwidth,
+                            double frequency, int ref, int pad, int baselines, double min_snr, double* delay_s, double* rate_s_per_chunk,
+                            double* snr, double* base_out) {
+    int lk_log, lt_log;
+    if (const int rc = check_fringe_fit(p, rows, n_chunks, mem_kind, bandwidth, frequency, ref, pad, baselines, min_snr, delay_s,
+                                        rate_s_per_chunk, &lk_log, &lt_log))
+        return rc;
+    return fringe_fit_run(p, static_cast<const cf*>(rows), static_cast<const float*>(weights), n_chunks, mem_kind, bandwidth, frequency, ref,
+                          lk_log, lt_log, true, baselines, min_snr, delay_s, rate_s_per_chunk, snr, base_out);
 }
 
 int fxc_flag_rows(fxc_plan* p, const void* rows, const void* prior, int64_t n_chunks, int mem_kind, int64_t window, float time_threshold,

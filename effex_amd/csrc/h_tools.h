@@ -153,15 +153,62 @@ int estimate_delays_batch(fxc_plan* p, const cf* const* streams, int n_streams, 
     return FXC_OK;
 }
 
-// The fringe fit of the baselines (ref, b), b != ref (fxcorr.h fxc_fringe_fit; kernels in k_fringe.h).  The baselines go
-// through in batches of as many as fit the workspace target (FXC_WS_MB): gather, frequency transform, time transform + peak,
-// stencil; every batch's result words go into one block: one copy to the host and one synchronisation for the whole call.
-int fringe_fit_batch(fxc_plan* p, const cf* rows, int64_t n_chunks, int mem_kind, double bandwidth, double frequency, int ref,
-                     int lk_log, int lt_log, double* delay_s, double* rate_s_per_chunk, double* snr) {
+// The argument checks of both fringe fits, in the order that gives each call its code and message; the plain call has neither a
+// baselines mode nor a threshold (FXC_FRINGE_REF, 0).  Sets the logarithms of the padded grid.
+int check_fringe_fit(fxc_plan* p, const void* rows, int64_t n_chunks, int mem_kind, double bandwidth, double frequency, int ref, int pad,
+                     int baselines, double min_snr, const double* delay_s, const double* rate_s_per_chunk, int* lk_log, int* lt_log) {
+    if (!p || !rows || !delay_s || !rate_s_per_chunk) return fail(p, FXC_ERR_ARG, "NULL argument");
+    if (p->n_ant < 2) return fail(p, FXC_ERR_ARG, "a fringe fit needs 2 or more antennas, the plan has %d", p->n_ant);
+    if (ref < 0 || ref >= p->n_ant) return fail(p, FXC_ERR_ARG, "ref=%d outside [0, %d)", ref, p->n_ant);
+    if (n_chunks < 2) return fail(p, FXC_ERR_ARG, "n_chunks=%lld: a fringe fit needs 2 or more chunks", (long long)n_chunks);
+    if (pad != 1 && pad != 2 && pad != 4 && pad != 8) return fail(p, FXC_ERR_ARG, "pad=%d is not 1, 2, 4 or 8", pad);
+    if (!std::isfinite(bandwidth) || !(bandwidth > 0.0)) return fail(p, FXC_ERR_ARG, "bandwidth must be finite and > 0");
+    if (!std::isfinite(frequency) || !(frequency > 0.0)) return fail(p, FXC_ERR_ARG, "frequency must be finite and > 0");
+    if (const int rc = bad_mem_kind(p, mem_kind)) return rc;
+    if (baselines != FXC_FRINGE_REF && baselines != FXC_FRINGE_ALL)
+        return fail(p, FXC_ERR_ARG, "baselines=%d is neither FXC_FRINGE_REF nor FXC_FRINGE_ALL", baselines);
+    if (!std::isfinite(min_snr) || min_snr < 0.0) return fail(p, FXC_ERR_ARG, "min_snr must be finite and >= 0");
+    if (baselines == FXC_FRINGE_REF && min_snr != 0.0)
+        return fail(p, FXC_ERR_ARG, "min_snr=%g: the baselines to ref are not selected, min_snr must be 0 with FXC_FRINGE_REF", min_snr);
+    if (p->nchan == 1) return fail(p, FXC_ERR_UNSUPPORTED, "a fringe fit needs a frequency axis: nchan is 1");
+    *lk_log = *lt_log = 0;
+    while ((1ll << *lk_log) < (int64_t)pad * p->nchan) ++*lk_log;
+    while (*lt_log < 13 && (1ll << *lt_log) < (int64_t)pad * n_chunks) ++*lt_log;
+    if (*lt_log > 12)
+        return fail(p, FXC_ERR_UNSUPPORTED, "Lt = pad * n_chunks rounded up to a power of two exceeds 4096 (pad %d, %lld chunks)", pad,
+                    (long long)n_chunks);
+    if (*lk_log > 16)
+        return fail(p, FXC_ERR_UNSUPPORTED, "Lk = pad * nchan rounded up to a power of two exceeds 65536 (pad %d, %d channels)", pad,
+                    p->nchan);
+    return FXC_OK;
+}
+
+// one fit of a fringe_fit_batch call: cross row `row` of the rows, conjugated first where `conj`
+struct FringeItem {
+    int64_t row;
+    int conj;
+};
+// its result: delay in seconds, rate in seconds per chunk, peak over root power, and the power sum |R|^2 itself
+struct FringeFit {
+    double delay, rate, snr, power;
+};
+
+// row (a, b), a < b, in the baseline order of the results
+int64_t cross_row(int a, int b, int n_ant) { return (int64_t)a * (2 * n_ant - a - 1) / 2 + (b - a - 1); }
+
+// The fringe fits of a list of (row, conj) pairs (fxcorr.h fxc_fringe_fit: the baselines to ref; fxc_fringe_fit_weighted: those, or
+// every cross row; kernels in k_fringe.h).  The fits go through in batches of as many as fit the workspace target (FXC_WS_MB), the
+// staging of host rows and host weights counted: gather (the weighted one where there are weights), frequency transform, time
+// transform + peak, stencil; every batch's result words go into one block sized by the list: one copy to the host and one
+// synchronisation for the whole call.  fits[i] belongs to items[i]; with zero_guard a fit without power is all 0 (the plain call
+// divides by it, as it always has).
+int fringe_fit_batch(fxc_plan* p, const cf* rows, const float* weights, int64_t n_chunks, int mem_kind, double bandwidth, double frequency,
+                     int lk_log, int lt_log, bool zero_guard, const std::vector<FringeItem>& items, std::vector<FringeFit>& fits) {
     FXC_DEVICE(p, p->device);
-    const int n_ant = p->n_ant, nchan = p->nchan, n_other = n_ant - 1;
+    const int nchan = p->nchan, n_items = (int)items.size();
     const int64_t lk = 1ll << lk_log, lt = 1ll << lt_log;
     const int64_t n_rows = p->n_prod;
+    const bool host = mem_kind == FXC_MEM_HOST;
     // the time-axis tile: as many adjacent columns (a power of two, 64 at most) as fit the LDS budget beside the twiddles
     int tm_log = 0, pad = 1;
     for (int cand = 6; cand >= 0; --cand) {
@@ -174,46 +221,57 @@ int fringe_fit_batch(fxc_plan* p, const cf* rows, int64_t n_chunks, int mem_kind
     }
     const int64_t lds = (lt * (1ll << tm_log) + (lt >> 4) * pad + lt) * (int64_t)sizeof(cf);
     const int first_log = lt_log % 4 ? lt_log % 4 : 4;
-    // workspace: two transform buffers [n_chunks][Lk] per baseline of a batch, its rows staged when they are host memory,
-    // and the result words of every baseline (best[n_other], stencil[n_other][5] complex128, part[n_other][kFringeParts])
+    // workspace: two transform buffers [n_chunks][Lk] per fit of a batch, its rows -- and its weights, as many elements -- staged
+    // when they are host memory, and the result words of every fit (best[n], stencil[n][5] complex128, part[n][kFringeParts]; with weights wmax[n])
     const int64_t buf_one = n_chunks * lk * (int64_t)sizeof(cf);
-    const int64_t stage_one = mem_kind == FXC_MEM_HOST ? up256(n_chunks * nchan * (int64_t)sizeof(cf)) : 0;
-    const int64_t res_bytes = up256((int64_t)n_other * (8 + 80 + 8 * kFringeParts));
-    const int64_t per_base = 2 * buf_one + stage_one;
-    const int64_t fit = (ws_target() - res_bytes) / per_base;
-    const int batch = (int)std::max<int64_t>(1, std::min<int64_t>(fit, std::min(n_other, kFringeBatch)));
+    const int64_t stage_one = host ? up256(n_chunks * nchan * (int64_t)sizeof(cf)) : 0;
+    const int64_t stage_elems = stage_one / (int64_t)sizeof(cf);
+    const int64_t stage_w_one = host && weights ? stage_elems * (int64_t)sizeof(float) : 0;
+    const int64_t res_bytes = up256((int64_t)n_items * (8 + 80 + 8 * kFringeParts + (weights ? 4 : 0)));
+    const int64_t per_fit = 2 * buf_one + stage_one + stage_w_one;
+    const int64_t fit = (ws_target() - res_bytes) / per_fit;
+    const int batch = (int)std::max<int64_t>(1, std::min<int64_t>(fit, std::min(n_items, kFringeBatch)));
     WsCarver ws;
     const int64_t o_gbuf[2] = {ws.take(batch * buf_one), ws.take(batch * buf_one)};
-    const int64_t o_stage = ws.take(batch * stage_one), o_res = ws.take(res_bytes);
+    const int64_t o_stage = ws.take(batch * stage_one), o_res = ws.take(res_bytes), o_stage_w = ws.take(batch * stage_w_one);
     if (const int rc = ensure_ws(p, ws.total())) return rc;
     FXC_HIP(p, hipFuncSetAttribute(reinterpret_cast<const void*>(&fringe_time_peak_kernel),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, kFringeLdsBytes));
     cf* gbuf[2] = {ws_at<cf>(p, o_gbuf[0]), ws_at<cf>(p, o_gbuf[1])};
     cf* stage = ws_at<cf>(p, o_stage);
+    float* stage_w = ws_at<float>(p, o_stage_w);
     unsigned long long* best = ws_at<unsigned long long>(p, o_res);
-    double* stencil = ws_at<double>(p, o_res + 8 * (int64_t)n_other);
-    double* part = stencil + 10 * (int64_t)n_other;
-    const std::vector<int> others = all_but(ref, n_ant);
-    FXC_HIP(p, hipMemsetAsync(best, 0, 8 * (size_t)n_other, p->stream));
-    for (int b0 = 0; b0 < n_other; b0 += batch) {
-        const int nb = std::min(batch, n_other - b0);
+    double* stencil = ws_at<double>(p, o_res + 8 * (int64_t)n_items);
+    double* part = stencil + 10 * (int64_t)n_items;
+    unsigned* wmax = reinterpret_cast<unsigned*>(part + (int64_t)kFringeParts * n_items);      // the largest counted weight, float bits
+    FXC_HIP(p, hipMemsetAsync(best, 0, 8 * (size_t)n_items, p->stream));
+    if (weights) FXC_HIP(p, hipMemsetAsync(wmax, 0, 4 * (size_t)n_items, p->stream));
+    for (int b0 = 0; b0 < n_items; b0 += batch) {
+        const int nb = std::min(batch, n_items - b0);
         FringeRows br{};
         for (int q = 0; q < nb; ++q) {
-            const int b = others[(size_t)(b0 + q)], lo = std::min(ref, b), hi = std::max(ref, b);
-            const int64_t row = (int64_t)lo * (2 * n_ant - lo - 1) / 2 + (hi - lo - 1);     // the baseline order of the results
-            br.conj[q] = b < ref;
-            if (mem_kind == FXC_MEM_HOST) {
-                cf* st = stage + q * (stage_one / (int64_t)sizeof(cf));
-                FXC_HIP(p, copy_rows(p, st, nchan, rows + row * nchan, n_rows * nchan, nchan, n_chunks, hipMemcpyHostToDevice));
-                br.off[q] = st - stage;
+            const int64_t row = items[(size_t)(b0 + q)].row;
+            br.conj[q] = items[(size_t)(b0 + q)].conj;
+            if (host) {
+                // a baseline's staged weights lie like its staged rows: one offset serves both
+                br.off[q] = q * stage_elems;
+                FXC_HIP(p, copy_rows(p, stage + br.off[q], nchan, rows + row * nchan, n_rows * nchan, nchan, n_chunks, hipMemcpyHostToDevice));
+                if (weights)
+                    FXC_HIP(p, copy_rows(p, stage_w + br.off[q], nchan, weights + row * nchan, (int64_t)p->n_base * nchan, nchan, n_chunks,
+                                         hipMemcpyHostToDevice));
             } else {
                 br.off[q] = row * nchan;
             }
         }
-        const cf* src = mem_kind == FXC_MEM_HOST ? stage : rows;
-        const int64_t t_stride = mem_kind == FXC_MEM_HOST ? nchan : n_rows * nchan;
-        hipLaunchKernelGGL(fringe_gather_kernel, dim3(kFringeParts, nb), dim3(kFringeThreads), 0, p->stream, src, br, t_stride, gbuf[0],
-                           part + (int64_t)b0 * kFringeParts, (int)n_chunks, nchan, lk_log);
+        const cf* src = host ? stage : rows;
+        const int64_t t_stride = host ? nchan : n_rows * nchan;
+        if (weights)
+            hipLaunchKernelGGL(fringe_gather_weighted_kernel, dim3(kFringeParts, nb), dim3(kFringeThreads), 0, p->stream, src,
+                               host ? stage_w : weights, br, t_stride, host ? (int64_t)nchan : (int64_t)p->n_base * nchan, gbuf[0],
+                               part + (int64_t)b0 * kFringeParts, wmax + b0, (int)n_chunks, nchan, lk_log);
+        else
+            hipLaunchKernelGGL(fringe_gather_kernel, dim3(kFringeParts, nb), dim3(kFringeThreads), 0, p->stream, src, br, t_stride, gbuf[0],
+                               part + (int64_t)b0 * kFringeParts, (int)n_chunks, nchan, lk_log);
         // frequency axis: forward Stockham stages over the nb n_chunks rows
         const cf* g = gbuf[stockham_lines(p, gbuf, (int64_t)nb * n_chunks, lk, lk_log, -1.0)];
         hipLaunchKernelGGL(fringe_time_peak_kernel, dim3((unsigned)(lk >> tm_log), nb), dim3(kFringeThreads), (size_t)lds, p->stream, g,
@@ -225,22 +283,200 @@ int fringe_fit_batch(fxc_plan* p, const cf* rows, int64_t n_chunks, int mem_kind
     std::vector<char> h_res;
     if (const int rc = read_back(p, best, res_bytes, h_res)) return rc;
     const unsigned long long* h_best = reinterpret_cast<const unsigned long long*>(h_res.data());
-    const double* h_st = reinterpret_cast<const double*>(h_res.data() + 8 * (int64_t)n_other);
-    const double* h_part = h_st + 10 * (int64_t)n_other;
-    for (int i = 0; i < n_other; ++i) {
+    const double* h_st = reinterpret_cast<const double*>(h_res.data() + 8 * (int64_t)n_items);
+    const double* h_part = h_st + 10 * (int64_t)n_items;
+    const float* h_wmax = reinterpret_cast<const float*>(h_part + (int64_t)kFringeParts * n_items);
+    fits.assign((size_t)n_items, FringeFit{0.0, 0.0, 0.0, 0.0});
+    for (int i = 0; i < n_items; ++i) {
+        double power = 0.0;
+        for (int k = 0; k < kFringeParts; ++k) power += h_part[(int64_t)i * kFringeParts + k];
+        FringeFit& f = fits[(size_t)i];
+        f.power = power;
+        if (zero_guard && power == 0.0) continue;      // nothing counted: delay, rate and snr 0, the peak words are not used
         const unsigned lin = (unsigned)(0xFFFFFFFFull - (h_best[i] & 0xFFFFFFFFull));
         int64_t q = (int64_t)(lin >> lk_log) & (lt - 1), m = (int64_t)lin & (lk - 1);
         double a[5];
         for (int k = 0; k < 5; ++k) a[k] = std::hypot(h_st[(i * 5 + k) * 2], h_st[(i * 5 + k) * 2 + 1]);
+        const double peak = a[0];
+        if (weights) {
+            // the magnitudes as of weights / 2^e, e = floor(log2 of the largest counted weight): exact, and it makes the logarithms
+            // -- every bit -- independent of a common power-of-two factor of the weights; e = 0 for weights of 1
+            int e;
+            std::frexp((double)h_wmax[i], &e);
+            for (int k = 0; k < 5; ++k) a[k] = std::ldexp(a[k], 1 - e);
+        }
         const double dm = peak_offset(a[1], a[0], a[2]), dq = peak_offset(a[3], a[0], a[4]);
         if (m >= lk / 2) m -= lk;
         if (q >= lt / 2) q -= lt;
-        double power = 0.0;
-        for (int k = 0; k < kFringeParts; ++k) power += h_part[(int64_t)i * kFringeParts + k];
-        const int b = others[(size_t)i];
-        delay_s[b] = ((double)m + dm) * (double)nchan / ((double)lk * bandwidth);
-        rate_s_per_chunk[b] = ((double)q + dq) / ((double)lt * frequency);
-        if (snr) snr[b] = a[0] / std::sqrt(power);
+        f.delay = ((double)m + dm) * (double)nchan / ((double)lk * bandwidth);
+        f.rate = ((double)q + dq) / ((double)lt * frequency);
+        f.snr = peak / std::sqrt(power);
+    }
+    return FXC_OK;
+}
+
+// The antennas' delays from the baselines' (fxcorr.h fxc_fringe_fit_weighted, FXC_FRINGE_ALL; float64, on the host).  x[i] = the
+// estimate of X_b - X_a of cross row i = (a, b), s[i] its snr, period the range x is known modulo; `used` and the tree's start
+// values x0 (reached[a]: antenna a hangs on ref through used baselines) come from fringe_tree.  Unwraps every used baseline between
+// reached antennas onto the tree, solves min sum s^2 (X_b - X_a - x)^2 with X_ref = 0 (normal equations in ascending row order,
+// Cholesky) and wraps the solution into the principal range; antennas not reached get 0.
+void fringe_solve_axis(int n_ant, int ref, const std::vector<double>& x, const std::vector<double>& s, const std::vector<char>& used,
+                       const std::vector<char>& reached, const std::vector<double>& x0, double period, double* out) {
+    std::vector<int> slot((size_t)n_ant, -1);
+    int n = 0;
+    for (int a = 0; a < n_ant; ++a) {
+        out[a] = 0.0;
+        if (reached[(size_t)a] && a != ref) slot[(size_t)a] = n++;
+    }
+    if (n == 0) return;
+    std::vector<double> nm((size_t)n * n, 0.0), y((size_t)n, 0.0);
+    int64_t i = 0;
+    for (int a = 0; a < n_ant; ++a) {
+        for (int b = a + 1; b < n_ant; ++b, ++i) {
+            if (!used[(size_t)i] || !reached[(size_t)a] || !reached[(size_t)b]) continue;
+            const double d = x[(size_t)i] + period * std::nearbyint((x0[(size_t)b] - x0[(size_t)a] - x[(size_t)i]) / period);
+            const double w = s[(size_t)i] * s[(size_t)i];
+            const int ia = slot[(size_t)a], ib = slot[(size_t)b];
+            if (ia >= 0) {
+                nm[(size_t)ia * n + ia] += w;
+                y[(size_t)ia] -= w * d;
+            }
+            if (ib >= 0) {
+                nm[(size_t)ib * n + ib] += w;
+                y[(size_t)ib] += w * d;
+            }
+            if (ia >= 0 && ib >= 0) {
+                nm[(size_t)ia * n + ib] -= w;
+                nm[(size_t)ib * n + ia] -= w;
+            }
+        }
+    }
+    // Cholesky nm = L L^T in the lower triangle (the grounded Laplacian of a connected graph is positive definite), then the two
+    // triangular solves in place
+    for (int j = 0; j < n; ++j) {
+        double d = nm[(size_t)j * n + j];
+        for (int k = 0; k < j; ++k) d -= nm[(size_t)j * n + k] * nm[(size_t)j * n + k];
+        d = std::sqrt(d);
+        nm[(size_t)j * n + j] = d;
+        for (int r = j + 1; r < n; ++r) {
+            double v = nm[(size_t)r * n + j];
+            for (int k = 0; k < j; ++k) v -= nm[(size_t)r * n + k] * nm[(size_t)j * n + k];
+            nm[(size_t)r * n + j] = v / d;
+        }
+    }
+    for (int r = 0; r < n; ++r) {
+        double v = y[(size_t)r];
+        for (int k = 0; k < r; ++k) v -= nm[(size_t)r * n + k] * y[(size_t)k];
+        y[(size_t)r] = v / nm[(size_t)r * n + r];
+    }
+    for (int r = n - 1; r >= 0; --r) {
+        double v = y[(size_t)r];
+        for (int k = r + 1; k < n; ++k) v -= nm[(size_t)k * n + r] * y[(size_t)k];
+        y[(size_t)r] = v / nm[(size_t)r * n + r];
+    }
+    for (int a = 0; a < n_ant; ++a)
+        if (slot[(size_t)a] >= 0) {
+            const double v = y[(size_t)slot[(size_t)a]];
+            out[a] = v - period * std::nearbyint(v / period);
+        }
+}
+
+// The antenna solution of FXC_FRINGE_ALL from base[n_base][3] = (delay, rate, snr) of every cross row: the baselines of snr >=
+// threshold are used; a tree grows from ref by the used baseline of largest snr (ties: the lowest row) that joins a reached antenna
+// to one not yet reached, and gives the start values; fringe_solve_axis does the rest for the delays (period pd) and the rates
+// (pr).  snr[a] = the root of the sum of snr^2 over the used baselines between reached antennas that touch a; snr[ref] = 0.
+void fringe_solve_antennas(int n_ant, int ref, const double* base, double threshold, double pd, double pr, double* delay_s,
+                           double* rate_s_per_chunk, double* snr) {
+    const int64_t n_base = (int64_t)n_ant * (n_ant - 1) / 2;
+    std::vector<double> d((size_t)n_base), r((size_t)n_base), s((size_t)n_base);
+    std::vector<char> used((size_t)n_base), reached((size_t)n_ant, 0);
+    for (int64_t i = 0; i < n_base; ++i) {
+        d[(size_t)i] = base[3 * i];
+        r[(size_t)i] = base[3 * i + 1];
+        s[(size_t)i] = base[3 * i + 2];
+        used[(size_t)i] = s[(size_t)i] >= threshold;
+    }
+    std::vector<double> d0((size_t)n_ant, 0.0), r0((size_t)n_ant, 0.0);
+    reached[(size_t)ref] = 1;
+    for (;;) {
+        int64_t pick = -1, i = 0;
+        int pa = 0, pb = 0;
+        for (int a = 0; a < n_ant; ++a)
+            for (int b = a + 1; b < n_ant; ++b, ++i)
+                if (used[(size_t)i] && reached[(size_t)a] != reached[(size_t)b] && (pick < 0 || s[(size_t)i] > s[(size_t)pick])) {
+                    pick = i;
+                    pa = a;
+                    pb = b;
+                }
+        if (pick < 0) break;
+        if (reached[(size_t)pa]) {
+            d0[(size_t)pb] = d0[(size_t)pa] + d[(size_t)pick];
+            r0[(size_t)pb] = r0[(size_t)pa] + r[(size_t)pick];
+            reached[(size_t)pb] = 1;
+        } else {
+            d0[(size_t)pa] = d0[(size_t)pb] - d[(size_t)pick];
+            r0[(size_t)pa] = r0[(size_t)pb] - r[(size_t)pick];
+            reached[(size_t)pa] = 1;
+        }
+    }
+    fringe_solve_axis(n_ant, ref, d, s, used, reached, d0, pd, delay_s);
+    fringe_solve_axis(n_ant, ref, r, s, used, reached, r0, pr, rate_s_per_chunk);
+    if (snr) {
+        std::vector<double> sum((size_t)n_ant, 0.0);
+        int64_t i = 0;
+        for (int a = 0; a < n_ant; ++a)
+            for (int b = a + 1; b < n_ant; ++b, ++i)
+                if (used[(size_t)i] && reached[(size_t)a] && reached[(size_t)b]) {
+                    sum[(size_t)a] += s[(size_t)i] * s[(size_t)i];
+                    sum[(size_t)b] += s[(size_t)i] * s[(size_t)i];
+                }
+        for (int a = 0; a < n_ant; ++a) snr[a] = a == ref ? 0.0 : std::sqrt(sum[(size_t)a]);
+    }
+}
+
+// fxc_fringe_fit (not `weighted`: no weights, FXC_FRINGE_REF, no base_out) and fxc_fringe_fit_weighted after their checks: the list of fits, the
+// batches, and the outputs from the fits
+int fringe_fit_run(fxc_plan* p, const cf* rows, const float* weights, int64_t n_chunks, int mem_kind, double bandwidth, double frequency,
+                   int ref, int lk_log, int lt_log, bool weighted, int baselines, double min_snr, double* delay_s, double* rate_s_per_chunk, double* snr,
+                   double* base_out) {
+    const int n_ant = p->n_ant;
+    const int64_t n_base = p->n_base;
+    std::vector<FringeItem> items;
+    if (baselines == FXC_FRINGE_ALL) {
+        for (int64_t i = 0; i < n_base; ++i) items.push_back(FringeItem{i, 0});
+    } else {
+        for (int b : all_but(ref, n_ant)) items.push_back(FringeItem{cross_row(std::min(ref, b), std::max(ref, b), n_ant), b < ref});
+    }
+    std::vector<FringeFit> fits;
+    if (const int rc = fringe_fit_batch(p, rows, weights, n_chunks, mem_kind, bandwidth, frequency, lk_log, lt_log, weighted, items, fits))
+        return rc;
+    if (baselines == FXC_FRINGE_ALL) {
+        std::vector<double> base((size_t)n_base * 3);
+        for (int64_t i = 0; i < n_base; ++i) {
+            base[(size_t)(3 * i)] = fits[(size_t)i].delay;
+            base[(size_t)(3 * i + 1)] = fits[(size_t)i].rate;
+            base[(size_t)(3 * i + 2)] = fits[(size_t)i].snr;
+        }
+        const double threshold = min_snr > 0.0 ? min_snr : std::sqrt(std::log((double)(1ll << lk_log) * (double)(1ll << lt_log)) + std::log(1000.0));
+        fringe_solve_antennas(n_ant, ref, base.data(), threshold, (double)p->nchan / bandwidth, 1.0 / frequency, delay_s, rate_s_per_chunk,
+                              snr);
+        if (base_out) std::memcpy(base_out, base.data(), base.size() * sizeof(double));
+        return FXC_OK;
+    }
+    if (base_out) std::memset(base_out, 0, (size_t)n_base * 3 * sizeof(double));
+    const std::vector<int> others = all_but(ref, n_ant);
+    for (size_t i = 0; i < others.size(); ++i) {
+        const int b = others[i];
+        delay_s[b] = fits[i].delay;
+        rate_s_per_chunk[b] = fits[i].rate;
+        if (snr) snr[b] = fits[i].snr;
+        if (base_out) {
+            // as the row (lo, hi) reads: the conjugate's delay and rate are the negatives
+            double* o = base_out + 3 * items[i].row;
+            o[0] = items[i].conj ? -fits[i].delay : fits[i].delay;
+            o[1] = items[i].conj ? -fits[i].rate : fits[i].rate;
+            o[2] = fits[i].snr;
+        }
     }
     delay_s[ref] = 0.0;
     rate_s_per_chunk[ref] = 0.0;

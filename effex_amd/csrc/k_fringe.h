@@ -7,6 +7,7 @@ namespace {
 // fringe fit (fxcorr.h fxc_fringe_fit): the zero-padded 2-D DFT of the SPECTRUM rows of one baseline over
 // frequency (delay, index m < Lk) and over the chunks (fringe rate, index q < Lt), and the arg-max of its magnitude.
 //   gather   rows of the baselines (ref, b) -> G0[b][t][Lk], conjugated where b < ref, zero-padded; sum |R|^2 in fixed order
+//            (fxc_fringe_fit_weighted with weights: fringe_gather_weighted_kernel, the rows times their weights, any list of rows)
 //   frequency axis: the batched Stockham stages of k_delay.h over the n_chunks rows of every baseline -> G[b][t][m]
 //   time axis + peak (fringe_time_peak_kernel): a tile of adjacent delay columns in LDS, Lt-point transforms in place,
 //            |F|^2 and one packed arg-max word per baseline; the 2-D spectrum never reaches HBM
@@ -47,6 +48,60 @@ fringe_gather_kernel(const cf* __restrict__ rows, FringeRows br, int64_t t_strid
     }
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = red[0];
+        for (int w = 1; w < kFringeThreads / 64; ++w) s += red[w];
+        part[(int64_t)q * kFringeParts + blockIdx.x] = s;
+    }
+}
+
+// The gather of fxc_fringe_fit_weighted: g0[q][t][j] = Rw_q[t][j] = w > 0 ? (w x, w y) : (+0, +0) with (x, y) = R_q[t][j] and
+// w = weights at the same place (off[q] + t w_stride + j: a baseline's weights lie like its rows); part as above, of |Rw|^2.
+// Rows (8 bytes a lane) and weights (4 bytes a lane) are read once each; the sample and its weight are selected first and
+// multiplied after, so what a sample that does not count holds (NaN, Inf, 1e30) never meets an operation.  The loop, the
+// lanes and the order of the sums are the plain gather's: weights of 1.0f give its g0 and its partial sums bit for bit.
+// wmax[q] (zeroed by the caller) = the largest counted weight of the baseline as float bits: positive floats order like their
+// bits, and a maximum does not depend on the order it is taken in.
+__global__ void __launch_bounds__(kFringeThreads)
+fringe_gather_weighted_kernel(const cf* __restrict__ rows, const float* __restrict__ weights, FringeRows br, int64_t t_stride,
+                              int64_t w_stride, cf* __restrict__ g0, double* __restrict__ part, unsigned* __restrict__ wmax,
+                              int n_chunks, int nchan, int lk_log) {
+    __shared__ double red[kFringeThreads / 64];
+    const int q = blockIdx.y;
+    const cf* __restrict__ src = rows + br.off[q];
+    const float* __restrict__ wsrc = weights + br.off[q];
+    const float sgn = br.conj[q] ? -1.f : 1.f;
+    cf* __restrict__ dst = g0 + (((int64_t)q * n_chunks) << lk_log);
+    const int64_t total = (int64_t)n_chunks << lk_log;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    double acc = 0.0;
+    float wm = 0.f;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += stride) {
+        const int64_t t = idx >> lk_log;
+        const int j = (int)(idx & ((1ll << lk_log) - 1));
+        cf v = fxc::mk(0.f, 0.f);
+        if (j < nchan) {
+            const cf r = src[t * t_stride + j];
+            const float w = wsrc[t * w_stride + j];
+            const bool live = w > 0.f;                  // false for 0, negative and NaN weights
+            const float wl = live ? w : 0.f;
+            wm = wl > wm ? wl : wm;
+            v.x = wl * (live ? r.x : 0.f);
+            v.y = wl * (live ? r.y * sgn : 0.f);
+            acc += (double)v.x * (double)v.x + (double)v.y * (double)v.y;
+        }
+        dst[idx] = v;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        acc += __shfl_down(acc, off);
+        const float o = __shfl_down(wm, off);
+        wm = o > wm ? o : wm;
+    }
+    if ((threadIdx.x & 63) == 0) {
+        red[threadIdx.x >> 6] = acc;
+        atomicMax(wmax + q, __float_as_uint(wm));
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
         double s = red[0];

@@ -792,19 +792,47 @@ class FxPlan(object):
         out = np.zeros(shape, dtype=dtype)
         return out, out.ctypes.data
 
-    def fringe_fit(self, rows, bandwidth, frequency, ref=0, pad=2):
+    def fringe_fit(self, rows, bandwidth, frequency, ref=0, pad=2, weights=None, baselines="ref", min_snr=None,
+                   return_baselines=False):
         """Residual delay and delay rate of every antenna against antenna ``ref`` from SPECTRUM rows (fxcorr.h fxc_fringe_fit):
         ``rows`` = [n_chunks, n_rows, nchan] complex64 as ``fx_rows(x)`` returns them (numpy, or a CUDA tensor on the plan's
         device) -> (delays_s, rates_s_per_chunk, snr), float64 [n_ant] each, entry ``ref`` 0.  Added to what
-        ``set_delay_track`` was given they stop the fringes."""
+        ``set_delay_track`` was given they stop the fringes.
+
+        ``weights``, ``baselines``, ``min_snr`` and ``return_baselines`` (fxcorr.h fxc_fringe_fit_weighted; with all four at
+        their defaults the call is fxc_fringe_fit as it was): ``weights`` = float32 [n_chunks, n_baselines, nchan], numpy for
+        host rows or a CUDA tensor on the plan's device for device rows, for instance from ``flag_rows``; a sample counts iff
+        its weight is > 0, and what a sample that does not count holds (NaN, a tone) is never used.  ``baselines`` = "ref": the
+        baselines to ``ref`` alone; "all": every baseline is fitted, those of snr >= ``min_snr`` (None: the threshold of a 1e-3
+        false-alarm probability on the padded grid) are kept, and the antennas are solved for by least squares over them -- an
+        antenna whose baseline to ``ref`` is flagged is still measured, one that no kept baseline reaches gets 0 with snr 0.
+        With ``return_baselines`` a fourth result, float64 [n_baselines, 3] = (delay, rate, snr) per fitted baseline (b minus
+        a of row (a, b)), is returned.  The loop with the detector::
+
+            w = plan.flag_rows(rows)
+            d, r, s = plan.fringe_fit(rows, bw, fc, weights=w, baselines="all")
+        """
         self._sync_stream()
         keep, ptr, kind, shape = self._rows_in(rows, allow_2d=False)
+        if baselines not in ("ref", "all"):
+            raise ValueError("baselines must be 'ref' or 'all', got {!r}".format(baselines))
         delays = np.zeros(self.n_ant, dtype=np.float64)
         rates = np.zeros(self.n_ant, dtype=np.float64)
         snr = np.zeros(self.n_ant, dtype=np.float64)
-        self._check(self._lib.fxc_fringe_fit(self._h, ptr, int(shape[0]), kind, float(bandwidth), float(frequency), int(ref),
-                                             int(pad), delays.ctypes.data, rates.ctypes.data, snr.ctypes.data))
-        return delays, rates, snr
+        if weights is None and baselines == "ref" and min_snr is None and not return_baselines:
+            self._check(self._lib.fxc_fringe_fit(self._h, ptr, int(shape[0]), kind, float(bandwidth), float(frequency), int(ref),
+                                                 int(pad), delays.ctypes.data, rates.ctypes.data, snr.ctypes.data))
+            return delays, rates, snr
+        w_keep, w_ptr = None, None
+        if weights is not None:
+            w_keep, w_ptr = self._weights_in(weights, "weights", keep, shape[0])
+        base = np.zeros((self.n_baselines, 3), dtype=np.float64)
+        mode = _lib.FXC_FRINGE_ALL if baselines == "all" else _lib.FXC_FRINGE_REF
+        self._check(self._lib.fxc_fringe_fit_weighted(self._h, ptr, w_ptr, int(shape[0]), kind, float(bandwidth), float(frequency),
+                                                      int(ref), int(pad), mode, 0.0 if min_snr is None else float(min_snr),
+                                                      delays.ctypes.data, rates.ctypes.data, snr.ctypes.data,
+                                                      base.ctypes.data if return_baselines else None))
+        return (delays, rates, snr, base) if return_baselines else (delays, rates, snr)
 
     def solve_gains(self, rows, interval=0, ref=0, iters=50, weights=None, model=None):
         """Every antenna's complex gain per bin from SPECTRUM rows of a calibrator (fxcorr.h fxc_solve_gains): ``rows`` =

@@ -398,7 +398,8 @@ int fxc_estimate_delays(fxc_plan* plan, const void* x, int64_t n, int mem_kind, 
  * Limits: |delay| < nchan / (2 bandwidth) and |rate| < 1 / (2 frequency) per chunk are the unambiguous ranges.  The search takes
  * the fringe rate to be the same in every bin (f_k ~ frequency in the time term), which neglects the delay drift over the scan,
  * |rate| * n_chunks * bandwidth samples: n_chunks * bandwidth / (2 frequency) at the rate limit, 0.2 sample for 256 chunks at
- * 2.4 MHz / 1.4204 GHz.  Only the n_ant - 1 baselines to `ref` are used.
+ * 2.4 MHz / 1.4204 GHz.  Only the n_ant - 1 baselines to `ref` are used, and every sample as it stands; weights, and the
+ * least-squares solution over all baselines: fxc_fringe_fit_weighted below.
  * The |F|^2 of the search is formed in float32 and never written out; the five values of the two parabolas are summed again in
  * float64.  The baselines go through in batches as large as the workspace target allows, and no value depends on the batching.
  * Uses the plan's device, stream and workspace; synchronises like fxc_estimate_delays; neither reads nor changes the rot tables,
@@ -408,6 +409,58 @@ int fxc_estimate_delays(fxc_plan* plan, const void* x, int64_t n, int mem_kind, 
  * FXC_ERR_UNSUPPORTED: Lt > 4096, Lk > 65536, nchan == 1.  The outputs are written on FXC_OK only. */
 int fxc_fringe_fit(fxc_plan* plan, const void* rows, int64_t n_chunks, int mem_kind, double bandwidth, double frequency,
                    int ref, int pad, double* delay_s, double* rate_s_per_chunk, double* snr);
+
+/* Fringe fit with weights, over the baselines to `ref` or by least squares over all baselines: fxc_fringe_fit for
+ * rows that the detector (fxc_flag_rows) has been over, and for arrays whose baseline to `ref` may be missing.
+ * rows is as for fxc_fringe_fit.  weights = [n_chunks][n_baselines][nchan] float32 in the memory kind of rows, the layout of
+ * fxc_solve_gains_weighted and fxc_flag_rows; NULL: no buffer is read and every weight is 1.
+ * A sample counts iff its weight w > 0: a zero, negative or NaN weight leaves it out.  With (x, y) the sample,
+ *   Rw[t][j] = (w x, w y) if w > 0, else (+0, +0): float32 products, one rounding each, so that w = 1.0f gives R exactly.
+ * What a sample that does not count holds is never used: NaN, Inf or 1e30 there changes no output bit.  A counted value that is
+ * not finite propagates.
+ * The fit of one baseline is fxc_fringe_fit's, term for term, with Rw for R: Lk, Lt, the padded 2-D DFT F, the first arg-max
+ * (q0, m0), the two log-parabolas dm and dq, delay = (m + dm) nchan / (Lk bandwidth), rate = (q + dq) / (Lt frequency) and
+ * snr = |F[q0][m0]| / sqrt(sum_t sum_j |Rw[t][j]|^2).  The power sum is float64 in the order of fxc_fringe_fit: 128 fixed
+ * partial sums per baseline, added on the host in order.  A baseline whose power sum is 0 -- nothing counted -- gets delay 0,
+ * rate 0 and snr 0; its peak is not used (fxc_fringe_fit itself divides by the sum).  One term is added: with weights given,
+ * the magnitudes a, b, c of the two log-parabolas are divided by 2^e, e = floor(log2(the largest counted weight of the baseline)),
+ * before the logarithms -- exact, and e = 0 for weights of 1.  With it, multiplying every weight by the same power of two changes
+ * no output bit, barring overflow and underflow (ln(4 a) and ln(a) round differently; snr is a ratio and needs no such term).
+ * baselines = FXC_FRINGE_REF: the baselines to `ref` are fitted, conjugated where b < ref, and delay_s, rate_s_per_chunk and snr
+ *   are as fxc_fringe_fit defines them; min_snr must be 0.  With NULL weights, or with every weight 1.0f, the three outputs are
+ *   fxc_fringe_fit's bit for bit.  base_out (when given) holds (delay, rate, snr) of every fitted baseline at its row index, as
+ *   row (lo, hi) reads -- not conjugated: the estimate of D_hi - D_lo --, and 0 in every other row.
+ * baselines = FXC_FRINGE_ALL: every cross row i = (a, b), a < b, is fitted as it stands: base[i] = (d_i, r_i, s_i), the
+ *   estimates of D_b - D_a, which base_out receives.  Then on the host, in float64:
+ *   used     baseline i is used iff s_i >= T; T = min_snr if min_snr > 0, else T = sqrt(ln(Lk Lt) + ln(1000)): |F|^2 / sum |Rw|^2
+ *            is exponential with mean 1 in each of the Lk Lt cells of noise alone (padding makes the count of independent cells
+ *            an over-estimate), so a baseline of noise is used with a probability of 1e-3 at most.  T = 3.99 at Lk 128, Lt 64.
+ *   tree     from {ref}: again and again the used baseline of largest s that joins a reached antenna to one not reached (ties:
+ *            the lowest row index) is added, and the new antenna's D0, R0 are the reached end's plus or minus (d_i, r_i).
+ *            Antennas never reached get delay, rate and snr 0.
+ *   unwrap   with the periods Pd = nchan / bandwidth and Pr = 1 / frequency (a baseline measures a difference modulo the period),
+ *            every used baseline between reached antennas takes d_i += Pd nearbyint((D0_b - D0_a - d_i) / Pd), r_i likewise with Pr.
+ *   solve    minimise sum_i s_i^2 (D_b - D_a - d_i)^2 over the reached antennas, D_ref = 0, and the same for the rates: the
+ *            normal equations are formed in ascending row order and solved by Cholesky.
+ *            snr[a] = sqrt(sum of s_i^2 over the used baselines between reached antennas that touch a); snr[ref] = 0.
+ *            Each result is wrapped into the principal range, x - P nearbyint(x / P).
+ *   For baselines of equal sensitivity the solution has sqrt(2 / n_ant) of the error of the baselines to `ref`, and an antenna
+ *   whose baseline to `ref` is flagged is still measured through the others.
+ * delay_s, rate_s_per_chunk and snr are host double[n_ant] (snr may be NULL); base_out is host double[n_baselines][3] and may
+ * be NULL.  Limits: those of fxc_fringe_fit per baseline; n_ant <= 64 (2016 baselines); fringes too weak for any single baseline
+ * are not found (no coherent search across baselines); the auto rows are not used.
+ * The baselines go through in batches as large as the workspace target allows, host rows and host weights staged baseline by
+ * baseline; no bit of base_out or of the three outputs depends on the batches, the workspace target, or host against device
+ * input.  Uses the plan's device, stream and workspace; one copy to the host and one synchronisation end the call; neither reads
+ * nor changes the rot tables, the tracks or their counters.
+ * FXC_ERR_ARG, before any device work: every case of fxc_fringe_fit; baselines neither FXC_FRINGE_REF nor FXC_FRINGE_ALL; min_snr
+ * negative or not finite, or not 0 with FXC_FRINGE_REF.  FXC_ERR_UNSUPPORTED: the cases of fxc_fringe_fit.  The outputs are
+ * written on FXC_OK only. */
+#define FXC_FRINGE_REF 0
+#define FXC_FRINGE_ALL 1
+int fxc_fringe_fit_weighted(fxc_plan* plan, const void* rows, const void* weights, int64_t n_chunks, int mem_kind,
+                            double bandwidth, double frequency, int ref, int pad, int baselines, double min_snr,
+                            double* delay_s, double* rate_s_per_chunk, double* snr, double* base_out);
 
 /* Gain solve: every antenna's complex gain per bin from the SPECTRUM rows of n_chunks consecutive chunks of a point source at
  * the phase centre (a calibrator; model visibility 1), by least squares over ALL baselines -- what is left
