@@ -88,6 +88,29 @@ def random_weights(seed, n_beam, n_ant, nchan):
     return ((rng.standard_normal(shape) + 1j * rng.standard_normal(shape)) / np.sqrt(2.0)).astype(np.complex64)
 
 
+# more frames than a frame range of the kernel, (n_ant, nchan, ntaps, n_pts, n_chunks, n_beam) -- tests/test_gpu_beamform.py says what
+# each is for.  Their window is window_cases.rough_window: a chunk's first frame meets data through the window's last taps alone, the
+# designed window's smallest, and a first frame lost or doubled would hide under the bounds; with independent taps it counts
+LONG_SHAPES = [(3, 64, 4, 37, 2, 3), (2, 16, 4, 70, 2, 9), (9, 63, 4, 37, 2, 5), (4, 32, 4, 37, 2, 2)]
+
+
+def shape_case(shape):
+    """-> x, w, window of a shape of the GPU test"""
+    import window_cases
+    from effex_amd.window import design_window
+    n_ant, nchan, ntaps, n_pts, n_chunks, n_beam = shape
+    x = noise_and_source(1000 * n_ant + nchan + n_beam, n_chunks, n_ant, nchan * n_pts)
+    w = random_weights(17 * n_ant + n_beam, n_beam, n_ant, nchan)
+    window = window_cases.rough_window(ntaps, nchan) if tuple(shape) in LONG_SHAPES else design_window(ntaps, nchan)
+    return x, w, window
+
+
+def tints_of(n_pts):
+    """frames per time bin that the GPU test gives a shape: the whole chunk (0 and n_pts), single frames, 3; 5 and 33 where the chunk
+    has as many; and n_pts - 1, one full bin and a bin of one frame, each a frame range of its own"""
+    return sorted({0, 1, 3, n_pts, n_pts - 1} | {t for t in (5, 33) if t <= n_pts})
+
+
 # -- coherent gain ----------------------------------------------------------------------------------------------------------------
 # gains_ref.samples: x_a = c_a s + sigma n_a.  The beamformer is linear in x, so the source's and the noise's shares of a beam are
 # the beams of the two parts alone.  With w_a = conj(c_a) / |c_a|^2 / n_ant the on-source beam is s + (sigma / n_ant) sum_a n_a /

@@ -99,6 +99,121 @@ def test_partial_last_time_bin_by_hand():
         assert np.array_equal(shifted[(k + n // 2) % n], k)
 
 
+# -- frame ranges, tiles and the bin flush of beam_kernel ---------------------------------------------------------------------------
+K_BEAM_FRAMES = 8        # k_beam.h::kBeamFrames
+K_GRID_MAX = 65535       # h_plan.h::kGridMax
+LONG_FRAMES = (37, 70)   # the frame counts of beam_ref.LONG_SHAPES
+
+
+def frames_per_range(n_pts, tint, power=True):
+    """h_tools.h::beamform_dev: whole time bins (VOLTAGE: whole tiles), 32 frames or more where a bin is shorter, and no more ranges
+    than gridDim.y holds"""
+    unit = (tint or n_pts) if power else K_BEAM_FRAMES
+    fpr = unit * max(1, 32 // unit)
+    return max(fpr, ((n_pts + K_GRID_MAX - 1) // K_GRID_MAX + unit - 1) // unit * unit)
+
+
+def walk(n_pts, tint, power=True):
+    """beam_kernel's loops over one (column, chunk): -> ranges [(i0, i1)], tiles [(range, frames read)], and -- POWER -- the flushes
+    [(bin, frames added since the last flush, count the sum is divided by)]; VOLTAGE: [(frame stored, [frame read], 1)]"""
+    tint = tint or n_pts
+    fpr = frames_per_range(n_pts, tint, power)
+    ranges, tiles, flushes = [], [], []
+    for y in range(-(-n_pts // fpr)):
+        i0 = y * fpr
+        i1 = i0 + fpr if i0 + fpr < n_pts else n_pts
+        ranges.append((i0, i1))
+        added, cnt = [], 0
+        for i in range(i0, i1, K_BEAM_FRAMES):
+            read = [i + f if i + f < i1 else i1 - 1 for f in range(K_BEAM_FRAMES)]
+            tiles.append((y, read))
+            for f in range(K_BEAM_FRAMES):
+                frame = i + f
+                if frame >= i1:
+                    break
+                if not power:
+                    flushes.append((frame, [read[f]], 1))
+                    continue
+                added.append(read[f])
+                cnt += 1
+                if cnt == tint or frame == n_pts - 1:
+                    flushes.append((frame // tint, added, cnt))
+                    added, cnt = [], 0
+        assert not added, "a range ends inside a time bin"
+    return ranges, tiles, flushes
+
+
+def test_frame_ranges_are_the_ones_the_shapes_claim():
+    assert [walk(37, t)[0] for t in (3, 5)] == [[(0, 30), (30, 37)]] * 2
+    assert walk(37, 0, power=False)[0] == [(0, 32), (32, 37)] and walk(70, 0, power=False)[0] == [(0, 32), (32, 64), (64, 70)]
+    assert walk(37, 36)[0] == [(0, 36), (36, 37)] and walk(70, 69)[0] == [(0, 69), (69, 70)] and walk(70, 33)[0] == [(0, 33), (33, 66), (66, 70)]
+    assert walk(37, 1)[0] == [(0, 32), (32, 37)] and walk(37, 0)[0] == walk(37, 37)[0] == [(0, 37)]
+    assert walk(8, 3)[0] == [(0, 8)] and walk(16, 1, power=False)[0] == [(0, 16)]          # the earlier shapes: one range, full tiles
+    for n_pts in LONG_FRAMES:
+        for tint, power in [(t, True) for t in beam_ref.tints_of(n_pts)] + [(0, False)]:
+            ranges, tiles, _ = walk(n_pts, tint, power)
+            assert ranges[0][0] == 0 and ranges[-1][1] == n_pts and all(a[1] == b[0] for a, b in zip(ranges, ranges[1:]))
+            for y, read in tiles:                                        # every read stays inside its range
+                assert all(ranges[y][0] <= i < ranges[y][1] for i in read)
+            if tint not in (0, n_pts):
+                assert len(ranges) > 1, (n_pts, tint)
+            # the last range's last tile is partial; at 37 frames every range's is, but for the ranges of 32 (single frames, voltages)
+            last = [[r for yy, r in tiles if yy == y][-1] for y in range(len(ranges))]
+            partial = [len(set(r)) < K_BEAM_FRAMES for r in last]
+            assert partial[-1] and (n_pts != 37 or tint == 1 or not power or all(partial)), (n_pts, tint, partial)
+
+
+def beam_tiles(n_beam):
+    """the kernel instantiations (beams per thread) of a call's beam tiles: h_tools.h::beamform_dev"""
+    out = []
+    for b0 in range(0, n_beam, 8):
+        left = n_beam - b0
+        out.append(8 if left > 4 else 4 if left > 2 else 2 if left > 1 else 1)
+    return out
+
+
+def test_every_beam_tile_meets_a_second_range_and_a_partial_tile():
+    """every shape of beam_ref.LONG_SHAPES has both in every mode (above), and between them they launch every instantiation"""
+    assert [beam_tiles(s[5]) for s in beam_ref.LONG_SHAPES] == [[4], [8, 1], [8], [2]]
+    assert [beam_tiles(n) for n in (1, 2, 3, 4, 5, 8, 9, 10, 16)] == [[1], [2], [4], [4], [8], [8], [8, 1], [8, 2], [8, 8]]
+
+
+@pytest.mark.parametrize("n_pts", LONG_FRAMES)
+def test_every_frame_lands_in_exactly_one_bin_with_its_count(n_pts):
+    assert beam_ref.tints_of(37) == [0, 1, 3, 5, 33, 36, 37] and beam_ref.tints_of(70) == [0, 1, 3, 5, 33, 69, 70]
+    assert beam_ref.tints_of(8) == [0, 1, 3, 5, 7, 8] and beam_ref.tints_of(16) == [0, 1, 3, 5, 15, 16]
+    for tint in beam_ref.tints_of(n_pts):
+        bins = beam_ref.time_bins(n_pts, tint)
+        _, _, flushes = walk(n_pts, tint)
+        assert [j for j, _, _ in flushes] == list(range(len(bins))), tint          # every bin stored once, no other
+        for j, added, cnt in flushes:
+            i0, i1 = bins[j]
+            assert added == list(range(i0, i1)) and cnt == i1 - i0, (tint, j)      # its frames in order, the divisor power() uses
+        assert sorted(i for _, added, _ in flushes for i in added) == list(range(n_pts))
+    _, _, stored = walk(n_pts, 0, power=False)
+    assert [(frame, read) for frame, read, _ in stored] == [(i, [i]) for i in range(n_pts)]
+
+
+@pytest.mark.parametrize("shape", beam_ref.LONG_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_a_range_boundary_frame_lost_or_doubled_moves_the_power_ten_ceilings(shape):
+    """what test_gpu_beamform.py would see, on its own inputs, of a range that drops its last frame or adds its first one twice
+    (the bin keeps its divisor)"""
+    assert sorted({s[3] for s in beam_ref.LONG_SHAPES}) == list(LONG_FRAMES)
+    n_ant, nchan, ntaps, n_pts, n_chunks, n_beam = shape
+    ceiling = 1e-5                                                           # (TOL_BEAM_POWER's)
+    x, w, window = beam_ref.shape_case(shape)
+    y = beam_ref.voltages(beam_ref.spectra(x, nchan, window), w)
+    assert y.shape == (n_chunks, n_beam, n_pts, nchan)
+    for tint in beam_ref.tints_of(n_pts):
+        want = beam_ref.power(y, tint)
+        for i0, i1 in walk(n_pts, tint)[0]:
+            for frame, factor, what in ((i1 - 1, 0.0, "dropped"), (i0, np.sqrt(2.0), "counted twice")):
+                bad = y.copy()
+                bad[:, :, frame] *= factor
+                err = np.abs(beam_ref.power(bad, tint) - want).max() / np.abs(want).max()
+                assert err >= 10.0 * ceiling, (tint, frame, what, err)
+
+
 # -- coherent gain ----------------------------------------------------------------------------------------------------------------
 def coherent_gain_deviation(seed, beamform=None):
     """the deviation of beam_ref.gain_deviation for one seed; beamform(x, w) -> power [n_chunks, n_beam, 1, nchan] (default: the

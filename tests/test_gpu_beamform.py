@@ -70,14 +70,16 @@ def both_inputs(plan, torch, x, w, **kw):
 # front of the F stage (its buffer and the workspace carve)
 SHAPES = [(2, 64, 4, 8, 3, 1), (3, 16, 4, 8, 2, 3), (8, 64, 4, 16, 3, 8), (9, 64, 4, 8, 2, 9), (64, 64, 4, 8, 1, 16),
           (5, 1000, 4, 8, 2, 4), (3, 63, 4, 8, 2, 2), (4, 4096, 4, 8, 2, 2), (2, 8192, 4, 8, 1, 2), (3, 64, 8, 8, 2, 2)]
+# ... and more frames than a frame range (h_tools.h::beamform_dev: ranges of fpr frames ride in grid.y, beam_kernel walks a range in
+# tiles of 8 frames): 37 frames are VOLTAGE ranges of 32 + 5 and ranges of 30 + 7 at 3 or 5 frames a bin, every range's last tile
+# partial, the chunk's last bin too (37 = 12 x 3 + 1 = 7 x 5 + 2); 70 frames are 32 + 32 + 6, with two beam tiles (8 + 1) and part of
+# a wave; the one-antenna tail trip at an odd channel count with three beams of the tile idle; two beams.  Between them every beam
+# tile -- 4, 8 and 1, 8, 2 -- meets a second range and a partial tile (tests/test_beam_host.py restates the ranges, tiles and bins)
+# Their window is window_cases.rough_window (beam_ref.py says why)
+SHAPES += beam_ref.LONG_SHAPES
 
 
-def shape_case(shape):
-    n_ant, nchan, ntaps, n_pts, n_chunks, n_beam = shape
-    x = beam_ref.noise_and_source(1000 * n_ant + nchan + n_beam, n_chunks, n_ant, nchan * n_pts)
-    w = beam_ref.random_weights(17 * n_ant + n_beam, n_beam, n_ant, nchan)
-    window = design_window(ntaps, nchan)
-    return x, w, window
+shape_case = beam_ref.shape_case
 
 
 def shape_errors(plan_mod, torch, shape, log=print):
@@ -87,7 +89,7 @@ def shape_errors(plan_mod, torch, shape, log=print):
     y = beam_ref.voltages(beam_ref.spectra(x, nchan, window), w)          # the float64 reference, once per shape
     errs = {}
     with plan_mod.FxPlan(n_ant, nchan, ntaps, nchan * n_pts, window=window) as plan:
-        for tint in (0, 1, 3, n_pts):
+        for tint in beam_ref.tints_of(n_pts):
             want = beam_ref.power(y, tint)
             got = both_inputs(plan, torch, x, w, tint=tint)
             assert got.shape == want.shape == (n_chunks, n_beam, -(-n_pts // (tint or n_pts)), nchan) and got.dtype == np.float32
@@ -129,7 +131,13 @@ def test_power_equals_the_expansion_of_the_plans_own_rows(plan_mod, torch, n_ant
 # -- tracks -----------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("gains", [False, True], ids=["delay track", "delay and gain track"])
 def test_tracks_fold_the_chunks_tables_into_the_weights(plan_mod, torch, gains):
-    n_ant, nchan, n_pts, n_chunks, n_beam, first = 4, 64, 8, 5, 3, 5
+    """8 frames, and 37: two frame ranges -- 30 + 7 frames at 3 a bin, 32 + 5 voltages -- under each chunk's effective weights"""
+    for n_pts in (8, 37):
+        tracks_case(plan_mod, torch, gains, n_pts)
+
+
+def tracks_case(plan_mod, torch, gains, n_pts):
+    n_ant, nchan, n_chunks, n_beam, first = 4, 64, 5, 3, 5
     x = beam_ref.noise_and_source(77, n_chunks, n_ant, nchan * n_pts)
     w = beam_ref.random_weights(78, n_beam, n_ant, nchan)
     window = design_window(4, nchan)
