@@ -89,6 +89,9 @@ SIGNATURES = {
     "fxc_delay_track_tables": (_c.c_int, [_vp, _c.c_int64, _vp]),
     "fxc_set_track_gains": (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int64, _c.c_int64]),
     "fxc_track_gains_info": (_c.c_int, [_vp, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64)]),
+    "fxc_set_sample_delays": (_c.c_int, [_vp, _vp]),
+    "fxc_set_delay_track_aligned": (_c.c_int, [_vp, _vp, _vp, _c.c_double, _c.c_double, _c.c_int64]),
+    "fxc_sample_delays": (_c.c_int, [_vp, _c.c_int64, _vp]),
     "fxc_set_products": (_c.c_int, [_vp, _c.c_int]),
     "fxc_plan_products": (_c.c_int, [_vp, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
     "fxc_channelize": (_c.c_int, [_vp, _vp, _vp, _c.c_int64, _c.c_int]),

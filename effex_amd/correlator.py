@@ -305,8 +305,13 @@ class Correlator(object):
     def __init__(self, run_time=1, bandwidth=2.4e6, frequency=1.4204e9, num_samp=2 ** 18, nbins=2 ** 12,
                  gain=49.6, mode='SPECTRUM', loglevel='INFO',
                  source=None, device=0, max_num_samp=None, output_file=None, remove_dc=True, calibrate=True,
-                 output_format='csv', batch=1, autos=False, device_sweep=False):
+                 output_format='csv', batch=1, autos=False, device_sweep=False, whole_samples=False):
         self.logger = logging.getLogger(__name__)
+        # whole_samples=True: every place that sends calibrated_delay to the plan sends it split (FxPlan.set_delays /
+        # set_delay_track with whole_samples=True): antenna 1's stream is moved by rint(delay * bandwidth) samples and the table
+        # keeps the rest.  A phase slope alone loses about d / nbins of the amplitude for a delay of d samples.  Off (the
+        # reference's behaviour, effex.py:516-519): the whole delay as a phase slope.
+        self.whole_samples = bool(whole_samples)
         self.logger.setLevel(getattr(logging, loglevel))
         self._max_num_samp = int(max_num_samp) if max_num_samp else Correlator._MAX_NUM_SAMP
         self.source = source if source is not None else SyntheticSource()
@@ -576,7 +581,10 @@ class Correlator(object):
             self._rot_key = None
         key = (self.bandwidth, self.frequency, self.calibrated_delay)
         if key != self._rot_key:      # rot only changes on calibration / TEST sweep
-            self._fx_plan.set_rot(rot_table(int(self.nbins), self.bandwidth, self.frequency, self.calibrated_delay))
+            if self.whole_samples:
+                self._fx_plan.set_delays([0.0, float(self.calibrated_delay)], self.bandwidth, self.frequency, whole_samples=True)
+            else:
+                self._fx_plan.set_rot(rot_table(int(self.nbins), self.bandwidth, self.frequency, self.calibrated_delay))
             self._rot_key = key
         return self._fx_plan
 
@@ -754,8 +762,8 @@ class Correlator(object):
         if 'TEST' == self.mode:
             # row j of the sweep is phased for calibrated_delay + (j + 1) steps: the loop adds the step before the first row too
             plan.set_delay_track(self.calibrated_delay + self.test_delay_sweep_step, self.test_delay_sweep_step,
-                                 self.bandwidth, self.frequency)
-            self._rot_key = None          # (the next _plan() sets a static table again, which ends the track)
+                                 self.bandwidth, self.frequency, whole_samples=self.whole_samples)
+            self._rot_key = None         # (the next _plan() sets a static table again, which ends the track)
 
         def emit(out):          # out: [k, 1, nchan] complex64 or [k, 1] complex128
             for row in out[:, 0]:

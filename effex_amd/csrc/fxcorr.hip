@@ -3,7 +3,7 @@
 // One translation unit.  This file holds the ABI entry points -- argument checks, then a driver of the h_*.h files; it includes
 //   fx_math.h, fx_fused4096.h, fx_tiled.h, fx_small.h, fx_mixed.h   index maps, butterflies and kernel phases (also compiled by
 //                                           g++ for the host emulation under tests/emul)
-//   k_generic.h k_finish.h k_xmfma.h k_fused4096.h k_tiled.h k_small.h k_prepass.h k_stream.h k_conditioning.h k_track.h k_synth.h
+//   k_generic.h k_finish.h k_xmfma.h k_fused4096.h k_tiled.h k_small.h k_prepass.h k_stream.h k_conditioning.h k_track.h k_align.h k_synth.h
 //   k_delay.h k_fringe.h k_gains.h k_flag.h k_average.h k_beam.h
 //                                           the __global__ kernels, one file per path / step and per rows tool (delays, fringe fit,
 //                                           gain solve, detector, averager, beamformer)
@@ -140,6 +140,7 @@ int64_t ws_target() {
 #include "k_stream.h"
 #include "k_conditioning.h"
 #include "k_track.h"
+#include "k_align.h"
 #include "k_delay.h"
 #include "k_fringe.h"
 #include "k_gains.h"
@@ -202,7 +203,8 @@ int fxc_plan_destroy(fxc_plan* p) {
     }
     void* bufs[] = {p->d_win, p->d_tw, p->d_rot, p->d_win4, p->d_tw1, p->d_tw2, p->d_tw0, p->d_tw_small, p->d_stamps,
                     p->d_acc, p->d_sums, p->d_cont, p->d_rowpart, p->d_ws, p->d_stage[0], p->d_stage[1], p->d_stage[2], p->d_dc, p->d_hpre,
-                    p->d_ones, p->d_pre, p->d_tw8192, p->d_unit4, p->d_chirp, p->d_blud, p->d_rot_ant, p->d_pair, p->d_track_par, p->d_track, p->d_one, p->d_gain_q};
+                    p->d_ones, p->d_pre, p->d_tw8192, p->d_unit4, p->d_chirp, p->d_blud, p->d_rot_ant, p->d_pair, p->d_track_par, p->d_track, p->d_one, p->d_gain_q,
+                    p->d_shift, p->d_tshift, p->d_align};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (p->ev_t0) (void)hipEventDestroy(p->ev_t0);
@@ -368,9 +370,39 @@ int end_track(fxc_plan* p) {
     if (p->track && p->acc_track && !acc_empty(p))
         return fail(p, FXC_ERR_STATE, "the accumulator holds chunks accumulated under the delay track: finalize or reset it first");
     p->track = false;
+    p->track_align = false;      // (the per-chunk shifts of an aligned track end with it; static shifts are not the track's)
     p->gain_n = 0;      // the gains were solved under this track: they end with it (release_gain_q frees them once the stream is idle)
     return FXC_OK;
 }
+
+// the static whole-sample shifts, or none of them (shifts == nullptr); the caller has synchronised the plan's stream
+int store_sample_shifts(fxc_plan* p, const int64_t* shifts) {
+    bool any = false;
+    for (int a = 0; shifts && a < p->n_ant; ++a) any = any || shifts[a] != 0;
+    if (!any) {
+        p->shifted = false;
+        p->sample_shift.clear();
+        return FXC_OK;
+    }
+    std::vector<int> s32((size_t)p->n_ant);
+    for (int a = 0; a < p->n_ant; ++a) s32[(size_t)a] = (int)shifts[a];      // (|s| < num_samp <= 2^27: checked by the caller)
+    if (!p->d_shift) FXC_HIP(p, hipMalloc(reinterpret_cast<void**>(&p->d_shift), (size_t)p->n_ant * sizeof(int)));
+    FXC_HIP(p, hipMemcpy(p->d_shift, s32.data(), (size_t)p->n_ant * sizeof(int), hipMemcpyHostToDevice));
+    p->sample_shift.assign(shifts, shifts + p->n_ant);
+    p->shifted = true;
+    return FXC_OK;
+}
+
+// s_a(t) of an aligned track as track_shift (k_align.h) forms it on the device: the same individually rounded operations
+int64_t track_shift_host(const fxc_plan* p, int a, int64_t t) {
+#pragma clang fp contract(off)
+    const double tau = p->track_par_h[(size_t)a] + (double)t * p->track_par_h[(size_t)(p->n_ant + a)];
+    double v = tau * p->track_bw;
+    v = v > 2147483647.0 ? 2147483647.0 : (v < -2147483647.0 ? -2147483647.0 : v);
+    return (int64_t)std::llrint(v);
+}
+
+constexpr int64_t kAlignMaxSamp = 1ll << 27;      // a stream within one buffer descriptor (align_c64_kernel)
 
 // frees the table of a gain track that has ended; the caller has synchronised the plan's stream
 void release_gain_q(fxc_plan* p) {
@@ -381,8 +413,11 @@ void release_gain_q(fxc_plan* p) {
 }
 }  // namespace
 
-int fxc_set_delay_track(fxc_plan* p, const double* tau0_s, const double* rate_s_per_chunk, double bandwidth, double frequency,
-                        int64_t first_chunk) {
+namespace {
+// fxc_set_delay_track and, `aligned`, fxc_set_delay_track_aligned: the same track, with the whole samples of every chunk's delays
+// taken out of the tables and applied to the samples
+int set_delay_track(fxc_plan* p, const double* tau0_s, const double* rate_s_per_chunk, double bandwidth, double frequency,
+                    int64_t first_chunk, bool aligned) {
     if (!p || !tau0_s || !rate_s_per_chunk) return fail(p, FXC_ERR_ARG, "NULL argument");
     if (p->n_ant < 2) return fail(p, FXC_ERR_ARG, "a delay track needs 2 or more antennas, the plan has %d", p->n_ant);
     if (!(bandwidth > 0.0) || !std::isfinite(bandwidth) || !std::isfinite(frequency))
@@ -391,6 +426,8 @@ int fxc_set_delay_track(fxc_plan* p, const double* tau0_s, const double* rate_s_
     for (int a = 0; a < p->n_ant; ++a)
         if (!std::isfinite(tau0_s[a]) || !std::isfinite(rate_s_per_chunk[a]))
             return fail(p, FXC_ERR_ARG, "delay or rate of antenna %d is not finite", a);
+    if (aligned && p->num_samp > kAlignMaxSamp)
+        return fail(p, FXC_ERR_UNSUPPORTED, "whole-sample delays take chunks of up to 2^27 samples, the plan's have %lld", (long long)p->num_samp);
     if (p->live_pipes) return fail(p, FXC_ERR_STATE, "an fxc_pipe uses the plan");
     if (!acc_empty(p) && !p->acc_track)
         return fail(p, FXC_ERR_STATE, "the accumulator holds chunks accumulated without a delay track: finalize or reset it first");
@@ -416,6 +453,51 @@ int fxc_set_delay_track(fxc_plan* p, const double* tau0_s, const double* rate_s_
     p->rot_ant = false;
     p->gain_n = 0;      // gains were solved on rows made under one particular track: a new track drops them
     release_gain_q(p);
+    p->track_align = aligned;
+    if (aligned) {
+        p->track_bw = bandwidth;
+        p->track_par_h.assign(tau0_s, tau0_s + A);
+        p->track_par_h.insert(p->track_par_h.end(), rate_s_per_chunk, rate_s_per_chunk + A);
+        return store_sample_shifts(p, nullptr);      // the track's own shifts take the place of static ones
+    }
+    return FXC_OK;
+}
+}  // namespace
+
+int fxc_set_delay_track(fxc_plan* p, const double* tau0_s, const double* rate_s_per_chunk, double bandwidth, double frequency,
+                        int64_t first_chunk) {
+    return set_delay_track(p, tau0_s, rate_s_per_chunk, bandwidth, frequency, first_chunk, false);
+}
+
+int fxc_set_delay_track_aligned(fxc_plan* p, const double* tau0_s, const double* rate_s_per_chunk, double bandwidth, double frequency,
+                                int64_t first_chunk) {
+    return set_delay_track(p, tau0_s, rate_s_per_chunk, bandwidth, frequency, first_chunk, true);
+}
+
+int fxc_set_sample_delays(fxc_plan* p, const int64_t* shift_samples) {
+    if (!p) return fail(p, FXC_ERR_ARG, "NULL plan");
+    bool any = false;
+    for (int a = 0; shift_samples && a < p->n_ant; ++a) {
+        const int64_t s = shift_samples[a];
+        if (s >= p->num_samp || s <= -p->num_samp)
+            return fail(p, FXC_ERR_ARG, "shift %lld of antenna %d leaves none of the chunk's %lld samples", (long long)s, a, (long long)p->num_samp);
+        any = any || s != 0;
+    }
+    if (any && p->track && p->track_align)
+        return fail(p, FXC_ERR_STATE, "the aligned delay track sets the shifts of every chunk: end it first");
+    if (any && p->num_samp > kAlignMaxSamp)
+        return fail(p, FXC_ERR_UNSUPPORTED, "whole-sample delays take chunks of up to 2^27 samples, the plan's have %lld", (long long)p->num_samp);
+    FXC_DEVICE(p, p->device);
+    // ordered after any queued alignment that still reads the old shifts
+    FXC_HIP(p, hipStreamSynchronize(p->stream));
+    return store_sample_shifts(p, shift_samples);
+}
+
+int fxc_sample_delays(const fxc_plan* p, int64_t chunk, int64_t* shift_samples_out) {
+    if (!p || !shift_samples_out) return fail(p, FXC_ERR_ARG, "NULL argument");
+    if (chunk < 0) return fail(p, FXC_ERR_ARG, "chunk < 0");
+    for (int a = 0; a < p->n_ant; ++a)
+        shift_samples_out[a] = p->track && p->track_align ? track_shift_host(p, a, chunk) : (p->shifted ? p->sample_shift[(size_t)a] : 0);
     return FXC_OK;
 }
 
@@ -508,6 +590,8 @@ int fxc_delay_track_tables(fxc_plan* p, int64_t chunk, double* out_re_im) {
     const size_t bytes = (size_t)p->n_ant * p->nchan * sizeof(cd);
     const int rg = grow(p, &p->d_stage[1], &p->stage_bytes[1], bytes);
     if (rg) return rg;
+    if (p->track_align)      // the chunk's whole-sample shifts, where the aligned table kernels read them
+        if (const int rs = track_shifts_pass(p, chunk, 1)) return rs;
     const int rc = track_tables(p, chunk, 1, static_cast<cd*>(p->d_stage[1]), false);
     if (rc) return rc;
     FXC_HIP(p, hipMemcpyAsync(out_re_im, p->d_stage[1], bytes, hipMemcpyDeviceToHost, p->stream));
@@ -1118,6 +1202,10 @@ int fxc_beamform(fxc_plan* p, const void* x, const void* weights, int n_beam, vo
     if (n_chunks == 0 || p->n_pts == 0) return FXC_OK;
     if (!x || !weights || !out) return fail(p, FXC_ERR_ARG, "NULL buffer");
     if (p->track && p->live_pipes) return fail(p, FXC_ERR_STATE, "an fxc_pipe uses the plan");
+    if (aligning(p))
+        return fail(p, FXC_ERR_UNSUPPORTED, "the plan applies whole-sample delays (%s) and the beamformer's passes are not aligned: beams of "
+                    "unaligned samples would lose amplitude silently.  Clear the shifts or use a plain delay track",
+                    p->shifted ? "fxc_set_sample_delays" : "fxc_set_delay_track_aligned");
     FXC_DEVICE(p, p->device);
     const int64_t t0 = p->track_t;
     int rc;

@@ -59,6 +59,9 @@ int pinned_rows_out(fxc_plan* p, void** out, int* mem_kind, int64_t n_chunks, in
     return FXC_OK;
 }
 
+// whole-sample delays in force (fxc_set_sample_delays, fxc_set_delay_track_aligned): every pass is aligned before the plan's kernels
+bool aligning(const fxc_plan* p) { return p->shifted || (p->track && p->track_align); }
+
 // ---- conditioning launches (also what the stand-alone fxc_remove_dc / fxc_convert_u8 run) -------------------------------------
 // workgroups per stream of the subtract / narrow pass: enough to fill the chip when a call has few streams (one chunk
 // pair: the reference's own call), a handful when it has thousands
@@ -105,8 +108,9 @@ struct PassInput {
 
 // uint8 I,Q in: fused plans (2 antennas: nchan 4096 / ntaps 4, the tiled ring and wave-local kernels, the mixed-radix F + X
 // kernel) read the bytes in the F+X kernel itself; every other plan converts a pass into a complex64 staging buffer first
+// (never with whole-sample delays in force: the bytes are converted, then aligned)
 bool u8_fused_in(const fxc_plan* p) {
-    return p->n_ant == 2 && !p->autos && !p->prefilter && (p->path == FXC_PATH_FUSED || (p->path == FXC_PATH_TILED && (p->tiled_ring || p->small || p->x8192)) ||
+    return p->n_ant == 2 && !p->autos && !p->prefilter && !aligning(p) && (p->path == FXC_PATH_FUSED || (p->path == FXC_PATH_TILED && (p->tiled_ring || p->small || p->x8192)) ||
                                                            (p->path == FXC_PATH_GENERIC && p->mixed_xf && FXC_DEV_ENV_INT("FXC_MIXED_U8", 1)));
 }
 
@@ -192,22 +196,54 @@ int condition_iq(fxc_plan* p, const void* xb, int64_t nc, int fmt, bool remove_d
     return FXC_OK;
 }
 
+// ---- whole-sample delays: the pass's complex64 samples, conditioned or the caller's own, into the plan's d_align, never in place ----
+// Static shifts come from d_shift; under an aligned track the shifts of the pass's chunks -- p->track_t onwards at this moment --
+// are written first, for the alignment here and for the tables of the same chunks behind it (track_shifts_pass, h_run.h).
+void launch_align_c64(fxc_plan* p, const cf* x, cf* out, const int* shifts, int shift_stride, int64_t n_streams) {
+    const int slices = cond_slices(p, n_streams);
+    KernelTimer kt(p);
+    hipLaunchKernelGGL(align_c64_kernel, dim3(slices, (unsigned)n_streams), dim3(256), 0, p->stream, x, out, shifts, shift_stride, p->n_ant,
+                       p->num_samp, slices);
+    kt.stop();
+}
+
+int align_pass(fxc_plan* p, int64_t nc, PassInput* in) {
+    const int64_t n_streams = nc * p->n_ant;
+    int rc = grow(p, &p->d_align, &p->align_bytes, (size_t)n_streams * p->num_samp * sizeof(cf));
+    if (rc) return rc;
+    const bool tracked = p->track && p->track_align;
+    if (tracked) {
+        rc = track_shifts_pass(p, p->track_t, nc);
+        if (rc) return rc;
+    }
+    cf* xa = static_cast<cf*>(p->d_align);
+    launch_align_c64(p, in->x, xa, tracked ? static_cast<const int*>(p->d_tshift) : p->d_shift, tracked ? p->n_ant : 0, n_streams);
+    FXC_HIP(p, hipGetLastError());
+    *in = {xa};
+    return FXC_OK;
+}
+
 // ---- the device-side driver ------------------------------------------------------------------------------------------------
 // x on the device in call.fmt.  x_is_scratch: x is the library's own copy (the staging copy of a host buffer, a pipe slot), so
-// complex64 samples are de-meaned in place.  Plain complex64 goes to the plan's kernels whole; every other format in passes.
+// complex64 samples are de-meaned in place.  Plain complex64 goes to the plan's kernels whole; every other format in passes --
+// and so does plain complex64 with whole-sample delays in force: each pass is conditioned as its format asks, then aligned.
 int fx_call_dev(fxc_plan* p, const FxCall& c, const void* x, void* out, int64_t n_chunks, bool x_is_scratch) {
     const auto run = [&](const PassInput& in, void* o, int64_t nc) {
         return c.rows ? fx_rows_dev(p, in.x, o, nc, c.mode, c.bandwidth, in.dc_u8, in.dck) : fx_accumulate_dev(p, in.x, nc, in.dc_u8, in.dck);
     };
-    if (c.fmt == FXC_IQ_C64 && !c.remove_dc) return run({static_cast<const cf*>(x)}, out, n_chunks);
+    const bool al = aligning(p);
+    const bool plain = c.fmt == FXC_IQ_C64 && !c.remove_dc;
+    if (plain && !al) return run({static_cast<const cf*>(x)}, out, n_chunks);
     const bool u8 = c.fmt == FXC_IQ_U8;
     const bool fused_in = u8 && u8_fused_in(p);
     const bool in_place = x_is_scratch && c.fmt == FXC_IQ_C64;
     // chunks per pass: at most 65535 streams (the stream index rides in a grid dimension of the conditioning kernels), and a
-    // pass that is conditioned into the complex64 staging buffer stays within the workspace target
+    // pass that is conditioned into the complex64 staging buffer stays within the workspace target -- together with the
+    // alignment's staging buffer where whole-sample delays are in force
     int64_t per_pass = 65535 / p->n_ant;
     if (u8) per_pass = std::min<int64_t>(16384, per_pass);
-    if (!fused_in && !in_place) per_pass = std::min<int64_t>(per_pass, ws_target() / ((int64_t)p->n_ant * p->num_samp * (int64_t)sizeof(cf)));
+    const int stagings = (!plain && !fused_in && !in_place ? 1 : 0) + (al ? 1 : 0);
+    if (stagings) per_pass = std::min<int64_t>(per_pass, ws_target() / (stagings * (int64_t)p->n_ant * p->num_samp * (int64_t)sizeof(cf)));
     if (!u8) per_pass = std::min<int64_t>(per_pass, n_chunks);
     per_pass = std::max<int64_t>(1, per_pass);
     for (int64_t c0 = 0; c0 < n_chunks; c0 += per_pass) {
@@ -215,9 +251,17 @@ int fx_call_dev(fxc_plan* p, const FxCall& c, const void* x, void* out, int64_t 
         const char* xb = static_cast<const char*>(x) + input_bytes(p, c.fmt, c0);
         void* ob = c.rows ? static_cast<char*>(out) + (size_t)c0 * row_bytes(p, c.mode) : nullptr;
         PassInput in;
-        int rc = u8 ? condition_u8(p, reinterpret_cast<const unsigned char*>(xb), nc, c.remove_dc, fused_in, &in)
+        int rc = FXC_OK;
+        if (plain)
+            in.x = reinterpret_cast<const cf*>(xb);
+        else
+            rc = u8 ? condition_u8(p, reinterpret_cast<const unsigned char*>(xb), nc, c.remove_dc, fused_in, &in)
                     : condition_iq(p, xb, nc, c.fmt, c.remove_dc, in_place, &in);
         if (rc) return rc;
+        if (al) {
+            rc = align_pass(p, nc, &in);
+            if (rc) return rc;
+        }
         rc = run(in, ob, nc);
         if (rc) return rc;
     }

@@ -109,6 +109,22 @@ struct fxc_plan {
     // natural bin order, written once by track_gain_inverse_kernel; gain_n == 0: none, track_tables_kernel runs as before
     cd* d_gain_q = nullptr;
     int64_t gain_n = 0, gain_interval = 0, gain_first = 0;
+    // whole-sample delays: antenna a's samples are read s_a later, zeros where there are none (align_c64_kernel, k_align.h),
+    // pass by pass in fx_call_dev into d_align.  shifted: the static shifts of fxc_set_sample_delays, sample_shift on the host
+    // and d_shift [n_ant] on the device.  track_align: the per-chunk shifts of fxc_set_delay_track_aligned,
+    // s_a(t) = llrint(tau_a(t) track_bw), written for every pass into d_tshift [chunks][n_ant] (tshift_t0: the chunk of its
+    // first row) and read by the alignment and by the aligned table kernels alike; track_par_h: tau0, rate on the host
+    bool shifted = false;
+    std::vector<int64_t> sample_shift;
+    int* d_shift = nullptr;
+    bool track_align = false;
+    double track_bw = 0.0;
+    std::vector<double> track_par_h;
+    void* d_tshift = nullptr;
+    size_t tshift_bytes = 0;
+    int64_t tshift_t0 = 0;
+    void* d_align = nullptr;         // the aligned samples of one pass
+    size_t align_bytes = 0;
     f4* d_win4 = nullptr;          // [nchan] window quads (one unit tap behind the pre-filter): fused, tiled ring, wave-local, lean fx_spec.h
     cf* d_tw1 = nullptr;
     cf* d_tw2 = nullptr;

@@ -53,10 +53,37 @@ bool fused_autos(const fxc_plan* p) { return p->autos && p->path == FXC_PATH_FUS
 // Plans with a delay track (fxc_set_delay_track) go to the tracked instantiations: the pass's rows are [chunk][p->n_prod] on
 // every route (two antennas: 1 row, or cross + 2 autos), its chunks take the plan's counter onwards, and track_pass writes
 // their tables first.  The counter advances here, pass by pass; fx_rows_dev puts it back when a call fails half way.
+//
+// An aligned track (fxc_set_delay_track_aligned) first writes the whole-sample shifts of a run of chunks to d_tshift
+// (track_shifts_pass: fx_call_dev for every pass, fxc_delay_track_tables for its chunk); the alignment of the pass and the
+// aligned table kernels read them from there, so track_tables is only asked for chunks of the run written last.
+int track_shifts_pass(fxc_plan* p, int64_t t0, int64_t n_t) {
+    const int rg = grow(p, &p->d_tshift, &p->tshift_bytes, (size_t)(n_t * p->n_ant) * sizeof(int));
+    if (rg) return rg;
+    const TrackPar tp = {p->d_track_par, p->d_track_par + p->n_ant, p->track_df, p->track_freq};
+    hipLaunchKernelGGL(track_shifts_kernel, dim3(grid_for(n_t * p->n_ant, 256, p->cu_count)), dim3(256), 0, p->stream, tp, p->track_bw,
+                       static_cast<int*>(p->d_tshift), p->n_ant, t0, n_t);
+    FXC_HIP(p, hipGetLastError());
+    p->tshift_t0 = t0;
+    return FXC_OK;
+}
+
 int track_tables(fxc_plan* p, int64_t t0, int64_t n_t, cd* out, bool pair) {
     const TrackPar tp = {p->d_track_par, p->d_track_par + p->n_ant, p->track_df, p->track_freq};
     const dim3 grid(grid_for(n_t * (pair ? 1 : p->n_ant) * p->nchan, 256, p->cu_count));
-    if (p->gain_n > 0) {      // a gain track (fxc_set_track_gains): the same tables times 1 / g of the chunk's solution
+    if (p->track_align) {
+        const TrackAlign al = {static_cast<const int*>(p->d_tshift), p->tshift_t0};
+        const bool gain = p->gain_n > 0;
+        const GainTrack gt = {p->d_gain_q, p->gain_n, p->gain_interval > 0 ? p->gain_interval : 1, p->gain_first};
+        const auto launch = [&](auto pr, auto gn) {
+            hipLaunchKernelGGL((track_tables_aligned_kernel<decltype(pr)::value, decltype(gn)::value>), grid, dim3(256), 0, p->stream, tp, al,
+                               gt, out, p->n_ant, p->nchan, t0, n_t);
+        };
+        if (pair && gain) launch(std::true_type{}, std::true_type{});
+        else if (pair) launch(std::true_type{}, std::false_type{});
+        else if (gain) launch(std::false_type{}, std::true_type{});
+        else launch(std::false_type{}, std::false_type{});
+    } else if (p->gain_n > 0) {      // a gain track (fxc_set_track_gains): the same tables times 1 / g of the chunk's solution
         const GainTrack gt = {p->d_gain_q, p->gain_n, p->gain_interval > 0 ? p->gain_interval : 1, p->gain_first};
         if (pair)
             hipLaunchKernelGGL(track_gain_tables_kernel<true>, grid, dim3(256), 0, p->stream, tp, gt, out, p->n_ant, p->nchan, t0, n_t);

@@ -130,7 +130,68 @@ __global__ void track_gain_tables_kernel(TrackPar tp, GainTrack gt, cd* __restri
     }
 }
 
-// Tracked integration: acc[p][k] += (sum over the splits and leading parts of chunk c's raw row p) * conj(w_c[k]), chunk after
+// ------------------------------------------------------------------------------------------
+// aligned track (fxc_set_delay_track_aligned): chunk t's samples of antenna a are read s = s_a(t) whole samples later
+// (k_align.h), which has already undone the baseband slope kk s / nchan turns of the table; the table keeps the rest:
+//     u = f_k tau - rint(f_k tau),  m = (kk s) mod nchan (integers, non-negative),  v = u - m / nchan,
+//     r_a[k](t) = exp(2 pi i (v - rint(v)))
+// every operation rounded on its own, as in track_phasor.  s comes from the array track_shifts_kernel wrote for the pass,
+// shifts[(t - t0) n_ant + a]: the same integer the alignment of chunk t used.  Sibling kernels: the plain track's
+// instantiations above are untouched.  GAIN: times q[s(t)][a][k], as track_gain_tables_kernel.
+// ------------------------------------------------------------------------------------------
+struct TrackAlign {
+    const int* shifts;       // [n_t][n_ant]
+    int64_t t0;              // the chunk of shifts[0]
+};
+
+__device__ __forceinline__ cd track_phasor_aligned(const TrackPar& tp, const TrackAlign& al, int n_ant, int a, int k, int nchan, int64_t t) {
+#pragma clang fp contract(off)
+    const int kk = k < (nchan + 1) / 2 ? k : k - nchan;
+    const double f = (double)kk * tp.df + tp.frequency;
+    const double tau = tp.tau0[a] + (double)t * tp.rate[a];
+    const double turns = f * tau;
+    const double u = turns - rint(turns);
+    int64_t m = ((int64_t)kk * (int64_t)al.shifts[(t - al.t0) * n_ant + a]) % nchan;
+    if (m < 0) m += nchan;
+    const double v = u - (double)m / (double)nchan;
+    cd r;
+    sincospi(2.0 * (v - rint(v)), &r.y, &r.x);
+    return r;
+}
+
+template <bool PAIR, bool GAIN>
+__global__ void track_tables_aligned_kernel(TrackPar tp, TrackAlign al, GainTrack gt, cd* __restrict__ out, int n_ant, int nchan, int64_t t0,
+                                            int64_t n_t) {
+#pragma clang fp contract(off)
+    const int rows = PAIR ? 1 : n_ant;
+    const int64_t total = n_t * rows * nchan;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += stride) {
+        const int k = (int)(idx % nchan);
+        const int64_t ta = idx / nchan;
+        const int64_t t = t0 + ta / rows;
+        const cd* q = nullptr;
+        if constexpr (GAIN) q = gt.q + gain_solution(gt, t) * n_ant * nchan + k;
+        if constexpr (PAIR) {
+            cd ra = track_phasor_aligned(tp, al, n_ant, 0, k, nchan, t), rb = track_phasor_aligned(tp, al, n_ant, 1, k, nchan, t);
+            if constexpr (GAIN) {
+                ra = gain_apply(ra, q[0]);
+                rb = gain_apply(rb, q[nchan]);
+            }
+            cd w;
+            w.x = rb.x * ra.x + rb.y * ra.y;
+            w.y = rb.y * ra.x - rb.x * ra.y;
+            out[idx] = w;
+        } else {
+            const int a = (int)(ta % rows);
+            cd r = track_phasor_aligned(tp, al, n_ant, a, k, nchan, t);
+            if constexpr (GAIN) r = gain_apply(r, q[(int64_t)a * nchan]);
+            out[idx] = r;
+        }
+    }
+}
+
+// Tracked integration: acc[p][k] +=(sum over the splits and leading parts of chunk c's raw row p) * conj(w_c[k]), chunk after
 // chunk in the order of the stream, in float64 with explicit fused multiply-adds -- so the accumulator after chunks t0 .. t1 is
 // the same bits whatever calls and passes brought them.  The accumulator is in natural bin order and holds rotated sums
 // (auto rows: the plain sum of the real parts); the raw rows are the ones the rows kernels read (one row set per chunk).

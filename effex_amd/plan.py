@@ -69,10 +69,40 @@ def rot_tables(nbins, bandwidth, frequency, delays):
     return np.stack([rot_table(nbins, bandwidth, frequency, d) for d in np.asarray(delays, dtype=np.float64).reshape(-1)])
 
 
-def gain_tables(gains, n_ant, nchan, delays_s=None, bandwidth=None, frequency=None):
+def split_delays(delays_s, bandwidth):
+    """A delay's two halves: ``(shifts int64 [n], remainder_s float64 [n])`` with ``shifts = rint(tau * bandwidth)`` (ties to
+    even) whole samples for ``FxPlan.set_sample_delays`` and ``remainder = tau - shifts / bandwidth`` seconds, at most half a
+    sample, which a phase slope corrects without loss."""
+    tau = np.asarray(delays_s, dtype=np.float64).reshape(-1)
+    shifts = np.rint(tau * float(bandwidth)).astype(np.int64)
+    return shifts, tau - shifts / float(bandwidth)
+
+
+def aligned_rot_tables(nchan, bandwidth, frequency, delays_s, shifts):
+    """Per-antenna tables [n_ant, nchan] complex128 for streams that ``FxPlan.set_sample_delays(shifts)`` has already moved by
+    whole samples (fxcorr.h fxc_set_sample_delays): the full table of ``delays_s`` without the baseband slope ``kk s / nchan``
+    turns the shift has undone, the carrier term ``frequency * tau`` kept.  With kk the integer bin index of ``np.fft.fftfreq``
+    and f_k = kk df + frequency: u = f_k tau - rint(f_k tau), m = (kk s) mod nchan in integers, v = u - m / nchan,
+    r[k] = exp(2 pi i (v - rint(v)))."""
+    nchan = int(nchan)
+    tau = np.asarray(delays_s, dtype=np.float64).reshape(-1)
+    shifts = np.asarray(shifts, dtype=np.int64).reshape(-1)
+    if shifts.shape != tau.shape:
+        raise ValueError("delays_s and shifts must have the same number of entries")
+    freqs = np.fft.fftfreq(nchan, d=1.0 / bandwidth) + frequency
+    kk = np.arange(nchan, dtype=np.int64)
+    kk = np.where(kk < (nchan + 1) // 2, kk, kk - nchan)
+    turns = freqs[None, :] * tau[:, None]
+    u = turns - np.rint(turns)
+    m = np.mod(kk[None, :] * shifts[:, None], nchan)
+    v = u - m.astype(np.float64) / float(nchan)
+    return np.exp(2j * np.pi * (v - np.rint(v)))
+
+
+def gain_tables(gains, n_ant, nchan, delays_s=None, bandwidth=None, frequency=None, shifts=None):
     """Per-antenna tables [n_ant, nchan] complex128 for ``FxPlan.set_rot_ant`` that undo the gains ``gains`` [n_ant, nchan] of
     ``FxPlan.solve_gains`` (bins in the rows' fftshifted order): ``ifftshift(1 / g_a)``, 0 where g_a is 0, times the rot table
-    of ``delays_s[a]`` when delays are given."""
+    of ``delays_s[a]`` when delays are given (``shifts``: the ``aligned_rot_tables`` of streams moved by those whole samples)."""
     gains = np.asarray(gains, dtype=np.complex128)
     if gains.shape != (n_ant, nchan):
         raise ValueError("gains must have shape ({}, {})".format(n_ant, nchan))
@@ -85,7 +115,10 @@ def gain_tables(gains, n_ant, nchan, delays_s=None, bandwidth=None, frequency=No
         delays = np.asarray(delays_s, dtype=np.float64).reshape(-1)
         if delays.shape != (n_ant,):
             raise ValueError("delays_s must have {} entries".format(n_ant))
-        tables = tables * rot_tables(nchan, bandwidth, frequency, delays)
+        if shifts is None:
+            tables = tables * rot_tables(nchan, bandwidth, frequency, delays)
+        else:
+            tables = tables * aligned_rot_tables(nchan, bandwidth, frequency, delays, shifts)
     return tables
 
 
@@ -150,12 +183,14 @@ def gain_track_solution(chunk, n_solutions, interval, first_chunk):
     return min(max((int(chunk) - int(first_chunk)) // int(interval), 0), int(n_solutions) - 1)
 
 
-def gain_track_tables(gains, interval, first_chunk, chunk, delays, rates, bandwidth, frequency):
+def gain_track_tables(gains, interval, first_chunk, chunk, delays, rates, bandwidth, frequency, whole_samples=False):
     """The numpy form of one chunk's tables under a delay track with a gain track (fxcorr.h fxc_set_track_gains): [n_ant, nchan]
     complex128, ``rot_tables(nchan, bandwidth, frequency, delays + chunk * rates)`` times ``ifftshift(1 / g)`` of the chunk's
     solution.  ``gains`` is [n_ant, nchan] or [n_solutions, n_ant, nchan] as ``FxPlan.solve_gains`` returns them (bins in the
     rows' fftshifted order).  The inverse is (x / d, -y / d) with d = x x + y y, 0 where g is 0, and the product
-    (c qx - s qy, c qy + s qx), each operation rounded on its own, as the device forms them."""
+    (c qx - s qy, c qy + s qx), each operation rounded on its own, as the device forms them.  ``whole_samples``: the tables of
+    an aligned track (``FxPlan.set_delay_track(.., whole_samples=True)``), ``aligned_rot_tables`` with the chunk's shifts
+    ``rint(tau * bandwidth)``."""
     gains = np.asarray(gains, dtype=np.complex128)
     if gains.ndim == 2:
         gains = gains[None]
@@ -174,7 +209,11 @@ def gain_track_tables(gains, interval, first_chunk, chunk, delays, rates, bandwi
     live = d != 0
     safe = np.where(live, d, 1.0)
     qx, qy = np.where(live, x / safe, 0.0), np.where(live, -y / safe, 0.0)
-    rot = rot_tables(nchan, bandwidth, frequency, delays + float(int(chunk)) * rates)
+    tau = delays + float(int(chunk)) * rates
+    if whole_samples:
+        rot = aligned_rot_tables(nchan, bandwidth, frequency, tau, np.rint(tau * float(bandwidth)).astype(np.int64))
+    else:
+        rot = rot_tables(nchan, bandwidth, frequency, tau)
     c, s = rot.real, rot.imag
     return (c * qx - s * qy) + 1j * (c * qy + s * qx)
 
@@ -360,9 +399,34 @@ class FxPlan(object):
         self._check(self._lib.fxc_set_rot_ant(self._h, tables.ctypes.data))
         self.tracked = False
 
-    def set_delays(self, delays_s, bandwidth, frequency):
-        """Phase every baseline for the per-antenna delays ``delays_s`` [n_ant] (seconds, e.g. from ``estimate_delays``)."""
-        self.set_rot_ant(rot_tables(self.nchan, bandwidth, frequency, delays_s))
+    def set_delays(self, delays_s, bandwidth, frequency, whole_samples=False):
+        """Phase every baseline for the per-antenna delays ``delays_s`` [n_ant] (seconds, e.g. from ``estimate_delays``).
+        ``whole_samples``: split every delay (``split_delays``): the whole samples move the antenna's stream
+        (``set_sample_delays``), the tables (``aligned_rot_tables``) keep the rest -- a phase slope alone loses about
+        ``d / nchan`` of the amplitude for a delay of d samples."""
+        if not whole_samples:
+            self.set_rot_ant(rot_tables(self.nchan, bandwidth, frequency, delays_s))
+            return
+        shifts, _ = split_delays(delays_s, bandwidth)
+        self.set_rot_ant(aligned_rot_tables(self.nchan, bandwidth, frequency, delays_s, shifts))
+        self.set_sample_delays(shifts)
+
+    def set_sample_delays(self, shifts):
+        """Whole-sample delays (fxcorr.h fxc_set_sample_delays): antenna a's samples are read ``shifts[a]`` later, zeros where
+        a chunk has none.  ``None`` or all zeros removes them.  Independent of ``set_rot*``; an aligned track sets its own."""
+        if shifts is None:
+            self._check(self._lib.fxc_set_sample_delays(self._h, None))
+            return
+        shifts = np.ascontiguousarray(np.asarray(shifts).reshape(-1), dtype=np.int64)
+        if shifts.shape != (self.n_ant,):
+            raise ValueError("shifts must have {} entries".format(self.n_ant))
+        self._check(self._lib.fxc_set_sample_delays(self._h, shifts.ctypes.data))
+
+    def sample_delays(self, chunk=0):
+        """The whole-sample shifts [n_ant] int64 chunk ``chunk`` gets: the static ones, an aligned track's, or zeros."""
+        out = np.zeros(self.n_ant, dtype=np.int64)
+        self._check(self._lib.fxc_sample_delays(self._h, int(chunk), out.ctypes.data))
+        return out
 
     def _per_antenna(self, v, name):
         v = np.asarray(v, dtype=np.float64)
@@ -373,16 +437,17 @@ class FxPlan(object):
             raise ValueError("{} must have {} entries".format(name, self.n_ant))
         return v
 
-    def set_delay_track(self, delays_s, rates_s_per_chunk, bandwidth, frequency, first_chunk=0):
+    def set_delay_track(self, delays_s, rates_s_per_chunk, bandwidth, frequency, first_chunk=0, whole_samples=False):
         """Delays that move: chunk t is phased for ``delays_s[a] + t * rates_s_per_chunk[a]`` (fxcorr.h fxc_set_delay_track).
         Every ``fx_rows`` / ``fx_accumulate`` call and every pipe batch takes the next chunk indices, from ``first_chunk`` on.
         A scalar delay / rate on a two-antenna plan means antenna 1 against antenna 0.  Ends at the next ``set_rot*``.
         A new track drops the gains of ``set_track_gains``: they were solved on rows made under the earlier one, so solve or
-        send them again."""
+        send them again.  ``whole_samples``: the aligned track (fxcorr.h fxc_set_delay_track_aligned): chunk t's streams are also
+        moved by ``rint(tau_a(t) * bandwidth)`` whole samples and its tables keep the rest; ``track_tables`` returns those."""
         tau0 = self._per_antenna(delays_s, "delays_s")
         rate = self._per_antenna(rates_s_per_chunk, "rates_s_per_chunk")
-        self._check(self._lib.fxc_set_delay_track(self._h, tau0.ctypes.data, rate.ctypes.data, float(bandwidth), float(frequency),
-                                                  int(first_chunk)))
+        fn = self._lib.fxc_set_delay_track_aligned if whole_samples else self._lib.fxc_set_delay_track
+        self._check(fn(self._h, tau0.ctypes.data, rate.ctypes.data, float(bandwidth), float(frequency), int(first_chunk)))
         self.tracked = True
 
     @property
@@ -923,11 +988,19 @@ class FxPlan(object):
         self._check(self._lib.fxc_average_rows(self._h, ptr, w_ptr, int(shape[0]), kind, time_bin, freq_bin, v_ptr, s_ptr))
         return vis, wsum
 
-    def set_gains(self, gains, delays_s=None, bandwidth=None, frequency=None):
+    def set_gains(self, gains, delays_s=None, bandwidth=None, frequency=None, whole_samples=False):
         """Correct the rows for the per-antenna gains ``gains`` [n_ant, nchan] (one solution of ``solve_gains``, bins in the
         rows' order): antenna a's table is ``ifftshift(1 / g_a)``, 0 where g_a is 0 so that a dead channel stays zero, times
-        ``rot_tables(nchan, bandwidth, frequency, delays_s)[a]`` when delays are given, handed to ``set_rot_ant``."""
-        self.set_rot_ant(gain_tables(gains, self.n_ant, self.nchan, delays_s, bandwidth, frequency))
+        ``rot_tables(nchan, bandwidth, frequency, delays_s)[a]`` when delays are given, handed to ``set_rot_ant``.
+        ``whole_samples`` (needs delays): the delays are split as in ``set_delays(.., whole_samples=True)``."""
+        if not whole_samples:
+            self.set_rot_ant(gain_tables(gains, self.n_ant, self.nchan, delays_s, bandwidth, frequency))
+            return
+        if delays_s is None or bandwidth is None or frequency is None:
+            raise ValueError("whole_samples needs delays_s, bandwidth and frequency")
+        shifts, _ = split_delays(delays_s, bandwidth)
+        self.set_rot_ant(gain_tables(gains, self.n_ant, self.nchan, delays_s, bandwidth, frequency, shifts=shifts))
+        self.set_sample_delays(shifts)
 
     # -- measurement ------------------------------------------------------------------------
     def timer_start(self):

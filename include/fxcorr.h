@@ -232,6 +232,50 @@ int fxc_delay_track_tables(fxc_plan* plan, int64_t chunk, double* out_re_im);
 int fxc_set_track_gains(fxc_plan* plan, const double* gains_re_im, int64_t n_solutions, int64_t interval, int64_t first_chunk);
 int fxc_track_gains_info(const fxc_plan* plan, int64_t* n_solutions, int64_t* interval, int64_t* first_chunk);
 
+/* Whole-sample delays: every delay above is a phase slope applied after the FFT -- the fractional-sample half of a correlator's
+ * delay correction.  A slope cannot put back samples that sit in different frames: for a delay of d samples two antennas' frames
+ * overlap only partly and the correlated amplitude falls roughly as 1 - d/nchan whatever the tables hold (half the signal at 64
+ * channels and d = 42).  These calls are the whole-sample half: they move the sample stream.
+ * A shift s_a (either sign) means that the plan's kernels read, for chunk c, antenna a and sample n, the delivered sample
+ *   x[c][a][n + s_a]   when 0 <= n + s_a < num_samp,   and exactly 0 otherwise.
+ * Chunks stay independent: nothing is fetched from a neighbouring chunk, so rows keep not depending on how calls batch the
+ * chunks.  The sign is that of the delays above: a stream that is late by d samples (fxc_estimate_delays(..) * rate == +d) takes
+ * s = +d, so s_a = rint(tau_a * bandwidth).  DC removal subtracts the mean of the chunk's num_samp delivered samples, as without
+ * shifts, before the shift; the fill is exact zeros.  The zero fill costs baseline (a,b) the amplitude factor of about
+ *   1 - |s_a - s_b| / num_samp.
+ * With the whole samples applied to the stream the tables must keep only the rest.  Natural bin order, float64, kk the integer
+ * bin index of fftfreq, f_k = kk*df + frequency:
+ *   u = f_k*tau - rint(f_k*tau),   m = (kk*s) mod nchan (non-negative, exact in integers),   v = u - m/nchan,
+ *   r[k] = exp(2*pi*i*(v - rint(v))):
+ * the full table of tau without the baseband slope kk*s/nchan turns the shift has undone; the carrier term frequency*tau stays.
+ * fxc_set_sample_delays: static shifts, shift_samples = [n_ant]; NULL or all zeros removes them, and the plan then launches
+ * exactly the kernels it launches without this call.  The tables stay the caller's (fxc_set_rot / fxc_set_rot_ant with the
+ * table above); the shifts are independent of those calls, survive them and survive a plain fxc_set_delay_track.  It synchronises
+ * the plan's stream and, like fxc_set_rot_ant, may be called while a pipe uses the plan (it applies to the batches submitted
+ * afterwards).  FXC_ERR_ARG: NULL plan, |s| >= num_samp.  FXC_ERR_STATE: a non-zero shift while an aligned track is in force.
+ * FXC_ERR_UNSUPPORTED: num_samp > 2^27.
+ * fxc_set_delay_track_aligned: fxc_set_delay_track plus, for every chunk t, the shifts
+ *   s_a(t) = llrint(tau_a(t) * bandwidth)   (tau_a(t) rounded as in the tables; ties to even, as numpy's rint)
+ * and the tables above with s = s_a(t), every operation rounded on its own, ending in sincospi.  The alignment of chunk t and the
+ * table of chunk t read the same integer from one device array, written once per pass.  |s_a(t)| >= num_samp is no error: that
+ * stream is all zeros.  It clears static shifts; arguments, errors, gain tracks (fxc_set_track_gains), fxc_delay_track_seek, the
+ * chunk counter and fxc_delay_track_tables (which returns the aligned tables) behave as under a plain track, and whatever ends a
+ * track ends it; a plain fxc_set_delay_track ends the aligned behaviour and keeps a track.
+ * fxc_sample_delays: the shifts chunk `chunk` gets, shift_samples_out = [n_ant]: the static shifts whatever the chunk, the
+ * track's under an aligned track, all zeros when none are set.  FXC_ERR_ARG: a NULL argument, chunk < 0.
+ * How it runs, and what it costs: every call that takes antennas' samples (fxc_fx_rows*, fxc_fx_accumulate*, pipes) goes in
+ * passes; a pass is conditioned as its format asks (bytes converted, complex128 narrowed, DC removed: the kernels of plans
+ * without shifts, unchanged) and then copied once, shifted, into a buffer of the plan (never in place; the fused byte ingest is
+ * off for such plans).  A complex64 sample that was read once (8 bytes) is additionally read and written once: about 3 x the
+ * sample traffic at the headline shape (derived, not measured).  Reading at an offset inside the F kernels is the follow-up that
+ * removes that cost.  fxc_beamform on a plan with shifts or an aligned track returns FXC_ERR_UNSUPPORTED (its passes are not
+ * aligned; it forms no unaligned beams silently).  fxc_channelize, fxc_estimate_delay(s), fxc_remove_dc and fxc_convert_u8 take
+ * streams, not antennas, and are untouched. */
+int fxc_set_sample_delays(fxc_plan* plan, const int64_t* shift_samples);
+int fxc_set_delay_track_aligned(fxc_plan* plan, const double* tau0_s, const double* rate_s_per_chunk, double bandwidth,
+                                double frequency, int64_t first_chunk);
+int fxc_sample_delays(const fxc_plan* plan, int64_t chunk, int64_t* shift_samples_out);
+
 /* F-stage only — replaces cusignal.filtering.channelize_poly + .T at effex.py:553 (and the
  * complex128 copy at :551).  x = [n_streams][num_samp] complex64, out = [n_streams][n_pts][nchan]
  * complex64, natural (un-shifted) bin order; trailing num_samp mod nchan samples ignored; zero
