@@ -4,9 +4,9 @@
 //   fx_math.h, fx_fused4096.h, fx_tiled.h, fx_small.h, fx_mixed.h   index maps, butterflies and kernel phases (also compiled by
 //                                           g++ for the host emulation under tests/emul)
 //   k_generic.h k_finish.h k_xmfma.h k_fused4096.h k_tiled.h k_small.h k_prepass.h k_stream.h k_conditioning.h k_track.h k_align.h k_synth.h
-//   k_delay.h k_fringe.h k_gains.h k_flag.h k_average.h k_beam.h
+//   k_delay.h k_fringe.h k_gains.h k_flag.h k_average.h k_beam.h k_kurtosis.h
 //                                           the __global__ kernels, one file per path / step and per rows tool (delays, fringe fit,
-//                                           gain solve, detector, averager, beamformer)
+//                                           gain solve, detector, averager, beamformer, spectral kurtosis)
 //   h_plan.h h_rtc.h h_launch.h h_build.h h_run.h h_ingest.h h_tools.h h_rccl.h
 //                                           fxc_plan, the kernels compiled per channel count, the per-path launchers and
 //                                           workspace passes, plan construction (route, tables), the device-resident
@@ -147,6 +147,7 @@ int64_t ws_target() {
 #include "k_flag.h"
 #include "k_average.h"
 #include "k_beam.h"
+#include "k_kurtosis.h"
 #include "k_synth.h"
 #include "h_plan.h"
 #include "h_rtc.h"
@@ -1221,6 +1222,52 @@ int fxc_beamform(fxc_plan* p, const void* x, const void* weights, int n_beam, vo
     }
     if (rc) p->track_t = t0;
     return rc;
+}
+
+int fxc_kurtosis(fxc_plan* p, const void* x, void* sk_out, void* power_out, int64_t n_chunks, int mem_kind, int64_t tint) {
+    bool done;
+    if (const int rc = check_kurtosis(p, n_chunks, mem_kind, tint, &done)) return rc;
+    if (done) return FXC_OK;
+    if (!x || !sk_out) return fail(p, FXC_ERR_ARG, "NULL buffer");
+    FXC_DEVICE(p, p->device);
+    if (mem_kind == FXC_MEM_DEVICE)
+        return kurtosis_dev(p, static_cast<const cf*>(x), static_cast<float*>(sk_out), static_cast<float*>(power_out), n_chunks, tint);
+    // host memory: sk and power leave through one staging block, sk first
+    const int64_t n_tbin = tint ? (p->n_pts + tint - 1) / tint : 1;
+    const size_t elems = (size_t)n_chunks * p->n_ant * n_tbin * p->nchan;
+    std::vector<float> both;
+    void* out = sk_out;
+    if (power_out) {
+        both.resize(2 * elems);
+        out = both.data();
+    }
+    const int rc = with_host_staging(p, x, (size_t)n_chunks * p->n_ant * p->num_samp * sizeof(cf), out, (power_out ? 2 : 1) * elems * sizeof(float),
+                                     [&](const cf* dx, void* dout) {
+                                         float* d = static_cast<float*>(dout);
+                                         return kurtosis_dev(p, dx, d, power_out ? d + elems : nullptr, n_chunks, tint);
+                                     });
+    if (rc) return rc;
+    if (power_out) {
+        std::memcpy(sk_out, both.data(), elems * sizeof(float));
+        std::memcpy(power_out, both.data() + elems, elems * sizeof(float));
+    }
+    return FXC_OK;
+}
+
+int fxc_kurtosis_weights(fxc_plan* p, const void* sk, int64_t n_chunks, int64_t tint, double lo, double hi, void* weights_out, int mem_kind) {
+    bool done;
+    if (const int rc = check_kurtosis(p, n_chunks, mem_kind, tint, &done)) return rc;
+    if (!std::isfinite(lo) || !std::isfinite(hi) || lo > hi) return fail(p, FXC_ERR_ARG, "the thresholds must be finite with lo <= hi");
+    if (done) return FXC_OK;
+    if (!sk || !weights_out) return fail(p, FXC_ERR_ARG, "NULL buffer");
+    FXC_DEVICE(p, p->device);
+    if (mem_kind == FXC_MEM_DEVICE)
+        return kurtosis_weights_dev(p, static_cast<const float*>(sk), static_cast<float*>(weights_out), n_chunks, tint, lo, hi);
+    const int64_t n_tbin = tint ? (p->n_pts + tint - 1) / tint : 1;
+    return with_host_staging(p, sk, (size_t)n_chunks * p->n_ant * n_tbin * p->nchan * sizeof(float), weights_out,
+                             (size_t)n_chunks * p->n_base * p->nchan * sizeof(float), [&](const cf* dsk, void* dout) {
+                                 return kurtosis_weights_dev(p, reinterpret_cast<const float*>(dsk), static_cast<float*>(dout), n_chunks, tint, lo, hi);
+                             });
 }
 
 int fxc_solve_gains_weighted(fxc_plan* p, const void* rows, const void* weights, int64_t n_chunks, int mem_kind, const void* model,

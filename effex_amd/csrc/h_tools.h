@@ -1,5 +1,6 @@
 // Part of libfxcorr's single translation unit: included by fxcorr.hip (not a stand-alone header).
-// The rows tools' drivers -- delays, fringe fit, gain solve, detector, averager, beamformer -- and the host helpers they share.
+// The rows tools' drivers -- delays, fringe fit, gain solve, detector, averager, beamformer, spectral kurtosis -- and the host helpers
+// they share.
 // The entry points that check a call's arguments and hand it to a driver are in fxcorr.hip.
 #pragma once
 
@@ -831,6 +832,89 @@ int beamform_dev(fxc_plan* p, const cf* x, const cf* weights, bool weights_on_ho
         kt.stop();
         FXC_HIP(p, hipGetLastError());
     }
+    return FXC_OK;
+}
+
+// the arguments fxc_kurtosis and fxc_kurtosis_weights share; *done: the call has nothing to do
+int check_kurtosis(fxc_plan* p, int64_t n_chunks, int mem_kind, int64_t tint, bool* done) {
+    *done = false;
+    if (!p) return fail(p, FXC_ERR_ARG, "NULL plan");
+    if (n_chunks < 0) return fail(p, FXC_ERR_ARG, "n_chunks < 0");
+    if (const int rc = bad_mem_kind(p, mem_kind)) return rc;
+    if (tint < 0 || tint == 1 || tint > p->n_pts)
+        return fail(p, FXC_ERR_ARG, "tint=%lld is not 0 or within 2 .. %lld frames", (long long)tint, (long long)p->n_pts);
+    if (p->n_pts < 2) return fail(p, FXC_ERR_UNSUPPORTED, "n_pts=%lld: the estimator needs 2 or more frames a chunk", (long long)p->n_pts);
+    *done = n_chunks == 0;
+    return FXC_OK;
+}
+
+// A launch of kurtosis_kernel (k_kurtosis.h) over the spectra of n_streams consecutive (chunk, antenna) streams: what the call
+// site means; the geometry is decided here alone
+struct KurtosisLaunch {
+    const cf* spec;                  // [stream][frame][nchan], natural bin order
+    float* sk;                       // [stream][n_tbin][nchan]
+    float* power;                    // the same shape, or nullptr
+    int64_t n_streams;               // at most kGridMax
+    int64_t tint, n_tbin;            // frames a time bin (1 .. n_pts) and bins a chunk
+};
+
+int launch_kurtosis(fxc_plan* p, const KurtosisLaunch& k) {
+    // bins of one segment: a wave takes as many bins as make a segment's worth of frames, a workgroup no more waves than there are
+    // bins for; longer bins: a workgroup a bin.  More bins than grid.y holds: the kernel walks on.  No bit depends on any of it.
+    if ((int64_t)kKurtSegment * p->nchan >= (1ll << 31))      // (kurt_segment's 32-bit row offsets)
+        return fail(p, FXC_ERR_UNSUPPORTED, "nchan=%d: a segment of %d spectra is addressed in 32 bits", p->nchan, kKurtSegment);
+    int64_t bpw = 0, waves = kKurtWaves, groups = k.n_tbin;
+    if (k.tint <= kKurtSegment) {
+        bpw = std::max<int64_t>(1, kKurtSegment / k.tint);
+        waves = std::min<int64_t>(kKurtWaves, (k.n_tbin + bpw - 1) / bpw);
+        groups = (k.n_tbin + bpw * waves - 1) / (bpw * waves);
+    }
+    const dim3 grid((unsigned)((p->nchan + kKurtLanes - 1) / kKurtLanes), (unsigned)std::min(groups, kGridMax), (unsigned)k.n_streams);
+    hipLaunchKernelGGL(kurtosis_kernel, grid, dim3((unsigned)(kKurtLanes * waves)), 0, p->stream, k.spec, k.sk, k.power, p->n_pts, p->nchan,
+                       k.tint, k.n_tbin, bpw);
+    FXC_HIP(p, hipGetLastError());
+    return FXC_OK;
+}
+
+// Spectral kurtosis (fxcorr.h fxc_kurtosis; kernels in k_kurtosis.h), everything on the device, the route of beamform_dev: the
+// workspace holds a pass's spectra [chunk][antenna][frame][nchan]; a pass takes as many chunks as the workspace target (FXC_WS_MB)
+// allows, one at least.  An output element belongs to one workgroup of one launch and no sum crosses a chunk, so no bit depends on
+// the passes.  The samples are taken as delivered: no shifts, no tables, and the track's counter stays.
+int kurtosis_dev(fxc_plan* p, const cf* x, float* sk, float* power, int64_t n_chunks, int64_t tint) {
+    const int nchan = p->nchan, n_ant = p->n_ant;
+    if (tint == 0) tint = p->n_pts;
+    const int64_t n_tbin = (p->n_pts + tint - 1) / tint;
+    const int64_t spec_per_chunk = (int64_t)n_ant * p->n_pts * nchan * (int64_t)sizeof(cf);
+    const int64_t cb = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_chunks, kGridMax / n_ant), ws_target() / spec_per_chunk));
+    WsCarver ws;
+    const int64_t o_spec = ws.take(up256(cb * spec_per_chunk));
+    int rc = ensure_ws(p, ws.total());      // (flushes a pending fold: it lives in the workspace)
+    if (rc) return rc;
+    cf* spec = ws_at<cf>(p, o_spec);
+    const int64_t out_per_chunk = (int64_t)n_ant * n_tbin * nchan;
+    for (int64_t c0 = 0; c0 < n_chunks; c0 += cb) {
+        const int64_t nc = std::min(cb, n_chunks - c0);
+        rc = run_channelize(p, chunk_at(p, x, c0), spec, nc * n_ant);
+        if (rc) return rc;
+        KernelTimer kt(p);
+        rc = launch_kurtosis(p, {spec, sk + c0 * out_per_chunk, power ? power + c0 * out_per_chunk : nullptr, nc * n_ant, tint, n_tbin});
+        kt.stop();
+        if (rc) return rc;
+    }
+    return FXC_OK;
+}
+
+// The row weights from sk (fxc_kurtosis_weights), both on the device
+int kurtosis_weights_dev(fxc_plan* p, const float* sk, float* weights, int64_t n_chunks, int64_t tint, double lo, double hi) {
+    if (tint == 0) tint = p->n_pts;
+    const int64_t n_tbin = (p->n_pts + tint - 1) / tint;
+    // a partial last bin has another count than the thresholds were made for: it is counted only as the chunk's only bin
+    const int64_t n_count = p->n_pts % tint != 0 && n_tbin > 1 ? n_tbin - 1 : n_tbin;
+    const int64_t total = n_chunks * p->n_base * p->nchan;
+    if (total == 0) return FXC_OK;
+    hipLaunchKernelGGL(kurtosis_weights_kernel, dim3(grid_for(total, 256, p->cu_count)), dim3(256), 0, p->stream, sk, weights, p->n_ant,
+                       p->n_base, p->nchan, n_tbin, n_count, n_chunks, lo, hi);
+    FXC_HIP(p, hipGetLastError());
     return FXC_OK;
 }
 

@@ -175,6 +175,20 @@ def averaged_freqs(nchan, bandwidth, frequency, freq_bin=1):
     return np.array([freqs[k:k + freq_bin].mean() for k in range(0, nchan, freq_bin)])
 
 
+def sk_thresholds(M, sigma=3.0):
+    """(lo, hi) = 1 -/+ sigma sqrt(mu2) for ``FxPlan.kurtosis_weights``, with mu2 = 4 M^2 / ((M - 1)(M + 2)(M + 3)) the variance
+    of the spectral kurtosis estimator over ``M`` spectra of Gaussian noise (Nita & Gary 2010).  A symmetric approximation of a
+    skewed distribution: the false-alarm share on clean noise is a measured figure (tests/golden/kurtosis_bounds.json), not the
+    Gaussian tail of ``sigma``."""
+    M = int(M)
+    if M < 2:
+        raise ValueError("M={}: the estimator needs 2 or more spectra".format(M))
+    if not sigma > 0:
+        raise ValueError("sigma must be > 0")
+    half = float(sigma) * float(np.sqrt(4.0 * M * M / ((M - 1.0) * (M + 2.0) * (M + 3.0))))
+    return 1.0 - half, 1.0 + half
+
+
 def gain_track_solution(chunk, n_solutions, interval, first_chunk):
     """The solution chunk ``chunk`` takes under a gain track (fxcorr.h fxc_set_track_gains):
     ``clamp(floor((chunk - first_chunk) / interval), 0, n_solutions - 1)``; interval 0 (one solution) is solution 0."""
@@ -554,6 +568,92 @@ class FxPlan(object):
         self._beam_keep = (keep, w_keep)     # until the next call: the queued kernels read them
         self._check(self._lib.fxc_beamform(self._h, ptr, w_ptr, n_beam, o_ptr, n, kind, m, tint))
         return out
+
+    def _float_out(self, out, shape, device, like, name="out"):
+        """a float32 result of ``shape`` in the memory of the samples: ``out`` checked, or a new array / tensor -> (array, ptr)"""
+        if out is not None:
+            if _is_torch(out) != device:
+                raise ValueError("{} must be of the same kind (host array / CUDA tensor) as x".format(name))
+            if device:
+                import torch
+                if out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous() or not out.is_cuda or \
+                        out.device.index != self.device:
+                    raise ValueError("{} must be a contiguous float32 CUDA tensor of shape {}".format(name, shape))
+            elif out.dtype != np.float32 or out.shape != shape or not out.flags.c_contiguous or not out.flags.writeable:
+                raise ValueError("{} must be a writable C-contiguous float32 array of shape {}".format(name, shape))
+        elif device:
+            import torch
+            out = torch.empty(shape, dtype=torch.float32, device=like.device)
+        else:
+            out = np.empty(shape, dtype=np.float32)
+        return out, (out.data_ptr() if device else out.ctypes.data)
+
+    def kurtosis(self, x, tint=0, return_power=False, out=None):
+        """Spectral kurtosis of every antenna's spectra (fxcorr.h fxc_kurtosis): ``x`` = [n_chunks, n_ant, num_samp] complex64
+        (numpy, or a CUDA tensor on the plan's device) -> sk float32 [n_chunks, n_ant, n_tbin, nchan] over time bins of ``tint``
+        frames (0: the whole chunk; 1 is refused; the last may be partial), bins in the rows' fftshifted order: 1 for Gaussian
+        noise whatever its power, 0 for a steady carrier, about 1 / d - 1 at duty cycle d.  With ``return_power`` -> (sk, power),
+        power = the mean of |f|^2 over the same bins.  The samples are taken as delivered: no shifts, tables, track or gains, and
+        the track's counter stays.  numpy in, numpy out; CUDA tensor in, CUDA tensor out.  ``out``: an array / tensor of the
+        result's shape to receive sk -- with ``return_power`` a pair (sk, power).  The loop with the detectors::
+
+            w = plan.kurtosis_weights(plan.kurtosis(x))
+            rows = plan.fx_rows(x)
+            w = plan.flag_rows(rows, prior=w)
+            vis, wsum = plan.average_rows(rows, weights=w)
+        """
+        ptr, kind, n, keep = self._in(x, (self.n_ant, self.num_samp))
+        device = kind == _lib.FXC_MEM_DEVICE
+        tint = int(tint)
+        n_tbin = -(-self.n_pts // tint) if 0 < tint <= self.n_pts else 1      # (a tint out of range: the call answers)
+        shape = (n, self.n_ant, n_tbin, self.nchan)
+        if return_power:
+            if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
+                raise ValueError("with return_power, out must be a pair (sk, power)")
+            o_sk, o_pw = out if out is not None else (None, None)
+        else:
+            if isinstance(out, (tuple, list)):
+                raise ValueError("out is a pair only with return_power")
+            o_sk, o_pw = out, None
+        sk, s_ptr = self._float_out(o_sk, shape, device, keep)
+        power, p_ptr = self._float_out(o_pw, shape, device, keep, "out's power") if return_power else (None, None)
+        if device and not self._follow:      # a stream of the plan's own: torch's may still be using the blocks it handed out
+            import torch
+            torch.cuda.current_stream(keep.device).synchronize()
+        self._sk_keep = keep                 # until the next call: the queued kernels read it
+        self._check(self._lib.fxc_kurtosis(self._h, ptr, s_ptr, p_ptr, n, kind, tint))
+        return (sk, power) if return_power else sk
+
+    def kurtosis_weights(self, sk, lo=None, hi=None, tint=0, sigma=3.0):
+        """The row weights from ``kurtosis``'s sk (fxcorr.h fxc_kurtosis_weights): ``sk`` = float32 [n_chunks, n_ant, n_tbin, nchan]
+        as ``kurtosis(x, tint=tint)`` returned it -> float32 [n_chunks, n_baselines, nchan] in the memory of sk, the array
+        ``flag_rows(prior=)``, ``solve_gains(weights=)``, ``fringe_fit(weights=)`` and ``average_rows(weights=)`` take: 1 where
+        ``lo <= sk <= hi`` in every counted bin of both antennas of the baseline, else 0 (a NaN gives 0).  A partial last bin is
+        not counted unless it is the chunk's only bin.  Thresholds that are not given come from ``sk_thresholds(M, sigma)``
+        with M the frames of a full bin."""
+        self._sync_stream()
+        tint = int(tint)
+        device = _is_torch(sk)
+        if device:
+            import torch
+            if sk.dtype != torch.float32 or not sk.is_cuda or sk.device.index != self.device:
+                raise ValueError("device sk must be a float32 CUDA tensor on device {}".format(self.device))
+            keep = sk.contiguous()
+            ptr, kind = keep.data_ptr(), _lib.FXC_MEM_DEVICE
+        else:
+            keep = np.ascontiguousarray(sk, dtype=np.float32)
+            ptr, kind = keep.ctypes.data, _lib.FXC_MEM_HOST
+        n_tbin = -(-self.n_pts // tint) if 0 < tint <= self.n_pts else 1
+        shape = tuple(keep.shape)
+        if len(shape) != 4 or shape[1:] != (self.n_ant, n_tbin, self.nchan):
+            raise ValueError("sk must have shape (n_chunks, {}, {}, {}), got {}".format(self.n_ant, n_tbin, self.nchan, shape))
+        if lo is None or hi is None:
+            t_lo, t_hi = sk_thresholds(tint if 0 < tint <= self.n_pts else self.n_pts, sigma)
+            lo, hi = (t_lo if lo is None else lo), (t_hi if hi is None else hi)
+        weights, w_ptr = self._out_like_rows((shape[0], self.n_baselines, self.nchan), np.float32, keep, device)
+        self._sk_keep = keep
+        self._check(self._lib.fxc_kurtosis_weights(self._h, ptr, int(shape[0]), tint, float(lo), float(hi), w_ptr, kind))
+        return weights
 
     # -- F + X ------------------------------------------------------------------------------
     def fx_accumulate(self, x, remove_dc=False, c128=False):

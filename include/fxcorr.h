@@ -700,6 +700,43 @@ enum fxc_beam_mode { FXC_BEAM_POWER = 0, FXC_BEAM_VOLTAGE = 1 };
 int fxc_beamform(fxc_plan* plan, const void* x, const void* weights, int n_beam, void* out, int64_t n_chunks, int mem_kind, int mode,
                  int64_t tint);
 
+/* Spectral kurtosis per antenna, from the spectra (Nita & Gary 2010): the interference detector that runs before
+ * any correlation -- on unstopped fringes, on one receiver's own interference, and inside a chunk, where fxc_flag_rows sees
+ * nothing.  f_a[c,i,k] = antenna a's spectrum of frame i of chunk c as fxc_channelize writes it.  Time bins hold `tint` frames
+ * (0: the chunk); the last bin of a chunk may be partial and uses its own count M_j.  Over the M_j frames of bin j, with
+ * p_i = |f_a[c,i,k]|^2, S1 = sum p_i, S2 = sum p_i^2:
+ *     power[c][a][j][k'] = S1 / M_j
+ *     sk[c][a][j][k']    = (M_j + 1) / (M_j - 1) * (M_j S2 / S1^2 - 1)
+ * both float32 [n_chunks][n_ant][n_tbin][nchan], n_tbin = ceil(n_pts / tint), k' = (k + nchan / 2) % nchan: the rows' fftshifted
+ * order, odd channel counts included.  sk is 1 for Gaussian noise whatever its power, 0 for a carrier of constant amplitude,
+ * about 1 / d - 1 for a signal of duty cycle d (so blind near d = 1 / 2), and does not change when the bin is scaled: it needs no
+ * bandpass, gains or delays.  Special cases, in this order: M_j < 2 gives sk = 1 exactly (one frame is no evidence; the power is
+ * still written); a non-finite sample -- or sums beyond float32 -- gives NaN; S1 == 0 (a dead stream) gives sk = 0.
+ * The statistic is taken on each antenna's stream as delivered: sample shifts (fxc_set_sample_delays, an aligned track), the
+ * tables of fxc_set_rot / fxc_set_rot_ant, the delay track and its gains are NOT applied -- sk is invariant to all of them but the
+ * zero fill of a shift -- and the track's counter does not move.  The accumulator is untouched (a pending fold is launched first).
+ * x = [n_chunks][n_ant][num_samp] complex64; x, sk_out and power_out (may be NULL) all host memory (FXC_MEM_HOST: staged,
+ * synchronous) or all device memory (FXC_MEM_DEVICE: queued on the plan's stream).  The plan's F stage runs a pass of chunks into
+ * the workspace and one kernel reads every spectrum once; the passes are sized by the workspace target (FXC_WS_MB).  A bin's
+ * frames are added in an order that depends on (n_pts, tint) alone -- float32 sums over segments of 64 frames from the bin's
+ * first frame, the segments' sums added in float64 in segment order -- so no output bit depends on the batch size, the workspace
+ * target or host against device input.
+ * FXC_OK: n_chunks == 0 (nothing is read).  FXC_ERR_ARG: a NULL plan, x or sk_out, n_chunks < 0, tint < 0, tint == 1,
+ * tint > n_pts, an unknown mem_kind (FXC_MEM_DEVICE_TO_PINNED included).  FXC_ERR_UNSUPPORTED: n_pts < 2.
+ * Out of scope: uint8 and complex128 input, pipes, Correlator integration, per-antenna weights for the beamformer. */
+int fxc_kurtosis(fxc_plan* plan, const void* x, void* sk_out, void* power_out, int64_t n_chunks, int mem_kind, int64_t tint);
+
+/* The row weights from fxc_kurtosis's sk: the array every `weights` and `prior` argument takes (fxc_flag_rows,
+ * fxc_solve_gains_weighted, fxc_fringe_fit_weighted, fxc_average_rows).  sk = [n_chunks][n_ant][n_tbin][nchan] float32 as
+ * fxc_kurtosis(.., tint) wrote it, weights_out = [n_chunks][n_baselines][nchan] float32 in the memory of sk (mem_kind), baselines
+ * (a, b), a < b, a-major.  A bin is counted unless it is a partial last bin and not the only bin of its chunk (its count is not
+ * the one the thresholds were made for).  Element (c, (a,b), k') is 1.0 iff lo <= sk <= hi holds for every counted bin of antenna
+ * a and of antenna b, else 0.0: a conjunction of comparisons in float64, so a NaN gives 0.  One threshold pair serves all bins.
+ * FXC_OK: n_chunks == 0.  FXC_ERR_ARG: a NULL plan, sk or weights_out, n_chunks < 0, tint < 0, tint == 1, tint > n_pts, an unknown
+ * mem_kind, lo or hi not finite, lo > hi.  FXC_ERR_UNSUPPORTED: n_pts < 2. */
+int fxc_kurtosis_weights(fxc_plan* plan, const void* sk, int64_t n_chunks, int64_t tint, double lo, double hi, void* weights_out,
+                         int mem_kind);
+
 /* Host-fed front end: replaces the reference's blocking per-chunk copies
  * (effex.py:391-392, 508-509, 693).  A pipe owns `depth` slots of pinned host staging + device buffers.
  * fxc_pipe_acquire hands the producer the pinned input buffer of the next free slot
