@@ -38,6 +38,7 @@ FXC_MODE_SPECTRUM = 0
 FXC_MODE_CONTINUUM = 1
 FXC_BEAM_POWER = 0
 FXC_BEAM_VOLTAGE = 1
+FXC_BEAM_INCOHERENT = 2
 FXC_FRINGE_REF = 0
 FXC_FRINGE_ALL = 1
 FXC_IQ_C64 = 0
@@ -134,6 +135,9 @@ SIGNATURES = {
                                  _vp]),
     "fxc_average_rows": (_c.c_int, [_vp, _vp, _vp, _c.c_int64, _c.c_int, _c.c_int64, _c.c_int, _vp, _vp]),
     "fxc_beamform": (_c.c_int, [_vp, _vp, _vp, _c.c_int, _vp, _c.c_int64, _c.c_int, _c.c_int, _c.c_int64]),
+    "fxc_beamform_ex": (_c.c_int, [_vp, _vp, _vp, _c.c_int, _vp, _c.c_int64, _vp, _c.c_int64, _c.c_int, _c.c_int, _c.c_int64, _c.c_int]),
+    "fxc_kurtosis_antenna_mask": (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int64, _c.c_double, _c.c_double, _c.c_double, _c.c_double, _vp,
+                                             _c.c_int]),
     "fxc_kurtosis": (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int64, _c.c_int, _c.c_int64]),
     "fxc_kurtosis_weights": (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int64, _c.c_double, _c.c_double, _vp, _c.c_int]),
     "fxc_pipe_create": (_c.c_int, [_c.POINTER(_vp), _vp, _c.c_int64, _c.c_int, _c.c_int, _c.c_double]),

@@ -1191,37 +1191,79 @@ int fxc_average_rows(fxc_plan* p, const void* rows, const void* weights, int64_t
                               static_cast<cf*>(out_rows), static_cast<float*>(out_weights));
 }
 
-int fxc_beamform(fxc_plan* p, const void* x, const void* weights, int n_beam, void* out, int64_t n_chunks, int mem_kind, int mode,
-                 int64_t tint) {
+namespace {
+
+// fxc_beamform (no mask, modes POWER and VOLTAGE, align 0) and fxc_beamform_ex: the argument checks in the order that gives each
+// call its code and message, then the driver on the device or through the host staging; a failed call puts the track's counter back
+int beamform_call(fxc_plan* p, const void* x, const void* weights, int n_beam, const void* mask, int64_t mask_tint, void* out,
+                  int64_t n_chunks, int mem_kind, int mode, int n_modes, int64_t tint, int align) {
     if (!p) return fail(p, FXC_ERR_ARG, "NULL plan");
     if (n_chunks < 0) return fail(p, FXC_ERR_ARG, "n_chunks < 0");
     if (n_beam < 1) return fail(p, FXC_ERR_ARG, "n_beam=%d is not 1 or more", n_beam);
-    if (mode != FXC_BEAM_POWER && mode != FXC_BEAM_VOLTAGE) return fail(p, FXC_ERR_ARG, "bad beam mode %d", mode);
+    if (mode < 0 || mode >= n_modes) return fail(p, FXC_ERR_ARG, "bad beam mode %d", mode);
     if (const int rc = bad_mem_kind(p, mem_kind)) return rc;
     if (tint < 0 || tint > p->n_pts) return fail(p, FXC_ERR_ARG, "tint=%lld is not within 0 .. %lld frames", (long long)tint, (long long)p->n_pts);
+    if (mask_tint < 0 || mask_tint > p->n_pts)
+        return fail(p, FXC_ERR_ARG, "mask_tint=%lld is not within 0 .. %lld frames", (long long)mask_tint, (long long)p->n_pts);
+    if (align != 0 && align != 1) return fail(p, FXC_ERR_ARG, "align=%d is neither 0 nor 1", align);
     if (n_beam > kBeamMax) return fail(p, FXC_ERR_UNSUPPORTED, "n_beam=%d: a call forms %d beams at most", n_beam, kBeamMax);
     if (n_chunks == 0 || p->n_pts == 0) return FXC_OK;
     if (!x || !weights || !out) return fail(p, FXC_ERR_ARG, "NULL buffer");
     if (p->track && p->live_pipes) return fail(p, FXC_ERR_STATE, "an fxc_pipe uses the plan");
-    if (aligning(p))
-        return fail(p, FXC_ERR_UNSUPPORTED, "the plan applies whole-sample delays (%s) and the beamformer's passes are not aligned: beams of "
-                    "unaligned samples would lose amplitude silently.  Clear the shifts or use a plain delay track",
-                    p->shifted ? "fxc_set_sample_delays" : "fxc_set_delay_track_aligned");
+    if (aligning(p)) {
+        if (!align)
+            return fail(p, FXC_ERR_UNSUPPORTED, "the plan applies whole-sample delays (%s) and the beamformer's passes are not aligned: beams of "
+                        "unaligned samples would lose amplitude silently.  Clear the shifts or use a plain delay track",
+                        p->shifted ? "fxc_set_sample_delays" : "fxc_set_delay_track_aligned");
+        if (p->live_pipes) return fail(p, FXC_ERR_STATE, "an fxc_pipe uses the plan");      // (its passes are aligned into the same buffer)
+    }
     FXC_DEVICE(p, p->device);
     const int64_t t0 = p->track_t;
     int rc;
     if (mem_kind == FXC_MEM_DEVICE) {
-        rc = beamform_dev(p, static_cast<const cf*>(x), static_cast<const cf*>(weights), false, n_beam, out, n_chunks, mode, tint);
+        rc = beamform_dev(p, static_cast<const cf*>(x), static_cast<const cf*>(weights), false, n_beam, static_cast<const float*>(mask),
+                          mask_tint, out, n_chunks, mode, tint, align != 0);
     } else {
         const int64_t n_tbin = tint ? (p->n_pts + tint - 1) / tint : 1;
-        const size_t ob = mode == FXC_BEAM_POWER ? (size_t)n_chunks * n_beam * n_tbin * p->nchan * sizeof(float)
-                                                 : (size_t)n_chunks * n_beam * p->n_pts * p->nchan * sizeof(cf);
+        const size_t ob = mode == FXC_BEAM_VOLTAGE ? (size_t)n_chunks * n_beam * p->n_pts * p->nchan * sizeof(cf)
+                                                   : (size_t)n_chunks * n_beam * n_tbin * p->nchan * sizeof(float);
         rc = with_host_staging(p, x, (size_t)n_chunks * p->n_ant * p->num_samp * sizeof(cf), out, ob, [&](const cf* dx, void* dout) {
-            return beamform_dev(p, dx, static_cast<const cf*>(weights), true, n_beam, dout, n_chunks, mode, tint);
+            return beamform_dev(p, dx, static_cast<const cf*>(weights), true, n_beam, static_cast<const float*>(mask), mask_tint, dout,
+                                n_chunks, mode, tint, align != 0);
         });
     }
     if (rc) p->track_t = t0;
     return rc;
+}
+
+}  // namespace
+
+int fxc_beamform(fxc_plan* p, const void* x, const void* weights, int n_beam, void* out, int64_t n_chunks, int mem_kind, int mode,
+                 int64_t tint) {
+    return beamform_call(p, x, weights, n_beam, nullptr, 0, out, n_chunks, mem_kind, mode, 2, tint, 0);
+}
+
+int fxc_beamform_ex(fxc_plan* p, const void* x, const void* weights, int n_beam, const void* mask, int64_t mask_tint, void* out,
+                    int64_t n_chunks, int mem_kind, int mode, int64_t tint, int align) {
+    return beamform_call(p, x, weights, n_beam, mask, mask_tint, out, n_chunks, mem_kind, mode, 3, tint, align);
+}
+
+int fxc_kurtosis_antenna_mask(fxc_plan* p, const void* sk, int64_t n_chunks, int64_t tint, double lo, double hi, double lo_last,
+                              double hi_last, void* mask_out, int mem_kind) {
+    bool done;
+    if (const int rc = check_kurtosis(p, n_chunks, mem_kind, tint, &done)) return rc;
+    if (std::isnan(lo) || std::isnan(hi) || lo > hi || std::isnan(lo_last) || std::isnan(hi_last) || lo_last > hi_last)
+        return fail(p, FXC_ERR_ARG, "the thresholds must be numbers with lo <= hi and lo_last <= hi_last");
+    if (done) return FXC_OK;
+    if (!sk || !mask_out) return fail(p, FXC_ERR_ARG, "NULL buffer");
+    FXC_DEVICE(p, p->device);
+    if (mem_kind == FXC_MEM_DEVICE)
+        return kurtosis_mask_dev(p, static_cast<const float*>(sk), static_cast<float*>(mask_out), n_chunks, tint, lo, hi, lo_last, hi_last);
+    const int64_t n_tbin = tint ? (p->n_pts + tint - 1) / tint : 1;
+    const size_t bytes = (size_t)n_chunks * p->n_ant * n_tbin * p->nchan * sizeof(float);
+    return with_host_staging(p, sk, bytes, mask_out, bytes, [&](const cf* dsk, void* dout) {
+        return kurtosis_mask_dev(p, reinterpret_cast<const float*>(dsk), static_cast<float*>(dout), n_chunks, tint, lo, hi, lo_last, hi_last);
+    });
 }
 
 int fxc_kurtosis(fxc_plan* p, const void* x, void* sk_out, void* power_out, int64_t n_chunks, int mem_kind, int64_t tint) {

@@ -766,19 +766,93 @@ int average_rows_batch(fxc_plan* p, const cf* rows, const float* weights, int64_
 // the pass's effective weights [chunk][beam][antenna][nchan].  A pass takes as many chunks as the workspace target (FXC_WS_MB)
 // allows, one at least; an output element belongs to one thread of one launch and no sum crosses a chunk, so no bit depends on
 // the passes.  Under a track the pass's chunks take the plan's counter onwards; the caller puts it back when the call fails.
-int beamform_dev(fxc_plan* p, const cf* x, const cf* weights, bool weights_on_host, int n_beam, void* out, int64_t n_chunks, int mode,
-                 int64_t tint) {
+//
+// fxc_beamform_ex adds: a mask [chunk][antenna][n_mbin][nchan] -- a host mask is staged pass by pass into a
+// workspace block of its own --, the incoherent mode, and `align`: on a plan with whole-sample delays every pass goes through
+// align_pass (h_ingest.h) into the plan's d_align first, exactly as a pass of fx_call_dev does, and the F stage reads from there;
+// under an aligned track align_pass writes the pass's shifts, which track_tables reads for the same chunks right behind it.  The
+// alignment buffer counts against the workspace target like the blocks of the workspace itself.
+//
+// A launch of the beam kernels (k_beam.h) over the spectra of a pass: what the call site means; the tile of beams, the kernel and
+// the geometry are decided in launch_beam alone.
+struct BeamLaunch {
+    const cf* spec;                  // [chunk][antenna][frame][nchan], natural bin order
+    const cf* weff;                  // [n_beam][antenna][nchan], w_chunk elements between chunks (0: one set for every chunk)
+    int64_t w_chunk;
+    const float* mask;               // the pass's [chunk][antenna][n_mbin][nchan], or nullptr: every antenna counts
+    int64_t mask_tint, n_mbin;
+    void* out;                       // the pass's first output element
+    int64_t n_chunks;                // of the pass, at most kGridMax
+    int n_beam, mode;
+    int64_t tint, n_tbin;            // frames a time bin (1 .. n_pts) and bins a chunk
+};
+
+int launch_beam(fxc_plan* p, const BeamLaunch& k) {
     const int nchan = p->nchan, n_ant = p->n_ant;
-    const bool power = mode == FXC_BEAM_POWER;
+    // frames per range (grid.y): whole time bins, 32 frames or more where a bin is shorter; a function of (n_pts, tint) alone
+    const int64_t unit = k.mode == FXC_BEAM_VOLTAGE ? kBeamFrames : k.tint;
+    int64_t fpr = unit * std::max<int64_t>(1, 32 / unit);
+    fpr = std::max(fpr, ((p->n_pts + kGridMax - 1) / kGridMax + unit - 1) / unit * unit);
+    const dim3 grid((unsigned)((nchan + kBeamThreads - 1) / kBeamThreads), (unsigned)((p->n_pts + fpr - 1) / fpr), (unsigned)k.n_chunks);
+    const dim3 block(kBeamThreads);
+    const auto launch = [&](auto bt, int b0) {
+        constexpr int BT = decltype(bt)::value;
+        if (k.mode == FXC_BEAM_INCOHERENT) {
+            if (k.mask)
+                hipLaunchKernelGGL((beam_inc_kernel<BT, true>), grid, block, 0, p->stream, k.spec, k.weff, k.w_chunk, k.mask, k.mask_tint,
+                                   k.n_mbin, static_cast<float*>(k.out), n_ant, p->n_pts, nchan, k.n_beam, b0, k.tint, fpr, k.n_tbin);
+            else
+                hipLaunchKernelGGL((beam_inc_kernel<BT, false>), grid, block, 0, p->stream, k.spec, k.weff, k.w_chunk, k.mask, (int64_t)1,
+                                   (int64_t)0, static_cast<float*>(k.out), n_ant, p->n_pts, nchan, k.n_beam, b0, k.tint, fpr, k.n_tbin);
+        } else if (k.mask) {
+            if (k.mode == FXC_BEAM_POWER)
+                hipLaunchKernelGGL((beam_mask_kernel<BT, true>), grid, block, 0, p->stream, k.spec, k.weff, k.w_chunk, k.mask, k.mask_tint,
+                                   k.n_mbin, k.out, n_ant, p->n_pts, nchan, k.n_beam, b0, k.tint, fpr, k.n_tbin);
+            else
+                hipLaunchKernelGGL((beam_mask_kernel<BT, false>), grid, block, 0, p->stream, k.spec, k.weff, k.w_chunk, k.mask, k.mask_tint,
+                                   k.n_mbin, k.out, n_ant, p->n_pts, nchan, k.n_beam, b0, k.tint, fpr, k.n_tbin);
+        } else if (k.mode == FXC_BEAM_POWER) {
+            hipLaunchKernelGGL((beam_kernel<BT, true>), grid, block, 0, p->stream, k.spec, k.weff, k.w_chunk, k.out, n_ant, p->n_pts, nchan,
+                               k.n_beam, b0, k.tint, fpr, k.n_tbin);
+        } else {
+            hipLaunchKernelGGL((beam_kernel<BT, false>), grid, block, 0, p->stream, k.spec, k.weff, k.w_chunk, k.out, n_ant, p->n_pts, nchan,
+                               k.n_beam, b0, k.tint, fpr, k.n_tbin);
+        }
+    };
+    for (int b0 = 0; b0 < k.n_beam; b0 += kBeamTile) {      // the tile of a call's beams is a function of n_beam alone
+        const int left = k.n_beam - b0;
+        if (left > 4) launch(std::integral_constant<int, 8>{}, b0);
+        else if (left > 2) launch(std::integral_constant<int, 4>{}, b0);
+        else if (left > 1) launch(std::integral_constant<int, 2>{}, b0);
+        else launch(std::integral_constant<int, 1>{}, b0);
+    }
+    FXC_HIP(p, hipGetLastError());
+    return FXC_OK;
+}
+
+int beamform_dev(fxc_plan* p, const cf* x, const cf* weights, bool weights_on_host, int n_beam, const float* mask, int64_t mask_tint,
+                 void* out, int64_t n_chunks, int mode, int64_t tint, bool align) {
+    const int nchan = p->nchan, n_ant = p->n_ant;
+    const bool voltage = mode == FXC_BEAM_VOLTAGE;
+    const bool al = align && aligning(p);
     if (tint == 0) tint = p->n_pts;
+    if (mask_tint == 0) mask_tint = p->n_pts;
     const int64_t n_tbin = (p->n_pts + tint - 1) / tint;
+    const int64_t n_mbin = (p->n_pts + mask_tint - 1) / mask_tint;
     const int64_t w_elems = (int64_t)n_beam * n_ant * nchan;
+    const int64_t m_elems = (int64_t)n_ant * n_mbin * nchan;      // of a chunk's mask
     const int64_t wcopy_bytes = weights_on_host ? up256(w_elems * (int64_t)sizeof(cf)) : 0;
     const int64_t spec_per_chunk = (int64_t)n_ant * p->n_pts * nchan * (int64_t)sizeof(cf);
     const int64_t weff_per_chunk = p->track ? w_elems * (int64_t)sizeof(cf) : 0;
-    const int64_t cb = std::max<int64_t>(1, std::min<int64_t>(std::min(n_chunks, kGridMax), (ws_target() - wcopy_bytes) / (spec_per_chunk + weff_per_chunk)));
+    const int64_t mask_per_chunk = mask && weights_on_host ? m_elems * (int64_t)sizeof(float) : 0;      // a host mask is staged
+    const int64_t align_per_chunk = al ? (int64_t)n_ant * p->num_samp * (int64_t)sizeof(cf) : 0;
+    int64_t cb = std::min<int64_t>(std::min(n_chunks, kGridMax),
+                                   (ws_target() - wcopy_bytes) / (spec_per_chunk + weff_per_chunk + mask_per_chunk + align_per_chunk));
+    if (al) cb = std::min<int64_t>(cb, kGridMax / n_ant);      // (the stream index rides in a grid dimension of the alignment kernel)
+    cb = std::max<int64_t>(1, cb);
     WsCarver ws;
     const int64_t o_wcopy = ws.take(wcopy_bytes), o_spec = ws.take(up256(cb * spec_per_chunk)), o_weff = ws.take(up256(cb * weff_per_chunk));
+    const int64_t o_mask = ws.take(up256(cb * mask_per_chunk));
     int rc = ensure_ws(p, ws.total());      // (flushes a pending fold: it lives in the workspace)
     if (rc) return rc;
     cf* spec = ws_at<cf>(p, o_spec);
@@ -787,16 +861,22 @@ int beamform_dev(fxc_plan* p, const cf* x, const cf* weights, bool weights_on_ho
         FXC_HIP(p, hipMemcpyAsync(ws_at<cf>(p, o_wcopy), weights, (size_t)w_elems * sizeof(cf), hipMemcpyHostToDevice, p->stream));
         weights = ws_at<cf>(p, o_wcopy);
     }
-    // frames per range (grid.y): whole time bins, 32 frames or more where a bin is shorter; a function of (n_pts, tint) alone
-    const int64_t unit = power ? tint : kBeamFrames;
-    int64_t fpr = unit * std::max<int64_t>(1, 32 / unit);
-    fpr = std::max(fpr, ((p->n_pts + kGridMax - 1) / kGridMax + unit - 1) / unit * unit);
-    const int64_t out_per_chunk = power ? (int64_t)n_beam * n_tbin * nchan * (int64_t)sizeof(float)
-                                        : (int64_t)n_beam * p->n_pts * nchan * (int64_t)sizeof(cf);
+    const int64_t out_per_chunk = voltage ? (int64_t)n_beam * p->n_pts * nchan * (int64_t)sizeof(cf)
+                                          : (int64_t)n_beam * n_tbin * nchan * (int64_t)sizeof(float);
     for (int64_t c0 = 0; c0 < n_chunks; c0 += cb) {
         const int64_t nc = std::min(cb, n_chunks - c0);
-        rc = run_channelize(p, chunk_at(p, x, c0), spec, nc * n_ant);
+        PassInput in{chunk_at(p, x, c0)};
+        if (al) {      // (under an aligned track: the shifts of the chunks p->track_t onwards, the chunks of the tables below)
+            rc = align_pass(p, nc, &in);
+            if (rc) return rc;
+        }
+        rc = run_channelize(p, in.x, spec, nc * n_ant);
         if (rc) return rc;
+        const float* mk = mask ? mask + c0 * m_elems : nullptr;
+        if (mask_per_chunk) {
+            FXC_HIP(p, hipMemcpyAsync(ws_at<float>(p, o_mask), mk, (size_t)(nc * m_elems) * sizeof(float), hipMemcpyHostToDevice, p->stream));
+            mk = ws_at<float>(p, o_mask);
+        }
         const cf* wk = weights;
         if (p->track) {
             const int rg = grow(p, &p->d_track, &p->track_bytes, (size_t)(nc * n_ant * nchan) * sizeof(cd));
@@ -809,29 +889,27 @@ int beamform_dev(fxc_plan* p, const cf* x, const cf* weights, bool weights_on_ho
             FXC_HIP(p, hipGetLastError());
             wk = weff;
         }
-        void* o = static_cast<char*>(out) + c0 * out_per_chunk;
-        const dim3 grid((unsigned)((nchan + kBeamThreads - 1) / kBeamThreads), (unsigned)((p->n_pts + fpr - 1) / fpr), (unsigned)nc);
         KernelTimer kt(p);
-#define FXC_BEAM_LAUNCH(BT, B0)                                                                                                  \
-    do {                                                                                                                         \
-        if (power)                                                                                                               \
-            hipLaunchKernelGGL((beam_kernel<BT, true>), grid, dim3(kBeamThreads), 0, p->stream, spec, wk, p->track ? w_elems : 0, o, \
-                               n_ant, p->n_pts, nchan, n_beam, B0, tint, fpr, n_tbin);                                           \
-        else                                                                                                                     \
-            hipLaunchKernelGGL((beam_kernel<BT, false>), grid, dim3(kBeamThreads), 0, p->stream, spec, wk, p->track ? w_elems : 0, o, \
-                               n_ant, p->n_pts, nchan, n_beam, B0, tint, fpr, n_tbin);                                           \
-    } while (0)
-        for (int b0 = 0; b0 < n_beam; b0 += kBeamTile) {      // the tile of a call's beams is a function of n_beam alone
-            const int left = n_beam - b0;
-            if (left > 4) FXC_BEAM_LAUNCH(8, b0);
-            else if (left > 2) FXC_BEAM_LAUNCH(4, b0);
-            else if (left > 1) FXC_BEAM_LAUNCH(2, b0);
-            else FXC_BEAM_LAUNCH(1, b0);
-        }
-#undef FXC_BEAM_LAUNCH
+        rc = launch_beam(p, {spec, wk, p->track ? w_elems : 0, mk, mask_tint, n_mbin, static_cast<char*>(out) + c0 * out_per_chunk, nc, n_beam,
+                             mode, tint, n_tbin});
         kt.stop();
-        FXC_HIP(p, hipGetLastError());
+        if (rc) return rc;
     }
+    return FXC_OK;
+}
+
+// The antenna mask from sk (fxc_kurtosis_antenna_mask), both on the device
+int kurtosis_mask_dev(fxc_plan* p, const float* sk, float* mask, int64_t n_chunks, int64_t tint, double lo, double hi, double lo_last,
+                      double hi_last) {
+    if (tint == 0) tint = p->n_pts;
+    const int64_t n_tbin = (p->n_pts + tint - 1) / tint;
+    // a partial last bin that is not the chunk's only bin has the thresholds of its own count
+    const int64_t n_full = p->n_pts % tint != 0 && n_tbin > 1 ? n_tbin - 1 : n_tbin;
+    const int64_t total = n_chunks * p->n_ant * n_tbin * p->nchan;
+    if (total == 0) return FXC_OK;
+    hipLaunchKernelGGL(kurtosis_mask_kernel, dim3(grid_for(total, 256, p->cu_count)), dim3(256), 0, p->stream, sk, mask, p->nchan, n_tbin,
+                       n_full, total, lo, hi, lo_last, hi_last);
+    FXC_HIP(p, hipGetLastError());
     return FXC_OK;
 }
 

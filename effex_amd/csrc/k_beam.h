@@ -132,4 +132,257 @@ __global__ __launch_bounds__(kBeamThreads) void beam_kernel(const cf* __restrict
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// antenna masks and incoherent beams (fxcorr.h fxc_beamform_ex).  mask = [chunk][antenna][n_mbin][nchan] float32 in
+// the rows' fftshifted channel order -- the layout of fxc_kurtosis's sk --, frame i under mask bin i / mtint; antenna a counts in a
+// cell iff its value is > 0.  A sample that does not count is selected away on the loaded value, ahead of the multiply-adds: a NaN
+// in it reaches no sum, and with every value > 0 the sums are beam_kernel's own, bit for bit.  The mask is read at kout, contiguous
+// across the wave but for the one wrap of the fftshift, through L2 (no nontemporal hint: a value serves up to mtint frames).
+// ------------------------------------------------------------------------------------------
+
+// The mask bins of a thread's frames: frame i is in bin j with r frames of the bin behind it.  tile() gives the row offsets of the
+// 8 frames from the current one and moves on by 8; the frames past `end` repeat the last one's bin, as their samples do.
+struct MaskWalk {
+    int64_t j, r, mtint;
+    __device__ __forceinline__ MaskWalk(int64_t i, int64_t mtint_) : j(i / mtint_), r(i % mtint_), mtint(mtint_) {}
+    // -> true when the tile lies inside one mask bin (off[0] serves every frame)
+    __device__ __forceinline__ bool tile(int64_t i, int64_t end, int nchan, int64_t (&off)[kBeamFrames]) {
+        const int64_t j0 = j;
+#pragma unroll
+        for (int f = 0; f < kBeamFrames; ++f) {
+            off[f] = j * nchan;
+            if (i + f + 1 < end && ++r == mtint) {
+                r = 0;
+                ++j;
+            }
+        }
+        return off[kBeamFrames - 1] == j0 * nchan;
+    }
+};
+
+// z = m > 0 ? z : 0 on the loaded samples of a trip: one mask value an antenna (ONE: the tile lies in one mask bin), or one a frame
+template <int NA, bool ONE>
+__device__ __forceinline__ void beam_load_masked(cf (&z)[NA][kBeamFrames], const cf* __restrict__ s, int64_t s_ant,
+                                                 const int64_t (&off)[kBeamFrames], const float* __restrict__ mk, int64_t m_ant,
+                                                 const int64_t (&moff)[kBeamFrames]) {
+    float m[NA][ONE ? 1 : kBeamFrames];
+#pragma unroll
+    for (int u = 0; u < NA; ++u) {
+#pragma unroll
+        for (int f = 0; f < kBeamFrames; ++f) z[u][f] = FXC_X_LOAD(s + u * s_ant + off[f]);
+#pragma unroll
+        for (int f = 0; f < (ONE ? 1 : kBeamFrames); ++f) m[u][f] = mk[u * m_ant + moff[f]];
+    }
+#pragma unroll
+    for (int u = 0; u < NA; ++u)
+#pragma unroll
+        for (int f = 0; f < kBeamFrames; ++f) {
+            const bool in = m[u][ONE ? 0 : f] > 0.f;
+            z[u][f].x = in ? z[u][f].x : 0.f;
+            z[u][f].y = in ? z[u][f].y : 0.f;
+        }
+}
+
+// beam_trip with the trip's mask values: the same multiply-adds in the same order on the selected samples
+template <int BT, int NA, bool ONE>
+__device__ __forceinline__ void beam_trip(cf (&y)[BT][kBeamFrames], const cf* __restrict__ s, int64_t s_ant,
+                                          const int64_t (&off)[kBeamFrames], const cf* __restrict__ w, int nchan,
+                                          const int64_t (&wb)[BT], const float* __restrict__ mk, int64_t m_ant,
+                                          const int64_t (&moff)[kBeamFrames]) {
+    cf z[NA][kBeamFrames], g[NA][BT];
+    beam_load_masked<NA, ONE>(z, s, s_ant, off, mk, m_ant, moff);
+#pragma unroll
+    for (int u = 0; u < NA; ++u)
+#pragma unroll
+        for (int b = 0; b < BT; ++b) g[u][b] = w[wb[b] + (int64_t)u * nchan];
+#pragma unroll
+    for (int u = 0; u < NA; ++u)
+#pragma unroll
+        for (int b = 0; b < BT; ++b)
+#pragma unroll
+            for (int f = 0; f < kBeamFrames; ++f) {
+                y[b][f].x = __builtin_fmaf(-g[u][b].y, z[u][f].y, __builtin_fmaf(g[u][b].x, z[u][f].x, y[b][f].x));
+                y[b][f].y = __builtin_fmaf(g[u][b].y, z[u][f].x, __builtin_fmaf(g[u][b].x, z[u][f].y, y[b][f].y));
+            }
+}
+
+// beam_kernel under a mask: its grid, ranges, tiles, sums and stores; mask = the pass's [chunk][n_ant][n_mbin][nchan]
+template <int BT, bool POWER>
+__global__ __launch_bounds__(kBeamThreads, 2) void beam_mask_kernel(const cf* __restrict__ spec, const cf* __restrict__ weff, int64_t w_chunk,
+                                                                 const float* __restrict__ mask, int64_t mtint, int64_t n_mbin,
+                                                                 void* __restrict__ out, int n_ant, int64_t n_pts, int nchan, int n_beam,
+                                                                 int b0, int64_t tint, int64_t fpr, int64_t n_tbin) {
+    const int pos = blockIdx.x * kBeamThreads + threadIdx.x;
+    if (pos >= nchan) return;      // part of a wave
+    const int64_t c = blockIdx.z;
+    const int64_t i0 = (int64_t)blockIdx.y * fpr;
+    const int64_t i1 = i0 + fpr < n_pts ? i0 + fpr : n_pts;
+    const int64_t s_ant = n_pts * nchan;
+    const int64_t m_ant = n_mbin * nchan;
+    const cf* __restrict__ s = spec + c * n_ant * s_ant + pos;
+    const cf* __restrict__ w = weff + c * w_chunk + pos;
+    int64_t wb[BT];
+#pragma unroll
+    for (int b = 0; b < BT; ++b) wb[b] = (int64_t)(b0 + b < n_beam ? b0 + b : n_beam - 1) * n_ant * nchan;
+    float pacc[BT];
+#pragma unroll
+    for (int b = 0; b < BT; ++b) pacc[b] = 0.f;
+    int64_t cnt = 0;
+    int kout = pos + nchan / 2;
+    if (kout >= nchan) kout -= nchan;
+    const float* __restrict__ mk = mask + c * n_ant * m_ant + kout;
+    MaskWalk walk(i0, mtint);
+    for (int64_t i = i0; i < i1; i += kBeamFrames) {
+        int64_t off[kBeamFrames], moff[kBeamFrames];
+#pragma unroll
+        for (int f = 0; f < kBeamFrames; ++f) off[f] = (i + f < i1 ? i + f : i1 - 1) * nchan;
+        const bool one = walk.tile(i, i1, nchan, moff);
+        cf y[BT][kBeamFrames];
+#pragma unroll
+        for (int b = 0; b < BT; ++b)
+#pragma unroll
+            for (int f = 0; f < kBeamFrames; ++f) y[b][f] = fxc::mk(0.f, 0.f);
+        int a = 0;
+        if (one) {
+            for (; a + 2 <= n_ant; a += 2)
+                beam_trip<BT, 2, true>(y, s + a * s_ant, s_ant, off, w + (int64_t)a * nchan, nchan, wb, mk + a * m_ant, m_ant, moff);
+            if (a < n_ant) beam_trip<BT, 1, true>(y, s + a * s_ant, s_ant, off, w + (int64_t)a * nchan, nchan, wb, mk + a * m_ant, m_ant, moff);
+        } else {      // a mask value a frame: one antenna a trip, so that the 8-beam tile stays within 256 registers
+            for (; a < n_ant; ++a)
+                beam_trip<BT, 1, false>(y, s + a * s_ant, s_ant, off, w + (int64_t)a * nchan, nchan, wb, mk + a * m_ant, m_ant, moff);
+        }
+#pragma unroll
+        for (int f = 0; f < kBeamFrames; ++f) {
+            const int64_t frame = i + f;
+            if (frame >= i1) break;
+            if constexpr (POWER) {
+#pragma unroll
+                for (int b = 0; b < BT; ++b) pacc[b] += __builtin_fmaf(y[b][f].y, y[b][f].y, y[b][f].x * y[b][f].x);
+                ++cnt;
+                if (cnt == tint || frame == n_pts - 1) {
+                    const int64_t j = frame / tint;
+                    const float n = (float)cnt;
+#pragma unroll
+                    for (int b = 0; b < BT; ++b) {
+                        if (b0 + b < n_beam)
+                            static_cast<float*>(out)[((c * n_beam + b0 + b) * n_tbin + j) * nchan + kout] = pacc[b] / n;
+                        pacc[b] = 0.f;
+                    }
+                    cnt = 0;
+                }
+            } else {
+#pragma unroll
+                for (int b = 0; b < BT; ++b)
+                    if (b0 + b < n_beam) static_cast<cf*>(out)[((c * n_beam + b0 + b) * n_pts + frame) * nchan + pos] = y[b][f];
+            }
+        }
+    }
+}
+
+// NA antennas into the incoherent sums: p = |z|^2 once per antenna and frame, g2 = |weff|^2 once per antenna and beam, then
+// q = fma(g2, p, q), the antennas in index order.  MASKED: z is selected first (p = 0 where the antenna does not count).
+template <int BT, int NA, bool MASKED, bool ONE>
+__device__ __forceinline__ void beam_inc_trip(float (&q)[BT][kBeamFrames], const cf* __restrict__ s, int64_t s_ant,
+                                              const int64_t (&off)[kBeamFrames], const cf* __restrict__ w, int nchan,
+                                              const int64_t (&wb)[BT], const float* __restrict__ mk, int64_t m_ant,
+                                              const int64_t (&moff)[kBeamFrames]) {
+    cf z[NA][kBeamFrames], g[NA][BT];
+    if constexpr (MASKED) {
+        beam_load_masked<NA, ONE>(z, s, s_ant, off, mk, m_ant, moff);
+    } else {
+#pragma unroll
+        for (int u = 0; u < NA; ++u)
+#pragma unroll
+            for (int f = 0; f < kBeamFrames; ++f) z[u][f] = FXC_X_LOAD(s + u * s_ant + off[f]);
+    }
+#pragma unroll
+    for (int u = 0; u < NA; ++u)
+#pragma unroll
+        for (int b = 0; b < BT; ++b) g[u][b] = w[wb[b] + (int64_t)u * nchan];
+#pragma unroll
+    for (int u = 0; u < NA; ++u) {
+        float pw[kBeamFrames];
+#pragma unroll
+        for (int f = 0; f < kBeamFrames; ++f) pw[f] = __builtin_fmaf(z[u][f].y, z[u][f].y, z[u][f].x * z[u][f].x);
+#pragma unroll
+        for (int b = 0; b < BT; ++b) {
+            const float g2 = __builtin_fmaf(g[u][b].y, g[u][b].y, g[u][b].x * g[u][b].x);
+#pragma unroll
+            for (int f = 0; f < kBeamFrames; ++f) q[b][f] = __builtin_fmaf(g2, pw[f], q[b][f]);
+        }
+    }
+}
+
+// Incoherent beams: out[c][b][j][k'] = mean_{i in bin j} sum_{a counted} |weff[c,b,a,k]|^2 |f_a[c,i,k]|^2, float32, with POWER's grid,
+// ranges, bins, partial-last-bin rule and store.  The bin adds a frame's q in frame order from 0 and divides by its own count.
+template <int BT, bool MASKED>
+__global__ __launch_bounds__(kBeamThreads) void beam_inc_kernel(const cf* __restrict__ spec, const cf* __restrict__ weff, int64_t w_chunk,
+                                                                const float* __restrict__ mask, int64_t mtint, int64_t n_mbin,
+                                                                float* __restrict__ out, int n_ant, int64_t n_pts, int nchan, int n_beam,
+                                                                int b0, int64_t tint, int64_t fpr, int64_t n_tbin) {
+#pragma clang fp contract(off)
+    const int pos = blockIdx.x * kBeamThreads + threadIdx.x;
+    if (pos >= nchan) return;      // part of a wave
+    const int64_t c = blockIdx.z;
+    const int64_t i0 = (int64_t)blockIdx.y * fpr;
+    const int64_t i1 = i0 + fpr < n_pts ? i0 + fpr : n_pts;
+    const int64_t s_ant = n_pts * nchan;
+    const int64_t m_ant = n_mbin * nchan;
+    const cf* __restrict__ s = spec + c * n_ant * s_ant + pos;
+    const cf* __restrict__ w = weff + c * w_chunk + pos;
+    int64_t wb[BT];
+#pragma unroll
+    for (int b = 0; b < BT; ++b) wb[b] = (int64_t)(b0 + b < n_beam ? b0 + b : n_beam - 1) * n_ant * nchan;
+    float pacc[BT];
+#pragma unroll
+    for (int b = 0; b < BT; ++b) pacc[b] = 0.f;
+    int64_t cnt = 0;
+    int kout = pos + nchan / 2;
+    if (kout >= nchan) kout -= nchan;
+    const float* __restrict__ mk = MASKED ? mask + c * n_ant * m_ant + kout : nullptr;      // (not MASKED: never read)
+    MaskWalk walk(i0, MASKED ? mtint : 1);
+    for (int64_t i = i0; i < i1; i += kBeamFrames) {
+        int64_t off[kBeamFrames], moff[kBeamFrames];
+#pragma unroll
+        for (int f = 0; f < kBeamFrames; ++f) off[f] = (i + f < i1 ? i + f : i1 - 1) * nchan;
+        bool one = true;
+        if constexpr (MASKED) one = walk.tile(i, i1, nchan, moff);
+        float q[BT][kBeamFrames];
+#pragma unroll
+        for (int b = 0; b < BT; ++b)
+#pragma unroll
+            for (int f = 0; f < kBeamFrames; ++f) q[b][f] = 0.f;
+        int a = 0;
+        if (one) {
+            for (; a + 2 <= n_ant; a += 2)
+                beam_inc_trip<BT, 2, MASKED, true>(q, s + a * s_ant, s_ant, off, w + (int64_t)a * nchan, nchan, wb, mk + a * m_ant, m_ant, moff);
+            if (a < n_ant)
+                beam_inc_trip<BT, 1, MASKED, true>(q, s + a * s_ant, s_ant, off, w + (int64_t)a * nchan, nchan, wb, mk + a * m_ant, m_ant, moff);
+        } else {
+            for (; a + 2 <= n_ant; a += 2)
+                beam_inc_trip<BT, 2, MASKED, false>(q, s + a * s_ant, s_ant, off, w + (int64_t)a * nchan, nchan, wb, mk + a * m_ant, m_ant, moff);
+            if (a < n_ant)
+                beam_inc_trip<BT, 1, MASKED, false>(q, s + a * s_ant, s_ant, off, w + (int64_t)a * nchan, nchan, wb, mk + a * m_ant, m_ant, moff);
+        }
+#pragma unroll
+        for (int f = 0; f < kBeamFrames; ++f) {
+            const int64_t frame = i + f;
+            if (frame >= i1) break;
+#pragma unroll
+            for (int b = 0; b < BT; ++b) pacc[b] += q[b][f];
+            ++cnt;
+            if (cnt == tint || frame == n_pts - 1) {
+                const int64_t j = frame / tint;
+                const float n = (float)cnt;
+#pragma unroll
+                for (int b = 0; b < BT; ++b) {
+                    if (b0 + b < n_beam) out[((c * n_beam + b0 + b) * n_tbin + j) * nchan + kout] = pacc[b] / n;
+                    pacc[b] = 0.f;
+                }
+                cnt = 0;
+            }
+        }
+    }
+}
+
 }  // namespace

@@ -154,4 +154,19 @@ __global__ __launch_bounds__(256) void kurtosis_weights_kernel(const float* __re
     }
 }
 
+// The antenna mask of fxc_kurtosis_antenna_mask: mask[c][a][j][k'] = 1 iff lo_j <= sk <= hi_j, else 0 -- comparisons in float64 on
+// the float32 values, so a NaN gives 0.  sk and mask = [n_chunks][n_ant][n_tbin][nchan]; (lo_j, hi_j) = (lo_last, hi_last) for bin
+// j >= n_full (a partial last bin that is not the chunk's only bin), (lo, hi) otherwise.  One thread per element.
+__global__ __launch_bounds__(256) void kurtosis_mask_kernel(const float* __restrict__ sk, float* __restrict__ mask, int nchan, int64_t n_tbin,
+                                                            int64_t n_full, int64_t total, double lo, double hi, double lo_last,
+                                                            double hi_last) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += stride) {
+        const int64_t j = idx / nchan % n_tbin;
+        const bool last = j >= n_full;
+        const double v = (double)sk[idx], l = last ? lo_last : lo, h = last ? hi_last : hi;
+        mask[idx] = l <= v && v <= h ? 1.f : 0.f;
+    }
+}
+
 }  // namespace

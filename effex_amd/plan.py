@@ -512,7 +512,7 @@ class FxPlan(object):
         self._check(self._lib.fxc_channelize(self._h, ptr, optr, n, kind))
         return out
 
-    def beamform(self, x, weights, tint=0, mode="POWER", out=None):
+    def beamform(self, x, weights, tint=0, mode="POWER", out=None, *, mask=None, mask_tint=0, whole_samples=False):
         """Tied-array beams: phased sums of the antennas' spectra (fxcorr.h fxc_beamform).  ``x`` = [n_chunks, n_ant, num_samp]
         complex64 (numpy, or a CUDA tensor on the plan's device), ``weights`` = [n_beam, n_ant, nchan] complex64 in natural bin
         order (``beam_weights``; [n_ant, nchan] is one beam; numpy weights with a CUDA ``x`` are moved to the device).  Under a
@@ -520,8 +520,33 @@ class FxPlan(object):
         ``set_rot`` / ``set_rot_ant`` are not applied.  mode "POWER" -> [n_chunks, n_beam, n_tbin, nchan] float32, the mean of
         |y|^2 over time bins of ``tint`` frames (0: the whole chunk; the last may be partial), bins in the rows' fftshifted
         order; "VOLTAGE" -> [n_chunks, n_beam, n_pts, nchan] complex64, natural bin order.  numpy in, numpy out; CUDA tensor in,
-        CUDA tensor out.  ``out``: an array / tensor of the result's shape and dtype to receive it.  At most 16 beams."""
-        m = BEAM_MODES[mode.upper()]
+        CUDA tensor out.  ``out``: an array / tensor of the result's shape and dtype to receive it.  At most 16 beams.
+
+        ``mask``, ``mask_tint`` and ``whole_samples`` (fxcorr.h fxc_beamform_ex; with all three at their defaults the call is
+        fxc_beamform as it was): ``mask`` = float32 [n_chunks, n_ant, n_mbin, nchan] in the memory of ``x`` (a numpy mask with a
+        CUDA ``x`` is moved to the device), channels in the rows' fftshifted order, n_mbin = ceil(n_pts / mask_tint) bins of
+        ``mask_tint`` frames (0: the whole chunk) -- what ``kurtosis_mask(kurtosis(x, tint=mask_tint), tint=mask_tint)`` returns.
+        An antenna counts in a cell iff its value is > 0; a sample that does not count is selected away, so a NaN or a tone in it
+        changes no bit.  Nothing is normalised: ``(mask > 0).sum(axis=1)`` is the count of antennas, and ``(n_ant / count) ** 2``
+        rescales a point source's power (``tint == mask_tint`` keeps one count a bin).  ``whole_samples=True`` aligns every pass
+        on a plan with whole-sample delays (``set_sample_delays``, ``set_delays(.., whole_samples=True)``, an aligned track);
+        without it such a plan is refused (NotImplementedError).  The loop::
+
+            sk = plan.kurtosis(x, tint=64)
+            m = plan.kurtosis_mask(sk, tint=64)
+            P = plan.beamform(x, w, tint=64, mask=m, mask_tint=64, whole_samples=True)
+        """
+        return self._beamform(x, weights, tint, BEAM_MODES[mode.upper()], out, mask, mask_tint, whole_samples)
+
+    def beamform_incoherent(self, x, weights, tint=0, out=None, *, mask=None, mask_tint=0, whole_samples=False):
+        """Incoherent beams (fxcorr.h fxc_beamform_ex, FXC_BEAM_INCOHERENT): the mean over time bins of
+        ``sum_a |weff[b, a, k]|^2 |f_a|^2`` over the counted antennas -> float32 [n_chunks, n_beam, n_tbin, nchan], every
+        argument, the bins and the order of the channels as ``beamform(.., mode="POWER")``.  The robust, wide-field companion
+        of a tied-array beam: ``beamform(..) - beamform_incoherent(..)`` is the beam's cross-only power.  A gain track scales
+        the antennas, a plain delay track changes nothing."""
+        return self._beamform(x, weights, tint, _lib.FXC_BEAM_INCOHERENT, out, mask, mask_tint, whole_samples)
+
+    def _beamform(self, x, weights, tint, m, out, mask, mask_tint, whole_samples):
         ptr, kind, n, keep = self._in(x, (self.n_ant, self.num_samp))
         device = kind == _lib.FXC_MEM_DEVICE
         if device:
@@ -543,11 +568,29 @@ class FxPlan(object):
         if len(w_shape) != 3 or w_shape[0] < 1 or w_shape[1:] != (self.n_ant, self.nchan):
             raise ValueError("weights must have shape (n_beam, {}, {}), got {}".format(self.n_ant, self.nchan, tuple(w_keep.shape)))
         n_beam, tint = int(w_shape[0]), int(tint)
-        if m == _lib.FXC_BEAM_POWER:
+        if m != _lib.FXC_BEAM_VOLTAGE:
             n_tbin = -(-self.n_pts // tint) if 0 < tint <= self.n_pts else 1      # (a tint out of range: the call answers)
             shape, dtype = (n, n_beam, n_tbin, self.nchan), np.float32
         else:
             shape, dtype = (n, n_beam, self.n_pts, self.nchan), np.complex64
+        mask_tint, m_keep, m_ptr = int(mask_tint), None, None
+        if mask is not None:
+            if device:
+                if not _is_torch(mask):
+                    mask = torch.from_numpy(np.ascontiguousarray(mask, dtype=np.float32)).to(keep.device)
+                if mask.dtype != torch.float32 or not mask.is_cuda or mask.device.index != self.device:
+                    raise ValueError("a device mask must be a float32 CUDA tensor on device {}".format(self.device))
+                m_keep = mask.contiguous()
+                m_ptr = m_keep.data_ptr()
+            else:
+                if _is_torch(mask):
+                    raise ValueError("mask must be in the memory of x: a numpy mask for host samples")
+                m_keep = np.ascontiguousarray(mask, dtype=np.float32)
+                m_ptr = m_keep.ctypes.data
+            n_mbin = -(-self.n_pts // mask_tint) if 0 < mask_tint <= self.n_pts else 1      # (out of range: the call answers)
+            if tuple(m_keep.shape) != (n, self.n_ant, n_mbin, self.nchan):
+                raise ValueError("mask must have shape ({}, {}, {}, {}), got {}".format(n, self.n_ant, n_mbin, self.nchan,
+                                                                                        tuple(m_keep.shape)))
         if out is not None:
             if _is_torch(out) != device:
                 raise ValueError("out must be of the same kind (host array / CUDA tensor) as x")
@@ -565,9 +608,48 @@ class FxPlan(object):
         o_ptr = out.data_ptr() if device else out.ctypes.data
         if device and not self._follow:      # a stream of the plan's own: torch's may still be filling the moved weights
             torch.cuda.current_stream(keep.device).synchronize()
-        self._beam_keep = (keep, w_keep)     # until the next call: the queued kernels read them
-        self._check(self._lib.fxc_beamform(self._h, ptr, w_ptr, n_beam, o_ptr, n, kind, m, tint))
+        self._beam_keep = (keep, w_keep, m_keep)     # until the next call: the queued kernels read them
+        if mask is None and mask_tint == 0 and not whole_samples and m != _lib.FXC_BEAM_INCOHERENT:
+            self._check(self._lib.fxc_beamform(self._h, ptr, w_ptr, n_beam, o_ptr, n, kind, m, tint))
+        else:
+            self._check(self._lib.fxc_beamform_ex(self._h, ptr, w_ptr, n_beam, m_ptr, mask_tint, o_ptr, n, kind, m, tint,
+                                                  int(bool(whole_samples))))
         return out
+
+    def kurtosis_mask(self, sk, lo=None, hi=None, tint=0, sigma=3.0):
+        """The antenna mask from ``kurtosis``'s sk (fxcorr.h fxc_kurtosis_antenna_mask): ``sk`` = float32 [n_chunks, n_ant, n_tbin,
+        nchan] as ``kurtosis(x, tint=tint)`` returned it -> float32 of the same shape in the memory of sk, the ``mask`` of
+        ``beamform(.., mask_tint=tint)``: 1 where ``lo <= sk <= hi``, else 0 (a NaN gives 0).  Thresholds that are not given come
+        from ``sk_thresholds(M, sigma)`` with M the frames of a full bin; a partial last bin that is not the chunk's only bin gets
+        ``sk_thresholds(M_last, sigma)`` of its own count whatever ``lo`` and ``hi`` are, and (-inf, inf) below 2 frames, where sk
+        is exactly 1."""
+        self._sync_stream()
+        tint = int(tint)
+        device = _is_torch(sk)
+        if device:
+            import torch
+            if sk.dtype != torch.float32 or not sk.is_cuda or sk.device.index != self.device:
+                raise ValueError("device sk must be a float32 CUDA tensor on device {}".format(self.device))
+            keep = sk.contiguous()
+            ptr, kind = keep.data_ptr(), _lib.FXC_MEM_DEVICE
+        else:
+            keep = np.ascontiguousarray(sk, dtype=np.float32)
+            ptr, kind = keep.ctypes.data, _lib.FXC_MEM_HOST
+        span = tint if 0 < tint <= self.n_pts else self.n_pts
+        n_tbin = -(-self.n_pts // span) if span else 1
+        shape = tuple(keep.shape)
+        if len(shape) != 4 or shape[1:] != (self.n_ant, n_tbin, self.nchan):
+            raise ValueError("sk must have shape (n_chunks, {}, {}, {}), got {}".format(self.n_ant, n_tbin, self.nchan, shape))
+        if lo is None or hi is None:
+            t_lo, t_hi = sk_thresholds(span, sigma)
+            lo, hi = (t_lo if lo is None else lo), (t_hi if hi is None else hi)
+        m_last = self.n_pts % span if span else 0
+        lo_last, hi_last = sk_thresholds(m_last, sigma) if m_last >= 2 else (-np.inf, np.inf)
+        mask, m_ptr = self._out_like_rows(shape, np.float32, keep, device)
+        self._sk_keep = keep
+        self._check(self._lib.fxc_kurtosis_antenna_mask(self._h, ptr, int(shape[0]), tint, float(lo), float(hi), float(lo_last),
+                                                        float(hi_last), m_ptr, kind))
+        return mask
 
     def _float_out(self, out, shape, device, like, name="out"):
         """a float32 result of ``shape`` in the memory of the samples: ``out`` checked, or a new array / tensor -> (array, ptr)"""

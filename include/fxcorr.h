@@ -269,7 +269,7 @@ int fxc_track_gains_info(const fxc_plan* plan, int64_t* n_solutions, int64_t* in
  * off for such plans).  A complex64 sample that was read once (8 bytes) is additionally read and written once: about 3 x the
  * sample traffic at the headline shape (derived, not measured).  Reading at an offset inside the F kernels is the follow-up that
  * removes that cost.  fxc_beamform on a plan with shifts or an aligned track returns FXC_ERR_UNSUPPORTED (its passes are not
- * aligned; it forms no unaligned beams silently).  fxc_channelize, fxc_estimate_delay(s), fxc_remove_dc and fxc_convert_u8 take
+ * aligned; it forms no unaligned beams silently); fxc_beamform_ex with align = 1 aligns them.  fxc_channelize, fxc_estimate_delay(s), fxc_remove_dc and fxc_convert_u8 take
  * streams, not antennas, and are untouched. */
 int fxc_set_sample_delays(fxc_plan* plan, const int64_t* shift_samples);
 int fxc_set_delay_track_aligned(fxc_plan* plan, const double* tau0_s, const double* rate_s_per_chunk, double bandwidth,
@@ -693,12 +693,45 @@ int fxc_average_rows(fxc_plan* plan, const void* rows, const void* weights, int6
  * input.  The call does not touch the accumulator (a pending fold is launched first).
  * FXC_OK: n_chunks == 0 (nothing is read).  FXC_ERR_ARG: a NULL argument, n_beam < 1, n_chunks < 0, an unknown mode or mem_kind
  * (FXC_MEM_DEVICE_TO_PINNED included), tint < 0 or tint > n_pts.  FXC_ERR_UNSUPPORTED: n_beam > 16.  FXC_ERR_STATE: the plan has
- * a track and an fxc_pipe uses the plan.
- * Out of scope: uint8 and complex128 input, pipes, more than 16 beams, incoherent beams (sums of the antennas' powers),
- * Correlator integration, bench.py. */
+ * a track and an fxc_pipe uses the plan.  A plan with whole-sample delays: FXC_ERR_UNSUPPORTED (fxc_beamform_ex aligns its passes).
+ * Out of scope: uint8 and complex128 input, pipes, more than 16 beams, Correlator integration, bench.py. */
 enum fxc_beam_mode { FXC_BEAM_POWER = 0, FXC_BEAM_VOLTAGE = 1 };
+enum fxc_beam_mode_ex { FXC_BEAM_INCOHERENT = 2 };      /* the third mode, of fxc_beamform_ex alone: fxc_beamform's modes stay two */
 int fxc_beamform(fxc_plan* plan, const void* x, const void* weights, int n_beam, void* out, int64_t n_chunks, int mem_kind, int mode,
                  int64_t tint);
+
+/* fxc_beamform with an antenna mask, incoherent beams and aligned passes.  With mask == NULL, mode POWER or
+ * VOLTAGE and align == 0 it is fxc_beamform: the same kernels, the same bits.  Everything fxc_beamform's contract says holds
+ * here; what follows is what is added.
+ * mask (may be NULL: every antenna counts) = float32 [n_chunks][n_ant][n_mbin][nchan] in the memory of x (mem_kind), channels in
+ * the rows' fftshifted order k' = (k + nchan / 2) % nchan: exactly the layout fxc_kurtosis(.., tint = mask_tint) writes sk in and
+ * fxc_kurtosis_antenna_mask writes the mask in.  mask_tint = frames per mask bin, 0 = n_pts, 1 .. n_pts allowed; n_mbin =
+ * ceil(n_pts / mask_tint); frame i is under mask bin i / mask_tint; mask_tint and tint are independent.  Antenna a counts in a
+ * cell iff its mask value is > 0 (a NaN does not count): the convention of every `weights` argument.  A sample that does not count
+ * is selected away, not multiplied: a NaN, an Inf or a tone in it changes no bit of the output.
+ * POWER, VOLTAGE:  y_b[c,i,k] = sum_{a counted} weff[c,b,a,k] f_a[c,i,k], weff = w * rho as in fxc_beamform; the select is made on
+ *   the loaded sample, ahead of the same fused multiply-adds in the same antenna and frame order, so a mask that is > 0 everywhere
+ *   gives fxc_beamform's output bit for bit.  No normalisation is written: the sum of (mask > 0) over the antennas is the count of
+ *   antennas in a cell, and the caller rescales by (n_ant / count)^2 for a point source (tint == mask_tint keeps one count a bin).
+ * FXC_BEAM_INCOHERENT:  out[c][b][j][k'] = mean_{i in bin j} sum_{a counted} |weff[c,b,a,k]|^2 |f_a[c,i,k]|^2, float32 with POWER's
+ *   shape, bins and partial-last-bin rule.  A gain track therefore scales the antennas and a plain delay track changes nothing.
+ *   The arithmetic, float32: p = fma(im, im, re re) of the sample, g2 = fma(gy, gy, gx gx) of weff; per frame q = fma(g2, p, q) over
+ *   the antennas in index order from q = 0; the bin adds the frames' q in frame order from 0 and divides by its own count.  The
+ *   coherent power minus this is the cross-only power 2 Re sum_{a<b} weff_a conj(weff_b) f_a conj(f_b).
+ * align = 0: a plan with whole-sample delays (fxc_set_sample_delays, fxc_set_delay_track_aligned) is refused exactly as fxc_beamform
+ *   refuses it.  align = 1: every pass is first copied, shifted, into the plan's alignment buffer exactly as a pass of fxc_fx_rows
+ *   is, and the F stage reads from there; under an aligned track the pass's chunks take the shifts and the aligned tables of the
+ *   plan's counter onwards.  The pass costs what it costs fxc_fx_rows (fxc_set_sample_delays above).  On a plan without
+ *   whole-sample delays align has no effect and no alignment kernel is launched.
+ * The passes keep the spectra, the effective weights, the staging of a host mask and the alignment buffer within the workspace
+ * target; no output bit depends on the pass, the workspace target, the batch or host against device input.
+ * FXC_ERR_ARG: as fxc_beamform, and a mode outside the three, mask_tint < 0 or > n_pts, align not 0 or 1 (INCOHERENT has no
+ * voltage form: its output is always power).  FXC_ERR_UNSUPPORTED: n_beam > 16; whole-sample delays with align == 0.
+ * FXC_ERR_STATE: a pipe on a plan with a track, or on a plan with whole-sample delays and align == 1.  A failed call puts the
+ * track's counter back.
+ * Out of scope: uint8 and complex128 input, pipes, Correlator integration, a normalised output, more than 16 beams, per-beam masks. */
+int fxc_beamform_ex(fxc_plan* plan, const void* x, const void* weights, int n_beam, const void* mask, int64_t mask_tint, void* out,
+                    int64_t n_chunks, int mem_kind, int mode, int64_t tint, int align);
 
 /* Spectral kurtosis per antenna, from the spectra (Nita & Gary 2010): the interference detector that runs before
  * any correlation -- on unstopped fringes, on one receiver's own interference, and inside a chunk, where fxc_flag_rows sees
@@ -723,7 +756,7 @@ int fxc_beamform(fxc_plan* plan, const void* x, const void* weights, int n_beam,
  * target or host against device input.
  * FXC_OK: n_chunks == 0 (nothing is read).  FXC_ERR_ARG: a NULL plan, x or sk_out, n_chunks < 0, tint < 0, tint == 1,
  * tint > n_pts, an unknown mem_kind (FXC_MEM_DEVICE_TO_PINNED included).  FXC_ERR_UNSUPPORTED: n_pts < 2.
- * Out of scope: uint8 and complex128 input, pipes, Correlator integration, per-antenna weights for the beamformer. */
+ * Out of scope: uint8 and complex128 input, pipes, Correlator integration. */
 int fxc_kurtosis(fxc_plan* plan, const void* x, void* sk_out, void* power_out, int64_t n_chunks, int mem_kind, int64_t tint);
 
 /* The row weights from fxc_kurtosis's sk: the array every `weights` and `prior` argument takes (fxc_flag_rows,
@@ -736,6 +769,17 @@ int fxc_kurtosis(fxc_plan* plan, const void* x, void* sk_out, void* power_out, i
  * mem_kind, lo or hi not finite, lo > hi.  FXC_ERR_UNSUPPORTED: n_pts < 2. */
 int fxc_kurtosis_weights(fxc_plan* plan, const void* sk, int64_t n_chunks, int64_t tint, double lo, double hi, void* weights_out,
                          int mem_kind);
+
+/* The antenna mask from fxc_kurtosis's sk: the `mask` of fxc_beamform_ex (mask_tint = tint), which sums antennas, not baselines.
+ * sk and mask_out = [n_chunks][n_ant][n_tbin][nchan] float32 in the memory of sk (mem_kind), sk as fxc_kurtosis(.., tint) wrote it.
+ * mask[c][a][j][k'] = 1.0 iff lo_j <= sk <= hi_j, else 0.0: comparisons in float64 on the float32 values, so a NaN gives 0.
+ * (lo_j, hi_j) = (lo_last, hi_last) for a partial last bin that is not the chunk's only bin -- its count is not the one (lo, hi)
+ * were made for --, and (lo, hi) otherwise.  Infinite thresholds are allowed (a last bin of one frame has sk = 1 exactly and no
+ * evidence: Python gives it (-inf, inf)).
+ * FXC_OK: n_chunks == 0.  FXC_ERR_ARG: a NULL plan, sk or mask_out, n_chunks < 0, tint < 0, tint == 1, tint > n_pts, an unknown
+ * mem_kind, a threshold that is NaN, lo > hi, lo_last > hi_last.  FXC_ERR_UNSUPPORTED: n_pts < 2. */
+int fxc_kurtosis_antenna_mask(fxc_plan* plan, const void* sk, int64_t n_chunks, int64_t tint, double lo, double hi, double lo_last,
+                              double hi_last, void* mask_out, int mem_kind);
 
 /* Host-fed front end: replaces the reference's blocking per-chunk copies
  * (effex.py:391-392, 508-509, 693).  A pipe owns `depth` slots of pinned host staging + device buffers.

@@ -18,6 +18,10 @@ With 4 beams the beam pass reads the bytes of the X-engine pass and issues its 1
 complex multiply-adds against 28 cross products and 8 autos); the expectation is beam pass <= 1.15 x X-engine pass.
 
     python tools/bench_beamform.py [--reps 10] [--out profiles/beamform/times.json] [--quick]
+
+Masks and incoherent beams (fxc_beamform_ex; mask_main below): the masked and the incoherent passes beside the
+unmasked beam_kernel pass of the same run, 1, 4 and 8 beams:
+    python tools/bench_beamform.py --mask-tint 8 --mask-tint 64 [--mode INCOHERENT] [--reps 7] --out profiles/beam_mask/times.json
 """
 import argparse
 import csv
@@ -72,8 +76,80 @@ def write(path, rec):
             fh.write("\n")
 
 
+def mask_main(args):
+    """--mask-tint / --mode INCOHERENT (fxc_beamform_ex): in one run, per beam count (1, 4, 8) and mask_tint, the
+    beam pass -- a call's kernel time minus the F stage's of the same rep -- of beam_kernel (no mask), of the masked kernel and of the
+    incoherent kernel with and without the mask, tint 0, and each one's ratio to the unmasked pass of the same run.  The derived
+    traffic ratio of a masked pass is 1 + 1 / (2 mask_tint) (4 mask bytes per mask_tint frames beside 8 sample bytes a frame); what
+    exceeds it is instruction issue.  No time is a pass / fail condition."""
+    import torch
+    import numpy as np
+    from effex_amd.plan import FxPlan, synth_fill
+    assert torch.cuda.is_available(), "bench_beamform.py measures on the GPU only"
+    n_chunks = 8 if args.quick else N_CHUNKS
+    n_pts = NUM_SAMP // NCHAN
+    mask_tints = args.mask_tint or [8, 64]
+    x = torch.empty((n_chunks, N_ANT, NUM_SAMP), dtype=torch.complex64, device="cuda")
+    synth_fill(x, 2024, delays=np.arange(N_ANT) % 5)
+    gen = torch.Generator(device="cuda").manual_seed(7)
+    lines = []
+    with FxPlan(N_ANT, NCHAN, NTAPS, NUM_SAMP) as plan:
+        plan.kernel_profiling(True)
+        for n_beam in (1, 4, 8):
+            w = torch.view_as_complex(torch.randn((n_beam, N_ANT, NCHAN, 2), generator=gen, device="cuda") / 2.0 ** 0.5)
+            out = torch.empty((n_chunks, n_beam, 1, NCHAN), dtype=torch.float32, device="cuda")
+            for mt in mask_tints:
+                n_mbin = -(-n_pts // mt)
+                mask = (torch.rand((n_chunks, N_ANT, n_mbin, NCHAN), generator=gen, device="cuda") >= 0.3).to(torch.float32)
+                runs = {"unmasked": lambda: plan.beamform(x, w, out=out),
+                        "masked": lambda: plan.beamform(x, w, out=out, mask=mask, mask_tint=mt),
+                        "incoherent": lambda: plan.beamform_incoherent(x, w, out=out),
+                        "incoherent_masked": lambda: plan.beamform_incoherent(x, w, out=out, mask=mask, mask_tint=mt)}
+                if args.mode == "INCOHERENT":
+                    runs = {k: v for k, v in runs.items() if k != "masked"}
+                t = {k: [] for k in runs}
+                t["f"] = []
+                for rep in range(args.warmup + args.reps):
+                    plan.kernel_time()
+                    spec = plan.channelize(x.view(-1, NUM_SAMP))
+                    torch.cuda.synchronize()
+                    f_ms = plan.kernel_time()[0]
+                    del spec
+                    got = {}
+                    for name, fn in runs.items():
+                        fn()
+                        torch.cuda.synchronize()
+                        got[name] = plan.kernel_time()[0] - f_ms
+                    if rep >= args.warmup:
+                        t["f"].append(f_ms)
+                        for name, v in got.items():
+                            t[name].append(v)
+                spectra_bytes = n_chunks * N_ANT * n_pts * NCHAN * 8
+                line = {"kind": "beam_mask", "device": torch.cuda.get_device_name(0), "n_ant": N_ANT, "nchan": NCHAN, "ntaps": NTAPS,
+                        "num_samp": NUM_SAMP, "n_chunks": n_chunks, "n_beam": n_beam, "tint": 0, "mask_tint": mt, "reps": args.reps,
+                        "spectra_bytes": spectra_bytes, "mask_bytes": int(mask.numel()) * 4,
+                        "derived_traffic_ratio": round(1.0 + 1.0 / (2.0 * mt), 4)}
+                for key, v in t.items():
+                    line[key + "_pass_ms" if key != "f" else "f_ms"] = round(median(v), 4)
+                    line[(key + "_pass_ms" if key != "f" else "f_ms") + "_all"] = [round(q, 4) for q in v]
+                for key in runs:
+                    if key != "unmasked":
+                        line[key + "_over_unmasked"] = round(line[key + "_pass_ms"] / line["unmasked_pass_ms"], 3)
+                    line[key + "_TBs"] = round(spectra_bytes / (line[key + "_pass_ms"] * 1e-3) / 1e12, 3)
+                print(json.dumps(line), flush=True)
+                lines.append(line)
+                del mask
+            del w, out
+    if args.out:
+        write(args.out, {"lines": lines})
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--mask-tint", type=int, action="append", default=[], metavar="N",
+                    help="time the masked and incoherent passes at N frames a mask bin beside the unmasked pass (repeatable; with "
+                         "--mode INCOHERENT alone: 8 and 64); --out profiles/beam_mask/times.json")
+    ap.add_argument("--mode", default="POWER", choices=["POWER", "INCOHERENT"], help="INCOHERENT: the incoherent passes (and the unmasked one) only")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
@@ -84,6 +160,8 @@ def main():
     args = ap.parse_args()
     if args.merge:
         return merge(args)
+    if args.mask_tint or args.mode == "INCOHERENT":
+        return mask_main(args)
     import torch
     import numpy as np
     from effex_amd.plan import FxPlan, synth_fill
