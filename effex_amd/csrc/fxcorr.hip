@@ -4,7 +4,7 @@
 //   fx_math.h, fx_fused4096.h, fx_tiled.h, fx_small.h, fx_mixed.h   index maps, butterflies and kernel phases (also compiled by
 //                                           g++ for the host emulation under tests/emul)
 //   k_generic.h k_finish.h k_xmfma.h k_fused4096.h k_tiled.h k_small.h k_prepass.h k_stream.h k_conditioning.h k_track.h k_align.h k_synth.h
-//   k_delay.h k_fringe.h k_gains.h k_flag.h k_average.h k_beam.h k_kurtosis.h
+//   k_delay.h k_fringe.h k_gains.h k_flag.h k_average.h k_beam.h k_kurtosis.h k_dedisperse.h
 //                                           the __global__ kernels, one file per path / step and per rows tool (delays, fringe fit,
 //                                           gain solve, detector, averager, beamformer, spectral kurtosis)
 //   h_plan.h h_rtc.h h_launch.h h_build.h h_run.h h_ingest.h h_tools.h h_rccl.h
@@ -148,6 +148,7 @@ int64_t ws_target() {
 #include "k_average.h"
 #include "k_beam.h"
 #include "k_kurtosis.h"
+#include "k_dedisperse.h"
 #include "k_synth.h"
 #include "h_plan.h"
 #include "h_rtc.h"
@@ -1189,6 +1190,24 @@ int fxc_average_rows(fxc_plan* p, const void* rows, const void* weights, int64_t
     if (time_bin == 0 || time_bin > n_chunks) time_bin = n_chunks;
     return average_rows_batch(p, static_cast<const cf*>(rows), static_cast<const float*>(weights), n_chunks, mem_kind, time_bin, freq_bin,
                               static_cast<cf*>(out_rows), static_cast<float*>(out_weights));
+}
+
+int fxc_dedisperse(fxc_plan* p, const void* power, int64_t n_chunks, int64_t n_series, int64_t n_tbin, int mem_kind, const int32_t* shifts,
+                   int n_dm, const float* chan_weights, void* out, int64_t* info_out) {
+    if (!p || !power || !shifts || !out) return fail(p, FXC_ERR_ARG, "NULL argument");
+    if (n_chunks < 1 || n_series < 1 || n_tbin < 1)
+        return fail(p, FXC_ERR_ARG, "n_chunks=%lld, n_series=%lld, n_tbin=%lld: each must be 1 or more", (long long)n_chunks, (long long)n_series,
+                    (long long)n_tbin);
+    if (n_dm < 1) return fail(p, FXC_ERR_ARG, "n_dm=%d is not 1 or more", n_dm);
+    if (const int rc = bad_mem_kind(p, mem_kind)) return rc;
+    DedTable table;
+    if (const int rc = build_ded_table(p, shifts, n_dm, chan_weights, &table)) return rc;
+    if (n_chunks >= (1ll << 31) || n_tbin >= (1ll << 31) || n_chunks * n_tbin >= (1ll << 31))
+        return fail(p, FXC_ERR_UNSUPPORTED, "n_t = %lld chunks of %lld bins: the time axis is addressed in 31 bits", (long long)n_chunks,
+                    (long long)n_tbin);
+    if (table.s_max >= n_chunks * n_tbin)
+        return fail(p, FXC_ERR_ARG, "the largest shift %lld leaves no output: n_t is %lld", (long long)table.s_max, (long long)(n_chunks * n_tbin));
+    return dedisperse_batch(p, static_cast<const float*>(power), n_chunks, n_series, n_tbin, mem_kind, table, static_cast<float*>(out), info_out);
 }
 
 namespace {

@@ -1,6 +1,6 @@
 // Part of libfxcorr's single translation unit: included by fxcorr.hip (not a stand-alone header).
-// The rows tools' drivers -- delays, fringe fit, gain solve, detector, averager, beamformer, spectral kurtosis -- and the host helpers
-// they share.
+// The rows tools' drivers -- delays, fringe fit, gain solve, detector, averager, beamformer, spectral kurtosis, dedispersion -- and
+// the host helpers they share.
 // The entry points that check a call's arguments and hand it to a driver are in fxcorr.hip.
 #pragma once
 
@@ -993,6 +993,178 @@ int kurtosis_weights_dev(fxc_plan* p, const float* sk, float* weights, int64_t n
     hipLaunchKernelGGL(kurtosis_weights_kernel, dim3(grid_for(total, 256, p->cu_count)), dim3(256), 0, p->stream, sk, weights, p->n_ant,
                        p->n_base, p->nchan, n_tbin, n_count, n_chunks, lo, hi);
     FXC_HIP(p, hipGetLastError());
+    return FXC_OK;
+}
+
+// A call's trial table as the dedispersion kernels (k_dedisperse.h) read it, made on the host from the caller's shifts and channel
+// weights: the groups of kDedD consecutive trials, which of them the tiled kernel serves, and the geometry that follows.  The
+// decision tiled against direct and the LDS a launch needs are made here alone.
+struct DedTable {
+    int n_dm = 0, n_groups = 0, n_step = 0;
+    int64_t s_max = 0;
+    // shifts [n_groups][n_step 32][kDedD], chan [n_step 32], cnt [n_step], bs [n_groups][n_step][2], the tiled groups, the direct groups
+    std::vector<int> words;
+    int64_t o_chan = 0, o_cnt = 0, o_bs = 0, o_tiled = 0, o_direct = 0;      // offsets into words
+    int n_tiled = 0, n_direct = 0;          // groups
+    int64_t trials_tiled = 0, trials_direct = 0;
+    int wp = 0;                             // words of a channel's LDS line in the tiled launches: odd
+    DedTab on_device(const int* d_words) const {
+        return DedTab{d_words, d_words + o_chan, d_words + o_cnt, d_words + o_bs, n_step, n_dm};
+    }
+};
+
+// -> FXC_ERR_ARG for a negative shift (the only check of the table's values; the caller compares s_max with n_t)
+int build_ded_table(fxc_plan* p, const int32_t* shifts, int n_dm, const float* chan_weights, DedTable* t) {
+    const int nchan = p->nchan;
+    t->n_dm = n_dm;
+    t->n_groups = (n_dm + kDedD - 1) / kDedD;
+    t->n_step = (nchan + kDedStep - 1) / kDedStep;
+    for (int64_t i = 0; i < (int64_t)n_dm * nchan; ++i) {
+        if (shifts[i] < 0)
+            return fail(p, FXC_ERR_ARG, "shifts[%lld][%lld]=%d is negative", (long long)(i / nchan), (long long)(i % nchan), (int)shifts[i]);
+        t->s_max = std::max<int64_t>(t->s_max, shifts[i]);
+    }
+    const int64_t n_slots = (int64_t)t->n_step * kDedStep;
+    t->o_chan = (int64_t)t->n_groups * n_slots * kDedD;
+    t->o_cnt = t->o_chan + n_slots;
+    t->o_bs = t->o_cnt + t->n_step;
+    t->o_tiled = t->o_bs + (int64_t)t->n_groups * t->n_step * 2;
+    t->o_direct = t->o_tiled + t->n_groups;
+    t->words.assign((size_t)(t->o_direct + t->n_groups), 0);
+    int* const w = t->words.data();
+    // the counted channels of every step, in ascending order (a NaN weight does not count)
+    for (int q = 0; q < t->n_step; ++q)
+        for (int k = q * kDedStep; k < std::min(nchan, (q + 1) * kDedStep); ++k)
+            if (!chan_weights || chan_weights[k] > 0.f) w[t->o_chan + q * kDedStep + w[t->o_cnt + q]++] = k;
+    int span_max = 0;
+    for (int g = 0; g < t->n_groups; ++g) {
+        const int d0 = g * kDedD, nd = std::min(kDedD, n_dm - d0);
+        bool fits = true;
+        int span_g = 0;
+        for (int q = 0; q < t->n_step; ++q) {
+            int lo = INT32_MAX, hi = 0;
+            for (int i = 0; i < w[t->o_cnt + q]; ++i) {
+                const int64_t slot = (int64_t)q * kDedStep + i;
+                const int k = w[t->o_chan + slot];
+                for (int d = 0; d < kDedD; ++d) {
+                    const int sh = shifts[(int64_t)(d0 + (d < nd ? d : 0)) * nchan + k];
+                    w[((int64_t)g * n_slots + slot) * kDedD + d] = sh;
+                    lo = std::min(lo, sh);
+                    hi = std::max(hi, sh);
+                }
+            }
+            if (lo > hi) lo = hi = 0;      // no channel of the step counts: the step is skipped
+            w[t->o_bs + 2 * ((int64_t)g * t->n_step + q)] = lo;
+            w[t->o_bs + 2 * ((int64_t)g * t->n_step + q) + 1] = hi - lo;
+            if (hi - lo > kDedMaxSpan) fits = false;
+            span_g = std::max(span_g, hi - lo);
+        }
+        if (fits) {
+            w[t->o_tiled + t->n_tiled++] = g;
+            t->trials_tiled += nd;
+            span_max = std::max(span_max, span_g);
+        } else {
+            w[t->o_direct + t->n_direct++] = g;
+            t->trials_direct += nd;
+        }
+    }
+    t->wp = (kDedT + span_max) | 1;
+    return FXC_OK;
+}
+
+// A launch of the dedispersion kernels over n_o output times of n_series series that lie s_in (outputs: s_out) elements apart: what
+// the call site means; the grids are decided here alone, each dimension bounded by the grid limits
+struct DedLaunch {
+    DedIn in;
+    int64_t s_in;
+    int64_t n_series;
+    unsigned t_lo, n_o;              // the first output time, in the time axis of `in`, and the outputs
+    float* out;                      // output (series 0, trial 0, time t_lo)
+    int64_t s_out, o_stride;         // elements between series and between trials
+};
+
+int launch_dedisperse(fxc_plan* p, const DedTable& t, const int* d_words, const DedLaunch& k) {
+    const unsigned n_tiles = (k.n_o + kDedT - 1) / kDedT;
+    const size_t lds = (size_t)kDedStep * t.wp * sizeof(float);
+    const DedTab tb = t.on_device(d_words);
+    // the tiled kernel's x: the tiles rounded up to eight, times the groups of the launch -- as many as keep it within 31 bits
+    const int64_t tiles8 = ((int64_t)n_tiles + 7) / 8 * 8;
+    const int64_t ng_max = std::max<int64_t>(1, std::min<int64_t>(kGridMax, ((1ll << 31) - 1) / tiles8));
+    for (int64_t s0 = 0; s0 < k.n_series; s0 += kGridMax) {
+        const unsigned ns = (unsigned)std::min(kGridMax, k.n_series - s0);
+        DedIn in = k.in;
+        in.p += s0 * k.s_in;
+        float* out = k.out + s0 * k.s_out;
+        for (int64_t g0 = 0; g0 < t.n_tiled; g0 += ng_max) {
+            const int64_t ng = std::min<int64_t>(ng_max, t.n_tiled - g0);
+            hipLaunchKernelGGL(dedisperse_tiled_kernel, dim3((unsigned)(tiles8 * ng), 1, ns), dim3(kDedThreads), lds, p->stream, in, k.s_in, tb,
+                               d_words + t.o_tiled + g0, (unsigned)ng, n_tiles, k.t_lo, k.n_o, out, k.s_out, k.o_stride, t.wp);
+        }
+        constexpr int64_t per = kGridMax / kDedD;      // groups of a direct launch
+        for (int64_t g0 = 0; g0 < t.n_direct; g0 += per)
+            hipLaunchKernelGGL(dedisperse_direct_kernel, dim3(n_tiles, (unsigned)(std::min<int64_t>(per, t.n_direct - g0) * kDedD), ns),
+                               dim3(kDedThreads), 0, p->stream, in, k.s_in, tb, d_words + t.o_direct + g0, k.t_lo, k.n_o, out, k.s_out,
+                               k.o_stride);
+    }
+    FXC_HIP(p, hipGetLastError());
+    return FXC_OK;
+}
+
+// Dedispersion (fxcorr.h fxc_dedisperse; kernels in k_dedisperse.h) after the argument checks; the table is valid and s_max < n_t.
+// The workspace holds the table and, for host power, a slab: some whole chunks of one series (one strided copy in) and the
+// outputs of every trial over the slab's times (one strided copy back).  A slab's outputs are the times whose samples, s_max
+// further on included, lie inside it; the next slab starts with the chunk of the next output, so consecutive slabs overlap by the
+// halo.  Slabs are sized by the workspace target (FXC_WS_MB) and hold at least the chunks one output needs wherever it lies in its
+// chunk.  Device power needs no staging.  An output cell belongs to one thread of one launch, and no sum depends on the tile, so
+// no bit depends on the sizes.  One synchronisation ends the call.
+int dedisperse_batch(fxc_plan* p, const float* power, int64_t n_chunks, int64_t n_series, int64_t n_tbin, int mem_kind, const DedTable& t,
+                     float* out, int64_t* info_out) {
+    FXC_DEVICE(p, p->device);
+    const int nchan = p->nchan, n_dm = t.n_dm;
+    const int64_t n_t = n_chunks * n_tbin, n_out = n_t - t.s_max;
+    const int64_t chunk_elems = n_tbin * nchan;
+    const bool host = mem_kind == FXC_MEM_HOST;
+    const int64_t tab_bytes = up256((int64_t)t.words.size() * (int64_t)sizeof(int));
+    const int64_t need = std::min(n_chunks, 1 + (t.s_max + n_tbin - 1) / n_tbin);
+    const int64_t per_chunk = (chunk_elems + (int64_t)n_dm * n_tbin) * (int64_t)sizeof(float);
+    const int64_t cs = host ? std::min(n_chunks, std::max(need, (ws_target() - tab_bytes - 2 * 256) / per_chunk)) : 0;
+    WsCarver ws;
+    const int64_t o_tab = ws.take(tab_bytes), o_stage = ws.take(up256(cs * chunk_elems * (int64_t)sizeof(float)));
+    const int64_t o_res = ws.take(up256(cs * n_tbin * n_dm * (int64_t)sizeof(float)));
+    if (const int rc = ensure_ws(p, ws.total())) return rc;
+    FXC_HIP(p, hipFuncSetAttribute(reinterpret_cast<const void*>(&dedisperse_tiled_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   kDedLdsBytes));
+    int* d_words = ws_at<int>(p, o_tab);
+    FXC_HIP(p, hipMemcpyAsync(d_words, t.words.data(), t.words.size() * sizeof(int), hipMemcpyHostToDevice, p->stream));
+    if (!host) {
+        // one chunk, or one series: the time axis is contiguous
+        const bool flat = n_chunks == 1 || n_series == 1;
+        const DedIn in{power, flat ? 0 : (n_series - 1) * chunk_elems, (unsigned)(flat ? n_t : n_tbin), (unsigned)n_t, nchan};
+        if (const int rc = launch_dedisperse(p, t, d_words, {in, chunk_elems, n_series, 0u, (unsigned)n_out, out, (int64_t)n_dm * n_out, n_out}))
+            return rc;
+    } else {
+        float* stage = ws_at<float>(p, o_stage);
+        float* res = ws_at<float>(p, o_res);
+        const int64_t cap = cs * n_tbin;
+        for (int64_t s = 0; s < n_series; ++s) {
+            for (int64_t o0 = 0; o0 < n_out;) {
+                const int64_t c0 = o0 / n_tbin, c1 = std::min(n_chunks, c0 + cs), o1 = std::min(n_out, c1 * n_tbin - t.s_max);
+                const int64_t n_loc = (c1 - c0) * n_tbin;
+                FXC_HIP(p, copy_rows(p, stage, chunk_elems, power + (c0 * n_series + s) * chunk_elems, n_series * chunk_elems, chunk_elems,
+                                     c1 - c0, hipMemcpyHostToDevice));
+                const DedIn in{stage, 0, (unsigned)n_loc, (unsigned)n_loc, nchan};
+                if (const int rc = launch_dedisperse(p, t, d_words, {in, 0, 1, (unsigned)(o0 - c0 * n_tbin), (unsigned)(o1 - o0), res, 0, cap}))
+                    return rc;
+                FXC_HIP(p, copy_rows(p, out + s * n_dm * n_out + o0, n_out, res, cap, o1 - o0, (int64_t)n_dm, hipMemcpyDeviceToHost));
+                o0 = o1;
+            }
+        }
+    }
+    FXC_HIP(p, hipStreamSynchronize(p->stream));
+    if (info_out) {
+        info_out[0] = t.trials_tiled;
+        info_out[1] = t.trials_direct;
+    }
     return FXC_OK;
 }
 

@@ -175,6 +175,33 @@ def averaged_freqs(nchan, bandwidth, frequency, freq_bin=1):
     return np.array([freqs[k:k + freq_bin].mean() for k in range(0, nchan, freq_bin)])
 
 
+DM_CONSTANT_S = 4.148808e3      # seconds of delay per unit DM (pc cm^-3) at 1 MHz, against infinite frequency
+
+
+def dm_shifts(nchan, bandwidth, frequency, dms, tsamp):
+    """The shift table of ``FxPlan.dedisperse``, int32 [n_dm, nchan]: channel k of the rows' fftshifted order has the frequency
+    ``f = frequency + fftshift(fftfreq(nchan, 1 / bandwidth))[k]`` (the axis of ``averaged_freqs``), lags the top of the band by
+    ``4.148808e3 s * DM * ((f / MHz)^-2 - (f_max / MHz)^-2)`` at dispersion measure DM, and its shift is that delay over ``tsamp``
+    seconds rounded to the nearest sample, formed in float64.  The top channel's shift is 0.  A beam's ``tsamp`` is ``tint * nchan /
+    bandwidth``."""
+    nchan = int(nchan)
+    dms = np.atleast_1d(np.asarray(dms, dtype=np.float64))
+    if nchan < 1 or dms.ndim != 1 or dms.size < 1:
+        raise ValueError("nchan must be 1 or more and dms a list of one or more trials")
+    if not tsamp > 0 or not bandwidth > 0:
+        raise ValueError("tsamp and bandwidth must be > 0")
+    if not (np.isfinite(dms).all() and (dms >= 0).all()):
+        raise ValueError("the trial dispersion measures must be finite and >= 0")
+    f_mhz = (np.fft.fftshift(np.fft.fftfreq(nchan, d=1.0 / bandwidth)) + frequency) / 1e6
+    if not (f_mhz > 0).all():
+        raise ValueError("the band reaches 0 Hz or below")
+    delay = DM_CONSTANT_S * dms[:, None] * (f_mhz ** -2.0 - f_mhz.max() ** -2.0)[None, :]
+    steps = np.rint(delay / float(tsamp))
+    if steps.max() >= 2.0 ** 31:
+        raise ValueError("a shift does not fit 31 bits")
+    return steps.astype(np.int32)
+
+
 def sk_thresholds(M, sigma=3.0):
     """(lo, hi) = 1 -/+ sigma sqrt(mu2) for ``FxPlan.kurtosis_weights``, with mu2 = 4 M^2 / ((M - 1)(M + 2)(M + 3)) the variance
     of the spectral kurtosis estimator over ``M`` spectra of Gaussian noise (Nita & Gary 2010).  A symmetric approximation of a
@@ -1169,6 +1196,72 @@ class FxPlan(object):
         wsum, s_ptr = self._out_like_rows(out_shape, np.float32, keep, device)
         self._check(self._lib.fxc_average_rows(self._h, ptr, w_ptr, int(shape[0]), kind, time_bin, freq_bin, v_ptr, s_ptr))
         return vis, wsum
+
+    def dedisperse(self, power, shifts, chan_weights=None, out=None, return_info=False):
+        """Incoherent dedispersion of power at full time resolution (fxcorr.h fxc_dedisperse): ``power`` = float32 [n_chunks,
+        n_series, n_tbin, nchan] as ``beamform(.., mode="POWER")``, ``beamform_incoherent`` or ``kurtosis(.., return_power=True)``
+        return it (numpy, or a CUDA tensor on the plan's device); [n_series, n_t, nchan] and [n_t, nchan] are one chunk.
+        ``shifts`` = int32 [n_dm, nchan] from ``dm_shifts`` and ``chan_weights`` = float32 [nchan] or None are numpy, or are moved to
+        the host; a channel counts iff its weight is > 0 (None: all do), and what an uncounted channel holds is never used.
+        -> float32 [n_series, n_dm, n_t - shifts.max()] in the memory of power ([n_dm, ..] for 2-D power): the sum over the counted
+        channels of ``power[t + shifts[d, k], k]``, not normalised.  Every time bin must hold the same number of frames (``tint``
+        divides ``n_pts``).  ``out``: an array / tensor of the result's shape to receive it.  ``return_info`` -> (result, (trials
+        on the tiled kernel, trials on the direct kernel)).  The loop it closes::
+
+            P = plan.beamform(x, w, tint=16, mask=m, mask_tint=16)
+            sh = dm_shifts(nchan, bw, fc, dms, 16 * nchan / bw)
+            ts = plan.dedisperse(P, sh, chan_weights=band_ok)      # [n_beam, n_dm, n_t - sh.max()]
+        """
+        self._sync_stream()
+        device = _is_torch(power)
+        if device:
+            import torch
+            if power.dtype != torch.float32 or not power.is_cuda or power.device.index != self.device:
+                raise ValueError("device power must be a float32 CUDA tensor on device {}".format(self.device))
+            keep = power.contiguous()
+            ptr, kind = keep.data_ptr(), _lib.FXC_MEM_DEVICE
+        else:
+            if not isinstance(power, np.ndarray) or power.dtype != np.float32:
+                raise ValueError("power must be a float32 array or CUDA tensor")
+            keep = np.ascontiguousarray(power)
+            ptr, kind = keep.ctypes.data, _lib.FXC_MEM_HOST
+        shape = tuple(keep.shape)
+        if len(shape) not in (2, 3, 4) or shape[-1] != self.nchan or min(shape) < 1:
+            raise ValueError("power must have shape (n_chunks, n_series, n_tbin, {0}), (n_series, n_t, {0}) or (n_t, {0}), got {1}".format(
+                self.nchan, shape))
+        n_chunks, n_series, n_tbin = shape[:3] if len(shape) == 4 else ((1,) + shape[:2] if len(shape) == 3 else (1, 1, shape[0]))
+        if _is_torch(shifts):
+            shifts = shifts.cpu().numpy()
+        shifts = np.asarray(shifts)
+        if shifts.ndim != 2 or shifts.shape[1] != self.nchan or shifts.shape[0] < 1 or shifts.dtype.kind not in "iu":
+            raise ValueError("shifts must be an integer array of shape (n_dm, {}), got {} {}".format(self.nchan, shifts.dtype,
+                                                                                                      shifts.shape))
+        n_t = n_chunks * n_tbin
+        if shifts.min() < 0:
+            raise ValueError("shifts must be >= 0")
+        s_max = int(shifts.max())
+        if s_max >= n_t:
+            raise ValueError("the largest shift {} leaves no output: n_t is {}".format(s_max, n_t))
+        shifts = np.ascontiguousarray(shifts, dtype=np.int32)
+        w_ptr = None
+        if chan_weights is not None:
+            if _is_torch(chan_weights):
+                chan_weights = chan_weights.cpu().numpy()
+            chan_weights = np.asarray(chan_weights)
+            if chan_weights.shape != (self.nchan,) or chan_weights.dtype.kind != "f":
+                raise ValueError("chan_weights must be a float array of shape ({},)".format(self.nchan))
+            chan_weights = np.ascontiguousarray(chan_weights, dtype=np.float32)
+            w_ptr = chan_weights.ctypes.data
+        n_dm = int(shifts.shape[0])
+        want = (n_series, n_dm, n_t - s_max) if len(shape) != 2 else (n_dm, n_t - s_max)
+        res, o_ptr = self._float_out(out, want, device, keep)
+        if device and not self._follow:      # a stream of the plan's own: torch's may still be using the blocks it handed out
+            import torch
+            torch.cuda.current_stream(keep.device).synchronize()
+        info = np.zeros(2, dtype=np.int64)
+        self._check(self._lib.fxc_dedisperse(self._h, ptr, n_chunks, n_series, n_tbin, kind, shifts.ctypes.data, n_dm, w_ptr, o_ptr,
+                                             info.ctypes.data))
+        return (res, (int(info[0]), int(info[1]))) if return_info else res
 
     def set_gains(self, gains, delays_s=None, bandwidth=None, frequency=None, whole_samples=False):
         """Correct the rows for the per-antenna gains ``gains`` [n_ant, nchan] (one solution of ``solve_gains``, bins in the

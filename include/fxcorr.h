@@ -781,6 +781,44 @@ int fxc_kurtosis_weights(fxc_plan* plan, const void* sk, int64_t n_chunks, int64
 int fxc_kurtosis_antenna_mask(fxc_plan* plan, const void* sk, int64_t n_chunks, int64_t tint, double lo, double hi, double lo_last,
                               double hi_last, void* mask_out, int mem_kind);
 
+/* Incoherent dedispersion of power at full time resolution over trial dispersion measures: the step between a
+ * beam and a detection of a pulsar or a fast transient -- the channels added along the dispersion sweep, for many trials.
+ * power = float32 [n_chunks][n_series][n_tbin][nchan], nchan the plan's, channels in the rows' fftshifted order: exactly what
+ * fxc_beamform(.., FXC_BEAM_POWER), FXC_BEAM_INCOHERENT and the power_out of fxc_kurtosis write; n_series stands for beams or
+ * antennas.  mem_kind = FXC_MEM_HOST or FXC_MEM_DEVICE.  Time sample t = c n_tbin + j of chunk c, bin j; n_t = n_chunks n_tbin.
+ * Every bin must hold the same number of frames -- tint must divide n_pts --: the caller's business, stated, not checked.
+ * shifts = int32 [n_dm][nchan], HOST memory always: shifts[d][k] >= 0 is the number of time samples by which channel k lags at
+ * trial d.  chan_weights = float32 [nchan], HOST memory always, or NULL: channel k counts iff chan_weights == NULL or
+ * chan_weights[k] > 0 -- a NaN weight does not count, the convention of every `weights` argument here.  A channel that does not
+ * count is selected away, not multiplied: NaN, Inf or 1e30 in it changes no output bit.  A counted non-finite value propagates
+ * (stated, not checked).  Both are small, and the driver reads them before any device work.
+ * With S_max the largest entry of the whole table, counted channel or not, and n_out = n_t - S_max:
+ *   out[s][d][t] = sum over the counted k of P[t + shifts[d][k]][s][k],   t in [0, n_out)
+ * float32 [n_series][n_dm][n_out] in the memory kind of power.  Nothing is normalised: (chan_weights > 0).sum() is the count.
+ * The order of the additions: the channels are cut into segments of 64 from channel 0 of the rows' order, the last may be
+ * partial; a segment's sum is a float32 sum from +0 over its counted channels in ascending k -- plain adds, there is no product,
+ * so contraction cannot change it --; the output is the segments' sums added in float64 from 0 in segment order and rounded once
+ * to float32.  With no counted channel the output is +0.  No bit depends on which kernel served a trial, on how trials, times or
+ * series were tiled, on the workspace target, on host against device input or on the alignment of a device tensor.
+ * info_out (HOST, may be NULL): [0] the trials the tiled kernel served, [1] the trials the direct kernel served.  Trials go
+ * through in groups of 8 consecutive ones; a group takes the tiled kernel -- the samples of 32 channels transposed through LDS and
+ * read once for the whole group -- where, in every 32 channels, the spread of the group's shifts over the counted channels is at
+ * most 1023 samples, and the direct kernel, which keeps the contract total for any table with 0 <= shift < n_t, otherwise.
+ * Device power needs no staging; host power goes through the workspace per series in slabs of whole chunks with a halo of S_max
+ * samples, sized by the workspace target (FXC_WS_MB), a slab's outputs copied back; every output cell belongs to one launch.
+ * Uses the plan's device, stream and workspace; synchronises like fxc_average_rows (one synchronisation ends the call); neither
+ * reads nor changes the rot tables, the tracks, their counters or the accumulator (a pending fold is launched first).
+ * FXC_ERR_ARG, before any device work: a NULL plan / power / shifts / out, n_chunks, n_series, n_tbin or n_dm below 1, an unknown
+ * mem_kind (FXC_MEM_DEVICE_TO_PINNED included), a negative shift, S_max >= n_t.  FXC_ERR_UNSUPPORTED: n_t >= 2^31.
+ * out and info_out are written on FXC_OK only.
+ * Out of scope: coherent dedispersion of VOLTAGE beams, sub-band or tree algorithms, boxcar matched filtering and candidate
+ * sifting, folding, a per-time mask, frequency-averaged input, pipes, Correlator integration. */
+int fxc_dedisperse(fxc_plan* plan, const void* power, int64_t n_chunks, int64_t n_series, int64_t n_tbin, int mem_kind,
+                   const int32_t* shifts /* HOST, [n_dm][nchan] */, int n_dm,
+                   const float* chan_weights /* HOST, [nchan], may be NULL */,
+                   void* out /* [n_series][n_dm][n_out] float32, in the memory kind of power */,
+                   int64_t* info_out /* may be NULL: [0] trials on the tiled kernel, [1] trials on the direct kernel */);
+
 /* Host-fed front end: replaces the reference's blocking per-chunk copies
  * (effex.py:391-392, 508-509, 693).  A pipe owns `depth` slots of pinned host staging + device buffers.
  * fxc_pipe_acquire hands the producer the pinned input buffer of the next free slot
