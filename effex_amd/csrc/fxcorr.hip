@@ -1243,7 +1243,7 @@ int beamform_call(fxc_plan* p, const void* x, const void* weights, int n_beam, c
         rc = beamform_dev(p, static_cast<const cf*>(x), static_cast<const cf*>(weights), false, n_beam, static_cast<const float*>(mask),
                           mask_tint, out, n_chunks, mode, tint, align != 0);
     } else {
-        const int64_t n_tbin = tint ? (p->n_pts + tint - 1) / tint : 1;
+        const int64_t n_tbin = time_bins(p, tint).n_bin;
         const size_t ob = mode == FXC_BEAM_VOLTAGE ? (size_t)n_chunks * n_beam * p->n_pts * p->nchan * sizeof(cf)
                                                    : (size_t)n_chunks * n_beam * n_tbin * p->nchan * sizeof(float);
         rc = with_host_staging(p, x, (size_t)n_chunks * p->n_ant * p->num_samp * sizeof(cf), out, ob, [&](const cf* dx, void* dout) {
@@ -1278,7 +1278,7 @@ int fxc_kurtosis_antenna_mask(fxc_plan* p, const void* sk, int64_t n_chunks, int
     FXC_DEVICE(p, p->device);
     if (mem_kind == FXC_MEM_DEVICE)
         return kurtosis_mask_dev(p, static_cast<const float*>(sk), static_cast<float*>(mask_out), n_chunks, tint, lo, hi, lo_last, hi_last);
-    const int64_t n_tbin = tint ? (p->n_pts + tint - 1) / tint : 1;
+    const int64_t n_tbin = time_bins(p, tint).n_bin;
     const size_t bytes = (size_t)n_chunks * p->n_ant * n_tbin * p->nchan * sizeof(float);
     return with_host_staging(p, sk, bytes, mask_out, bytes, [&](const cf* dsk, void* dout) {
         return kurtosis_mask_dev(p, reinterpret_cast<const float*>(dsk), static_cast<float*>(dout), n_chunks, tint, lo, hi, lo_last, hi_last);
@@ -1294,7 +1294,7 @@ int fxc_kurtosis(fxc_plan* p, const void* x, void* sk_out, void* power_out, int6
     if (mem_kind == FXC_MEM_DEVICE)
         return kurtosis_dev(p, static_cast<const cf*>(x), static_cast<float*>(sk_out), static_cast<float*>(power_out), n_chunks, tint);
     // host memory: sk and power leave through one staging block, sk first
-    const int64_t n_tbin = tint ? (p->n_pts + tint - 1) / tint : 1;
+    const int64_t n_tbin = time_bins(p, tint).n_bin;
     const size_t elems = (size_t)n_chunks * p->n_ant * n_tbin * p->nchan;
     std::vector<float> both;
     void* out = sk_out;
@@ -1324,7 +1324,7 @@ int fxc_kurtosis_weights(fxc_plan* p, const void* sk, int64_t n_chunks, int64_t 
     FXC_DEVICE(p, p->device);
     if (mem_kind == FXC_MEM_DEVICE)
         return kurtosis_weights_dev(p, static_cast<const float*>(sk), static_cast<float*>(weights_out), n_chunks, tint, lo, hi);
-    const int64_t n_tbin = tint ? (p->n_pts + tint - 1) / tint : 1;
+    const int64_t n_tbin = time_bins(p, tint).n_bin;
     return with_host_staging(p, sk, (size_t)n_chunks * p->n_ant * n_tbin * p->nchan * sizeof(float), weights_out,
                              (size_t)n_chunks * p->n_base * p->nchan * sizeof(float), [&](const cf* dsk, void* dout) {
                                  return kurtosis_weights_dev(p, reinterpret_cast<const float*>(dsk), static_cast<float*>(dout), n_chunks, tint, lo, hi);

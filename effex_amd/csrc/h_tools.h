@@ -761,6 +761,18 @@ int average_rows_batch(fxc_plan* p, const cf* rows, const float* weights, int64_
     return FXC_OK;
 }
 
+// The time bins of a chunk's n_pts frames (beamformer, masks, kurtosis), the rule in one place: `tint` frames a bin, 0 given = the
+// whole chunk; n_bin = ceil(n_pts / tint), the last bin may be partial; n_full = the bins of tint frames: a partial last bin that is
+// not the chunk's only bin is not full (it has thresholds of its own count, or is not counted).  For 0 <= tint <= n_pts, n_pts > 0.
+struct TimeBins {
+    int64_t tint, n_bin, n_full;
+};
+TimeBins time_bins(const fxc_plan* p, int64_t tint) {
+    if (tint == 0) tint = p->n_pts;
+    const int64_t n_bin = (p->n_pts + tint - 1) / tint;
+    return {tint, n_bin, p->n_pts % tint != 0 && n_bin > 1 ? n_bin - 1 : n_bin};
+}
+
 // The beamformer (fxcorr.h fxc_beamform; kernels in k_beam.h), everything on the device.  The workspace holds, each from a
 // 256-byte boundary: the device copy of host weights, a pass's spectra [chunk][antenna][frame][nchan] and -- plans with a track --
 // the pass's effective weights [chunk][beam][antenna][nchan].  A pass takes as many chunks as the workspace target (FXC_WS_MB)
@@ -794,37 +806,21 @@ int launch_beam(fxc_plan* p, const BeamLaunch& k) {
     int64_t fpr = unit * std::max<int64_t>(1, 32 / unit);
     fpr = std::max(fpr, ((p->n_pts + kGridMax - 1) / kGridMax + unit - 1) / unit * unit);
     const dim3 grid((unsigned)((nchan + kBeamThreads - 1) / kBeamThreads), (unsigned)((p->n_pts + fpr - 1) / fpr), (unsigned)k.n_chunks);
-    const dim3 block(kBeamThreads);
-    const auto launch = [&](auto bt, int b0) {
+    // the kernel of a tile of BT beams: the three share one argument list (k_beam.h)
+    const auto kernel = [&](auto bt) {
         constexpr int BT = decltype(bt)::value;
-        if (k.mode == FXC_BEAM_INCOHERENT) {
-            if (k.mask)
-                hipLaunchKernelGGL((beam_inc_kernel<BT, true>), grid, block, 0, p->stream, k.spec, k.weff, k.w_chunk, k.mask, k.mask_tint,
-                                   k.n_mbin, static_cast<float*>(k.out), n_ant, p->n_pts, nchan, k.n_beam, b0, k.tint, fpr, k.n_tbin);
-            else
-                hipLaunchKernelGGL((beam_inc_kernel<BT, false>), grid, block, 0, p->stream, k.spec, k.weff, k.w_chunk, k.mask, (int64_t)1,
-                                   (int64_t)0, static_cast<float*>(k.out), n_ant, p->n_pts, nchan, k.n_beam, b0, k.tint, fpr, k.n_tbin);
-        } else if (k.mask) {
-            if (k.mode == FXC_BEAM_POWER)
-                hipLaunchKernelGGL((beam_mask_kernel<BT, true>), grid, block, 0, p->stream, k.spec, k.weff, k.w_chunk, k.mask, k.mask_tint,
-                                   k.n_mbin, k.out, n_ant, p->n_pts, nchan, k.n_beam, b0, k.tint, fpr, k.n_tbin);
-            else
-                hipLaunchKernelGGL((beam_mask_kernel<BT, false>), grid, block, 0, p->stream, k.spec, k.weff, k.w_chunk, k.mask, k.mask_tint,
-                                   k.n_mbin, k.out, n_ant, p->n_pts, nchan, k.n_beam, b0, k.tint, fpr, k.n_tbin);
-        } else if (k.mode == FXC_BEAM_POWER) {
-            hipLaunchKernelGGL((beam_kernel<BT, true>), grid, block, 0, p->stream, k.spec, k.weff, k.w_chunk, k.out, n_ant, p->n_pts, nchan,
-                               k.n_beam, b0, k.tint, fpr, k.n_tbin);
-        } else {
-            hipLaunchKernelGGL((beam_kernel<BT, false>), grid, block, 0, p->stream, k.spec, k.weff, k.w_chunk, k.out, n_ant, p->n_pts, nchan,
-                               k.n_beam, b0, k.tint, fpr, k.n_tbin);
-        }
+        if (k.mode == FXC_BEAM_INCOHERENT) return k.mask ? beam_inc_kernel<BT, true> : beam_inc_kernel<BT, false>;
+        if (k.mask) return k.mode == FXC_BEAM_POWER ? beam_mask_kernel<BT, true> : beam_mask_kernel<BT, false>;
+        return k.mode == FXC_BEAM_POWER ? beam_kernel<BT, true> : beam_kernel<BT, false>;
     };
     for (int b0 = 0; b0 < k.n_beam; b0 += kBeamTile) {      // the tile of a call's beams is a function of n_beam alone
         const int left = k.n_beam - b0;
-        if (left > 4) launch(std::integral_constant<int, 8>{}, b0);
-        else if (left > 2) launch(std::integral_constant<int, 4>{}, b0);
-        else if (left > 1) launch(std::integral_constant<int, 2>{}, b0);
-        else launch(std::integral_constant<int, 1>{}, b0);
+        const auto fn = left > 4   ? kernel(std::integral_constant<int, 8>{})
+                        : left > 2 ? kernel(std::integral_constant<int, 4>{})
+                        : left > 1 ? kernel(std::integral_constant<int, 2>{})
+                                   : kernel(std::integral_constant<int, 1>{});
+        hipLaunchKernelGGL(fn, grid, dim3(kBeamThreads), 0, p->stream, k.spec, k.weff, k.w_chunk, k.mask, k.mask_tint, k.n_mbin, k.out, n_ant,
+                           p->n_pts, nchan, k.n_beam, b0, k.tint, fpr, k.n_tbin);
     }
     FXC_HIP(p, hipGetLastError());
     return FXC_OK;
@@ -835,12 +831,9 @@ int beamform_dev(fxc_plan* p, const cf* x, const cf* weights, bool weights_on_ho
     const int nchan = p->nchan, n_ant = p->n_ant;
     const bool voltage = mode == FXC_BEAM_VOLTAGE;
     const bool al = align && aligning(p);
-    if (tint == 0) tint = p->n_pts;
-    if (mask_tint == 0) mask_tint = p->n_pts;
-    const int64_t n_tbin = (p->n_pts + tint - 1) / tint;
-    const int64_t n_mbin = (p->n_pts + mask_tint - 1) / mask_tint;
+    const TimeBins tb = time_bins(p, tint), mb = time_bins(p, mask_tint);
     const int64_t w_elems = (int64_t)n_beam * n_ant * nchan;
-    const int64_t m_elems = (int64_t)n_ant * n_mbin * nchan;      // of a chunk's mask
+    const int64_t m_elems = (int64_t)n_ant * mb.n_bin * nchan;      // of a chunk's mask
     const int64_t wcopy_bytes = weights_on_host ? up256(w_elems * (int64_t)sizeof(cf)) : 0;
     const int64_t spec_per_chunk = (int64_t)n_ant * p->n_pts * nchan * (int64_t)sizeof(cf);
     const int64_t weff_per_chunk = p->track ? w_elems * (int64_t)sizeof(cf) : 0;
@@ -862,7 +855,7 @@ int beamform_dev(fxc_plan* p, const cf* x, const cf* weights, bool weights_on_ho
         weights = ws_at<cf>(p, o_wcopy);
     }
     const int64_t out_per_chunk = voltage ? (int64_t)n_beam * p->n_pts * nchan * (int64_t)sizeof(cf)
-                                          : (int64_t)n_beam * n_tbin * nchan * (int64_t)sizeof(float);
+                                          : (int64_t)n_beam * tb.n_bin * nchan * (int64_t)sizeof(float);
     for (int64_t c0 = 0; c0 < n_chunks; c0 += cb) {
         const int64_t nc = std::min(cb, n_chunks - c0);
         PassInput in{chunk_at(p, x, c0)};
@@ -890,8 +883,8 @@ int beamform_dev(fxc_plan* p, const cf* x, const cf* weights, bool weights_on_ho
             wk = weff;
         }
         KernelTimer kt(p);
-        rc = launch_beam(p, {spec, wk, p->track ? w_elems : 0, mk, mask_tint, n_mbin, static_cast<char*>(out) + c0 * out_per_chunk, nc, n_beam,
-                             mode, tint, n_tbin});
+        rc = launch_beam(p, {spec, wk, p->track ? w_elems : 0, mk, mb.tint, mb.n_bin, static_cast<char*>(out) + c0 * out_per_chunk, nc, n_beam,
+                             mode, tb.tint, tb.n_bin});
         kt.stop();
         if (rc) return rc;
     }
@@ -901,14 +894,11 @@ int beamform_dev(fxc_plan* p, const cf* x, const cf* weights, bool weights_on_ho
 // The antenna mask from sk (fxc_kurtosis_antenna_mask), both on the device
 int kurtosis_mask_dev(fxc_plan* p, const float* sk, float* mask, int64_t n_chunks, int64_t tint, double lo, double hi, double lo_last,
                       double hi_last) {
-    if (tint == 0) tint = p->n_pts;
-    const int64_t n_tbin = (p->n_pts + tint - 1) / tint;
-    // a partial last bin that is not the chunk's only bin has the thresholds of its own count
-    const int64_t n_full = p->n_pts % tint != 0 && n_tbin > 1 ? n_tbin - 1 : n_tbin;
-    const int64_t total = n_chunks * p->n_ant * n_tbin * p->nchan;
+    const TimeBins tb = time_bins(p, tint);      // a bin that is not full has the thresholds of its own count
+    const int64_t total = n_chunks * p->n_ant * tb.n_bin * p->nchan;
     if (total == 0) return FXC_OK;
-    hipLaunchKernelGGL(kurtosis_mask_kernel, dim3(grid_for(total, 256, p->cu_count)), dim3(256), 0, p->stream, sk, mask, p->nchan, n_tbin,
-                       n_full, total, lo, hi, lo_last, hi_last);
+    hipLaunchKernelGGL(kurtosis_mask_kernel, dim3(grid_for(total, 256, p->cu_count)), dim3(256), 0, p->stream, sk, mask, p->nchan, tb.n_bin,
+                       tb.n_full, total, lo, hi, lo_last, hi_last);
     FXC_HIP(p, hipGetLastError());
     return FXC_OK;
 }
@@ -960,8 +950,7 @@ int launch_kurtosis(fxc_plan* p, const KurtosisLaunch& k) {
 // the passes.  The samples are taken as delivered: no shifts, no tables, and the track's counter stays.
 int kurtosis_dev(fxc_plan* p, const cf* x, float* sk, float* power, int64_t n_chunks, int64_t tint) {
     const int nchan = p->nchan, n_ant = p->n_ant;
-    if (tint == 0) tint = p->n_pts;
-    const int64_t n_tbin = (p->n_pts + tint - 1) / tint;
+    const TimeBins tb = time_bins(p, tint);
     const int64_t spec_per_chunk = (int64_t)n_ant * p->n_pts * nchan * (int64_t)sizeof(cf);
     const int64_t cb = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_chunks, kGridMax / n_ant), ws_target() / spec_per_chunk));
     WsCarver ws;
@@ -969,13 +958,13 @@ int kurtosis_dev(fxc_plan* p, const cf* x, float* sk, float* power, int64_t n_ch
     int rc = ensure_ws(p, ws.total());      // (flushes a pending fold: it lives in the workspace)
     if (rc) return rc;
     cf* spec = ws_at<cf>(p, o_spec);
-    const int64_t out_per_chunk = (int64_t)n_ant * n_tbin * nchan;
+    const int64_t out_per_chunk = (int64_t)n_ant * tb.n_bin * nchan;
     for (int64_t c0 = 0; c0 < n_chunks; c0 += cb) {
         const int64_t nc = std::min(cb, n_chunks - c0);
         rc = run_channelize(p, chunk_at(p, x, c0), spec, nc * n_ant);
         if (rc) return rc;
         KernelTimer kt(p);
-        rc = launch_kurtosis(p, {spec, sk + c0 * out_per_chunk, power ? power + c0 * out_per_chunk : nullptr, nc * n_ant, tint, n_tbin});
+        rc = launch_kurtosis(p, {spec, sk + c0 * out_per_chunk, power ? power + c0 * out_per_chunk : nullptr, nc * n_ant, tb.tint, tb.n_bin});
         kt.stop();
         if (rc) return rc;
     }
@@ -984,14 +973,11 @@ int kurtosis_dev(fxc_plan* p, const cf* x, float* sk, float* power, int64_t n_ch
 
 // The row weights from sk (fxc_kurtosis_weights), both on the device
 int kurtosis_weights_dev(fxc_plan* p, const float* sk, float* weights, int64_t n_chunks, int64_t tint, double lo, double hi) {
-    if (tint == 0) tint = p->n_pts;
-    const int64_t n_tbin = (p->n_pts + tint - 1) / tint;
-    // a partial last bin has another count than the thresholds were made for: it is counted only as the chunk's only bin
-    const int64_t n_count = p->n_pts % tint != 0 && n_tbin > 1 ? n_tbin - 1 : n_tbin;
+    const TimeBins tb = time_bins(p, tint);      // a bin that is not full has another count than the thresholds were made for: not counted
     const int64_t total = n_chunks * p->n_base * p->nchan;
     if (total == 0) return FXC_OK;
     hipLaunchKernelGGL(kurtosis_weights_kernel, dim3(grid_for(total, 256, p->cu_count)), dim3(256), 0, p->stream, sk, weights, p->n_ant,
-                       p->n_base, p->nchan, n_tbin, n_count, n_chunks, lo, hi);
+                       p->n_base, p->nchan, tb.n_bin, tb.n_full, n_chunks, lo, hi);
     FXC_HIP(p, hipGetLastError());
     return FXC_OK;
 }

@@ -33,6 +33,12 @@ def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
 
+def _torch_dtype(dtype):
+    """the torch type of a numpy ``dtype`` (they share their names)"""
+    import torch
+    return getattr(torch, np.dtype(dtype).name)
+
+
 BEAM_MODES = {"POWER": _lib.FXC_BEAM_POWER, "VOLTAGE": _lib.FXC_BEAM_VOLTAGE}
 IQ_FORMATS = {"c64": _lib.FXC_IQ_C64, "u8": _lib.FXC_IQ_U8, "c128": _lib.FXC_IQ_C128}
 _IQ_DTYPES = {"c64": np.complex64, "u8": np.uint8, "c128": np.complex128}
@@ -576,19 +582,8 @@ class FxPlan(object):
     def _beamform(self, x, weights, tint, m, out, mask, mask_tint, whole_samples):
         ptr, kind, n, keep = self._in(x, (self.n_ant, self.num_samp))
         device = kind == _lib.FXC_MEM_DEVICE
-        if device:
-            import torch
-            if not _is_torch(weights):
-                weights = torch.from_numpy(np.ascontiguousarray(weights, dtype=np.complex64)).to(keep.device)
-            if weights.dtype != torch.complex64 or not weights.is_cuda or weights.device.index != self.device:
-                raise ValueError("device weights must be a complex64 CUDA tensor on device {}".format(self.device))
-            w_keep = weights.contiguous()
-            w_ptr = w_keep.data_ptr()
-        else:
-            if _is_torch(weights):
-                raise ValueError("weights must be in the memory of x: numpy weights for host samples")
-            w_keep = np.ascontiguousarray(weights, dtype=np.complex64)
-            w_ptr = w_keep.ctypes.data
+        move_to = keep.device if device else None      # numpy weights and a numpy mask with a CUDA x are moved to the device
+        w_keep, w_ptr = self._like(weights, "weights", device, np.complex64, move_to, ("x: numpy weights for host samples", None))
         w_shape = tuple(w_keep.shape)
         if len(w_shape) == 2:
             w_shape = (1,) + w_shape
@@ -596,44 +591,18 @@ class FxPlan(object):
             raise ValueError("weights must have shape (n_beam, {}, {}), got {}".format(self.n_ant, self.nchan, tuple(w_keep.shape)))
         n_beam, tint = int(w_shape[0]), int(tint)
         if m != _lib.FXC_BEAM_VOLTAGE:
-            n_tbin = -(-self.n_pts // tint) if 0 < tint <= self.n_pts else 1      # (a tint out of range: the call answers)
-            shape, dtype = (n, n_beam, n_tbin, self.nchan), np.float32
+            shape, dtype = (n, n_beam, self._time_bins(tint)[1], self.nchan), np.float32
         else:
             shape, dtype = (n, n_beam, self.n_pts, self.nchan), np.complex64
         mask_tint, m_keep, m_ptr = int(mask_tint), None, None
         if mask is not None:
-            if device:
-                if not _is_torch(mask):
-                    mask = torch.from_numpy(np.ascontiguousarray(mask, dtype=np.float32)).to(keep.device)
-                if mask.dtype != torch.float32 or not mask.is_cuda or mask.device.index != self.device:
-                    raise ValueError("a device mask must be a float32 CUDA tensor on device {}".format(self.device))
-                m_keep = mask.contiguous()
-                m_ptr = m_keep.data_ptr()
-            else:
-                if _is_torch(mask):
-                    raise ValueError("mask must be in the memory of x: a numpy mask for host samples")
-                m_keep = np.ascontiguousarray(mask, dtype=np.float32)
-                m_ptr = m_keep.ctypes.data
-            n_mbin = -(-self.n_pts // mask_tint) if 0 < mask_tint <= self.n_pts else 1      # (out of range: the call answers)
-            if tuple(m_keep.shape) != (n, self.n_ant, n_mbin, self.nchan):
-                raise ValueError("mask must have shape ({}, {}, {}, {}), got {}".format(n, self.n_ant, n_mbin, self.nchan,
-                                                                                        tuple(m_keep.shape)))
-        if out is not None:
-            if _is_torch(out) != device:
-                raise ValueError("out must be of the same kind (host array / CUDA tensor) as x")
-            if device:
-                tdt = torch.float32 if dtype == np.float32 else torch.complex64
-                if out.dtype != tdt or tuple(out.shape) != shape or not out.is_contiguous() or not out.is_cuda or \
-                        out.device.index != self.device:
-                    raise ValueError("out must be a contiguous {} CUDA tensor of shape {}".format(np.dtype(dtype).name, shape))
-            elif out.dtype != dtype or out.shape != shape or not out.flags.c_contiguous or not out.flags.writeable:
-                raise ValueError("out must be a writable C-contiguous {} array of shape {}".format(np.dtype(dtype).name, shape))
-        elif device:
-            out = torch.empty(shape, dtype=torch.float32 if dtype == np.float32 else torch.complex64, device=keep.device)
-        else:
-            out = np.empty(shape, dtype=dtype)
-        o_ptr = out.data_ptr() if device else out.ctypes.data
+            m_keep, m_ptr = self._like(mask, "mask", device, np.float32, move_to, ("x: a numpy mask for host samples", "a device mask"))
+            want = (n, self.n_ant, self._time_bins(mask_tint)[1], self.nchan)
+            if tuple(m_keep.shape) != want:
+                raise ValueError("mask must have shape {}, got {}".format(want, tuple(m_keep.shape)))
+        out, o_ptr = self._out_like_x(out, shape, device, keep, dtype=dtype)
         if device and not self._follow:      # a stream of the plan's own: torch's may still be filling the moved weights
+            import torch
             torch.cuda.current_stream(keep.device).synchronize()
         self._beam_keep = (keep, w_keep, m_keep)     # until the next call: the queued kernels read them
         if mask is None and mask_tint == 0 and not whole_samples and m != _lib.FXC_BEAM_INCOHERENT:
@@ -650,52 +619,55 @@ class FxPlan(object):
         from ``sk_thresholds(M, sigma)`` with M the frames of a full bin; a partial last bin that is not the chunk's only bin gets
         ``sk_thresholds(M_last, sigma)`` of its own count whatever ``lo`` and ``hi`` are, and (-inf, inf) below 2 frames, where sk
         is exactly 1."""
-        self._sync_stream()
         tint = int(tint)
-        device = _is_torch(sk)
-        if device:
-            import torch
-            if sk.dtype != torch.float32 or not sk.is_cuda or sk.device.index != self.device:
-                raise ValueError("device sk must be a float32 CUDA tensor on device {}".format(self.device))
-            keep = sk.contiguous()
-            ptr, kind = keep.data_ptr(), _lib.FXC_MEM_DEVICE
-        else:
-            keep = np.ascontiguousarray(sk, dtype=np.float32)
-            ptr, kind = keep.ctypes.data, _lib.FXC_MEM_HOST
-        span = tint if 0 < tint <= self.n_pts else self.n_pts
-        n_tbin = -(-self.n_pts // span) if span else 1
-        shape = tuple(keep.shape)
-        if len(shape) != 4 or shape[1:] != (self.n_ant, n_tbin, self.nchan):
-            raise ValueError("sk must have shape (n_chunks, {}, {}, {}), got {}".format(self.n_ant, n_tbin, self.nchan, shape))
+        keep, ptr, kind, shape, span = self._sk_in(sk, tint)
         if lo is None or hi is None:
             t_lo, t_hi = sk_thresholds(span, sigma)
             lo, hi = (t_lo if lo is None else lo), (t_hi if hi is None else hi)
         m_last = self.n_pts % span if span else 0
         lo_last, hi_last = sk_thresholds(m_last, sigma) if m_last >= 2 else (-np.inf, np.inf)
-        mask, m_ptr = self._out_like_rows(shape, np.float32, keep, device)
+        mask, m_ptr = self._out_like_rows(shape, np.float32, keep, _is_torch(keep))
         self._sk_keep = keep
         self._check(self._lib.fxc_kurtosis_antenna_mask(self._h, ptr, int(shape[0]), tint, float(lo), float(hi), float(lo_last),
                                                         float(hi_last), m_ptr, kind))
         return mask
 
-    def _float_out(self, out, shape, device, like, name="out"):
-        """a float32 result of ``shape`` in the memory of the samples: ``out`` checked, or a new array / tensor -> (array, ptr)"""
+    def _out_like_x(self, out, shape, device, like, name="out", dtype=np.float32):
+        """a result of ``shape`` and ``dtype`` in the memory of the samples: ``out`` checked, or a new array / tensor -> (array, ptr)"""
+        kind = np.dtype(dtype).name
         if out is not None:
             if _is_torch(out) != device:
                 raise ValueError("{} must be of the same kind (host array / CUDA tensor) as x".format(name))
             if device:
-                import torch
-                if out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous() or not out.is_cuda or \
+                if out.dtype != _torch_dtype(dtype) or tuple(out.shape) != shape or not out.is_contiguous() or not out.is_cuda or \
                         out.device.index != self.device:
-                    raise ValueError("{} must be a contiguous float32 CUDA tensor of shape {}".format(name, shape))
-            elif out.dtype != np.float32 or out.shape != shape or not out.flags.c_contiguous or not out.flags.writeable:
-                raise ValueError("{} must be a writable C-contiguous float32 array of shape {}".format(name, shape))
+                    raise ValueError("{} must be a contiguous {} CUDA tensor of shape {}".format(name, kind, shape))
+            elif out.dtype != dtype or out.shape != shape or not out.flags.c_contiguous or not out.flags.writeable:
+                raise ValueError("{} must be a writable C-contiguous {} array of shape {}".format(name, kind, shape))
         elif device:
             import torch
-            out = torch.empty(shape, dtype=torch.float32, device=like.device)
+            out = torch.empty(shape, dtype=_torch_dtype(dtype), device=like.device)
         else:
-            out = np.empty(shape, dtype=np.float32)
+            out = np.empty(shape, dtype=dtype)
         return out, (out.data_ptr() if device else out.ctypes.data)
+
+    def _time_bins(self, tint):
+        """time bins of ``tint`` frames, 0: the whole chunk (h_tools.h time_bins) -> (frames of a full bin, bins a chunk).  A ``tint``
+        out of range gives the shape of one bin, and the C call answers"""
+        span = tint if 0 < tint <= self.n_pts else self.n_pts
+        return span, (-(-self.n_pts // span) if span else 1)
+
+    def _sk_in(self, sk, tint):
+        """sk as ``kurtosis(x, tint=tint)`` returned it, numpy or a CUDA tensor on the plan's device -> (keep, ptr, mem_kind, shape,
+        frames of a full bin)"""
+        self._sync_stream()
+        device = _is_torch(sk)
+        keep, ptr = self._like(sk, "sk", device)
+        span, n_tbin = self._time_bins(tint)
+        shape = tuple(keep.shape)
+        if len(shape) != 4 or shape[1:] != (self.n_ant, n_tbin, self.nchan):
+            raise ValueError("sk must have shape (n_chunks, {}, {}, {}), got {}".format(self.n_ant, n_tbin, self.nchan, shape))
+        return keep, ptr, (_lib.FXC_MEM_DEVICE if device else _lib.FXC_MEM_HOST), shape, span
 
     def kurtosis(self, x, tint=0, return_power=False, out=None):
         """Spectral kurtosis of every antenna's spectra (fxcorr.h fxc_kurtosis): ``x`` = [n_chunks, n_ant, num_samp] complex64
@@ -714,8 +686,7 @@ class FxPlan(object):
         ptr, kind, n, keep = self._in(x, (self.n_ant, self.num_samp))
         device = kind == _lib.FXC_MEM_DEVICE
         tint = int(tint)
-        n_tbin = -(-self.n_pts // tint) if 0 < tint <= self.n_pts else 1      # (a tint out of range: the call answers)
-        shape = (n, self.n_ant, n_tbin, self.nchan)
+        shape = (n, self.n_ant, self._time_bins(tint)[1], self.nchan)
         if return_power:
             if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
                 raise ValueError("with return_power, out must be a pair (sk, power)")
@@ -724,8 +695,8 @@ class FxPlan(object):
             if isinstance(out, (tuple, list)):
                 raise ValueError("out is a pair only with return_power")
             o_sk, o_pw = out, None
-        sk, s_ptr = self._float_out(o_sk, shape, device, keep)
-        power, p_ptr = self._float_out(o_pw, shape, device, keep, "out's power") if return_power else (None, None)
+        sk, s_ptr = self._out_like_x(o_sk, shape, device, keep)
+        power, p_ptr = self._out_like_x(o_pw, shape, device, keep, "out's power") if return_power else (None, None)
         if device and not self._follow:      # a stream of the plan's own: torch's may still be using the blocks it handed out
             import torch
             torch.cuda.current_stream(keep.device).synchronize()
@@ -740,26 +711,12 @@ class FxPlan(object):
         ``lo <= sk <= hi`` in every counted bin of both antennas of the baseline, else 0 (a NaN gives 0).  A partial last bin is
         not counted unless it is the chunk's only bin.  Thresholds that are not given come from ``sk_thresholds(M, sigma)``
         with M the frames of a full bin."""
-        self._sync_stream()
         tint = int(tint)
-        device = _is_torch(sk)
-        if device:
-            import torch
-            if sk.dtype != torch.float32 or not sk.is_cuda or sk.device.index != self.device:
-                raise ValueError("device sk must be a float32 CUDA tensor on device {}".format(self.device))
-            keep = sk.contiguous()
-            ptr, kind = keep.data_ptr(), _lib.FXC_MEM_DEVICE
-        else:
-            keep = np.ascontiguousarray(sk, dtype=np.float32)
-            ptr, kind = keep.ctypes.data, _lib.FXC_MEM_HOST
-        n_tbin = -(-self.n_pts // tint) if 0 < tint <= self.n_pts else 1
-        shape = tuple(keep.shape)
-        if len(shape) != 4 or shape[1:] != (self.n_ant, n_tbin, self.nchan):
-            raise ValueError("sk must have shape (n_chunks, {}, {}, {}), got {}".format(self.n_ant, n_tbin, self.nchan, shape))
+        keep, ptr, kind, shape, span = self._sk_in(sk, tint)
         if lo is None or hi is None:
-            t_lo, t_hi = sk_thresholds(tint if 0 < tint <= self.n_pts else self.n_pts, sigma)
+            t_lo, t_hi = sk_thresholds(span, sigma)
             lo, hi = (t_lo if lo is None else lo), (t_hi if hi is None else hi)
-        weights, w_ptr = self._out_like_rows((shape[0], self.n_baselines, self.nchan), np.float32, keep, device)
+        weights, w_ptr = self._out_like_rows((shape[0], self.n_baselines, self.nchan), np.float32, keep, _is_torch(keep))
         self._sk_keep = keep
         self._check(self._lib.fxc_kurtosis_weights(self._h, ptr, int(shape[0]), tint, float(lo), float(hi), w_ptr, kind))
         return weights
@@ -1027,22 +984,28 @@ class FxPlan(object):
             raise ValueError("rows must have shape (n_chunks, {}, {}), got {}".format(self.n_rows, self.nchan, tuple(keep.shape)))
         return keep, ptr, kind, shape
 
-    def _like_rows(self, x, name, device):
-        """float32 ``x`` (``weights``, ``prior``) in the memory of rows -> (keep, ptr)"""
+    def _like(self, x, name, device, dtype=np.float32, move_to=None, says=("rows: a CUDA tensor for device rows, numpy for host rows", None)):
+        """``x`` of ``dtype`` (``weights``, ``prior``, ``mask``, ``sk``) in the memory of the rows, or of the samples x -> (keep, ptr).
+        ``move_to``: the torch device a numpy ``x`` is moved to when the samples are on the device; ``says``: what the messages
+        call that memory, and the operand on the device where it is not "device <name>" """
+        if device and move_to is not None and not _is_torch(x):
+            import torch
+            x = torch.from_numpy(np.ascontiguousarray(x, dtype=dtype)).to(move_to)
         if _is_torch(x) != device:
-            raise ValueError("{} must be in the memory of rows: a CUDA tensor for device rows, numpy for host rows".format(name))
+            raise ValueError("{} must be in the memory of {}".format(name, says[0]))
         if device:
             import torch
-            if x.dtype != torch.float32 or not x.is_cuda or x.device.index != self.device:
-                raise ValueError("device {} must be a float32 CUDA tensor on device {}".format(name, self.device))
+            if x.dtype != _torch_dtype(dtype) or not x.is_cuda or x.device.index != self.device:
+                raise ValueError("{} must be a {} CUDA tensor on device {}".format(says[1] or "device " + name, np.dtype(dtype).name,
+                                                                                   self.device))
             keep = x.contiguous()
             return keep, keep.data_ptr()
-        keep = np.ascontiguousarray(x, dtype=np.float32)
+        keep = np.ascontiguousarray(x, dtype=dtype)
         return keep, keep.ctypes.data
 
     def _weights_in(self, x, name, keep_rows, n_chunks, either=False):
-        """``_like_rows`` of ``x`` shaped [n_chunks, n_baselines, nchan], 2-D for 2-D rows (``either``: or 3-D, the shape the message names)"""
-        keep, ptr = self._like_rows(x, name, _is_torch(keep_rows))
+        """``_like`` of ``x`` shaped [n_chunks, n_baselines, nchan], 2-D for 2-D rows (``either``: or 3-D, the shape the message names)"""
+        keep, ptr = self._like(x, name, _is_torch(keep_rows))
         full = (n_chunks, self.n_baselines, self.nchan)
         want = full[1:] if keep_rows.ndim == 2 else full
         got = tuple(keep.shape)
@@ -1059,7 +1022,7 @@ class FxPlan(object):
         """an output of a call in the memory of the rows ``keep`` -> (array, ptr); ``dtype`` = the numpy type"""
         if device:
             import torch
-            out = torch.empty(shape, dtype=getattr(torch, np.dtype(dtype).name), device=keep.device)      # the call writes every element
+            out = torch.empty(shape, dtype=_torch_dtype(dtype), device=keep.device)      # the call writes every element
             if not self._follow:      # a stream of the plan's own: torch's may still be using the block it handed out
                 torch.cuda.current_stream(keep.device).synchronize()
             return out, out.data_ptr()
@@ -1254,7 +1217,7 @@ class FxPlan(object):
             w_ptr = chan_weights.ctypes.data
         n_dm = int(shifts.shape[0])
         want = (n_series, n_dm, n_t - s_max) if len(shape) != 2 else (n_dm, n_t - s_max)
-        res, o_ptr = self._float_out(out, want, device, keep)
+        res, o_ptr = self._out_like_x(out, want, device, keep)
         if device and not self._follow:      # a stream of the plan's own: torch's may still be using the blocks it handed out
             import torch
             torch.cuda.current_stream(keep.device).synchronize()

@@ -84,7 +84,8 @@ def n_mbin(n_pts, mask_tint):
 
 def random_mask(seed, n_chunks, n_ant, n_pts, nchan, mask_tint):
     """float32 [n_chunks, n_ant, n_mbin, nchan]: about 30 % zeros, the rest 1 -- with a few values that count (0.25, 7) and a few
-    that do not (-1, NaN) --, plus one cell with every antenna out, one with all in, and one antenna out for a whole chunk"""
+    that do not (-1, NaN) --, plus one cell with every antenna out, one with all in, and one antenna out for a whole chunk (with a
+    single chunk: for all of it but the all-in cell)"""
     rng = np.random.default_rng(seed)
     nb = n_mbin(n_pts, mask_tint)
     m = (rng.random((n_chunks, n_ant, nb, nchan)) >= 0.3).astype(np.float32)
@@ -94,21 +95,25 @@ def random_mask(seed, n_chunks, n_ant, n_pts, nchan, mask_tint):
         m[tuple(row)] = v
     cells = special_cells(n_chunks, nb, nchan)
     m[cells["none"][0], :, cells["none"][1], cells["none"][2]] = 0.0
-    m[cells["all"][0], :, cells["all"][1], cells["all"][2]] = 1.0
     m[cells["chunk_out"][0], cells["chunk_out"][1] % n_ant] = 0.0
+    m[cells["all"][0], :, cells["all"][1], cells["all"][2]] = 1.0           # (last: with one chunk the cell lies in the antenna's chunk)
     with np.errstate(invalid="ignore"):
         on = m > 0
     assert not on[cells["none"][0], :, cells["none"][1], cells["none"][2]].any()
     assert on[cells["all"][0], :, cells["all"][1], cells["all"][2]].all()
-    assert not on[cells["chunk_out"][0], cells["chunk_out"][1] % n_ant].any()
-    assert 0.15 < 1.0 - on.mean() < 0.6 or on.size < 64
+    out = on[cells["chunk_out"][0], cells["chunk_out"][1] % n_ant].copy()
+    if cells["chunk_out"][0] == cells["all"][0]:
+        out[cells["all"][1], cells["all"][2]] = False
+    assert not out.any()
+    expected = 0.3 + 0.7 / (n_chunks * n_ant)                              # the drawn zeros, and the antenna that is out for a chunk
+    assert abs(1.0 - on.mean() - expected) < 0.15 or on.size < 64
     return m
 
 
 def special_cells(n_chunks, nb, nchan):
     """(chunk, mask bin, stored channel) of the cell with every antenna out and of the cell with all in (the last bin, and on
     either side of the fftshift's wrap), and (chunk, antenna) of the antenna that is out for a whole chunk: the last chunk, so
-    two chunks or more keep it off the two cells"""
+    two chunks or more keep it off the two cells (with one chunk random_mask lets the all-in cell stand)"""
     return {"none": (0, nb - 1, nchan // 2), "all": (0, 0, max(nchan // 2 - 1, 0)), "chunk_out": (n_chunks - 1, 1)}
 
 

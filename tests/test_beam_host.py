@@ -106,7 +106,7 @@ LONG_FRAMES = (37, 70)   # the frame counts of beam_ref.LONG_SHAPES
 
 
 def frames_per_range(n_pts, tint, power=True):
-    """h_tools.h::beamform_dev: whole time bins (VOLTAGE: whole tiles), 32 frames or more where a bin is shorter, and no more ranges
+    """h_tools.h::launch_beam: whole time bins (VOLTAGE: whole tiles), 32 frames or more where a bin is shorter, and no more ranges
     than gridDim.y holds"""
     unit = (tint or n_pts) if power else K_BEAM_FRAMES
     fpr = unit * max(1, 32 // unit)
@@ -164,7 +164,7 @@ def test_frame_ranges_are_the_ones_the_shapes_claim():
 
 
 def beam_tiles(n_beam):
-    """the kernel instantiations (beams per thread) of a call's beam tiles: h_tools.h::beamform_dev"""
+    """the kernel instantiations (beams per thread) of a call's beam tiles: h_tools.h::launch_beam"""
     out = []
     for b0 in range(0, n_beam, 8):
         left = n_beam - b0

@@ -33,9 +33,10 @@ BW, FC = 2.4e6, 1.4204e9
 
 # (n_ant, nchan, ntaps, n_pts, n_chunks, n_beam): the small case; part of a wave and an odd antenna count (the one-antenna trip); the
 # full tile; a second tile and an odd count above 8; an odd channel count (the fftshift's wrap inside the mask's index), ranges of
-# 32 + 5 frames and a rough window; 70 frames and two tiles; the kernel per channel count
+# 32 + 5 frames and a rough window; 70 frames and two tiles; the kernel per channel count; the two-beam tile with the one-antenna
+# tail trip; tiles of 8 + 2 beams over a second frame range, partial tiles and a partial last bin
 SHAPES = [(2, 64, 4, 8, 3, 1), (3, 16, 4, 8, 2, 3), (8, 64, 4, 16, 3, 8), (9, 64, 4, 8, 2, 9), (3, 63, 4, 37, 2, 5), (2, 16, 4, 70, 2, 9),
-          (5, 1000, 4, 8, 2, 4)]
+          (5, 1000, 4, 8, 2, 4), (3, 16, 4, 8, 2, 2), (2, 16, 4, 37, 1, 10)]
 ROUGH = {(3, 63, 4, 37, 2, 5), (2, 16, 4, 70, 2, 9)}
 ids = lambda s: "x".join(map(str, s))      # noqa: E731
 

@@ -70,7 +70,7 @@ def both_inputs(plan, torch, x, w, **kw):
 # front of the F stage (its buffer and the workspace carve)
 SHAPES = [(2, 64, 4, 8, 3, 1), (3, 16, 4, 8, 2, 3), (8, 64, 4, 16, 3, 8), (9, 64, 4, 8, 2, 9), (64, 64, 4, 8, 1, 16),
           (5, 1000, 4, 8, 2, 4), (3, 63, 4, 8, 2, 2), (4, 4096, 4, 8, 2, 2), (2, 8192, 4, 8, 1, 2), (3, 64, 8, 8, 2, 2)]
-# ... and more frames than a frame range (h_tools.h::beamform_dev: ranges of fpr frames ride in grid.y, beam_kernel walks a range in
+# ... and more frames than a frame range (h_tools.h::launch_beam: ranges of fpr frames ride in grid.y, beam_kernel walks a range in
 # tiles of 8 frames): 37 frames are VOLTAGE ranges of 32 + 5 and ranges of 30 + 7 at 3 or 5 frames a bin, every range's last tile
 # partial, the chunk's last bin too (37 = 12 x 3 + 1 = 7 x 5 + 2); 70 frames are 32 + 32 + 6, with two beam tiles (8 + 1) and part of
 # a wave; the one-antenna tail trip at an odd channel count with three beams of the tile idle; two beams.  Between them every beam
