@@ -1208,10 +1208,12 @@ def test_multi_antenna_fused_path(plan_mod, torch, n_ant, nchan, ntaps):
 
 @pytest.mark.parametrize("n_ant,nchan,ntaps,frames,n_chunks", [(9, 512, 4, 6, 3), (12, 1024, 4, 5, 2), (16, 4096, 4, 4, 3),
                                                              (17, 256, 4, 30, 2), (24, 2048, 8, 3, 1), (33, 64, 4, 50, 2),
-                                                             (64, 512, 4, 3, 1), (10, 8192, 4, 2, 2), (12, 64, 4, 3000, 2)])
+                                                             (64, 512, 4, 3, 1), (10, 8192, 4, 2, 2), (12, 64, 4, 3000, 2),
+                                                             (32, 64, 4, 9, 2), (48, 64, 4, 5, 2)])
 def test_more_than_eight_antennas(plan_mod, torch, n_ant, nchan, ntaps, frames, n_chunks):
-    """9 ... 64 antennas: an F-only kernel + the X-engine over blocks of 8 antennas (partial last blocks, every pair of
-    blocks), baselines in the order (0,1),(0,2)...: against the oracle's integration and the generic kernels' rows."""
+    """9 ... 64 antennas: an F-only kernel + the matrix-core X-engine (k_xmfma.h: one to four tiles of 16 antennas, padding
+    rows past the last antenna, every pair of tiles; 32 and 48: whole tiles, 48 with the idle load rows of a pass), baselines in
+    the order (0,1),(0,2)...: against the oracle's integration and the generic kernels' rows."""
     num_samp = nchan * frames + 5
     x = synth.synth_iq(31, n_chunks, n_ant, num_samp, delays=np.arange(n_ant) % 9)
     window = design_window(ntaps, nchan)
