@@ -7,12 +7,14 @@
 //   k_delay.h k_fringe.h k_gains.h k_flag.h k_average.h k_beam.h k_kurtosis.h k_dedisperse.h
 //                                           the __global__ kernels, one file per path / step and per rows tool (delays, fringe fit,
 //                                           gain solve, detector, averager, beamformer, spectral kurtosis)
-//   h_plan.h h_rtc.h h_launch.h h_build.h h_run.h h_ingest.h h_tools.h h_rccl.h
-//                                           fxc_plan, the kernels compiled per channel count, the per-path launchers and
-//                                           workspace passes, plan construction (route, tables), the device-resident
-//                                           fx_accumulate / fx_rows, the ingest front end of every entry point that takes
-//                                           samples (formats, DC removal, host / device dispatch), the rows tools' drivers and the
-//                                           helpers they share, the run-time binding of librccl
+//   h_own.h h_plan.h h_rtc.h h_launch.h h_build.h h_run.h h_modifiers.h h_ingest.h h_pipe.h h_tools.h h_rccl.h
+//                                           the owners of device memory, events and streams, fxc_plan, the kernels compiled per
+//                                           channel count, the per-path launchers and workspace passes, plan construction (route,
+//                                           tables), the device-resident fx_accumulate / fx_rows and the finalize queue, the row
+//                                           modifiers (rot tables, delay track, gain track, sample shifts), the ingest front end of
+//                                           every entry point that takes samples (formats, DC removal, host / device dispatch), the
+//                                           host-fed pipe, the rows tools' drivers and the helpers they share, the run-time binding
+//                                           of librccl
 //
 // Replaces, for effex's hot path:
 //   cusignal.filtering.channelize_poly FIR half   effex/effex.py:553   -> pfb_fir_kernel / pfb_fft_mixed_kernel / fused phase 1
@@ -69,6 +71,7 @@ ncclResult_t ncclCommGetAsyncError(ncclComm_t comm, ncclResult_t* asyncError);
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <type_traits>
@@ -150,12 +153,15 @@ int64_t ws_target() {
 #include "k_kurtosis.h"
 #include "k_dedisperse.h"
 #include "k_synth.h"
+#include "h_own.h"
 #include "h_plan.h"
 #include "h_rtc.h"
 #include "h_launch.h"
 #include "h_build.h"
 #include "h_run.h"
+#include "h_modifiers.h"
 #include "h_ingest.h"
+#include "h_pipe.h"
 #include "h_tools.h"
 #include "h_rccl.h"
 
@@ -198,32 +204,8 @@ int fxc_plan_destroy(fxc_plan* p) {
         return fail(p, FXC_ERR_STATE, "%d pipe(s) still use this plan: destroy them first", p->live_pipes);
     DeviceGuard device_guard__(p->device);
     (void)hipStreamSynchronize(p->stream);
-    if (p->s_copy) (void)hipStreamSynchronize(p->s_copy);   // an uncollected large result may still be on its way to h_res[]
-    for (auto& e : p->kev) {
-        (void)hipEventDestroy(e.first);
-        (void)hipEventDestroy(e.second);
-    }
-    void* bufs[] = {p->d_win, p->d_tw, p->d_rot, p->d_win4, p->d_tw1, p->d_tw2, p->d_tw0, p->d_tw_small, p->d_stamps,
-                    p->d_acc, p->d_sums, p->d_cont, p->d_rowpart, p->d_ws, p->d_stage[0], p->d_stage[1], p->d_stage[2], p->d_dc, p->d_hpre,
-                    p->d_ones, p->d_pre, p->d_tw8192, p->d_unit4, p->d_chirp, p->d_blud, p->d_rot_ant, p->d_pair, p->d_track_par, p->d_track, p->d_one, p->d_gain_q,
-                    p->d_shift, p->d_tshift, p->d_align};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    if (p->ev_t0) (void)hipEventDestroy(p->ev_t0);
-    if (p->ev_t1) (void)hipEventDestroy(p->ev_t1);
-    if (p->ev_order) (void)hipEventDestroy(p->ev_order);
-    for (int k = 0; k < fxc_plan::kResSlots; ++k) {
-        if (p->ev_res[k]) (void)hipEventDestroy(p->ev_res[k]);
-        if (p->h_res[k]) (void)hipHostFree(p->h_res[k]);
-        if (p->d_res_big[k]) (void)hipFree(p->d_res_big[k]);
-    }
-    if (p->s_copy) {
-        (void)hipStreamSynchronize(p->s_copy);
-        (void)hipStreamDestroy(p->s_copy);
-    }
-    if (p->ev_fin) (void)hipEventDestroy(p->ev_fin);
-    if (p->own_stream && p->stream) (void)hipStreamDestroy(p->stream);
-    delete p;
+    if (p->big_res) (void)hipStreamSynchronize(p->big_res.s_copy);   // an uncollected large result may still be on its way to h_res[]
+    delete p;      // memory, then events, then streams: the order of fxc_plan's members (h_plan.h)
     return FXC_OK;
 }
 
@@ -263,7 +245,7 @@ int fxc_plan_create(fxc_plan** out, int device, int n_ant, int nchan, int ntaps,
     p->lg2n = 0;
     while ((1 << p->lg2n) < nchan) ++p->lg2n;
     p->own_stream = (stream == FXC_STREAM_OWNED);
-    p->stream = p->own_stream ? nullptr : static_cast<hipStream_t>(stream);
+    if (!p->own_stream) p->stream.borrow(static_cast<hipStream_t>(stream));
     int rc = plan_route(p, force_path);
     if (rc == FXC_OK) {
         plan_spec(p);
@@ -332,7 +314,7 @@ int fxc_plan_get_info(const fxc_plan* p, fxc_info* info) {
     }
     info->device = p->device;
     info->cu_count = p->cu_count;
-    info->workspace_bytes = p->ws_bytes;
+    info->workspace_bytes = (int64_t)p->d_ws.bytes();
     return FXC_OK;
 }
 
@@ -363,109 +345,6 @@ int fxc_spec_probe(int nchan, int ntaps, int variant, const char* arch, char* re
     return FXC_OK;
 }
 
-namespace {
-bool acc_empty(const fxc_plan* p) { return !(p->spectra_count > 0.0) && !p->pend.valid; }
-
-// fxc_set_rot / fxc_set_rot_ant end a delay track -- unless the accumulator holds tracked chunks: their sums are rotated already,
-// a static table at finalize would rotate them again
-int end_track(fxc_plan* p) {
-    if (p->track && p->acc_track && !acc_empty(p))
-        return fail(p, FXC_ERR_STATE, "the accumulator holds chunks accumulated under the delay track: finalize or reset it first");
-    p->track = false;
-    p->track_align = false;      // (the per-chunk shifts of an aligned track end with it; static shifts are not the track's)
-    p->gain_n = 0;      // the gains were solved under this track: they end with it (release_gain_q frees them once the stream is idle)
-    return FXC_OK;
-}
-
-// the static whole-sample shifts, or none of them (shifts == nullptr); the caller has synchronised the plan's stream
-int store_sample_shifts(fxc_plan* p, const int64_t* shifts) {
-    bool any = false;
-    for (int a = 0; shifts && a < p->n_ant; ++a) any = any || shifts[a] != 0;
-    if (!any) {
-        p->shifted = false;
-        p->sample_shift.clear();
-        return FXC_OK;
-    }
-    std::vector<int> s32((size_t)p->n_ant);
-    for (int a = 0; a < p->n_ant; ++a) s32[(size_t)a] = (int)shifts[a];      // (|s| < num_samp <= 2^27: checked by the caller)
-    if (!p->d_shift) FXC_HIP(p, hipMalloc(reinterpret_cast<void**>(&p->d_shift), (size_t)p->n_ant * sizeof(int)));
-    FXC_HIP(p, hipMemcpy(p->d_shift, s32.data(), (size_t)p->n_ant * sizeof(int), hipMemcpyHostToDevice));
-    p->sample_shift.assign(shifts, shifts + p->n_ant);
-    p->shifted = true;
-    return FXC_OK;
-}
-
-// s_a(t) of an aligned track as track_shift (k_align.h) forms it on the device: the same individually rounded operations
-int64_t track_shift_host(const fxc_plan* p, int a, int64_t t) {
-#pragma clang fp contract(off)
-    const double tau = p->track_par_h[(size_t)a] + (double)t * p->track_par_h[(size_t)(p->n_ant + a)];
-    double v = tau * p->track_bw;
-    v = v > 2147483647.0 ? 2147483647.0 : (v < -2147483647.0 ? -2147483647.0 : v);
-    return (int64_t)std::llrint(v);
-}
-
-constexpr int64_t kAlignMaxSamp = 1ll << 27;      // a stream within one buffer descriptor (align_c64_kernel)
-
-// frees the table of a gain track that has ended; the caller has synchronised the plan's stream
-void release_gain_q(fxc_plan* p) {
-    if (p->gain_n == 0 && p->d_gain_q) {
-        (void)hipFree(p->d_gain_q);
-        p->d_gain_q = nullptr;
-    }
-}
-}  // namespace
-
-namespace {
-// fxc_set_delay_track and, `aligned`, fxc_set_delay_track_aligned: the same track, with the whole samples of every chunk's delays
-// taken out of the tables and applied to the samples
-int set_delay_track(fxc_plan* p, const double* tau0_s, const double* rate_s_per_chunk, double bandwidth, double frequency,
-                    int64_t first_chunk, bool aligned) {
-    if (!p || !tau0_s || !rate_s_per_chunk) return fail(p, FXC_ERR_ARG, "NULL argument");
-    if (p->n_ant < 2) return fail(p, FXC_ERR_ARG, "a delay track needs 2 or more antennas, the plan has %d", p->n_ant);
-    if (!(bandwidth > 0.0) || !std::isfinite(bandwidth) || !std::isfinite(frequency))
-        return fail(p, FXC_ERR_ARG, "bandwidth must be > 0 and finite, frequency finite");
-    if (first_chunk < 0) return fail(p, FXC_ERR_ARG, "first_chunk < 0");
-    for (int a = 0; a < p->n_ant; ++a)
-        if (!std::isfinite(tau0_s[a]) || !std::isfinite(rate_s_per_chunk[a]))
-            return fail(p, FXC_ERR_ARG, "delay or rate of antenna %d is not finite", a);
-    if (aligned && p->num_samp > kAlignMaxSamp)
-        return fail(p, FXC_ERR_UNSUPPORTED, "whole-sample delays take chunks of up to 2^27 samples, the plan's have %lld", (long long)p->num_samp);
-    if (p->live_pipes) return fail(p, FXC_ERR_STATE, "an fxc_pipe uses the plan");
-    if (!acc_empty(p) && !p->acc_track)
-        return fail(p, FXC_ERR_STATE, "the accumulator holds chunks accumulated without a delay track: finalize or reset it first");
-    FXC_DEVICE(p, p->device);
-    // ordered after any queued kernel that still reads the old parameters
-    FXC_HIP(p, hipStreamSynchronize(p->stream));
-    const size_t A = (size_t)p->n_ant, N = (size_t)p->nchan;
-    if (!p->d_track_par) FXC_HIP(p, hipMalloc(reinterpret_cast<void**>(&p->d_track_par), 2 * A * sizeof(double)));
-    if (!p->d_one) {
-        FXC_HIP(p, hipMalloc(reinterpret_cast<void**>(&p->d_one), N * sizeof(cd)));
-        cd one;
-        one.x = 1.0;
-        one.y = 0.0;
-        const std::vector<cd> ones(N, one);
-        FXC_HIP(p, hipMemcpy(p->d_one, ones.data(), N * sizeof(cd), hipMemcpyHostToDevice));
-    }
-    FXC_HIP(p, hipMemcpy(p->d_track_par, tau0_s, A * sizeof(double), hipMemcpyHostToDevice));
-    FXC_HIP(p, hipMemcpy(p->d_track_par + A, rate_s_per_chunk, A * sizeof(double), hipMemcpyHostToDevice));
-    p->track_df = 1.0 / ((double)p->nchan * (1.0 / bandwidth));      // np.fft.fftfreq(nchan, d = 1 / bandwidth), step by step
-    p->track_freq = frequency;
-    p->track_t = first_chunk;
-    p->track = true;
-    p->rot_ant = false;
-    p->gain_n = 0;      // gains were solved on rows made under one particular track: a new track drops them
-    release_gain_q(p);
-    p->track_align = aligned;
-    if (aligned) {
-        p->track_bw = bandwidth;
-        p->track_par_h.assign(tau0_s, tau0_s + A);
-        p->track_par_h.insert(p->track_par_h.end(), rate_s_per_chunk, rate_s_per_chunk + A);
-        return store_sample_shifts(p, nullptr);      // the track's own shifts take the place of static ones
-    }
-    return FXC_OK;
-}
-}  // namespace
-
 int fxc_set_delay_track(fxc_plan* p, const double* tau0_s, const double* rate_s_per_chunk, double bandwidth, double frequency,
                         int64_t first_chunk) {
     return set_delay_track(p, tau0_s, rate_s_per_chunk, bandwidth, frequency, first_chunk, false);
@@ -489,10 +368,7 @@ int fxc_set_sample_delays(fxc_plan* p, const int64_t* shift_samples) {
         return fail(p, FXC_ERR_STATE, "the aligned delay track sets the shifts of every chunk: end it first");
     if (any && p->num_samp > kAlignMaxSamp)
         return fail(p, FXC_ERR_UNSUPPORTED, "whole-sample delays take chunks of up to 2^27 samples, the plan's have %lld", (long long)p->num_samp);
-    FXC_DEVICE(p, p->device);
-    // ordered after any queued alignment that still reads the old shifts
-    FXC_HIP(p, hipStreamSynchronize(p->stream));
-    return store_sample_shifts(p, shift_samples);
+    return set_sample_delays(p, shift_samples);
 }
 
 int fxc_sample_delays(const fxc_plan* p, int64_t chunk, int64_t* shift_samples_out) {
@@ -524,40 +400,7 @@ int fxc_set_track_gains(fxc_plan* p, const double* gains_re_im, int64_t n_soluti
     if (!p->track) return fail(p, FXC_ERR_STATE, "the plan has no delay track");
     if (!acc_empty(p)) return fail(p, FXC_ERR_STATE, "the accumulator holds chunks: finalize or reset it first");
     if (p->live_pipes) return fail(p, FXC_ERR_STATE, "an fxc_pipe uses the plan");
-    FXC_DEVICE(p, p->device);
-    if (n_solutions == 0) {
-        FXC_HIP(p, hipStreamSynchronize(p->stream));
-        p->gain_n = p->gain_interval = p->gain_first = 0;
-        release_gain_q(p);
-        return FXC_OK;
-    }
-    // the new table is complete before the plan changes: a call that fails leaves an earlier gain track in force
-    const size_t bytes = count * sizeof(cd);
-    cd *g = nullptr, *q = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&q), bytes) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&g), bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        if (q) (void)hipFree(q);
-        return fail(p, FXC_ERR_NOMEM, "allocation of 2 x %zu bytes for the gain track failed", bytes);
-    }
-    hipError_t e = hipMemcpy(g, gains_re_im, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(track_gain_inverse_kernel, dim3(grid_for((int64_t)count, 256, p->cu_count)), dim3(256), 0, p->stream, g, q,
-                           p->nchan, (int64_t)count);
-        e = hipGetLastError();
-    }
-    // also ordered after any queued kernel that still reads the old table
-    if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-    (void)hipFree(g);
-    if (e != hipSuccess) {
-        (void)hipFree(q);
-        return fail(p, FXC_ERR_HIP, "forming the gain track's table failed: %s", hipGetErrorString(e));
-    }
-    if (p->d_gain_q) (void)hipFree(p->d_gain_q);
-    p->d_gain_q = q;
-    p->gain_n = n_solutions;
-    p->gain_interval = interval;
-    p->gain_first = first_chunk;
-    return FXC_OK;
+    return set_track_gains(p, gains_re_im, n_solutions, interval, first_chunk, count);
 }
 
 int fxc_track_gains_info(const fxc_plan* p, int64_t* n_solutions, int64_t* interval, int64_t* first_chunk) {
@@ -588,56 +431,18 @@ int fxc_delay_track_tables(fxc_plan* p, int64_t chunk, double* out_re_im) {
     if (!p || !out_re_im) return fail(p, FXC_ERR_ARG, "NULL argument");
     if (chunk < 0) return fail(p, FXC_ERR_ARG, "chunk < 0");
     if (!p->track) return fail(p, FXC_ERR_STATE, "the plan has no delay track");
-    FXC_DEVICE(p, p->device);
-    const size_t bytes = (size_t)p->n_ant * p->nchan * sizeof(cd);
-    const int rg = grow(p, &p->d_stage[1], &p->stage_bytes[1], bytes);
-    if (rg) return rg;
-    if (p->track_align)      // the chunk's whole-sample shifts, where the aligned table kernels read them
-        if (const int rs = track_shifts_pass(p, chunk, 1)) return rs;
-    const int rc = track_tables(p, chunk, 1, static_cast<cd*>(p->d_stage[1]), false);
-    if (rc) return rc;
-    FXC_HIP(p, hipMemcpyAsync(out_re_im, p->d_stage[1], bytes, hipMemcpyDeviceToHost, p->stream));
-    FXC_HIP(p, hipStreamSynchronize(p->stream));
-    return FXC_OK;
+    return delay_track_tables(p, chunk, out_re_im);
 }
 
 int fxc_set_rot(fxc_plan* p, const double* rot_re_im) {
     if (!p || !rot_re_im) return fail(p, FXC_ERR_ARG, "NULL argument");
-    if (const int rs = end_track(p)) return rs;
-    FXC_DEVICE(p, p->device);
-    // ordered after any queued finish kernel that still reads the old table
-    FXC_HIP(p, hipStreamSynchronize(p->stream));
-    release_gain_q(p);
-    FXC_HIP(p, hipMemcpy(p->d_rot, rot_re_im, (size_t)p->nchan * sizeof(cd), hipMemcpyHostToDevice));
-    p->rot_ant = false;
-    return FXC_OK;
+    return set_rot(p, rot_re_im);
 }
 
 int fxc_set_rot_ant(fxc_plan* p, const double* rot_ant_re_im) {
     if (!p || !rot_ant_re_im) return fail(p, FXC_ERR_ARG, "NULL argument");
     if (p->n_ant < 2) return fail(p, FXC_ERR_ARG, "per-antenna rot needs 2 or more antennas, the plan has %d", p->n_ant);
-    if (const int rs = end_track(p)) return rs;
-    FXC_DEVICE(p, p->device);
-    FXC_HIP(p, hipStreamSynchronize(p->stream));
-    release_gain_q(p);
-    const size_t N = (size_t)p->nchan;
-    const cd* r = reinterpret_cast<const cd*>(rot_ant_re_im);
-    if (p->n_ant == 2) {
-        // the one baseline's w = r_1 conj(r_0), in float64, into the shared table: every 2-antenna route runs as it is
-        std::vector<cd> w(N);
-        for (size_t k = 0; k < N; ++k) {
-            const cd ra = r[k], rb = r[N + k];
-            w[k].x = rb.x * ra.x + rb.y * ra.y;
-            w[k].y = rb.y * ra.x - rb.x * ra.y;
-        }
-        FXC_HIP(p, hipMemcpy(p->d_rot, w.data(), N * sizeof(cd), hipMemcpyHostToDevice));
-        p->rot_ant = false;
-        return FXC_OK;
-    }
-    if (!p->d_rot_ant) FXC_HIP(p, hipMalloc(&p->d_rot_ant, (size_t)p->n_ant * N * sizeof(cd)));
-    FXC_HIP(p, hipMemcpy(p->d_rot_ant, r, (size_t)p->n_ant * N * sizeof(cd), hipMemcpyHostToDevice));
-    p->rot_ant = true;
-    return FXC_OK;
+    return set_rot_ant(p, rot_ant_re_im);
 }
 
 int fxc_set_products(fxc_plan* p, int products) {
@@ -681,7 +486,7 @@ int fxc_set_stream(fxc_plan* p, void* stream) {
     // stream completes before anything on the new one starts (device-side dependency, no host wait)
     FXC_HIP(p, hipEventRecord(p->ev_order, p->stream));
     FXC_HIP(p, hipStreamWaitEvent(next, p->ev_order, 0));
-    p->stream = next;
+    p->stream.borrow(next);
     return FXC_OK;
 }
 
@@ -799,12 +604,12 @@ int fxc_comm_probe(void* rccl_comm, int64_t* ranks_summed) {
     if (!api->handle) return fail(nullptr, FXC_ERR_COMM, "%s", api->error.c_str());
     FXC_DEVICE(nullptr, c->device);
     // every rank puts in 1.0 (and its rank + 1 in a second slot): what comes back was added up by RCCL itself
-    double* d = nullptr;
-    hipStream_t s = nullptr;
-    FXC_HIP(nullptr, hipMalloc(reinterpret_cast<void**>(&d), 2 * sizeof(double)));
+    DevBuf<double> d;
+    Stream s;
+    FXC_HIP(nullptr, d.alloc(2));
     int rc = FXC_OK;
     double h[2] = {1.0, (double)(c->rank + 1)};
-    hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+    hipError_t e = s.create(hipStreamNonBlocking);
     if (e == hipSuccess) e = hipMemcpyAsync(d, h, sizeof h, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) {
         const ncclResult_t r = api->all_reduce(d, d, 2, ncclFloat64, ncclSum, c->comm, s);
@@ -812,8 +617,6 @@ int fxc_comm_probe(void* rccl_comm, int64_t* ranks_summed) {
     }
     if (e == hipSuccess && rc == FXC_OK) e = hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess && rc == FXC_OK) e = hipStreamSynchronize(s);
-    if (s) (void)hipStreamDestroy(s);
-    (void)hipFree(d);
     if (rc) return rc;
     if (e != hipSuccess) return fail(nullptr, FXC_ERR_HIP, "fxc_comm_probe: %s", hipGetErrorString(e));
     const double n = h[0];
@@ -898,82 +701,6 @@ int fxc_acc_export(fxc_plan* p, void* sums_dev) {
     return flush_pending(p, &fin);
 }
 
-namespace {
-
-// Queue the finalize of `sums_src` (exported, possibly cross-rank reduced sums) or, sums_src == nullptr, of the plan's
-// accumulator -- then together with the fold of the rows still pending and with the reset, in one kernel -- into the
-// next result slot; the slot's event marks the host copy complete.
-// user_out != nullptr (fxc_finalize_async_to): the result goes to that host buffer instead of the plan's pinned slot -- by
-// the finishing kernel itself when it is small and lies in fxc_host_alloc memory, by the side-stream copy when it is large
-// (a direct DMA for pinned memory) -- and fxc_finalize_wait copies nothing.
-int finalize_enqueue(fxc_plan* p, const cd* sums_src, int mode, double bandwidth, int reset, void* user_out = nullptr) {
-    if (mode != FXC_MODE_SPECTRUM && mode != FXC_MODE_CONTINUUM) return fail(p, FXC_ERR_ARG, "bad mode %d", mode);
-    if (mode == FXC_MODE_CONTINUUM && !(bandwidth > 0.0)) return fail(p, FXC_ERR_ARG, "bandwidth must be > 0");
-    if (p->res_head - p->res_tail >= fxc_plan::kResSlots)
-        return fail(p, FXC_ERR_STATE, "%d finalize results outstanding: collect one with fxc_finalize_wait first",
-                    fxc_plan::kResSlots);
-    if (!sums_src && !(p->spectra_count > 0.0)) return fail(p, FXC_ERR_STATE, "nothing accumulated");
-    const int slot = (int)(p->res_head % fxc_plan::kResSlots);
-    const int64_t n = (int64_t)p->n_prod * p->nchan;
-    const size_t bytes = mode == FXC_MODE_SPECTRUM ? (size_t)n * sizeof(cd) : (size_t)p->n_prod * sizeof(cd);
-    // small results are written into the pinned slot by the finishing kernel itself; large ones go through device
-    // memory and a copy on a side stream, off the F+X stream's critical path
-    const bool big = bytes > res_direct_bytes();
-    if (big && !p->s_copy) {
-        FXC_HIP(p, hipStreamCreateWithFlags(&p->s_copy, hipStreamNonBlocking));
-        FXC_HIP(p, hipEventCreateWithFlags(&p->ev_fin, hipEventDisableTiming));
-        for (int k = 0; k < fxc_plan::kResSlots; ++k) FXC_HIP(p, hipMalloc(&p->d_res_big[k], (size_t)acc_capacity(p) * sizeof(cd)));
-    }
-    cd* out = big ? p->d_res_big[slot] : p->d_res[slot];
-    cd* const user_mapped = (user_out && !big) ? static_cast<cd*>(pinned_device_ptr(user_out, bytes)) : nullptr;
-    if (user_mapped) out = user_mapped;
-    // where fxc_finalize_wait finds the bytes: the caller's buffer (nothing to copy) or the plan's slot
-    p->res_user[slot] = (user_out && (big || user_mapped)) ? user_out : nullptr;
-    p->res_dst[slot] = user_out;
-    if (!sums_src) {
-        // SPECTRUM: one kernel.  CONTINUUM needs the mean over the bins of the finished accumulator: export, then reduce
-        FoldFinish fin = {nullptr, out, nullptr, p->spectra_count, reset ? 1 : 0};
-        if (mode == FXC_MODE_CONTINUUM) {
-            // into a buffer of its own: d_sums may hold reduced sums (fxc_reduce) that fxc_finalize_sums(plan, NULL) has yet
-            // to read, and only fxc_reduce makes that copy valid
-            if (!p->d_cont) FXC_HIP(p, hipMalloc(&p->d_cont, ((size_t)acc_capacity(p) + 1) * sizeof(cd)));
-            fin.sums = p->d_cont;
-            fin.out = nullptr;
-            sums_src = p->d_cont;
-        }
-        // the slot's event rides on the last kernel's own completion (hipExtLaunchKernelGGL): an event recorded behind it is
-        // a packet of its own in the stream, and the next F+X kernel starts 11 us later for it
-        const int rc = flush_pending(p, &fin, (mode == FXC_MODE_SPECTRUM && !big) ? p->ev_res[slot] : nullptr);
-        if (rc) return rc;
-        if (reset) p->spectra_count = 0.0;
-    } else if (mode == FXC_MODE_SPECTRUM) {
-        const int rc = flush_pending(p);
-        if (rc) return rc;
-        with_finish_rot(p, true, [&](auto ant, auto rot) {
-            hipExtLaunchKernelGGL(finalize_spectrum_kernel<decltype(ant)::value>, dim3(grid_for(n, 256, p->cu_count)), dim3(256), 0, p->stream,
-                                  nullptr, big ? nullptr : p->ev_res[slot], 0, sums_src, out, rot, p->nchan, p->n_prod, p->n_base);
-        });
-    }
-    if (mode == FXC_MODE_CONTINUUM) {
-        with_finish_rot(p, true, [&](auto ant, auto rot) {
-            hipExtLaunchKernelGGL(finalize_continuum_kernel<decltype(ant)::value>, dim3(p->n_prod), dim3(256), 0, p->stream, nullptr,
-                                  big ? nullptr : p->ev_res[slot], 0, sums_src, out, rot, p->nchan, p->n_prod, 1.0 / bandwidth, p->n_base);
-        });
-    }
-    FXC_HIP(p, hipGetLastError());
-    if (big) {
-        FXC_HIP(p, hipEventRecord(p->ev_fin, p->stream));
-        FXC_HIP(p, hipStreamWaitEvent(p->s_copy, p->ev_fin, 0));
-        FXC_HIP(p, hipMemcpyAsync(user_out ? user_out : static_cast<void*>(p->h_res[slot]), out, bytes, hipMemcpyDeviceToHost, p->s_copy));
-        FXC_HIP(p, hipEventRecord(p->ev_res[slot], p->s_copy));
-    }
-    p->res_bytes[slot] = bytes;
-    p->res_head += 1;
-    return FXC_OK;
-}
-
-}  // namespace
-
 int fxc_finalize_async(fxc_plan* p, int mode, double bandwidth, int reset) {
     if (!p) return fail(p, FXC_ERR_ARG, "NULL plan");
     FXC_DEVICE(p, p->device);
@@ -1043,7 +770,7 @@ int fxc_remove_dc(fxc_plan* p, const void* x_dev, void* out_dev, int64_t n_strea
     const int n_slices = 32;
     rc = ensure_ws(p, n_streams * n_slices * 2 * (int64_t)sizeof(double));
     if (rc) return rc;
-    launch_remove_dc_c64(p, static_cast<const cf*>(x_dev), static_cast<cf*>(out_dev), static_cast<double*>(p->d_ws), n_streams, n_slices);
+    launch_remove_dc_c64(p, static_cast<const cf*>(x_dev), static_cast<cf*>(out_dev), static_cast<double*>(p->d_ws.get()), n_streams, n_slices);
     FXC_HIP(p, hipGetLastError());
     return FXC_OK;
 }
@@ -1055,7 +782,7 @@ int fxc_convert_u8(fxc_plan* p, const void* iq_u8_dev, void* out_dev, int64_t n_
     const int n_slices = 32;
     rc = ensure_ws(p, n_streams * n_slices * 2 * (int64_t)sizeof(double));
     if (rc) return rc;
-    double* part = static_cast<double*>(p->d_ws);
+    double* part = static_cast<double*>(p->d_ws.get());
     if (remove_dc) launch_dc_sum_u8(p, static_cast<const unsigned char*>(iq_u8_dev), part, n_streams, n_slices);
     launch_convert_u8(p, static_cast<const unsigned char*>(iq_u8_dev), static_cast<cf*>(out_dev), part, n_slices, n_streams, remove_dc != 0);
     FXC_HIP(p, hipGetLastError());
@@ -1347,24 +1074,7 @@ int fxc_solve_gains(fxc_plan* p, const void* rows, int64_t n_chunks, int mem_kin
 
 int fxc_pipe_destroy(fxc_pipe* q) {
     if (!q) return FXC_OK;
-    DeviceGuard device_guard__(q->plan->device);
-    if (q->counted) q->plan->live_pipes -= 1;
-    (void)hipStreamSynchronize(q->plan->stream);
-    if (q->s_in) (void)hipStreamSynchronize(q->s_in);
-    if (q->s_out) (void)hipStreamSynchronize(q->s_out);
-    for (auto& sl : q->slots) {
-        if (sl.h_in) (void)hipHostFree(sl.h_in);
-        if (sl.h_out) (void)hipHostFree(sl.h_out);
-        if (sl.d_in) (void)hipFree(sl.d_in);
-        if (sl.d_out) (void)hipFree(sl.d_out);
-        if (sl.ev_in) (void)hipEventDestroy(sl.ev_in);
-        if (sl.ev_compute) (void)hipEventDestroy(sl.ev_compute);
-        if (sl.ev_out) (void)hipEventDestroy(sl.ev_out);
-    }
-    if (q->s_in) (void)hipStreamDestroy(q->s_in);
-    if (q->s_out) (void)hipStreamDestroy(q->s_out);
-    delete q;
-    return FXC_OK;
+    return pipe_destroy(q);
 }
 
 int fxc_pipe_create(fxc_pipe** out, fxc_plan* p, int64_t chunks_per_batch, int depth, int mode, double bandwidth) {
@@ -1382,92 +1092,29 @@ int fxc_pipe_create_iq(fxc_pipe** out, fxc_plan* p, int64_t chunks_per_batch, in
     *out = nullptr;
     if (chunks_per_batch < 1 || depth < 1 || depth > 16) return fail(p, FXC_ERR_ARG, "bad batch size or depth");
     if (const int rc = check_call(p, {fmt, remove_dc != 0, true, mode, bandwidth})) return rc;
-    FXC_DEVICE(p, p->device);
-    fxc_pipe* q = new (std::nothrow) fxc_pipe();
-    if (!q) return fail(p, FXC_ERR_NOMEM, "host allocation failed");
-    q->plan = p;
-    q->chunks = chunks_per_batch;
-    q->depth = depth;
-    q->mode = mode;
-    q->bandwidth = bandwidth;
-    q->fmt = fmt;
-    q->remove_dc = remove_dc;
-    q->in_bytes = input_bytes(p, fmt, chunks_per_batch);
-    q->out_bytes = (size_t)chunks_per_batch * row_bytes(p, mode);
-    q->slots.resize((size_t)depth);
-    hipError_t e = hipStreamCreateWithFlags(&q->s_in, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&q->s_out, hipStreamNonBlocking);
-    for (auto& sl : q->slots) {
-        if (e == hipSuccess) e = hipHostMalloc(&sl.h_in, q->in_bytes, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc(&sl.h_out, q->out_bytes, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipMalloc(&sl.d_in, q->in_bytes);
-        if (e == hipSuccess) e = hipMalloc(&sl.d_out, q->out_bytes);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.ev_in, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.ev_compute, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.ev_out, hipEventDisableTiming);
-    }
-    if (e != hipSuccess) {
-        fxc_pipe_destroy(q);
-        return fail(p, e == hipErrorOutOfMemory ? FXC_ERR_NOMEM : FXC_ERR_HIP, "pipeline setup failed: %s",
-                    hipGetErrorString(e));
-    }
-    p->live_pipes += 1;
-    q->counted = true;
-    *out = q;
-    return FXC_OK;
+    return pipe_create(out, p, chunks_per_batch, depth, mode, bandwidth, fmt, remove_dc);
 }
 
 int fxc_pipe_in_flight(const fxc_pipe* q) { return q ? (int)(q->pushed - q->popped) : 0; }
 
 int fxc_pipe_acquire(fxc_pipe* q, void** in_host) {
     if (!q || !in_host) return fail(q ? q->plan : nullptr, FXC_ERR_ARG, "NULL argument");
-    if (q->pushed - q->popped >= q->depth)
-        return fail(q->plan, FXC_ERR_STATE, "all %d slots in flight: pop first", q->depth);
-    *in_host = q->slots[(size_t)(q->pushed % q->depth)].h_in;      // popped, hence idle
-    return FXC_OK;
+    return pipe_acquire(q, in_host);
 }
 
 int fxc_pipe_submit(fxc_pipe* q) {
     if (!q) return fail(nullptr, FXC_ERR_ARG, "NULL pipe");
-    fxc_plan* p = q->plan;
-    if (q->pushed - q->popped >= q->depth) return fail(p, FXC_ERR_STATE, "all %d slots in flight: pop first", q->depth);
-    FXC_DEVICE(p, p->device);
-    fxc_pipe_slot& sl = q->slots[(size_t)(q->pushed % q->depth)];
-    FXC_HIP(p, hipMemcpyAsync(sl.d_in, sl.h_in, q->in_bytes, hipMemcpyHostToDevice, q->s_in));
-    FXC_HIP(p, hipEventRecord(sl.ev_in, q->s_in));
-    FXC_HIP(p, hipStreamWaitEvent(p->stream, sl.ev_in, 0));
-    // the slot's device copy is the pipe's own (x_is_scratch): complex64 batches are de-meaned in place
-    int rc = fx_call_dev(p, {q->fmt, q->remove_dc != 0, true, q->mode, q->bandwidth}, sl.d_in, sl.d_out, q->chunks, true);
-    if (rc) return rc;
-    FXC_HIP(p, hipEventRecord(sl.ev_compute, p->stream));
-    FXC_HIP(p, hipStreamWaitEvent(q->s_out, sl.ev_compute, 0));
-    FXC_HIP(p, hipMemcpyAsync(sl.h_out, sl.d_out, q->out_bytes, hipMemcpyDeviceToHost, q->s_out));
-    FXC_HIP(p, hipEventRecord(sl.ev_out, q->s_out));
-    sl.busy = true;
-    q->pushed += 1;
-    return FXC_OK;
+    return pipe_submit(q);
 }
 
 int fxc_pipe_push(fxc_pipe* q, const void* x_host) {
     if (!q || !x_host) return fail(q ? q->plan : nullptr, FXC_ERR_ARG, "NULL argument");
-    void* dst = nullptr;
-    int rc = fxc_pipe_acquire(q, &dst);
-    if (rc) return rc;
-    std::memcpy(dst, x_host, q->in_bytes);
-    return fxc_pipe_submit(q);
+    return pipe_push(q, x_host);
 }
 
 int fxc_pipe_pop(fxc_pipe* q, void* out_host) {
     if (!q || !out_host) return fail(q ? q->plan : nullptr, FXC_ERR_ARG, "NULL argument");
-    fxc_plan* p = q->plan;
-    if (q->pushed == q->popped) return fail(p, FXC_ERR_STATE, "nothing in flight");
-    FXC_DEVICE(p, p->device);
-    fxc_pipe_slot& sl = q->slots[(size_t)(q->popped % q->depth)];
-    FXC_HIP(p, hipEventSynchronize(sl.ev_out));
-    std::memcpy(out_host, sl.h_out, q->out_bytes);
-    sl.busy = false;
-    q->popped += 1;
-    return FXC_OK;
+    return pipe_pop(q, out_host);
 }
 
 int fxc_timer_start(fxc_plan* p) {
@@ -1537,12 +1184,12 @@ int fxc_synth_fill(int device, void* stream, void* x_dev, uint64_t seed, int64_t
     hipStream_t st = static_cast<hipStream_t>(stream);
     float lut[256];
     for (int b = 0; b < 256; ++b) lut[b] = ((float)b - 127.5f) / 127.5f;
-    int* d_delays = nullptr;
-    cf* d_tone = nullptr;
-    float* d_lut = nullptr;
-    FXC_HIP(p, hipMalloc(&d_delays, (size_t)n_ant * sizeof(int)));
-    FXC_HIP(p, hipMalloc(&d_tone, (size_t)tone_period * sizeof(cf)));
-    FXC_HIP(p, hipMalloc(&d_lut, sizeof lut));
+    DevBuf<int> d_delays;
+    DevBuf<cf> d_tone;
+    DevBuf<float> d_lut;
+    FXC_HIP(p, d_delays.alloc((size_t)n_ant));
+    FXC_HIP(p, d_tone.alloc((size_t)tone_period));
+    FXC_HIP(p, d_lut.alloc(256));
     FXC_HIP(p, hipMemcpy(d_delays, delays, (size_t)n_ant * sizeof(int), hipMemcpyHostToDevice));
     FXC_HIP(p, hipMemcpy(d_tone, tone_re_im, (size_t)tone_period * sizeof(cf), hipMemcpyHostToDevice));
     FXC_HIP(p, hipMemcpy(d_lut, lut, sizeof lut, hipMemcpyHostToDevice));
@@ -1550,12 +1197,9 @@ int fxc_synth_fill(int device, void* stream, void* x_dev, uint64_t seed, int64_t
     int64_t grid = (total + 255) / 256;
     if (grid > 256 * 16) grid = 256 * 16;
     hipLaunchKernelGGL(synth_kernel, dim3((int)grid), dim3(256), 0, st, static_cast<cf*>(x_dev), seed, first_chunk,
-                       n_chunks, n_ant, num_samp, d_delays, d_tone, tone_period, d_lut);
+                       n_chunks, n_ant, num_samp, d_delays.get(), d_tone.get(), tone_period, d_lut.get());
     hipError_t e = hipGetLastError();
     hipError_t e2 = hipStreamSynchronize(st);
-    (void)hipFree(d_delays);
-    (void)hipFree(d_tone);
-    (void)hipFree(d_lut);
     if (e != hipSuccess) return fail(nullptr, FXC_ERR_HIP, "synth launch failed: %s", hipGetErrorString(e));
     if (e2 != hipSuccess) return fail(nullptr, FXC_ERR_HIP, "synth sync failed: %s", hipGetErrorString(e2));
     return FXC_OK;

@@ -153,9 +153,9 @@ void plan_spec(fxc_plan* p) {
 
 // ---- tables ------------------------------------------------------------------------------------------
 template <class V>
-int upload(fxc_plan* p, V** dst, const std::vector<V>& host) {
-    FXC_HIP(p, hipMalloc(dst, host.size() * sizeof(V)));
-    FXC_HIP(p, hipMemcpy(*dst, host.data(), host.size() * sizeof(V), hipMemcpyHostToDevice));
+int upload(fxc_plan* p, DevBuf<V>& dst, const std::vector<V>& host) {
+    FXC_HIP(p, dst.alloc(host.size()));
+    FXC_HIP(p, hipMemcpy(dst, host.data(), host.size() * sizeof(V), hipMemcpyHostToDevice));
     return FXC_OK;
 }
 
@@ -336,75 +336,74 @@ int plan_build(fxc_plan* p, const double* window) {
     hipDeviceProp_t prop;
     FXC_HIP(p, hipGetDeviceProperties(&prop, p->device));
     p->cu_count = prop.multiProcessorCount;
-    if (p->own_stream) FXC_HIP(p, hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-    FXC_HIP(p, hipEventCreate(&p->ev_t0));
-    FXC_HIP(p, hipEventCreate(&p->ev_t1));
-    FXC_HIP(p, hipEventCreateWithFlags(&p->ev_order, hipEventDisableTiming));
+    if (p->own_stream) FXC_HIP(p, p->stream.create(hipStreamNonBlocking));
+    FXC_HIP(p, p->ev_t0.create(hipEventDefault));
+    FXC_HIP(p, p->ev_t1.create(hipEventDefault));
+    FXC_HIP(p, p->ev_order.create(hipEventDisableTiming));
 
     const int N = p->nchan, T = p->ntaps;
     for (int t = 0; t < kMaxTaps; ++t) p->taps.h[t] = t < T ? (float)window[t] : 0.f;
     // window: float32 copy of the float64 design [ntaps][nchan]
     std::vector<float> wf((size_t)T * N);
     for (size_t n = 0; n < wf.size(); ++n) wf[n] = (float)window[n];
-    if (int rc = upload(p, &p->d_win, wf)) return rc;
+    if (int rc = upload(p, p->d_win, wf)) return rc;
     // window quads: the fused kernel, the tiled ring kernels, f8192_ring_kernel and the wave-local kernels (one unit tap behind the
     // pre-filter), and the lean builds of fx_spec.h (above 2048 channels, or with a prime factor of 17 ... 23), which read a point's
     // taps as one quad from L2
     const bool tiled_quads = p->small || p->small_f || (tiled_kernels(p) && (p->tiled_ring || p->f8192));
     const bool spec_quads = p->mixed && p->rtc && N <= 8192 && T <= 4;
     if (tiled_quads || spec_quads || p->path == FXC_PATH_FUSED)
-        if (int rc = upload(p, &p->d_win4, window_quads(wf, N, T, p->prefilter && tiled_quads))) return rc;
+        if (int rc = upload(p, p->d_win4, window_quads(wf, N, T, p->prefilter && tiled_quads))) return rc;
     if (p->prefilter || p->split8192)
-        if (int rc = upload(p, &p->d_hpre, reversed_taps(wf, N, T, p->pre_tp))) return rc;
+        if (int rc = upload(p, p->d_hpre, reversed_taps(wf, N, T, p->pre_tp))) return rc;
     if (p->prefilter && tiled_kernels(p))      // (the plain tiled kernel behind the pre-filter)
-        if (int rc = upload(p, &p->d_ones, std::vector<float>((size_t)N, 1.f))) return rc;
+        if (int rc = upload(p, p->d_ones, std::vector<float>((size_t)N, 1.f))) return rc;
     // generic FFT twiddles: [N/2] for the radix-2 kernel, [N] for the mixed-radix kernel and the direct DFT, [blu_nfft] for the chirp-z rows
     if (N > 1) {
         const int tn = p->mixed_blu ? p->blu_nfft : N;
-        if (int rc = upload(p, &p->d_tw, fft_twiddles((p->pow2 && !p->mixed) ? N / 2 : tn, tn))) return rc;
+        if (int rc = upload(p, p->d_tw, fft_twiddles((p->pow2 && !p->mixed) ? N / 2 : tn, tn))) return rc;
     }
     if (p->mixed_blu) {
         std::vector<cf> chirp, blud;
         chirp_tables(N, p->blu_nfft, &chirp, &blud);
-        if (int rc = upload(p, &p->d_chirp, chirp)) return rc;
-        if (int rc = upload(p, &p->d_blud, blud)) return rc;
+        if (int rc = upload(p, p->d_chirp, chirp)) return rc;
+        if (int rc = upload(p, p->d_blud, blud)) return rc;
     }
     if (p->path == FXC_PATH_FUSED || tiled_kernels(p)) {
-        if (int rc = upload(p, &p->d_tw1, stage_tw1())) return rc;
-        if (int rc = upload(p, &p->d_tw2, stage_tw2())) return rc;
+        if (int rc = upload(p, p->d_tw1, stage_tw1())) return rc;
+        if (int rc = upload(p, p->d_tw2, stage_tw2())) return rc;
     }
     if (tiled_kernels(p))
-        if (int rc = upload(p, &p->d_tw0, tiled_tw0(N))) return rc;
+        if (int rc = upload(p, p->d_tw0, tiled_tw0(N))) return rc;
     if (p->small || p->small_f)
-        if (int rc = upload(p, &p->d_tw_small, small_twiddles(N))) return rc;
+        if (int rc = upload(p, p->d_tw_small, small_twiddles(N))) return rc;
     if (p->split8192) {
-        if (int rc = upload(p, &p->d_tw8192, split_twiddles())) return rc;
-        if (int rc = upload(p, &p->d_unit4, window_quads(wf, fxc::fused::kN, T, true))) return rc;
+        if (int rc = upload(p, p->d_tw8192, split_twiddles())) return rc;
+        if (int rc = upload(p, p->d_unit4, window_quads(wf, fxc::fused::kN, T, true))) return rc;
     }
     cd one;
     one.x = 1.0;
     one.y = 0.0;
-    if (int rc = upload(p, &p->d_rot, std::vector<cd>((size_t)N, one))) return rc;
+    if (int rc = upload(p, p->d_rot, std::vector<cd>((size_t)N, one))) return rc;
     // baseline -> (a, b) for per-antenna rot (fxc_set_rot_ant), in the order of the X-engines: (0,1),(0,2)..(A-2,A-1)
     if (p->n_ant >= 3) {
         std::vector<int2> pair;
         for (int a = 0; a < p->n_ant; ++a)
             for (int b = a + 1; b < p->n_ant; ++b) pair.push_back(make_int2(a, b));
-        if (int rc = upload(p, &p->d_pair, pair)) return rc;
+        if (int rc = upload(p, p->d_pair, pair)) return rc;
     }
 
     const size_t acc_n = (size_t)acc_capacity(p);
-    FXC_HIP(p, hipMalloc(&p->d_acc, acc_n * sizeof(cd)));
+    FXC_HIP(p, p->d_acc.alloc(acc_n));
     FXC_HIP(p, hipMemset(p->d_acc, 0, acc_n * sizeof(cd)));
-    FXC_HIP(p, hipMalloc(&p->d_sums, (acc_n + 1) * sizeof(cd)));
+    FXC_HIP(p, p->d_sums.alloc(acc_n + 1));
     FXC_HIP(p, hipMemset(p->d_sums, 0, (acc_n + 1) * sizeof(cd)));
     // finalize results: pinned host memory the finishing kernels write through the device's mapping of it (coherent,
     // so the host sees the bytes once the slot's event has completed)
     for (int k = 0; k < fxc_plan::kResSlots; ++k) {
-        FXC_HIP(p, hipHostMalloc(reinterpret_cast<void**>(&p->h_res[k]), std::max<size_t>(acc_n, 16) * sizeof(cd),
-                                 hipHostMallocMapped | hipHostMallocCoherent));
+        FXC_HIP(p, p->h_res[k].alloc(std::max<size_t>(acc_n, 16) * sizeof(cd), hipHostMallocMapped | hipHostMallocCoherent));
         FXC_HIP(p, hipHostGetDevicePointer(reinterpret_cast<void**>(&p->d_res[k]), p->h_res[k], 0));
-        FXC_HIP(p, hipEventCreateWithFlags(&p->ev_res[k], hipEventReleaseToSystem));
+        FXC_HIP(p, p->ev_res[k].create(hipEventReleaseToSystem));
     }
 
     // the fused kernel (also behind the 8192-channel split): one 512-thread workgroup (136 KiB LDS) per CU

@@ -119,15 +119,15 @@ int condition_u8(fxc_plan* p, const unsigned char* xb, int64_t nc, bool remove_d
     const int64_t n_streams = nc * p->n_ant;
     // d_dc: the slice sums, then the conversion offsets
     const size_t part_bytes = (size_t)n_streams * kSlices * 2 * sizeof(double);
-    int rc = grow(p, &p->d_dc, &p->dc_bytes, part_bytes + (size_t)n_streams * sizeof(cf));
+    int rc = grow(p, p->d_dc, part_bytes + (size_t)n_streams * sizeof(cf));
     if (rc) return rc;
-    double* part = static_cast<double*>(p->d_dc);
-    cf* dc = reinterpret_cast<cf*>(static_cast<char*>(p->d_dc) + part_bytes);
+    double* part = static_cast<double*>(p->d_dc.get());
+    cf* dc = reinterpret_cast<cf*>(static_cast<char*>(p->d_dc.get()) + part_bytes);
     if (!fused_in) {
         if (remove_dc) launch_dc_sum_u8(p, xb, part, n_streams, kSlices);
-        rc = grow(p, &p->d_stage[2], &p->stage_bytes[2], (size_t)n_streams * p->num_samp * sizeof(cf));
+        rc = grow(p, p->d_stage[2], (size_t)n_streams * p->num_samp * sizeof(cf));
         if (rc) return rc;
-        cf* xc = static_cast<cf*>(p->d_stage[2]);
+        cf* xc = static_cast<cf*>(p->d_stage[2].get());
         launch_convert_u8(p, xb, xc, part, kSlices, n_streams, remove_dc);
         FXC_HIP(p, hipGetLastError());
         in->x = xc;
@@ -172,14 +172,14 @@ int condition_u8(fxc_plan* p, const unsigned char* xb, int64_t nc, bool remove_d
 int condition_iq(fxc_plan* p, const void* xb, int64_t nc, int fmt, bool remove_dc, bool in_place, PassInput* in) {
     const int64_t n_streams = nc * p->n_ant;
     const int n_slices = sum_slices(p, n_streams);
-    int rc = grow(p, &p->d_dc, &p->dc_bytes, (size_t)n_streams * n_slices * 2 * sizeof(double));
+    int rc = grow(p, p->d_dc, (size_t)n_streams * n_slices * 2 * sizeof(double));
     if (rc) return rc;
-    double* part = static_cast<double*>(p->d_dc);
+    double* part = static_cast<double*>(p->d_dc.get());
     cf* xc = in_place ? static_cast<cf*>(const_cast<void*>(xb)) : nullptr;
     if (!in_place) {
-        rc = grow(p, &p->d_stage[2], &p->stage_bytes[2], (size_t)n_streams * p->num_samp * sizeof(cf));
+        rc = grow(p, p->d_stage[2], (size_t)n_streams * p->num_samp * sizeof(cf));
         if (rc) return rc;
-        xc = static_cast<cf*>(p->d_stage[2]);
+        xc = static_cast<cf*>(p->d_stage[2].get());
     }
     if (fmt == FXC_IQ_C128) {
         const int app = cond_slices(p, n_streams);
@@ -209,15 +209,15 @@ void launch_align_c64(fxc_plan* p, const cf* x, cf* out, const int* shifts, int 
 
 int align_pass(fxc_plan* p, int64_t nc, PassInput* in) {
     const int64_t n_streams = nc * p->n_ant;
-    int rc = grow(p, &p->d_align, &p->align_bytes, (size_t)n_streams * p->num_samp * sizeof(cf));
+    int rc = grow(p, p->d_align, (size_t)n_streams * p->num_samp * sizeof(cf));
     if (rc) return rc;
     const bool tracked = p->track && p->track_align;
     if (tracked) {
         rc = track_shifts_pass(p, p->track_t, nc);
         if (rc) return rc;
     }
-    cf* xa = static_cast<cf*>(p->d_align);
-    launch_align_c64(p, in->x, xa, tracked ? static_cast<const int*>(p->d_tshift) : p->d_shift, tracked ? p->n_ant : 0, n_streams);
+    cf* xa = static_cast<cf*>(p->d_align.get());
+    launch_align_c64(p, in->x, xa, tracked ? static_cast<const int*>(p->d_tshift.get()) : p->d_shift, tracked ? p->n_ant : 0, n_streams);
     FXC_HIP(p, hipGetLastError());
     *in = {xa};
     return FXC_OK;

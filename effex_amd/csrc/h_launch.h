@@ -336,8 +336,8 @@ int64_t stream_blocks(const fxc_plan* p) {
 AntRot ant_rot_arg(const fxc_plan* p) { return {p->d_rot_ant, p->d_pair}; }
 // the delay track's tables of a pass (h_run.h::track_pass writes them): one per chunk for two antennas, one per chunk and antenna for more
 int64_t track_stride(const fxc_plan* p) { return (int64_t)(p->n_ant == 2 ? 1 : p->n_ant) * p->nchan; }
-TrackRot<false> track_rot_arg(const fxc_plan* p) { return {static_cast<const cd*>(p->d_track), track_stride(p)}; }
-TrackRot<true> track_ant_rot_arg(const fxc_plan* p) { return {{static_cast<const cd*>(p->d_track), p->d_pair}, track_stride(p)}; }
+TrackRot<false> track_rot_arg(const fxc_plan* p) { return {static_cast<const cd*>(p->d_track.get()), track_stride(p)}; }
+TrackRot<true> track_ant_rot_arg(const fxc_plan* p) { return {{static_cast<const cd*>(p->d_track.get()), p->d_pair}, track_stride(p)}; }
 // the shared table of the finishing side: a tracked integration's sums are rotated already
 const cd* finalize_rot(const fxc_plan* p) { return p->track ? p->d_one : p->d_rot; }
 
@@ -388,13 +388,13 @@ int fold_rows(fxc_plan* p, const cf* raw, cd* part, int64_t n_rows, int layout, 
         constexpr bool ANT = decltype(ant)::value;
         if (splits == 1) {
             hipExtLaunchKernelGGL(fold_finish_kernel<cf, ANT>, dim3(cols), dim3(256 * kFoldPhases), 0, p->stream, nullptr, done, 0, raw,
-                                  n_rows, p->d_acc, p->nchan, p->n_prod, layout, finish_with<ANT>(fin, rot));
+                                  n_rows, p->d_acc.get(), p->nchan, p->n_prod, layout, finish_with<ANT>(fin, rot));
         } else {
             hipLaunchKernelGGL(fold_partial_kernel, dim3(cols, splits), dim3(256 * kFoldPhases), 0, p->stream, raw, part, row_len,
                                n_rows, splits);
             // the partials are in the rows' own layout
             hipExtLaunchKernelGGL(fold_finish_kernel<cd, ANT>, dim3(cols), dim3(256 * kFoldPhases), 0, p->stream, nullptr, done, 0,
-                                  (const cd*)part, (int64_t)splits, p->d_acc, p->nchan, p->n_prod, layout, finish_with<ANT>(fin, rot));
+                                  (const cd*)part, (int64_t)splits, p->d_acc.get(), p->nchan, p->n_prod, layout, finish_with<ANT>(fin, rot));
         }
     });
     FXC_HIP(p, hipGetLastError());
@@ -414,7 +414,7 @@ int flush_pending(fxc_plan* p, const FoldFinish* fin, hipEvent_t done) {
         with_finish_rot(p, f.out != nullptr, [&](auto ant, auto rot) {
             constexpr bool ANT = decltype(ant)::value;
             hipExtLaunchKernelGGL(acc_finish_kernel<ANT>, dim3(grid_for(n, 256, p->cu_count)), dim3(256), 0, p->stream, nullptr, done, 0,
-                                  p->d_acc, p->nchan, p->n_prod, finish_with<ANT>(f, rot));
+                                  p->d_acc.get(), p->nchan, p->n_prod, finish_with<ANT>(f, rot));
         });
         FXC_HIP(p, hipGetLastError());
     } else if (done) {
@@ -460,7 +460,7 @@ int launch_fused(fxc_plan* p, const FusedLaunch& f) {
     if (f.n_pairs * p->n_pts >= (1ll << 31)) return fail(p, FXC_ERR_ARG, "more than 2^31 frames in one launch");
     unsigned long long* stamps = nullptr;
 #if FXC_STAMPS
-    if (!p->d_stamps) FXC_HIP(p, hipMalloc(&p->d_stamps, (size_t)p->fused_grid_max * 8 * kStampSegs * 8));
+    if (!p->d_stamps) FXC_HIP(p, p->d_stamps.alloc((size_t)p->fused_grid_max * 8 * kStampSegs));
     FXC_HIP(p, hipMemsetAsync(p->d_stamps, 0, (size_t)p->fused_grid_max * 8 * kStampSegs * 8, p->stream));
     stamps = p->d_stamps;
     p->stamp_grid = grid;
@@ -468,14 +468,14 @@ int launch_fused(fxc_plan* p, const FusedLaunch& f) {
     // kernel profiling (bench.py): the two events ride on the dispatch itself (hipExtLaunchKernelGGL: start and stop
     // time of this kernel, no barrier packets of their own in the stream -- events recorded around the launch cost 6 + 11 us
     // of stream time per launch, profiles/r03/experiments.md)
-    hipEvent_t ev_a = nullptr, ev_b = nullptr;
-    if (p->profiling && (hipEventCreate(&ev_a) != hipSuccess || hipEventCreate(&ev_b) != hipSuccess)) ev_a = ev_b = nullptr;
+    Event ev_a, ev_b;
+    if (p->profiling && (ev_a.create(hipEventDefault) != hipSuccess || ev_b.create(hipEventDefault) != hipSuccess)) ev_a.reset(), ev_b.reset();
     // the kernel's last two operands: the raw-row layout, or -- spectra out -- the stream pairs per chunk
     const bool spec_out = f.what == kFusedSpectra;
     const int unit = spec_out ? p->n_ant / 2 : (int)f.unit, by_chunk = spec_out || f.rows_are_chunks ? 1 : 0;
 #define FXC_FUSED_LAUNCH(KERNEL, LDS)                                                                                               \
     hipExtLaunchKernelGGL(KERNEL, dim3(grid), dim3(kThreads), LDS, p->stream, ev_a, ev_b, 0, f.x, num_samp, p->n_pts, f.n_pairs, win4, \
-                          p->d_tw1, p->d_tw2, f.out, stamps, f.dc_u8, seg, unit, by_chunk)
+                          p->d_tw1.get(), p->d_tw2.get(), f.out, stamps, f.dc_u8, seg, unit, by_chunk)
     if (f.dc_u8 && f.dck)
         FXC_FUSED_LAUNCH((fx_fused4096_kernel<false, true, true>), kLdsBytes + kDckLdsBytes);
     else if (f.dc_u8)
@@ -487,7 +487,7 @@ int launch_fused(fxc_plan* p, const FusedLaunch& f) {
     else
         FXC_FUSED_LAUNCH((fx_fused4096_kernel<false, false>), kLdsBytes);
 #undef FXC_FUSED_LAUNCH
-    if (ev_a) p->kev.emplace_back(ev_a, ev_b);
+    if (ev_a) p->kev.emplace_back(std::move(ev_a), std::move(ev_b));
     FXC_HIP(p, hipGetLastError());
     return FXC_OK;
 }
@@ -508,7 +508,7 @@ struct SpecLaunch {
 int launch_spec(fxc_plan* p, const SpecKernel* k, const SpecLaunch& s) {
     if (s.groups * s.ws > (1ll << 30)) return fail(p, FXC_ERR_ARG, "too many streams or chunks for one launch");
     SpecArgs a = {s.x, p->d_win, s.out, p->d_tw, s.dc_u8, (long long)p->num_samp, (long long)p->n_pts, (long long)s.n_streams, (int)s.ws,
-                  s.ant, reinterpret_cast<const float*>(p->d_win4), k->d_tw1, (long long)s.stride, s.spec0};
+                  s.ant, reinterpret_cast<const float*>(p->d_win4.get()), k->d_tw1, (long long)s.stride, s.spec0};
     void* params[] = {&a};
     FXC_HIP(p, hipModuleLaunchKernel(k->fn, (unsigned)(s.groups * s.ws), 1, 1, (unsigned)k->shape.threads(), 1, 1, 0, p->stream, params, nullptr));
     return FXC_OK;
@@ -641,9 +641,9 @@ int small_launch(fxc_plan* p, const TiledLaunch& t) {
 
 // y = pre-filtered copy of n_streams streams (plan buffer, grown on demand)
 int tiled_prefilter(fxc_plan* p, const cf* x, int64_t n_streams, const cf** y_out) {
-    const int rg = grow(p, &p->d_pre, &p->pre_bytes, (size_t)n_streams * p->num_samp * sizeof(cf));
+    const int rg = grow(p, p->d_pre, (size_t)n_streams * p->num_samp * sizeof(cf));
     if (rg) return rg;
-    cf* y = static_cast<cf*>(p->d_pre);
+    cf* y = static_cast<cf*>(p->d_pre.get());
     const int tp = p->pre_tp;
     // two adjacent positions per thread (16-byte accesses) for the 8-frame block (1024 channels / 8 taps: -6 %; the 16-frame
     // block would need 218 VGPRs: -2 % at 512 channels, +3 % at 2048; the 32-frame block has no registers to spare);
@@ -947,9 +947,9 @@ int tiled_raw_sums(fxc_plan* p, const cf* x, int64_t nc, int n_splits, cf* raw, 
         // to this route), its XM form runs antenna 1 through the same stages and multiplies by them as it goes --
         // raw[split][chunk][N] like the tiled kernels'.  Bytes in (dc_u8: the conversion offsets [chunk][2]): converted on their way
         // into the ring
-        int rc = grow(p, &p->d_pre, &p->pre_bytes, (size_t)nc * p->n_pts * p->nchan * sizeof(cf));
+        int rc = grow(p, p->d_pre, (size_t)nc * p->n_pts * p->nchan * sizeof(cf));
         if (rc) return rc;
-        cf* s0 = static_cast<cf*>(p->d_pre);
+        cf* s0 = static_cast<cf*>(p->d_pre.get());
         const int f_splits = ring8192_splits(p, nc);
         const dim3 grid_f = ring8192_grid(p, nc, f_splits), grid_x = ring8192_grid(p, nc, n_splits);
         // antenna 1's stream of the first chunk: num_samp samples (of 8 bytes, or of 2) behind antenna 0's
@@ -983,9 +983,9 @@ int tiled_raw_sums(fxc_plan* p, const cf* x, int64_t nc, int n_splits, cf* raw, 
 // rows) for nc chunks of 8192-channel input
 int split_raw_sums(fxc_plan* p, const cf* x, int64_t nc, cf* raw) {
     const int64_t half_samp = p->n_pts * 4096;
-    int rc = grow(p, &p->d_pre, &p->pre_bytes, (size_t)nc * 4 * half_samp * sizeof(cf));
+    int rc = grow(p, p->d_pre, (size_t)nc * 4 * half_samp * sizeof(cf));
     if (rc) return rc;
-    cf* y = static_cast<cf*>(p->d_pre);
+    cf* y = static_cast<cf*>(p->d_pre.get());
     const int tp = p->pre_tp;
     // two adjacent positions per thread (16-byte accesses) for the 4- and 8-frame blocks (the 16-frame one has no registers left)
     static const bool narrow = FXC_DEV_ENV_INT("FXC_PRE_W", 0) == 1;

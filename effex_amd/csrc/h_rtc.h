@@ -427,8 +427,19 @@ struct SpecKernel {
     int vgprs = 0;
     int source = kSpecNone;      // where the code object came from (SpecSource), and the seconds the whole search for it took
     double seconds = 0;
-    cf* d_tw1 = nullptr;         // lean builds: the first twiddles by stage, butterfly and thread (fx_spec.h, Args::tw1)
+    DevBuf<cf> d_tw1;            // lean builds: the first twiddles by stage, butterfly and thread (fx_spec.h, Args::tw1)
     std::string error;           // why there is none (fn == nullptr)
+    SpecKernel() = default;
+    SpecKernel(const SpecKernel&) = delete;
+    SpecKernel& operator=(const SpecKernel&) = delete;
+    ~SpecKernel() { release(); }
+    // gives the module and the table back; what describes the build (error, shape, source) stays readable
+    void release() {
+        if (module) (void)hipModuleUnload(module);
+        module = nullptr;
+        fn = nullptr;
+        d_tw1.reset();
+    }
 };
 
 // the argument block of fxm_fx2_kernel (fx_spec.h::Args), field for field
@@ -467,7 +478,14 @@ std::vector<cf> spec_tw1_table(const SpecShape& sh) {
 }
 
 std::mutex g_spec_mutex;
-std::map<std::string, SpecKernel*> g_spec_cache;     // (device, shape) -> kernel; entries live as long as the process
+// (device, shape) -> kernel, and the kernels whose build failed in a way that may not repeat: off the map, so the next plan tries
+// again, but kept, since the plan that asked still reads `error`.  Both live as long as the process and are never destroyed: at
+// exit the HIP runtime may be gone before a static destructor could unload a module.
+struct SpecCache {
+    std::map<std::string, std::unique_ptr<SpecKernel>> live;
+    std::vector<std::unique_ptr<SpecKernel>> retired;
+};
+SpecCache& g_spec_cache = *new SpecCache;
 
 // An integer of the kernel's metadata note in a code object (msgpack: the key as a string, then the value): -1 if absent.
 // (hipFuncGetAttribute's LOCAL_SIZE_BYTES does not report the scratch of a module function here: it read 80 for a kernel
@@ -926,24 +944,27 @@ const SpecKernel* spec_kernel(int device, int n, int taps, int variant) {
     char key[256];
     std::snprintf(key, sizeof key, "d%d n%d t%d v%d %s", device, n, taps, variant, spec_knob_key().c_str());
     std::lock_guard<std::mutex> lock(g_spec_mutex);
-    auto it = g_spec_cache.find(key);
-    if (it != g_spec_cache.end()) return it->second;
-    SpecKernel* k = new SpecKernel;
-    g_spec_cache[key] = k;
+    auto it = g_spec_cache.live.find(key);
+    if (it != g_spec_cache.live.end()) return it->second.get();
+    SpecKernel* k = (g_spec_cache.live[key] = std::make_unique<SpecKernel>()).get();
+    // a failure that is not remembered: `why` for the plan that asked, the module and the table released, the key free again
+    const auto retire = [&](const std::string& why) {
+        k->error = why;
+        k->release();
+        g_spec_cache.retired.push_back(std::move(g_spec_cache.live[key]));
+        g_spec_cache.live.erase(key);
+        return k;
+    };
     hipDeviceProp_t prop;
     // (a failure that may not repeat -- the device query, the module load, device memory -- is not remembered: the next plan tries again)
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) {
-        k->error = "hipGetDeviceProperties failed";
-        g_spec_cache.erase(key);
-        return k;
-    }
+    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return retire("hipGetDeviceProperties failed");
     const auto t0 = std::chrono::steady_clock::now();
     SpecBuild b = spec_search(n, taps, variant, spec_arch(prop.gcnArchName).c_str());
     k->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     k->source = b.source;
     if (b.image.empty()) {
+        if (b.error.find("libhiprtc") != std::string::npos) return retire(b.error);      // (no compiler in reach yet: not a property of the shape)
         k->error = b.error;
-        if (b.error.find("libhiprtc") != std::string::npos) g_spec_cache.erase(key);      // (no compiler in reach yet: not a property of the shape)
         return k;
     }
     k->shape = b.shape;
@@ -956,21 +977,11 @@ const SpecKernel* spec_kernel(int device, int n, int taps, int variant) {
     DeviceGuard guard(device);
     hipError_t e = hipModuleLoadData(&k->module, b.image.data());
     if (e == hipSuccess) e = hipModuleGetFunction(&k->fn, k->module, "fxm_fx2_kernel");
-    if (e != hipSuccess) {
-        k->error = std::string("loading the compiled kernel: ") + hipGetErrorString(e);
-        k->fn = nullptr;
-        g_spec_cache.erase(key);
-        return k;
-    }
+    if (e != hipSuccess) return retire(std::string("loading the compiled kernel: ") + hipGetErrorString(e));
     if (k->shape.lean) {
         const std::vector<cf> t = spec_tw1_table(k->shape);
-        if (hipMalloc(&k->d_tw1, t.size() * sizeof(cf)) != hipSuccess ||
-            hipMemcpy(k->d_tw1, t.data(), t.size() * sizeof(cf), hipMemcpyHostToDevice) != hipSuccess) {
-            k->error = "the twiddle table of the lean build: out of device memory";
-            k->fn = nullptr;
-            g_spec_cache.erase(key);
-            return k;
-        }
+        if (k->d_tw1.alloc(t.size()) != hipSuccess || hipMemcpy(k->d_tw1, t.data(), t.size() * sizeof(cf), hipMemcpyHostToDevice) != hipSuccess)
+            return retire("the twiddle table of the lean build: out of device memory");
     }
     int blocks = 0;
     k->wgs_per_cu = std::max(1, b.resident);

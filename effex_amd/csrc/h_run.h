@@ -58,11 +58,11 @@ bool fused_autos(const fxc_plan* p) { return p->autos && p->path == FXC_PATH_FUS
 // (track_shifts_pass: fx_call_dev for every pass, fxc_delay_track_tables for its chunk); the alignment of the pass and the
 // aligned table kernels read them from there, so track_tables is only asked for chunks of the run written last.
 int track_shifts_pass(fxc_plan* p, int64_t t0, int64_t n_t) {
-    const int rg = grow(p, &p->d_tshift, &p->tshift_bytes, (size_t)(n_t * p->n_ant) * sizeof(int));
+    const int rg = grow(p, p->d_tshift, (size_t)(n_t * p->n_ant) * sizeof(int));
     if (rg) return rg;
     const TrackPar tp = {p->d_track_par, p->d_track_par + p->n_ant, p->track_df, p->track_freq};
     hipLaunchKernelGGL(track_shifts_kernel, dim3(grid_for(n_t * p->n_ant, 256, p->cu_count)), dim3(256), 0, p->stream, tp, p->track_bw,
-                       static_cast<int*>(p->d_tshift), p->n_ant, t0, n_t);
+                       static_cast<int*>(p->d_tshift.get()), p->n_ant, t0, n_t);
     FXC_HIP(p, hipGetLastError());
     p->tshift_t0 = t0;
     return FXC_OK;
@@ -72,7 +72,7 @@ int track_tables(fxc_plan* p, int64_t t0, int64_t n_t, cd* out, bool pair) {
     const TrackPar tp = {p->d_track_par, p->d_track_par + p->n_ant, p->track_df, p->track_freq};
     const dim3 grid(grid_for(n_t * (pair ? 1 : p->n_ant) * p->nchan, 256, p->cu_count));
     if (p->track_align) {
-        const TrackAlign al = {static_cast<const int*>(p->d_tshift), p->tshift_t0};
+        const TrackAlign al = {static_cast<const int*>(p->d_tshift.get()), p->tshift_t0};
         const bool gain = p->gain_n > 0;
         const GainTrack gt = {p->d_gain_q, p->gain_n, p->gain_interval > 0 ? p->gain_interval : 1, p->gain_first};
         const auto launch = [&](auto pr, auto gn) {
@@ -98,9 +98,9 @@ int track_tables(fxc_plan* p, int64_t t0, int64_t n_t, cd* out, bool pair) {
 }
 
 int track_pass(fxc_plan* p, int64_t n_chunks) {
-    const int rg = grow(p, &p->d_track, &p->track_bytes, (size_t)(n_chunks * track_stride(p)) * sizeof(cd));
+    const int rg = grow(p, p->d_track, (size_t)(n_chunks * track_stride(p)) * sizeof(cd));
     if (rg) return rg;
-    const int rc = track_tables(p, p->track_t, n_chunks, static_cast<cd*>(p->d_track), p->n_ant == 2);
+    const int rc = track_tables(p, p->track_t, n_chunks, static_cast<cd*>(p->d_track.get()), p->n_ant == 2);
     if (rc) return rc;
     p->track_t += n_chunks;
     return FXC_OK;
@@ -121,9 +121,9 @@ int launch_rows_continuum(fxc_plan* p, const cf* raw, cd* out, int nchan, int64_
                           double scale, int slots, LeadRows lead, int n_prod, int n_cross) {
     const int slices = (int)std::min<int64_t>(32, nchan / 128);
     if (slices >= 2 && rows * 2 <= p->cu_count && rows <= 65535) {
-        const int rg = grow(p, &p->d_rowpart, &p->rowpart_bytes, (size_t)rows * slices * sizeof(cd));
+        const int rg = grow(p, p->d_rowpart, (size_t)rows * slices * sizeof(cd));
         if (rg) return rg;
-        cd* part = static_cast<cd*>(p->d_rowpart);
+        cd* part = static_cast<cd*>(p->d_rowpart.get());
         with_rows_rot(p, [&](auto ant, auto trk, auto rot) {
             hipLaunchKernelGGL((rows_continuum_part_kernel<decltype(ant)::value, decltype(trk)::value>), dim3(slices, (unsigned)rows),
                                dim3(256), 0, p->stream, raw, part, rot, nchan, rows, n_splits, split_stride, slots, lead, slices, n_prod,
@@ -192,7 +192,7 @@ int carve_ws(fxc_plan* p, bool fold, int64_t spec_bytes, int64_t raw_bytes, Work
     raw_bytes = up256(raw_bytes);
     const int rc = ensure_ws(p, spec_bytes + raw_bytes + (fold ? fold_part_bytes(p) : 0));
     if (rc) return rc;
-    char* base = static_cast<char*>(p->d_ws);
+    char* base = static_cast<char*>(p->d_ws.get());
     w->spec = reinterpret_cast<cf*>(base);
     w->raw = reinterpret_cast<cf*>(base + spec_bytes);
     w->part = fold ? reinterpret_cast<cd*>(base + spec_bytes + raw_bytes) : nullptr;
@@ -393,7 +393,7 @@ int with_host_staging(fxc_plan* p, const void* x, size_t x_bytes, void* out, siz
     void* out_mapped = out_bytes ? pinned_device_ptr(out, out_bytes) : nullptr;
     const size_t want[2] = {x_bytes ? x_bytes : 1, out_mapped ? 0 : out_bytes};
     for (int k = 0; k < 2; ++k) {
-        const int rg = grow(p, &p->d_stage[k], &p->stage_bytes[k], want[k]);
+        const int rg = grow(p, p->d_stage[k], want[k]);
         if (rg) return rg;
     }
     void* dx = p->d_stage[0];
@@ -409,6 +409,74 @@ int with_host_staging(fxc_plan* p, const void* x, size_t x_bytes, void* out, siz
     if (rc != FXC_OK) return rc;
     if (e != hipSuccess) return fail(p, FXC_ERR_HIP, "host staging copy failed: %s", hipGetErrorString(e));
     if (e2 != hipSuccess) return fail(p, FXC_ERR_HIP, "stream sync failed: %s", hipGetErrorString(e2));
+    return FXC_OK;
+}
+
+// Queue the finalize of `sums_src` (exported, possibly cross-rank reduced sums) or, sums_src == nullptr, of the plan's
+// accumulator -- then together with the fold of the rows still pending and with the reset, in one kernel -- into the
+// next result slot; the slot's event marks the host copy complete.
+// user_out != nullptr (fxc_finalize_async_to): the result goes to that host buffer instead of the plan's pinned slot -- by
+// the finishing kernel itself when it is small and lies in fxc_host_alloc memory, by the side-stream copy when it is large
+// (a direct DMA for pinned memory) -- and fxc_finalize_wait copies nothing.
+int finalize_enqueue(fxc_plan* p, const cd* sums_src, int mode, double bandwidth, int reset, void* user_out = nullptr) {
+    if (mode != FXC_MODE_SPECTRUM && mode != FXC_MODE_CONTINUUM) return fail(p, FXC_ERR_ARG, "bad mode %d", mode);
+    if (mode == FXC_MODE_CONTINUUM && !(bandwidth > 0.0)) return fail(p, FXC_ERR_ARG, "bandwidth must be > 0");
+    if (p->res_head - p->res_tail >= fxc_plan::kResSlots)
+        return fail(p, FXC_ERR_STATE, "%d finalize results outstanding: collect one with fxc_finalize_wait first",
+                    fxc_plan::kResSlots);
+    if (!sums_src && !(p->spectra_count > 0.0)) return fail(p, FXC_ERR_STATE, "nothing accumulated");
+    const int slot = (int)(p->res_head % fxc_plan::kResSlots);
+    const int64_t n = (int64_t)p->n_prod * p->nchan;
+    const size_t bytes = mode == FXC_MODE_SPECTRUM ? (size_t)n * sizeof(cd) : (size_t)p->n_prod * sizeof(cd);
+    // small results are written into the pinned slot by the finishing kernel itself; large ones go through device
+    // memory and a copy on a side stream, off the F+X stream's critical path
+    const bool big = bytes > res_direct_bytes();
+    if (big && !p->big_res) FXC_HIP(p, p->big_res.create(hipStreamNonBlocking, hipEventDisableTiming, (size_t)acc_capacity(p)));
+    cd* out = big ? p->big_res.d_res_big[slot] : p->d_res[slot];
+    cd* const user_mapped = (user_out && !big) ? static_cast<cd*>(pinned_device_ptr(user_out, bytes)) : nullptr;
+    if (user_mapped) out = user_mapped;
+    // where fxc_finalize_wait finds the bytes: the caller's buffer (nothing to copy) or the plan's slot
+    p->res_user[slot] = (user_out && (big || user_mapped)) ? user_out : nullptr;
+    p->res_dst[slot] = user_out;
+    if (!sums_src) {
+        // SPECTRUM: one kernel.  CONTINUUM needs the mean over the bins of the finished accumulator: export, then reduce
+        FoldFinish fin = {nullptr, out, nullptr, p->spectra_count, reset ? 1 : 0};
+        if (mode == FXC_MODE_CONTINUUM) {
+            // into a buffer of its own: d_sums may hold reduced sums (fxc_reduce) that fxc_finalize_sums(plan, NULL) has yet
+            // to read, and only fxc_reduce makes that copy valid
+            if (!p->d_cont) FXC_HIP(p, p->d_cont.alloc((size_t)acc_capacity(p) + 1));
+            fin.sums = p->d_cont;
+            fin.out = nullptr;
+            sums_src = p->d_cont;
+        }
+        // the slot's event rides on the last kernel's own completion (hipExtLaunchKernelGGL): an event recorded behind it is
+        // a packet of its own in the stream, and the next F+X kernel starts 11 us later for it
+        const int rc = flush_pending(p, &fin, (mode == FXC_MODE_SPECTRUM && !big) ? p->ev_res[slot] : nullptr);
+        if (rc) return rc;
+        if (reset) p->spectra_count = 0.0;
+    } else if (mode == FXC_MODE_SPECTRUM) {
+        const int rc = flush_pending(p);
+        if (rc) return rc;
+        with_finish_rot(p, true, [&](auto ant, auto rot) {
+            hipExtLaunchKernelGGL(finalize_spectrum_kernel<decltype(ant)::value>, dim3(grid_for(n, 256, p->cu_count)), dim3(256), 0, p->stream,
+                                  nullptr, big ? nullptr : p->ev_res[slot], 0, sums_src, out, rot, p->nchan, p->n_prod, p->n_base);
+        });
+    }
+    if (mode == FXC_MODE_CONTINUUM) {
+        with_finish_rot(p, true, [&](auto ant, auto rot) {
+            hipExtLaunchKernelGGL(finalize_continuum_kernel<decltype(ant)::value>, dim3(p->n_prod), dim3(256), 0, p->stream, nullptr,
+                                  big ? nullptr : p->ev_res[slot], 0, sums_src, out, rot, p->nchan, p->n_prod, 1.0 / bandwidth, p->n_base);
+        });
+    }
+    FXC_HIP(p, hipGetLastError());
+    if (big) {
+        FXC_HIP(p, hipEventRecord(p->big_res.ev_fin, p->stream));
+        FXC_HIP(p, hipStreamWaitEvent(p->big_res.s_copy, p->big_res.ev_fin, 0));
+        FXC_HIP(p, hipMemcpyAsync(user_out ? user_out : static_cast<void*>(p->h_res[slot]), out, bytes, hipMemcpyDeviceToHost, p->big_res.s_copy));
+        FXC_HIP(p, hipEventRecord(p->ev_res[slot], p->big_res.s_copy));
+    }
+    p->res_bytes[slot] = bytes;
+    p->res_head += 1;
     return FXC_OK;
 }
 

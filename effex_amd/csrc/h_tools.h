@@ -15,7 +15,7 @@ struct WsCarver {
     int64_t total() const { return off; }
 };
 template <typename T>
-T* ws_at(const fxc_plan* p, int64_t off) { return reinterpret_cast<T*>(static_cast<char*>(p->d_ws) + off); }
+T* ws_at(const fxc_plan* p, int64_t off) { return reinterpret_cast<T*>(static_cast<char*>(p->d_ws.get()) + off); }
 
 // Forward (sign -1, kernel exp(-2 pi i ...) like cp.fft.fft) or inverse (+1, un-normalised) transform of n_lines adjacent lines
 // of len = 2^lg points in buf[0], ping-pong with buf[1]: radix-16 passes, then one radix-8 / 4 / 2 pass for the remaining bits
@@ -872,13 +872,13 @@ int beamform_dev(fxc_plan* p, const cf* x, const cf* weights, bool weights_on_ho
         }
         const cf* wk = weights;
         if (p->track) {
-            const int rg = grow(p, &p->d_track, &p->track_bytes, (size_t)(nc * n_ant * nchan) * sizeof(cd));
+            const int rg = grow(p, p->d_track, (size_t)(nc * n_ant * nchan) * sizeof(cd));
             if (rg) return rg;
-            rc = track_tables(p, p->track_t, nc, static_cast<cd*>(p->d_track), false);
+            rc = track_tables(p, p->track_t, nc, static_cast<cd*>(p->d_track.get()), false);
             if (rc) return rc;
             p->track_t += nc;
             hipLaunchKernelGGL(beam_weights_kernel, dim3(grid_for(nc * w_elems, 256, p->cu_count)), dim3(256), 0, p->stream, weights,
-                               static_cast<const cd*>(p->d_track), weff, n_beam, n_ant, nchan, nc);
+                               static_cast<const cd*>(p->d_track.get()), weff, n_beam, n_ant, nchan, nc);
             FXC_HIP(p, hipGetLastError());
             wk = weff;
         }
