@@ -141,6 +141,8 @@ SIGNATURES = {
     "fxc_kurtosis": (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int64, _c.c_int, _c.c_int64]),
     "fxc_kurtosis_weights": (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int64, _c.c_double, _c.c_double, _vp, _c.c_int]),
     "fxc_dedisperse": (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int, _vp, _c.c_int, _vp, _vp, _vp]),
+    "fxc_boxcar_search": (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _c.c_int64, _c.c_double, _c.c_int,
+                                     _vp, _vp, _vp, _vp]),
     "fxc_pipe_create": (_c.c_int, [_c.POINTER(_vp), _vp, _c.c_int64, _c.c_int, _c.c_int, _c.c_double]),
     "fxc_pipe_create_u8": (_c.c_int, [_c.POINTER(_vp), _vp, _c.c_int64, _c.c_int, _c.c_int, _c.c_double, _c.c_int]),
     "fxc_pipe_create_iq": (_c.c_int, [_c.POINTER(_vp), _vp, _c.c_int64, _c.c_int, _c.c_int, _c.c_double, _c.c_int,

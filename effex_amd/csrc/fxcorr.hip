@@ -4,7 +4,7 @@
 //   fx_math.h, fx_fused4096.h, fx_tiled.h, fx_small.h, fx_mixed.h   index maps, butterflies and kernel phases (also compiled by
 //                                           g++ for the host emulation under tests/emul)
 //   k_generic.h k_finish.h k_xmfma.h k_fused4096.h k_tiled.h k_small.h k_prepass.h k_stream.h k_conditioning.h k_track.h k_align.h k_synth.h
-//   k_delay.h k_fringe.h k_gains.h k_flag.h k_average.h k_beam.h k_kurtosis.h k_dedisperse.h
+//   k_delay.h k_fringe.h k_gains.h k_flag.h k_average.h k_beam.h k_kurtosis.h k_dedisperse.h k_boxcar.h
 //                                           the __global__ kernels, one file per path / step and per rows tool (delays, fringe fit,
 //                                           gain solve, detector, averager, beamformer, spectral kurtosis)
 //   h_own.h h_plan.h h_rtc.h h_launch.h h_build.h h_run.h h_modifiers.h h_ingest.h h_pipe.h h_tools.h h_rccl.h
@@ -152,6 +152,7 @@ int64_t ws_target() {
 #include "k_beam.h"
 #include "k_kurtosis.h"
 #include "k_dedisperse.h"
+#include "k_boxcar.h"
 #include "k_synth.h"
 #include "h_own.h"
 #include "h_plan.h"
@@ -935,6 +936,22 @@ int fxc_dedisperse(fxc_plan* p, const void* power, int64_t n_chunks, int64_t n_s
     if (table.s_max >= n_chunks * n_tbin)
         return fail(p, FXC_ERR_ARG, "the largest shift %lld leaves no output: n_t is %lld", (long long)table.s_max, (long long)(n_chunks * n_tbin));
     return dedisperse_batch(p, static_cast<const float*>(power), n_chunks, n_series, n_tbin, mem_kind, table, static_cast<float*>(out), info_out);
+}
+
+int fxc_boxcar_search(fxc_plan* p, const void* series, int64_t n_rows, int64_t n_t, int mem_kind, int j_lo, int j_hi, int64_t block,
+                      double clip, int clip_iters, void* snr_out, void* width_out, void* time_out, double* stats_out) {
+    if (!p || !series || !snr_out || !width_out || !time_out) return fail(p, FXC_ERR_ARG, "NULL argument");
+    if (n_rows < 1 || n_t < 1 || block < 1)
+        return fail(p, FXC_ERR_ARG, "n_rows=%lld, n_t=%lld, block=%lld: each must be 1 or more", (long long)n_rows, (long long)n_t,
+                    (long long)block);
+    if (j_lo < 0 || j_hi > kBoxMaxJ || j_lo > j_hi) return fail(p, FXC_ERR_ARG, "widths 2^%d .. 2^%d are not within 2^0 .. 2^%d", j_lo, j_hi, kBoxMaxJ);
+    if ((1ll << j_lo) > n_t) return fail(p, FXC_ERR_ARG, "the narrowest width 2^%d leaves no start: n_t is %lld", j_lo, (long long)n_t);
+    if (!(clip >= 0.0)) return fail(p, FXC_ERR_ARG, "clip must be 0 or more");
+    if (clip_iters < 0 || clip_iters > 4) return fail(p, FXC_ERR_ARG, "clip_iters=%d outside 0 .. 4", clip_iters);
+    if (const int rc = bad_mem_kind(p, mem_kind)) return rc;
+    if (n_t >= (1ll << 31)) return fail(p, FXC_ERR_UNSUPPORTED, "n_t = %lld: the time axis is addressed in 31 bits", (long long)n_t);
+    return boxcar_batch(p, static_cast<const float*>(series), n_rows, n_t, mem_kind, j_lo, j_hi, block, clip, clip_iters,
+                        static_cast<float*>(snr_out), static_cast<int*>(width_out), static_cast<int*>(time_out), stats_out);
 }
 
 namespace {

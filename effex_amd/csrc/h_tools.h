@@ -1,5 +1,5 @@
 // Part of libfxcorr's single translation unit: included by fxcorr.hip (not a stand-alone header).
-// The rows tools' drivers -- delays, fringe fit, gain solve, detector, averager, beamformer, spectral kurtosis, dedispersion -- and
+// The rows tools' drivers -- delays, fringe fit, gain solve, detector, averager, beamformer, spectral kurtosis, dedispersion, boxcar search -- and
 // the host helpers they share.
 // The entry points that check a call's arguments and hand it to a driver are in fxcorr.hip.
 #pragma once
@@ -1150,6 +1150,161 @@ int dedisperse_batch(fxc_plan* p, const float* power, int64_t n_chunks, int64_t 
     if (info_out) {
         info_out[0] = t.trials_tiled;
         info_out[1] = t.trials_direct;
+    }
+    return FXC_OK;
+}
+
+// How a boxcar search cuts a row of n_t samples into cells (the output's blocks) and filter tiles (k_boxcar.h BoxGeom), and what
+// a launch of the filter needs: decided here alone.  A block that reaches past the starts is the one cell it leaves.
+struct BoxPlan {
+    BoxGeom g;
+    int64_t n_tiles;          // filter workgroups a row
+    int64_t n_seg;            // segments of 256 samples a row
+    size_t lds;               // bytes of the filter's two level buffers, or of the bests that take their place
+    bool partial() const { return g.tiles != 0; }
+};
+
+BoxPlan box_geometry(int64_t n_t, int j_lo, int j_hi, int64_t block) {
+    BoxPlan b{};
+    b.g.n_t = n_t;
+    b.g.j_lo = j_lo;
+    b.g.j_hi = j_hi;
+    while ((1ll << b.g.j_hi) > n_t) --b.g.j_hi;      // a width that does not fit has no start; 2^j_lo <= n_t
+    b.g.n_starts = n_t - (1ll << j_lo) + 1;
+    b.g.block = std::min(block, b.g.n_starts);
+    b.g.n_blk = (b.g.n_starts + b.g.block - 1) / b.g.block;
+    if (b.g.block <= kBoxT) {
+        b.g.cells = (unsigned)(kBoxT / b.g.block);
+        b.g.tiles = 0;
+        b.n_tiles = (b.g.n_blk + b.g.cells - 1) / b.g.cells;
+    } else {
+        b.g.cells = 0;
+        b.g.tiles = (unsigned)((b.g.block + kBoxT - 1) / kBoxT);
+        b.n_tiles = b.g.n_blk * b.g.tiles;
+    }
+    b.n_seg = (n_t + kBoxSeg - 1) / kBoxSeg;
+    b.lds = sizeof(float) * (size_t)std::max<int64_t>(2 * (kBoxT + (1ll << b.g.j_hi) - 1), 2 * kBoxBestWords);
+    return b;
+}
+
+// The kernels of a boxcar search over n rows that lie n_t samples apart on the device: the statistics' rounds, the filter and,
+// where a block is larger than a tile, the fold of the partial bests.  Each grid dimension is bounded here: rows go through in
+// launches of kGridMax at most.
+struct BoxLaunch {
+    const float* x;
+    int64_t n;
+    BoxRow* rows;
+    double* seg_sum;
+    int* seg_cnt;
+    const double* root;
+    float* p_snr;      // the partial bests (block > tile) ..
+    int *p_w, *p_t;
+    float* snr;        // .. and the outputs, [n][n_blk]
+    int *width, *time;
+};
+
+int launch_boxcar(fxc_plan* p, const BoxPlan& b, const BoxLaunch& k, double c2, int rounds) {
+    const BoxGeom& g = b.g;
+    hipLaunchKernelGGL(boxcar_rows_init_kernel, dim3((unsigned)((k.n + 255) / 256)), dim3(256), 0, p->stream, k.rows, k.n);
+    const unsigned sweep_x = (unsigned)((b.n_seg + kBoxSegs - 1) / kBoxSegs);
+    for (int round = 0; round <= rounds; ++round)
+        for (int second = 0; second < 2; ++second)
+            for (int64_t r0 = 0; r0 < k.n; r0 += kGridMax) {
+                const unsigned nr = (unsigned)std::min(kGridMax, k.n - r0);
+                hipLaunchKernelGGL(boxcar_sweep_kernel, dim3(sweep_x, nr), dim3(kBoxThreads), 0, p->stream, k.x + r0 * g.n_t, g.n_t,
+                                   k.rows + r0, k.seg_sum + r0 * b.n_seg, k.seg_cnt + r0 * b.n_seg, b.n_seg, second);
+                hipLaunchKernelGGL(boxcar_round_kernel, dim3(nr), dim3(kBoxThreads), 0, p->stream, k.rows + r0, k.seg_sum + r0 * b.n_seg,
+                                   k.seg_cnt + r0 * b.n_seg, b.n_seg, second, (int)(round == rounds), c2, k.root);
+            }
+    const int64_t stride = b.partial() ? b.n_tiles : g.n_blk;
+    for (int64_t r0 = 0; r0 < k.n; r0 += kGridMax) {
+        const unsigned nr = (unsigned)std::min(kGridMax, k.n - r0);
+        hipLaunchKernelGGL(boxcar_filter_kernel, dim3((unsigned)b.n_tiles, nr), dim3(kBoxThreads), b.lds, p->stream, k.x + r0 * g.n_t,
+                           k.rows + r0, g, (b.partial() ? k.p_snr : k.snr) + r0 * stride, (b.partial() ? k.p_w : k.width) + r0 * stride,
+                           (b.partial() ? k.p_t : k.time) + r0 * stride, stride);
+    }
+    if (b.partial()) {
+        constexpr int64_t per = (1ll << 31) - kBoxThreads;      // cells of a fold launch
+        for (int64_t r0 = 0; r0 < k.n;) {
+            const int64_t nr = std::max<int64_t>(1, std::min(k.n - r0, per / g.n_blk));
+            hipLaunchKernelGGL(boxcar_fold_kernel, dim3((unsigned)((nr * g.n_blk + kBoxThreads - 1) / kBoxThreads)), dim3(kBoxThreads), 0,
+                               p->stream, k.p_snr + r0 * stride, k.p_w + r0 * stride, k.p_t + r0 * stride, g, nr, k.snr + r0 * g.n_blk,
+                               k.width + r0 * g.n_blk, k.time + r0 * g.n_blk);
+            r0 += nr;
+        }
+    }
+    FXC_HIP(p, hipGetLastError());
+    return FXC_OK;
+}
+
+// The boxcar search (fxcorr.h fxc_boxcar_search; kernels in k_boxcar.h) after the argument checks.  The workspace holds the table of
+// sqrt(2^j), and per row of a slab its state, the tree's segment sums and counts, the partial bests where a block is larger than a
+// tile and, for host input, the row itself and its three outputs: a slab is some whole rows (one copy in, three copies back), sized
+// by the workspace target (FXC_WS_MB) and one row at least, whatever the row's size.  Device input needs no staging and its outputs
+// are written in place; it goes through in the same slabs, which bound the scratch.  No number depends on the slab: a row's
+// statistics and cells belong to its own workgroups.  One synchronisation ends the call.
+int boxcar_batch(fxc_plan* p, const float* x, int64_t n_rows, int64_t n_t, int mem_kind, int j_lo, int j_hi, int64_t block, double clip,
+                 int clip_iters, float* snr_out, int* width_out, int* time_out, double* stats_out) {
+    FXC_DEVICE(p, p->device);
+    const BoxPlan b = box_geometry(n_t, j_lo, j_hi, block);
+    const bool host = mem_kind == FXC_MEM_HOST;
+    const int64_t n_blk = b.g.n_blk, n_part = b.partial() ? b.n_tiles : 0;
+    const int rounds = clip == 0.0 ? 0 : clip_iters;
+    const double c2 = clip * clip;
+    double root[kBoxMaxJ + 1];
+    for (int j = 0; j <= kBoxMaxJ; ++j) root[j] = std::sqrt((double)(1ll << j));
+    const int64_t per_row = (int64_t)sizeof(BoxRow) + b.n_seg * 12 + n_part * 12 + (host ? (n_t + 3 * n_blk) * 4 : 0);
+    const int64_t fixed = 256 + 9 * 256;      // the table, and the rounding of the blocks
+    const int64_t slab = std::max<int64_t>(1, std::min(n_rows, (ws_target() - fixed) / per_row));
+    WsCarver ws;
+    const int64_t o_root = ws.take(256), o_rows = ws.take(up256(slab * (int64_t)sizeof(BoxRow)));
+    const int64_t o_sum = ws.take(up256(slab * b.n_seg * 8)), o_cnt = ws.take(up256(slab * b.n_seg * 4));
+    const int64_t o_ps = ws.take(up256(slab * n_part * 4)), o_pw = ws.take(up256(slab * n_part * 4)), o_pt = ws.take(up256(slab * n_part * 4));
+    const int64_t o_x = ws.take(host ? up256(slab * n_t * 4) : 0);
+    const int64_t o_s = ws.take(host ? up256(slab * n_blk * 4) : 0), o_w = ws.take(host ? up256(slab * n_blk * 4) : 0);
+    const int64_t o_t = ws.take(host ? up256(slab * n_blk * 4) : 0);
+    if (const int rc = ensure_ws(p, ws.total())) return rc;
+    FXC_HIP(p, hipMemcpyAsync(ws_at<double>(p, o_root), root, sizeof root, hipMemcpyHostToDevice, p->stream));
+    std::vector<BoxRow> states(stats_out ? (size_t)n_rows : 0);
+    for (int64_t r0 = 0; r0 < n_rows; r0 += slab) {
+        const int64_t n = std::min(slab, n_rows - r0);
+        BoxLaunch k{};
+        k.n = n;
+        k.rows = ws_at<BoxRow>(p, o_rows);
+        k.seg_sum = ws_at<double>(p, o_sum);
+        k.seg_cnt = ws_at<int>(p, o_cnt);
+        k.root = ws_at<double>(p, o_root);
+        k.p_snr = ws_at<float>(p, o_ps);
+        k.p_w = ws_at<int>(p, o_pw);
+        k.p_t = ws_at<int>(p, o_pt);
+        if (host) {
+            float* stage = ws_at<float>(p, o_x);
+            FXC_HIP(p, hipMemcpyAsync(stage, x + r0 * n_t, (size_t)(n * n_t) * sizeof(float), hipMemcpyHostToDevice, p->stream));
+            k.x = stage;
+            k.snr = ws_at<float>(p, o_s);
+            k.width = ws_at<int>(p, o_w);
+            k.time = ws_at<int>(p, o_t);
+        } else {
+            k.x = x + r0 * n_t;
+            k.snr = snr_out + r0 * n_blk;
+            k.width = width_out + r0 * n_blk;
+            k.time = time_out + r0 * n_blk;
+        }
+        if (const int rc = launch_boxcar(p, b, k, c2, rounds)) return rc;
+        if (host) {
+            const size_t bytes = (size_t)(n * n_blk) * 4;
+            FXC_HIP(p, hipMemcpyAsync(snr_out + r0 * n_blk, k.snr, bytes, hipMemcpyDeviceToHost, p->stream));
+            FXC_HIP(p, hipMemcpyAsync(width_out + r0 * n_blk, k.width, bytes, hipMemcpyDeviceToHost, p->stream));
+            FXC_HIP(p, hipMemcpyAsync(time_out + r0 * n_blk, k.time, bytes, hipMemcpyDeviceToHost, p->stream));
+        }
+        if (stats_out)
+            FXC_HIP(p, hipMemcpyAsync(states.data() + r0, k.rows, (size_t)n * sizeof(BoxRow), hipMemcpyDeviceToHost, p->stream));
+    }
+    FXC_HIP(p, hipStreamSynchronize(p->stream));
+    for (size_t i = 0; i < states.size(); ++i) {
+        stats_out[3 * i] = states[i].m;
+        stats_out[3 * i + 1] = states[i].stdv;
+        stats_out[3 * i + 2] = (double)states[i].n;
     }
     return FXC_OK;
 }

@@ -208,6 +208,64 @@ def dm_shifts(nchan, bandwidth, frequency, dms, tsamp):
     return steps.astype(np.int32)
 
 
+BOXCAR_MAX_J = 12      # kBoxMaxJ of csrc/k_boxcar.h
+
+
+def boxcar_widths(j_lo, j_hi):
+    """The widths of ``FxPlan.boxcar_search(.., widths=(j_lo, j_hi))`` in samples: ``1 << arange(j_lo, j_hi + 1)``; the ``width``
+    map holds the index j."""
+    j_lo, j_hi = int(j_lo), int(j_hi)
+    if not 0 <= j_lo <= j_hi <= BOXCAR_MAX_J:
+        raise ValueError("widths must satisfy 0 <= j_lo <= j_hi <= {}, got ({}, {})".format(BOXCAR_MAX_J, j_lo, j_hi))
+    return 1 << np.arange(j_lo, j_hi + 1)
+
+
+SIFT_DTYPE = np.dtype([("series", np.int64), ("dm_index", np.int64), ("time", np.int64), ("width", np.int64), ("snr", np.float32),
+                       ("n_cells", np.int64)])
+
+
+def sift_pulses(snr, width, time, threshold=6.0):
+    """Candidates from the maps of ``FxPlan.boxcar_search`` (host numpy; tensors are moved to the host): ``snr``, ``width``, ``time``
+    of one shape [n_series, n_dm, n_blk] ([n_dm, n_blk] and [n_blk] are one series / one trial).  Per series the cells with ``snr >
+    threshold`` are joined over the (trial, block) grid with 8-neighbour connectivity, and each cluster is reduced to its largest
+    cell -- ties to the smallest trial, then the smallest block.  -> a structured array with the fields ``series, dm_index, time``
+    (the start, samples), ``width`` (samples, ``1 << j``), ``snr, n_cells``, sorted by descending snr, then by (series, dm_index,
+    time)."""
+    maps = []
+    for a in (snr, width, time):
+        if _is_torch(a):
+            a = a.detach().cpu().numpy()
+        maps.append(np.asarray(a))
+    snr, width, time = maps
+    if not (snr.shape == width.shape == time.shape) or snr.ndim not in (1, 2, 3):
+        raise ValueError("snr, width and time must share one shape of 1 to 3 axes, got {} {} {}".format(snr.shape, width.shape, time.shape))
+    snr, width, time = (a.reshape((1,) * (3 - a.ndim) + a.shape) for a in (snr, width, time))
+    n_series, n_dm, n_blk = snr.shape
+    found = []
+    with np.errstate(invalid="ignore"):
+        above = snr > threshold
+    for s in range(n_series):
+        label = np.full((n_dm, n_blk), -1, np.int64)
+        for d0, b0 in zip(*np.nonzero(above[s])):          # ascending trial, then block: a cluster's first cell is its seed
+            if label[d0, b0] >= 0:
+                continue
+            label[d0, b0] = len(found)
+            stack, cells = [(int(d0), int(b0))], []
+            while stack:
+                d, b = stack.pop()
+                cells.append((d, b))
+                for dd in range(max(0, d - 1), min(n_dm, d + 2)):
+                    for bb in range(max(0, b - 1), min(n_blk, b + 2)):
+                        if above[s, dd, bb] and label[dd, bb] < 0:
+                            label[dd, bb] = len(found)
+                            stack.append((dd, bb))
+            best = min(cells, key=lambda c: (-float(snr[s][c]), c[0], c[1]))
+            found.append((s, best[0], int(time[s][best]), 1 << int(width[s][best]), snr[s][best], len(cells)))
+    out = np.array(found, dtype=SIFT_DTYPE) if found else np.zeros(0, SIFT_DTYPE)
+    order = np.lexsort((out["time"], out["dm_index"], out["series"], -out["snr"].astype(np.float64)))
+    return out[order]
+
+
 def sk_thresholds(M, sigma=3.0):
     """(lo, hi) = 1 -/+ sigma sqrt(mu2) for ``FxPlan.kurtosis_weights``, with mu2 = 4 M^2 / ((M - 1)(M + 2)(M + 3)) the variance
     of the spectral kurtosis estimator over ``M`` spectra of Gaussian noise (Nita & Gary 2010).  A symmetric approximation of a
@@ -1225,6 +1283,65 @@ class FxPlan(object):
         self._check(self._lib.fxc_dedisperse(self._h, ptr, n_chunks, n_series, n_tbin, kind, shifts.ctypes.data, n_dm, w_ptr, o_ptr,
                                              info.ctypes.data))
         return (res, (int(info[0]), int(info[1]))) if return_info else res
+
+    def boxcar_search(self, ts, widths=(0, 8), block=64, clip=3.0, clip_iters=2, out=None, return_stats=False):
+        """Single-pulse search on dedispersed series (fxcorr.h fxc_boxcar_search): ``ts`` = float32 [..., n_t] with 1 to 3 axes, as
+        ``dedisperse`` returns it (numpy, or a CUDA tensor on the plan's device).  Every row is normalised by its mean and standard
+        deviation after ``clip_iters`` rounds of clipping at ``clip`` standard deviations (``clip=0``: none), matched-filtered with
+        boxcars of the widths ``boxcar_widths(*widths)`` = 2^j_lo .. 2^j_hi samples, and reduced per block of ``block`` starts.
+        -> (snr float32, width int32 -- the index j --, time int32 -- the absolute start) of shape ``ts.shape[:-1] + (n_blk,)``,
+        ``n_blk = ceil((n_t - 2^j_lo + 1) / block)``, in the memory of ``ts``; ties go to the narrowest width, then the earliest
+        start.  ``out``: three arrays / tensors of that shape to receive them.  ``return_stats`` adds a float64 numpy array [..., 3]
+        of (mean, std, counted samples) per row; std = 0 marks a degenerate row, whose cells hold snr 0.  The loop it closes::
+
+            ts = plan.dedisperse(P, sh)
+            snr, w, t = plan.boxcar_search(ts)
+            cands = sift_pulses(snr, w, t)
+        """
+        self._sync_stream()
+        device = _is_torch(ts)
+        if device:
+            import torch
+            if ts.dtype != torch.float32 or not ts.is_cuda or ts.device.index != self.device:
+                raise ValueError("device series must be a float32 CUDA tensor on device {}".format(self.device))
+            keep = ts.contiguous()
+            ptr, kind = keep.data_ptr(), _lib.FXC_MEM_DEVICE
+        else:
+            if not isinstance(ts, np.ndarray) or ts.dtype != np.float32:
+                raise ValueError("ts must be a float32 array or CUDA tensor")
+            keep = np.ascontiguousarray(ts)
+            ptr, kind = keep.ctypes.data, _lib.FXC_MEM_HOST
+        shape = tuple(keep.shape)
+        if len(shape) not in (1, 2, 3) or min(shape) < 1:
+            raise ValueError("ts must have shape (n_series, n_dm, n_t), (n_dm, n_t) or (n_t,), got {}".format(shape))
+        try:
+            j_lo, j_hi = (int(j) for j in widths)
+        except (TypeError, ValueError):
+            raise ValueError("widths must be a pair (j_lo, j_hi)")
+        n_t = shape[-1]
+        if not 0 <= j_lo <= j_hi <= BOXCAR_MAX_J or (1 << j_lo) > n_t:
+            raise ValueError("widths must satisfy 0 <= j_lo <= j_hi <= {} and 2^j_lo <= n_t = {}, got {}".format(BOXCAR_MAX_J, n_t,
+                                                                                                              (j_lo, j_hi)))
+        block, clip_iters = int(block), int(clip_iters)
+        if block < 1 or not clip >= 0 or not 0 <= clip_iters <= 4:
+            raise ValueError("block must be 1 or more, clip 0 or more and clip_iters within 0 .. 4")
+        n_rows = int(np.prod(shape[:-1], dtype=np.int64))
+        n_blk = -(-(n_t - (1 << j_lo) + 1) // block)
+        want = shape[:-1] + (n_blk,)
+        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 3):
+            raise ValueError("out must be three arrays / tensors (snr, width, time)")
+        res, ptrs = [], []
+        for i, (name, dtype) in enumerate((("out[0] (snr)", np.float32), ("out[1] (width)", np.int32), ("out[2] (time)", np.int32))):
+            a, a_ptr = self._out_like_x(None if out is None else out[i], want, device, keep, name=name, dtype=dtype)
+            res.append(a)
+            ptrs.append(a_ptr)
+        if device and not self._follow:      # a stream of the plan's own: torch's may still be using the blocks it handed out
+            import torch
+            torch.cuda.current_stream(keep.device).synchronize()
+        stats = np.zeros(shape[:-1] + (3,), dtype=np.float64) if return_stats else None
+        self._check(self._lib.fxc_boxcar_search(self._h, ptr, n_rows, n_t, kind, j_lo, j_hi, block, float(clip), clip_iters, ptrs[0],
+                                                ptrs[1], ptrs[2], None if stats is None else stats.ctypes.data))
+        return tuple(res) + ((stats,) if return_stats else ())
 
     def set_gains(self, gains, delays_s=None, bandwidth=None, frequency=None, whole_samples=False):
         """Correct the rows for the per-antenna gains ``gains`` [n_ant, nchan] (one solution of ``solve_gains``, bins in the

@@ -811,13 +811,58 @@ int fxc_kurtosis_antenna_mask(fxc_plan* plan, const void* sk, int64_t n_chunks, 
  * FXC_ERR_ARG, before any device work: a NULL plan / power / shifts / out, n_chunks, n_series, n_tbin or n_dm below 1, an unknown
  * mem_kind (FXC_MEM_DEVICE_TO_PINNED included), a negative shift, S_max >= n_t.  FXC_ERR_UNSUPPORTED: n_t >= 2^31.
  * out and info_out are written on FXC_OK only.
- * Out of scope: coherent dedispersion of VOLTAGE beams, sub-band or tree algorithms, boxcar matched filtering and candidate
- * sifting, folding, a per-time mask, frequency-averaged input, pipes, Correlator integration. */
+ * Out of scope: coherent dedispersion of VOLTAGE beams, sub-band or tree algorithms, folding, a per-time mask,
+ * frequency-averaged input, pipes, Correlator integration.  (The detection on these series is fxc_boxcar_search.) */
 int fxc_dedisperse(fxc_plan* plan, const void* power, int64_t n_chunks, int64_t n_series, int64_t n_tbin, int mem_kind,
                    const int32_t* shifts /* HOST, [n_dm][nchan] */, int n_dm,
                    const float* chan_weights /* HOST, [nchan], may be NULL */,
                    void* out /* [n_series][n_dm][n_out] float32, in the memory kind of power */,
                    int64_t* info_out /* may be NULL: [0] trials on the tiled kernel, [1] trials on the direct kernel */);
+
+/* Single-pulse search on dedispersed series: every row is normalised by a clipped mean and standard deviation,
+ * matched-filtered with boxcars of the widths 2^j, j_lo <= j <= j_hi, and reduced to the best S/N of every block of `block`
+ * starts with its width and its time -- a small map, the only thing that has to leave the device.
+ * series = float32 [n_rows][n_t], mem_kind = FXC_MEM_HOST or FXC_MEM_DEVICE: a row is one (series, trial) of fxc_dedisperse's
+ * output, the leading axes flattened.  0 <= j_lo <= j_hi <= 12, block >= 1, clip >= 0, 0 <= clip_iters <= 4.
+ * Row statistics, every step one IEEE float64 operation, nothing contracted.  The tree sum of per-sample terms: the samples are
+ * cut into segments of 256 from t = 0; a segment's sum runs from +0 over its counted samples in ascending t; 256 consecutive
+ * segment sums are added in ascending order to a group sum; the group sums are added in ascending order.  A sample that does not
+ * count is selected away, never multiplied.  Round 0 counts every sample.  In a round with n counted samples
+ *   m = treesum(double(x)) / double(n),   e = double(x) - m,   v = treesum(e e) / double(n - 1)
+ * and the next round counts sample t iff e e <= c2 v, e against this round's m, c2 = clip clip formed once on the host and c2 v
+ * once per row: a sample dropped earlier may come back.  R = clip_iters rounds follow round 0, none if clip == 0; the last
+ * round's (m, v, n) are the row's statistics and std the correctly rounded float64 square root of v.  A round that counts fewer
+ * than 2 samples ends the rounds: the row is degenerate, as is one whose final v == 0.
+ * Filter: y[t] = float32(double(x[t]) - m); L_0 = y; L_j[t] = L_{j-1}[t] + L_{j-1}[t + 2^(j-1)], one float32 add, for t in
+ * [0, n_t - 2^j]; snr_j[t] = float32(double(L_j[t]) / den_j), den_j = std r_j formed once per row and width, r_j the float64
+ * sqrt(2^j) from a table of 13 entries made on the host.  A width with 2^j > n_t has no start and does not compete.
+ * Reduction: n_blk = ceil((n_t - 2^j_lo + 1) / block); block b owns the starts [b block, (b + 1) block); its candidates are
+ * ordered by ascending j, then ascending t; the best is the first candidate, replaced only by a candidate whose snr is strictly
+ * greater -- ties go to the narrowest width, then the earliest start.
+ * snr_out float32, width_out int32 (the index j, not the width), time_out int32 (the absolute start t): [n_rows][n_blk] each, in
+ * the memory kind of series.  A degenerate row gives snr +0, width j_lo and the block's first start in every cell.
+ * stats_out (HOST memory always, may be NULL): double [n_rows][3] = (m, std, n) of the last round made; std = 0 for a degenerate
+ * row.  With block = 1 and j_lo == j_hi the output is the whole matched-filtered series of that width.  A counted non-finite
+ * sample propagates (stated, not checked).  No output bit depends on the tiles, on host against device input, on the alignment of
+ * a device tensor or on the workspace target.
+ * On the device: two sweeps over the input per round (the mean, then the squares about it), each followed by a small step that
+ * adds the tree's upper levels and forms the round's numbers -- the host is not needed between rounds --; then a filter kernel
+ * whose workgroup loads a tile of 4096 starts and its halo of 2^j_hi - 1 samples once and forms the levels in LDS.  Where block is
+ * at most 4096 tiles begin on block boundaries and a cell belongs to one workgroup; a larger block is cut into tiles whose
+ * partial bests a fold step takes in tile order.  Device input needs no staging; host input goes through the workspace in slabs of
+ * whole rows sized by the workspace target (FXC_WS_MB), one row at least whatever its size, the three outputs of a slab copied back.
+ * Uses the plan's device, stream and workspace; one synchronisation ends the call; neither reads nor changes the rot tables, the
+ * tracks, their counters or the accumulator (a pending fold is launched first).
+ * FXC_ERR_ARG, before any device work: a NULL plan / series / snr_out / width_out / time_out, n_rows, n_t or block below 1, j_lo < 0,
+ * j_hi > 12, j_lo > j_hi, 2^j_lo > n_t, clip negative or NaN, clip_iters outside 0 .. 4, an unknown mem_kind
+ * (FXC_MEM_DEVICE_TO_PINNED included).  FXC_ERR_UNSUPPORTED: n_t >= 2^31.  The outputs are written on FXC_OK only.
+ * Out of scope: fusing the filter into the dedispersion kernel so that the series is never written, a running (windowed)
+ * baseline, widths that are not powers of two, a per-time mask, candidate grouping across beams, folding, pipes, Correlator
+ * integration. */
+int fxc_boxcar_search(fxc_plan* plan, const void* series, int64_t n_rows, int64_t n_t, int mem_kind, int j_lo, int j_hi, int64_t block,
+                      double clip, int clip_iters, void* snr_out /* float32 [n_rows][n_blk], in the memory kind of series */,
+                      void* width_out /* int32, likewise */, void* time_out /* int32, likewise */,
+                      double* stats_out /* HOST, [n_rows][3], may be NULL */);
 
 /* Host-fed front end: replaces the reference's blocking per-chunk copies
  * (effex.py:391-392, 508-509, 693).  A pipe owns `depth` slots of pinned host staging + device buffers.
